@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: CG iterations/sec + SpMV achieved HBM GB/s, 256^3 Poisson (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, spins the device up, runs the W warmup steps, times ONE solve of exactly K steps, writes that
+solve's outputs if --dump-outputs is given (solver_outputs: x, or a seeded sample of its rows, and the final residual)
+and prints the line; `roofline`, `cpu_baseline` and the other side blocks are null.  --full adds every block listed
+below (each takes runs of its own; about a minute at 256^3).
 
 A "step" is one CG iteration (one pass of the hot path: stencil SpMV + the BLAS-1 ops of
 SolverCg.hpp:96-123) on the per-GPU 256^3 7-point Poisson block of BASELINE.json configs[1]
@@ -10,7 +15,7 @@ exactly K iterations run).  For N > 1 (one rank per GPU) the global mesh is 256 
 row-partitioned in z-slabs (weak scaling): halo planes and dot-product all-reduces move inside
 libstorm_hip.so (RCCL, or the library's peer-window transport).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0 (the blocks after `value` need --full, or --contact's bounded set).
   value             256^3-block CG iterations per second summed over the GPUs (at N = 1 plain CG it/s) on the record
                     format the operator qualifies for (the natural-order box: byte-indexed canonical rows);
   value_general     the same solve on fp64 records, the format ANY mesh gets (Triangle, graded, renumbered);
@@ -52,8 +57,10 @@ N > 1: every rank process is a SUPERVISOR that never touches the GPU; it starts 
 a wall-clock budget.  The child runs a bounded pre-flight (one halo exchange + one all-reduce on a tiny slab stack,
 checked numerically) before the 256^3 setup.  If any rank's child fails or exceeds the budget, all children are
 killed and a FRESH set starts on the next transport of the chain.  The chain is rccl, ipc, host-staged: RCCL (the
-transport north_star names) and the peer windows are BOTH measured, `value` is the better, `transports_measured` holds
-both; host-staged runs only if neither worked.  The line records `transport`, `transports_measured`, `transport_fallback`.
+transport north_star names) and the peer windows are BOTH measured (--full; a plain run stops at the first transport that
+works), `value` is the better, `transports_measured` holds both; host-staged runs only if neither worked.  A plain run
+also leaves out the post-flight check and the comm_breakdown solve.  The line records `transport`, `transports_measured`,
+`transport_fallback`.
 """
 from __future__ import annotations
 
@@ -108,8 +115,8 @@ def main() -> int:
     ap.add_argument("--force-comm", action="store_true",
                     help="take the multi-rank code path (process group, RCCL communicator, all-reduces) even at N = 1")
     ap.add_argument("--min-seconds", type=float, default=0.25,
-                    help="the K-step solve is repeated (each repeat bracketed by barrier + sync, max over ranks) until "
-                         "the timed repeats add up to this; ms_per_step is the median repeat")
+                    help="--full: the side blocks' K-step solves are repeated until their timed repeats add up to this (the "
+                         "headline always times exactly ONE K-step solve)")
     ap.add_argument("--traffic", default="measure", choices=["measure", "profile", "off"],
                     help="roofline.traffic: measure = two rocprofv3 --pmc passes of a child process in this run (N = 1, "
                          "edge 256); profile = quote profiles/spmv_hbm_traffic.json as traffic_from_profile only")
@@ -134,9 +141,19 @@ def main() -> int:
                     help="first-contact mode for a short multi-GPU lease (< 20 s of GPU work per transport): edge 64 unless "
                          "--edge is given, pre-flight, one RCCL CG and one RCCL BiCGStab with the device-timestamp breakdown, the "
                          "compact line; no stand-alone SpMV / stress / config blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline, stand-alone SpMV, fp64 records, stress variants, tetrahedra, "
+                         "BASELINE configs, BLAS-1, copy rate, PMC traffic, CPU baseline; N > 1: post-flight, comm_breakdown, "
+                         "every transport of the chain.  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed solve returned to DIR/<name>.npy (float64): "
+                         "x (a fixed seeded sample of its rows when it exceeds 48 MB) and the final residual")
     args = ap.parse_args()
     if args.contact:
         contact_defaults(args)
+    elif not args.full:
+        lean_defaults(args)
+    extras = args.full or args.contact  # the side measurements of a full run, or --contact's bounded set of them
     if args.n is None:
         args.n = 256
     chain = [t for t in (args.transport or default_chain(args)).split(",") if t]
@@ -344,11 +361,9 @@ def main() -> int:
         torch.cuda.synchronize()
         local = time.perf_counter() - t0  # this rank's K steps are complete (every step holds two all-reduces)
         dist.barrier()
-        return dist.allreduce_max(local), s_
+        return dist.allreduce_max(local), s_, x_
 
-    # The driver's `--steps 20` is 6 ms of work: one interval would decide the headline.  The K-step solve is
-    # repeated until the timed repeats cover --min-seconds (same count on every rank: the elapsed times are
-    # already max-reduced) and the median repeat is reported; `steps` stays K.
+    # `--steps` is the number of timed steps: ONE K-step solve is timed, and ms_per_step is its time / K.
     IPC_KEYS = ("ipc_allreduce_wait_ticks", "ipc_allreduces", "ipc_ack_wait_ticks", "ipc_ack_waits",
                 "ipc_halo_slow_poll_ticks", "ipc_halo_slow_polls")
 
@@ -361,20 +376,19 @@ def main() -> int:
             return None
 
     phase("setup_spinup_warmup")
-    repeats = []
     comm0 = ipc_counters()
-    while True:
-        e_, s = timed_solve()
-        repeats.append(e_)
-        if sum(repeats) >= args.min_seconds or len(repeats) >= 2000:
-            break
+    elapsed, s, x_timed = timed_solve()
+    repeats = [elapsed]
     comm1 = ipc_counters()
-    elapsed = float(np.median(repeats))
     final_residual = s.absolute_error
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver_outputs(x_timed.to_numpy(), s, DUMP_BYTES // world),
+                     "" if world == 1 else f"_rank{rank}")
+    del x_timed
     # N > 1: where the communication time of an iteration went, from the device's own clock (peer-window transport: the
     # kernels time their waits, csrc/ipc_device.hpp IpcDev::stat); the worst rank's numbers are reported
     comm_breakdown = None
-    if world > 1 or args.force_comm:
+    if (world > 1 or args.force_comm) and extras:
         if comm0 is not None and comm1 is not None:
             d_ = {k_: comm1[k_] - comm0[k_] for k_ in IPC_KEYS}
             its_ = max(len(repeats) * K, 1)
@@ -449,7 +463,7 @@ def main() -> int:
     # vanish on every row away from the walls -- which fails iff a halo plane is stale or misplaced.  Any failure ends
     # this process with an error: the supervisors then start fresh ranks on the next transport.
     postflight = None
-    if world > 1:
+    if world > 1 and extras:
         ctx.set_option("cg_fuse", 0)
         s_ref, _ = run(K)
         ctx.set_option("cg_fuse", 1)
@@ -480,7 +494,7 @@ def main() -> int:
         if kv.split("=")[0] == "cg_march":
             march_planes = int(kv.split("=")[1])
     prof_iters = max(K, args.roofline_launches)  # (a sample of 21 launches moved the fraction by 0.07 between runs)
-    roof = spmv_roofline(op, st, prof_iters)
+    roof = spmv_roofline(op, st, prof_iters) if extras else None
     phase("postflight_and_roofline_launches")
     # The CPU baseline's samples are pure host work in ONE thread (ctypes calls: the interpreter lock is released): they run
     # beside the GPU-side blocks that follow (child processes, stress variants, BASELINE configs) instead of after them --
@@ -693,20 +707,21 @@ def main() -> int:
     # a measured device-copy ceiling in the same run (achievable HBM rate, for context)
     # (two 1 GiB buffers: far beyond the 256 MiB Infinity Cache, so this is an HBM number)
     copy_gbs = None
-    try:
-        nc = 1 << 27
-        src = api.DeviceVector(ctx, nc)
-        dst = api.DeviceVector(ctx, nc)
-        for _ in range(2):
-            dst <<= src
-        ctx.timer_start()
-        reps = 10
-        for _ in range(reps):
-            dst <<= src
-        copy_gbs = 16.0 * nc * reps / (ctx.timer_stop() * 1e-3) / 1e9
-        del src, dst
-    except Exception:
-        pass
+    if extras:
+        try:
+            nc = 1 << 27
+            src = api.DeviceVector(ctx, nc)
+            dst = api.DeviceVector(ctx, nc)
+            for _ in range(2):
+                dst <<= src
+            ctx.timer_start()
+            reps = 10
+            for _ in range(reps):
+                dst <<= src
+            copy_gbs = 16.0 * nc * reps / (ctx.timer_stop() * 1e-3) / 1e9
+            del src, dst
+        except Exception:
+            pass
 
     # ---- BLAS-1 rates at this size ("plus BLAS-1 GB/s per kernel") ------------------
     blas1 = None
@@ -764,11 +779,10 @@ def main() -> int:
                                "rccl-plain": "RCCL halo send/recv + all-reduce over xGMI, the plain form (cross-stream events, "
                                              "two-launch reductions, no early halo, no fused step)",
                                "host": "halo planes and scalars staged through host memory (gloo)"}[transport]),
-                "value_definition": "n_gpus x K / max-over-ranks wall time of a K-iteration solve (init residual included; "
-                                    "barrier + synchronize, clock, K steps, synchronize, clock, barrier); median over the "
-                                    "repeats listed in `timing`",
+                "value_definition": "n_gpus x K / max-over-ranks wall time of ONE K-iteration solve (init residual included; "
+                                    "barrier + synchronize, clock, K steps, synchronize, clock, barrier)",
             },
-            "roofline": {
+            "roofline": None if roof is None else {
                 "kernel": (("cg_step_march_kernel (one CG step per launch: x += alpha p, p' = r + beta p, z = A p', <p',z> partials; "
                             "blocks of 1024 rows marching through the planes)" if march_planes > 0 else
                             "spmv_canon_tile_kernel<FUSE> (one CG step per launch: x += alpha p, p' = r + beta p, z = A p', "
@@ -818,11 +832,11 @@ def main() -> int:
             "timing": {"repeats": len(repeats), "timed_seconds_total": float(sum(repeats)),
                        "ms_per_step_min": min(repeats) / K * 1e3, "ms_per_step_max": max(repeats) / K * 1e3,
                        "ms_per_step_median": elapsed / K * 1e3},
-            "cg": {"iterations_per_sec_global": K / elapsed,
+            "cg": {"iterations_per_sec_global": K / elapsed, **({} if roof is None else {
                    "algorithmic_bytes_per_iteration": roof["algorithmic_bytes_8d"] + 96 * N,
                    "reference_op_list_bytes_over_time_GBs_NOT_A_BANDWIDTH": (roof["algorithmic_bytes_8d"] + 96 * N) * K / elapsed / 1e9,
                    "bytes_really_moved_per_iteration": roof["bytes_per_launch"] + (24 if roof.get("fused_cg_step") else 64) * N,
-                   "achieved_GBs_bytes_really_moved": (roof["bytes_per_launch"] + (24 if roof.get("fused_cg_step") else 64) * N) * K / elapsed / 1e9,
+                   "achieved_GBs_bytes_really_moved": (roof["bytes_per_launch"] + (24 if roof.get("fused_cg_step") else 64) * N) * K / elapsed / 1e9}),
                    "final_residual": final_residual},
             "op_stats": st,
             "device": ctx.info()["name"],
@@ -1156,6 +1170,44 @@ def contact_defaults(args) -> None:
     args.roofline_launches = min(args.roofline_launches, 50)
     if args.attempt_seconds == "240,150,150":
         args.attempt_seconds = "90,90,60"
+
+
+def lean_defaults(args) -> None:
+    """A plain run (neither --full nor --contact): the headline alone -- set up, warm up, time the K steps, print the line.
+    No side block runs, whatever its own options say; N > 1 stops at the first transport of the chain that works."""
+    args.skip_general = args.skip_blas1 = args.skip_permuted = args.skip_unstructured = True
+    args.skip_unstructured3d = args.skip_spmv = args.skip_configs = True
+    args.traffic, args.cpu_iters, args.self_exchange = "off", 0, ""
+    args.one_transport = True
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: x in full up to this many bytes per run, else a seeded sample of its rows
+DUMP_SEED = 2024
+
+
+def solver_outputs(x, solver, budget=DUMP_BYTES) -> dict:
+    """What a caller of the timed path receives from its last solve, as float64 arrays: the solution x -- every row when it
+    fits `budget`, else a fixed seeded sample of rows (`x_sample`, ascending rows, and the rows as `x_sample_rows`) -- and
+    `residual` = [absolute, relative] error after the last iteration."""
+    import numpy as np
+
+    x = np.asarray(x, dtype=np.float64)
+    if x.nbytes <= budget:
+        out = {"x": x}
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, budget // 16, replace=False))
+        out = {"x_sample": x[rows], "x_sample_rows": rows.astype(np.float64)}
+    out["residual"] = np.array([solver.absolute_error, solver.relative_error], dtype=np.float64)
+    return out
+
+
+def dump_outputs(path, arrays, suffix="") -> None:
+    """`arrays` to path/<name><suffix>.npy (float64)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def baseline_configs(api, mesh, ctx, op, b, N, n, st, min_seconds, self_exchange=("cg", "bicgstab")):

@@ -148,3 +148,47 @@ def test_emit_writes_the_detail_file_and_prints_one_stdout_line(tmp_path, capsys
     detail = json.load(open(path))
     assert detail["spmv"]["general"]["rotating_3_pairs"]["launches"] == 60 and detail["roofline"]["note"] == LONG
     assert cap.err.startswith("bench_detail {")
+
+
+def test_dumped_outputs_are_float64_bounded_and_the_same_sample_every_run(tmp_path):
+    """--dump-outputs: x in full while it fits the budget, else the same seeded sample of rows every run (so that two builds
+    can be compared output for output), and the residual; float64 .npy files, under 64 MB in all at the headline size."""
+    import numpy as np
+
+    class Solver:
+        absolute_error, relative_error = 2.5, 0.125
+
+    small = np.arange(1000, dtype=np.float64)
+    out = bench.solver_outputs(small, Solver())
+    assert set(out) == {"x", "residual"} and np.array_equal(out["x"], small)
+    assert out["residual"].tolist() == [2.5, 0.125]
+    big = np.sin(np.arange(1 << 20, dtype=np.float64))
+    a = bench.solver_outputs(big, Solver(), budget=1 << 20)
+    b = bench.solver_outputs(big.copy(), Solver(), budget=1 << 20)
+    assert set(a) == {"x_sample", "x_sample_rows", "residual"}
+    rows = a["x_sample_rows"].astype(np.int64)
+    assert np.array_equal(a["x_sample_rows"], b["x_sample_rows"]) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["x_sample"], big[rows]) and a["x_sample"].nbytes + a["x_sample_rows"].nbytes <= 1 << 20
+    bench.dump_outputs(str(tmp_path), a)
+    assert sorted(os.listdir(tmp_path)) == ["residual.npy", "x_sample.npy", "x_sample_rows.npy"]
+    for k, v in a.items():
+        got = np.load(tmp_path / f"{k}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    assert bench.DUMP_BYTES + 16 <= 64 << 20 and 256 ** 3 * 8 > bench.DUMP_BYTES  # (the headline's x is sampled)
+
+
+def test_a_plain_run_leaves_out_every_side_block():
+    """Without --full (or --contact) a run is the headline alone: every side block's switch is off, N > 1 stops at the first
+    transport that works; the options themselves exist."""
+    import argparse
+    import subprocess
+
+    args = argparse.Namespace(skip_general=False, skip_blas1=False, skip_permuted=False, skip_unstructured=False,
+                              skip_unstructured3d=False, skip_spmv=False, skip_configs=False, traffic="measure", cpu_iters=20,
+                              self_exchange="cg,bicgstab", one_transport=False)
+    bench.lean_defaults(args)
+    assert all(getattr(args, k) for k in ("skip_general", "skip_blas1", "skip_permuted", "skip_unstructured",
+                                          "skip_unstructured3d", "skip_spmv", "skip_configs", "one_transport"))
+    assert args.traffic == "off" and args.cpu_iters == 0 and args.self_exchange == ""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout

@@ -78,7 +78,7 @@ def _run_bench(extra, timeout=420, launcher_ranks=0):
 
     with tempfile.TemporaryDirectory() as tmp:
         detail_path = os.path.join(tmp, "bench_detail.json")
-        cmd = [*front, os.path.join(ROOT, "bench.py"), "--shared-device", "--edge", "48", "--steps", "20", "--warmup", "3",
+        cmd = [*front, os.path.join(ROOT, "bench.py"), "--full", "--shared-device", "--edge", "48", "--steps", "20", "--warmup", "3",
                "--spinup-seconds", "0.2", "--min-seconds", "0.05", "--detail-path", detail_path, *extra]
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout,
@@ -172,7 +172,7 @@ def test_bench_line_contract_at_one_gpu(tmp_path):
     """`python bench.py` (N = 1) on a small edge: ONE JSON line carrying the contract's fields -- `roofline` with a
     physical fraction <= 1 that follows from its own bytes and time, `roofline_general`, `cpu_baseline`, `timing`."""
     detail_path = os.path.join(str(tmp_path), "bench_detail.json")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--edge", "96", "--steps", "20", "--warmup", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--edge", "96", "--steps", "20", "--warmup", "3",
            "--spinup-seconds", "0.2", "--min-seconds", "0.05", "--cpu-iters", "4", "--tet-edge", "12", "--self-exchange", "cg",
            "--detail-path", detail_path]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
@@ -237,6 +237,39 @@ def test_bench_line_contract_at_one_gpu(tmp_path):
     assert cpu["value_native_O3"] > 0 and cpu["value_native_O3_fast_math"] > 0 and lc["value_native_O3"] > 0
     assert cpu["value_native_O3_residual_rel_diff_vs_strict"] <= 1e-9 and cpu["value_native_O3_fast_math_residual_rel_diff_vs_strict"] <= 1e-6
     assert out["timing"]["repeats"] >= 1 and out["value"] > 10 * cpu["value"]
+
+
+def test_plain_bench_run_times_exactly_the_steps_and_dumps_the_solution(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (no --full): the headline alone -- ONE timed solve of exactly K steps,
+    no side block -- and `--dump-outputs` writes that solve's x and residual: the CPU oracle's after K iterations."""
+    import numpy as np
+
+    from oracle import oracle
+    from stormruler_amd import mesh
+
+    n, K = 32, 30
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--edge", str(n), "--steps", str(K), "--warmup", "3",
+           "--spinup-seconds", "0.2", "--dump-outputs", str(dump), "--detail-path", str(tmp_path / "bench_detail.json")]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(env, OMP_NUM_THREADS="1"), cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-2000:] + "\n" + p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) <= 8000
+    line = json.loads(lines[0])
+    assert line["steps"] == K and line["warmup"] == 3 and line["n_gpus"] == 1 and line["dtype"] == "f64"
+    assert line["unit"] == "iter/s" and line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(1e3 / line["ms_per_step"], rel=1e-4) and line["timing"]["repeats"] == 1
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["value_general"] is None
+    assert "configs" not in line and "blas1_frac" not in line
+    assert sorted(os.listdir(dump)) == ["residual.npy", "x.npy"]
+    x, res = np.load(dump / "x.npy"), np.load(dump / "residual.npy")
+    assert x.dtype == np.float64 and x.shape == (n ** 3,) and res.dtype == np.float64 and res.shape == (2,)
+    g = mesh.structured_box(n)
+    ref = oracle.solve("cg", oracle.StencilOperator(g, -1.0, 0.0), np.ones(g.n_cells), num_iterations=K, abs_tol=0.0, rel_tol=0.0)
+    assert np.linalg.norm(x - ref.x) / np.linalg.norm(ref.x) <= 1e-8
+    assert abs(res[0] - ref.absolute_error) <= 1e-8 * ref.absolute_error
+    assert abs(line["final_residual"] - res[0]) <= 1e-5 * res[0]
 
 
 def test_bench_two_ranks_on_the_production_kernels_measures_both_transports():

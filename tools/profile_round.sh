@@ -10,9 +10,9 @@ TAG=${1:-round}
 OUT=$PWD/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-( time python3 bench.py --detail-path "$OUT/${TAG}_bench_detail.json" 2>/dev/null | tail -1 > "$OUT/${TAG}_bench.json" ) 2> "$OUT/${TAG}_bench_wall.txt"
+( time python3 bench.py --full --detail-path "$OUT/${TAG}_bench_detail.json" 2>/dev/null | tail -1 > "$OUT/${TAG}_bench.json" ) 2> "$OUT/${TAG}_bench_wall.txt"
 rm -rf /tmp/prof_stats /tmp/prof_fetch /tmp/prof_write
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python3 bench.py --cpu-iters 0 --skip-blas1 --traffic off --skip-permuted --skip-unstructured --skip-unstructured3d --skip-configs --detail-path "$OUT/${TAG}_bench_under_rocprof_detail.json" 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_under_rocprof.json"
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python3 bench.py --full --cpu-iters 0 --skip-blas1 --traffic off --skip-permuted --skip-unstructured --skip-unstructured3d --skip-configs --detail-path "$OUT/${TAG}_bench_under_rocprof_detail.json" 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_under_rocprof.json"
 cp "$(find /tmp/prof_stats -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_kernel_stats.csv"
 # the stand-alone SpMV block in a process of its own: the AverageNs of spmv_canon_tile_kernel<false,...> and
 # spmv_sell_kernel<true, false,...> in this file is what `all_launches_mean_ms` of the JSON beside it must agree with
@@ -23,8 +23,8 @@ cp "$(find /tmp/prof_spmv -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_spm
 rm -rf /tmp/prof_tets
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_tets -- python3 bench.py --spmv-only --spmv-what tets 2>/dev/null | tail -1 > "$OUT/${TAG}_spmv_only_tets_under_rocprof.json"
 cp "$(find /tmp/prof_tets -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_spmv_only_tets_kernel_stats.csv"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/prof_fetch -- python3 bench.py --cpu-iters 0 --skip-blas1 --traffic off --skip-permuted --skip-unstructured --skip-unstructured3d --skip-configs --steps 20 --warmup 2 --spinup-seconds 0 --min-seconds 0 --detail-path '' > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/prof_write -- python3 bench.py --cpu-iters 0 --skip-blas1 --traffic off --skip-permuted --skip-unstructured --skip-unstructured3d --skip-configs --steps 20 --warmup 2 --spinup-seconds 0 --min-seconds 0 --detail-path '' > /dev/null 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/prof_fetch -- python3 bench.py --full --cpu-iters 0 --skip-blas1 --traffic off --skip-permuted --skip-unstructured --skip-unstructured3d --skip-configs --steps 20 --warmup 2 --spinup-seconds 0 --min-seconds 0 --detail-path '' > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/prof_write -- python3 bench.py --full --cpu-iters 0 --skip-blas1 --traffic off --skip-permuted --skip-unstructured --skip-unstructured3d --skip-configs --steps 20 --warmup 2 --spinup-seconds 0 --min-seconds 0 --detail-path '' > /dev/null 2>&1
 FMT=$(python3 -c "import json;print(json.load(open('$OUT/${TAG}_bench_detail.json'))['roofline']['record_format'])")
 ALG=$(python3 -c "import json;print(json.load(open('$OUT/${TAG}_bench_detail.json'))['roofline']['algorithmic_bytes_8d'])")
 FBY=$(python3 -c "import json;print(json.load(open('$OUT/${TAG}_bench_detail.json'))['roofline']['bytes_per_launch'])")
