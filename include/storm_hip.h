@@ -466,13 +466,14 @@ typedef struct storm_hip_op_stats {
   int64_t n_slices, max_row_len;
   int64_t n_interior_slices;            /* slices whose rows reference no halo column */
   int64_t device_bytes;
-  int64_t record_bytes;                 /* bytes of slice records one apply streams */
+  int64_t record_bytes;                 /* bytes of the slice records as stored (format 4: 8 per row, kept whether or not the row-record index is used) */
   int64_t value_dictionary_size;        /* > 0: weights stored as byte indices into this many distinct values */
   int64_t offset_dictionary_size;       /* > 0: columns stored as byte indices into this many distinct col - row */
   int64_t paired_rows;                  /* 1: two consecutive rows per lane share their 16-byte gathers; n_slices then counts 128-row groups; 2: the same with one common offset order (format 4); 3: format 5 (one byte per row) */
   int64_t tiled_planes;                 /* > 0: an unsplit apply runs the tiled format-4 kernel (lattice offsets -b,-a,-1,+1,+a,+b): tiles of 1024 rows x this many planes */
   int64_t spmv_blocks;                  /* workgroups of an unsplit apply */
   int64_t xcd_run_blocks;               /* (ABI 6) fp64-record kernel: runs of this many workgroups (256 rows each) go to one XCD */
+  int64_t streamed_record_bytes;        /* (ABI 6) record bytes one apply actually reads: record_bytes, or with the row-record index (format 4 on a lattice, <= 256 distinct row words, option spmv_record_index) one byte per row + the table of words */
 } storm_hip_op_stats;
 int storm_hip_op_get_stats(const storm_hip_op *op, storm_hip_op_stats *stats);
 int storm_hip_op_destroy(storm_hip_op *op);

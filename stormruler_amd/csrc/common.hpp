@@ -173,6 +173,7 @@ struct storm_hip_ctx {
   static constexpr int64_t opt_spmv_canon_groups = 2; // format-4 / 5 kernel: 128-row groups per wavefront (1 or 2)
   static constexpr int64_t opt_spmv_tile_lds_pad = 0;   // A/B knob: extra dynamic LDS per block of the tiled kernel (fewer resident tiles per CU)
   int64_t opt_spmv_canon_tile_min_rows = (int64_t)1 << 20;  // ... for operators of at least this many rows
+  int64_t opt_spmv_record_index = 1;  // format 4 with <= 256 distinct 8-byte row words: the tiled and marching kernels read one byte per row into a table of them (storm_hip_op::d_rec_idx) instead of the word (0: the 8-byte records)
   int64_t opt_spmv_canon_tile = 2;   // format 4 on a lattice (offsets -b,-a,-1,+1,+a,+b): tiles of 1024 rows x this many planes (2, or 4) with the +-a / +-1 neighbours from LDS and the +-b ones from registers; 0 = the plain kernel.  Measured at 256^3 (profiles/r03f, r03g): CG step 242 (2 planes) / 247 (4) us per iteration, BiCGStab 496 / 510
   static constexpr int64_t opt_vec_contiguous = 0;     // vectors in physically contiguous device memory (hipDeviceMallocContiguous)
   int64_t opt_mgs_steps = 4;          // throughput-path Gram-Schmidt: steps per pass over w (2: mgs_pair_kernel; 3, 4: mgs_multi_kernel)
@@ -245,6 +246,7 @@ struct storm_hip_ctx {
   int64_t opt_cg_march_fill = 2048;    // ... fewer planes per block on smaller lattices, so that the grid holds about this many blocks (0: cg_march as given)
   int64_t opt_cg_march_alternate = 1;  // odd z-chunks of the marching step kernel march downwards (spmv.hip MarchArgs::alternate)
   int64_t opt_cg_march = 8;   // ... as blocks of 1024 rows marching through this many planes (0: tiles, spmv_canon_tile planes deep); 256^3, us per CG iteration: tiles 239, 8 planes 230, 16 234, 32 236, 64 237 (profiles/r03k)
+  int64_t opt_cg_residual_march = 1;  // fused CG step, one rank, unsplit lattice operator: r -= alpha z by a kernel that recomputes z = A p' from p' in cg_r_kernel's row order (solvers.hip cg_r_recompute_kernel: the same bits), so z is never stored nor read back (0: cg_r_kernel streams z)
   int64_t opt_cg_fuse = 1;   // fused CG, one rank, tiled format-4 operator: the SpMV kernel ends the previous iteration (x += alpha p, p = r + beta p) itself
   static constexpr int64_t opt_fold_pz = 1;   // CG, one rank, > 8192 SpMV partials: cg_r_kernel folds the first-pass partials of <p,z> itself (one launch fewer)
   static constexpr int64_t opt_fuse_dot = 1;  // 0: reductions after an SpMV run as separate kernels (A/B knob)
@@ -277,6 +279,7 @@ struct storm_hip_ctx {
   const int *api_done = nullptr;
   // diagnostics: which path the solves took (storm_hip_ctx_get_counter)
   int64_t n_resident_solves = 0, n_latency_solves = 0, n_throughput_solves = 0, n_engine_solves = 0, n_cg_fused_steps = 0;
+  int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   // communicator
   storm::Comm *comm = nullptr;
   int n_ranks = 1, rank = 0;
@@ -320,6 +323,9 @@ struct storm_hip_op {
   int offs_size = 0;               // > 0: records are 64 x 16-byte words (values + offsets as byte indices)
   int xcd_group_sell = 0;          // spmv_sell_kernel: runs of this many blocks per XCD (option spmv_xcd_remap at build time)
   int pair = 0;                    // 1: format 3 -- 128-row groups of paired rows, n_slices counts those groups; 2: format 4 (common offset order)
+  uint8_t *d_rec_idx = nullptr;    // format 4 with at most 256 distinct 8-byte row words: each row's index into d_rec_words
+  uint64_t *d_rec_words = nullptr; // ... the distinct words (d_pack keeps the words themselves for the other kernels)
+  int rec_words = 0;               // ... how many (0: no index)
   char *d_bnd_pack = nullptr;      // mixed operator: format-3 records of the boundary groups, in d_boundary order
   int bnd_width = 0;               // ... and their merged width
   int canon_k = 0, canon_m1 = -1;  // format 4: number of common offsets, slot of offset -1 (+1 follows)

@@ -24,6 +24,7 @@
 #include "solver_device.hpp"
 #include "ticket_device.hpp"
 #include "ipc_device.hpp"
+#include "spmv_device.hpp"
 
 namespace storm {
 
@@ -338,6 +339,136 @@ __global__ __launch_bounds__(kBlock) void cg_r_kernel(int64_t n, SolverState *st
       if (use_ipc != 2) do_step(STEP_CG_RR, st, GmresDev{});
     }
   }
+}
+
+// The residual recompute (option cg_residual_march): cg_r_kernel for the fused CG step on one rank, with z = A p'
+// RECOMPUTED instead of read back, so that the step kernel (cg_step_march_kernel) stores no z.  Per row it streams p'
+// (8 B), the record index (1 B) and r (read and written, 16 B): 25 B where z cost 8 B stored + 8 B read back.
+// Everything cg_r_kernel decides is kept: its grid, its rows per thread and their order, its statements -- so r AND
+// <r,r> are the same bits, and the solve is the one the z-storing loop computes.  A wave holds 64 consecutive row pairs
+// per unrolled step, so the +-1 neighbours come from the next lanes (lanes 0 and 63 load their outer one) and the
+// +-a / +-b lines are 16-byte gathers of p' (the tiled kernel's clamping: an absent neighbour has weight 0).  z is
+// lattice_pair_apply of the operands the step kernel had in its registers: p' from memory is what that kernel stored.
+template <bool IDX>
+__global__ __launch_bounds__(kBlock) void cg_r_recompute_kernel(int64_t n, SolverState *st, double *__restrict__ r,
+                                                                const double *__restrict__ p, SellArgs A, CanonTileArgs T,
+                                                                Scal alpha_s, Scal beta_s, const double *__restrict__ pz_partials,
+                                                                int n_pz, int reverse, TicketArgs tickets) {
+  if (st->done) return;
+  __shared__ double lds4[4];
+  __shared__ double dict_sh[32];
+  extern __shared__ __attribute__((aligned(16))) unsigned long long words_sh[];  // (IDX: the word table)
+  const int lane = threadIdx.x & (kWave - 1);
+  if (threadIdx.x < 32) dict_sh[threadIdx.x] = A.dict[threadIdx.x];
+  if (IDX) rec_table_fill(A, words_sh);
+  __syncthreads();
+  const unsigned bx = reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;  // (as cg_r_kernel)
+  double pz;
+  if (pz_partials) {
+    double v = 0.0;
+    for (int i = threadIdx.x; i < n_pz; i += kBlock) v += pz_partials[i];
+    pz = block_sum256(v, lds4);
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_PZ] = pz;
+  } else {
+    pz = st->s[S_PZ];
+  }
+  const double alpha = safe_divide(st->s[S_GAMMA], pz);
+  if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_ALPHA] = alpha;  // for the next step kernel
+  const double op_alpha = ld_scal2(alpha_s), op_beta = ld_scal2(beta_s);
+  const int64_t a = T.a, b = T.b, mg = T.max_gather;
+  const char *pg = reinterpret_cast<const char *>(p) - (size_t)kVecGuard * 8;
+  auto pair_at = [&](int64_t row) {  // p'[row], p'[row + 1], row even; guard-relative and clamped like every gather
+    int64_t gi = row + kVecGuard;
+    gi = gi < 0 ? 0 : (gi > mg ? mg : gi);
+    return *reinterpret_cast<const double2v *>(pg + (size_t)gi * 8);
+  };
+  auto one_at = [&](int64_t row) {
+    int64_t gi = row + kVecGuard;
+    gi = gi < 0 ? 0 : (gi > mg + 1 ? mg + 1 : gi);
+    return *reinterpret_cast<const double *>(pg + (size_t)gi * 8);
+  };
+  double acc = 0.0;
+  const int64_t n2 = n >> 1;
+  double2v *r2 = reinterpret_cast<double2v *>(r);
+  // (the loop runs while the wave's FIRST pair is in range, every lane inside it: the lane moves need the whole wave;
+  //  a lane past the end works on the last pair and neither stores nor sums -- as cg_r_kernel's thread skips it)
+  for (int64_t base = (int64_t)bx * (kBlock * kUnroll) + threadIdx.x; base - lane < n2;
+       base += (int64_t)gridDim.x * (kBlock * kUnroll)) {
+    double2v vr[kUnroll], c[kUnroll], nb[kUnroll][4];
+    double el[kUnroll];
+    RecRaw<IDX> w[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int64_t i = base + u * kBlock;
+      const int64_t row = 2 * (i < n2 ? i : n2 - 1);
+      vr[u] = r2[row >> 1];
+      c[u] = pair_at(row);
+      w[u] = rec_load<IDX>(A, (uint32_t)row);
+      nb[u][0] = pair_at(row - b), nb[u][1] = pair_at(row - a), nb[u][2] = pair_at(row + a), nb[u][3] = pair_at(row + b);
+      el[u] = 0.0;
+      if (lane == 0) el[u] = one_at(row - 1);
+      if (lane == kWave - 1) el[u] = one_at(row + 2);
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int64_t i = base + u * kBlock;
+      double2v xg[6];
+      xg[0] = nb[u][0], xg[1] = nb[u][1], xg[4] = nb[u][2], xg[5] = nb[u][3];
+      const double left = dpp_shift<0x138>(c[u].y);   // wave_shr:1 -- lane i receives lane i - 1
+      const double right = dpp_shift<0x130>(c[u].x);  // wave_shl:1 -- lane i receives lane i + 1
+      xg[2].x = lane == 0 ? el[u] : left;
+      xg[2].y = c[u].x;
+      xg[3].x = c[u].y;
+      xg[3].y = lane == kWave - 1 ? el[u] : right;
+      const double2v vz = lattice_pair_apply(dict_sh, rec_word<IDX>(w[u], words_sh), xg, c[u], op_alpha, op_beta);
+      if (i < n2) {  // cg_r_kernel's statements, verbatim
+        vr[u] -= alpha * vz;
+        r2[i] = vr[u];
+        acc += vr[u].x * vr[u].x;
+        acc += vr[u].y * vr[u].y;
+      }
+    }
+  }
+  // (an odd last row: cg_r_kernel's tail -- never here, the recompute takes operators with an even row count)
+  const double s = block_sum256(acc, lds4);
+  // <r, r> finishes here as in cg_r_kernel: the last block runs the scalar step of SolverCg.hpp:110-125
+  if (threadIdx.x >= kWave) return;
+  const double mine[1] = {s};
+  double total[1];
+  if (ticket_reduce_wave0<1>(tickets, mine, 1, bx, gridDim.x, total)) {
+    if (threadIdx.x == 0) {
+      st->s[S_GAMMA_NEW] = total[0];
+      do_step(STEP_CG_RR, st, GmresDev{});
+    }
+  }
+}
+
+// Whether the residual recompute takes iteration k > 0 of the fused CG loop: one rank, an unsplit operator with an even
+// row count whose fused step is the marching kernel, reductions finished by tickets, no ticket_verify (it reads z).
+static bool cg_r_recompute_applies(const storm_hip_op *op, bool tick) {
+  storm_hip_ctx *c = op->ctx;
+  MarchArgs M;
+  int nb = 0;
+  return c->opt_cg_residual_march != 0 && tick && c->comm == nullptr && c->opt_ticket_verify == 0 && op->n_rows % 2 == 0 &&
+         spmv_can_march(op) && cg_march_geometry(op, &M, &nb);
+}
+static int cg_r_recompute_run(const storm_hip_op *op, int nbv, Scal alpha, Scal beta, const double *p, SolverState *st, double *r,
+                              const double *pz_partials, int n_pz, int reverse) {
+  storm_hip_ctx *c = op->ctx;
+  CanonTileArgs T;
+  int nbt = 0;
+  STORM_REQUIRE(canon_tile_geometry(op, &T, &nbt), "cg: the residual recompute needs a lattice operator");
+  const SellArgs A = lattice_args(op);
+  const size_t lds = sizeof(uint64_t) * (size_t)A.rec_words_n;
+  const TicketArgs tk{c->d_tickets, c->d_partials, c->d_ticket_sums};
+  if (A.rec_idx != nullptr)
+    hipLaunchKernelGGL(cg_r_recompute_kernel<true>, dim3(nbv), dim3(kBlock), lds, c->stream, op->n_rows, st, r, p, A, T, alpha,
+                       beta, pz_partials, n_pz, reverse, tk);
+  else
+    hipLaunchKernelGGL(cg_r_recompute_kernel<false>, dim3(nbv), dim3(kBlock), lds, c->stream, op->n_rows, st, r, p, A, T, alpha,
+                       beta, pz_partials, n_pz, reverse, tk);
+  HIP_TRY(hipGetLastError());
+  return STORM_HIP_OK;
 }
 
 // Five streams (3 loads, 2 stores): measured best with ONE 16-byte access per stream and thread in flight
@@ -1314,6 +1445,10 @@ int solve_cg_body(const FusedSolveArgs &args) {
                      nbv <= kTicketGroup * kTicketMaxGroups;
   double *p_alt = nullptr;
   if (fuse_step) p_alt = pool.v[v0 + role[3]]->d, ++c->n_cg_fused_steps;
+  // (the residual recompute: from iteration 1 on, the step kernel stores no z and r -= alpha z recomputes it; iteration
+  //  0's plain apply writes z for cg_r_kernel)
+  const bool r_march = fuse_step && !rccl && cg_r_recompute_applies(op, tick);
+  if (r_march) ++c->n_cg_residual_marches;
   int64_t last_enqueued = -1;
   auto enqueue_iteration = [&]() -> int {
     const int q = fuse_step ? 0 : sweep ? (int)(cur_it & 1) : 0;  // (fused: the step kernel forward, cg_r backward, always)
@@ -1321,12 +1456,13 @@ int solve_cg_body(const FusedSolveArgs &args) {
     c->spmv_reverse = q;
     int pz_done = 0;  // <p,z> finished inside the SpMV kernel (tickets): cg_r reads it from the slab
     int st_apply;
+    const bool r_march_now = r_march && cur_it > 0;
     if (fuse_step && cur_it > 0) {
       const Driver::CgStep step{(long long)cur_it, x->d, r, p_alt};  // ends iteration cur_it - 1 (SolverCg.hpp:98, :123)
       // (<p,z>: per-wave partials for the final pass below -- finishing it inside the marching kernel by tickets was
       //  measured for this loop and dropped; the host loop's fused step, lazy.hip, does finish it there: one launch less
       //  in front of a host wait)
-      st_apply = d.apply(p, z, p, false, &nb, true, -1, -1, &pz_done, &step);
+      st_apply = d.apply(p, r_march_now ? nullptr : z, p, false, &nb, true, -1, -1, &pz_done, &step);
       std::swap(p, p_alt);
     } else {
       st_apply = d.apply(p, z, p, false, &nb, true, tick_spmv ? (int)S_PZ : -1, -1, &pz_done);
@@ -1362,11 +1498,15 @@ int solve_cg_body(const FusedSolveArgs &args) {
       STORM_TRY(d.finish(nb, 1, slots, STEP_NONE));
     }
     // r -= alpha z; gamma = <r,r>                     SolverCg.hpp:97,99,115
-    hipLaunchKernelGGL(cg_r_kernel, dim3(nbv), dim3(kBlock), 0, c->stream, n, d.st, r, z, c->d_partials,
-                       nt_stream, pz_partials, (int)kStage2, sweep ? 1 - q : 0,
-                       (tick || rtick) ? TicketArgs{c->d_tickets, c->d_partials, c->d_ticket_sums} : TicketArgs{nullptr, nullptr, nullptr},
-                       ipc_w, rtick ? 2 : (int)(ipc && tick));
-    HIP_TRY(hipGetLastError());
+    if (r_march_now) {
+      STORM_TRY(cg_r_recompute_run(op, nbv, host_scal(alpha), host_scal(beta), p, d.st, r, pz_partials, (int)kStage2, sweep ? 1 - q : 0));
+    } else {
+      hipLaunchKernelGGL(cg_r_kernel, dim3(nbv), dim3(kBlock), 0, c->stream, n, d.st, r, z, c->d_partials,
+                         nt_stream, pz_partials, (int)kStage2, sweep ? 1 - q : 0,
+                         (tick || rtick) ? TicketArgs{c->d_tickets, c->d_partials, c->d_ticket_sums} : TicketArgs{nullptr, nullptr, nullptr},
+                         ipc_w, rtick ? 2 : (int)(ipc && tick));
+      HIP_TRY(hipGetLastError());
+    }
     if (rtick) {
       STORM_TRY(comm_allreduce_sum(c, d.slot(S_GAMMA_NEW), 1));
       hipLaunchKernelGGL(step_kernel, dim3(1), dim3(1), 0, c->stream, (int)STEP_CG_RR, d.st, d.g, false);

@@ -202,6 +202,7 @@ int spmv_launch(const storm_hip_op *op, Scal alpha, Scal beta, const double *x, 
       }
       return spmv_march_run(op, M, nb_march, alpha, beta, x, y, dot, done, cgf, IpcSendArgs{});
     }
+    STORM_REQUIRE(y != nullptr, "spmv: only the marching CG step may leave z = A p' unstored");
     STORM_REQUIRE(!cg_fused || (cgf.ca != nullptr && cgf.cb != nullptr && cgf.iteration != nullptr),
                   "spmv: a fused CG step with immediate coefficients needs the marching kernel");
     STORM_TRY(launch_range(op, alpha, beta, x, y, nullptr, op->n_slices, dot, fuse_dot, done, accumulate, nullptr,
@@ -385,6 +386,9 @@ int storm_hip_op_get_stats(const storm_hip_op *op, storm_hip_op_stats *s) {
   s->tiled_planes = canon_tile_geometry(op, &T, &nbt, op->d_bnd_pack != nullptr) ? canon_tile_planes(op) : 0;  // (mixed operator: its interior planes)
   s->spmv_blocks = spmv_grid_blocks(op);
   s->xcd_run_blocks = op->xcd_group_sell;
+  // (the tiled and marching kernels: one byte per row and the word table where the row-record index is on)
+  const bool idx = s->tiled_planes > 0 && op->ctx->opt_spmv_record_index != 0 && op->rec_words > 0;
+  s->streamed_record_bytes = idx ? op->n_slices * 2 * kWave + (int64_t)sizeof(uint64_t) * op->rec_words : op->pack_bytes;
   return STORM_HIP_OK;
 }
 
@@ -396,6 +400,8 @@ int storm_hip_op_destroy(storm_hip_op *op) {
   (void)hipFree(op->d_slice_off);
   (void)hipFree(op->d_pack);
   (void)hipFree(op->d_bnd_pack);
+  (void)hipFree(op->d_rec_idx);
+  (void)hipFree(op->d_rec_words);
   (void)hipFree(op->d_dict);
   (void)hipFree(op->d_offs);
   (void)hipFree(op->d_tail_row);

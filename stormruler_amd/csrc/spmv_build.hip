@@ -296,6 +296,8 @@ static int build_op(storm_hip_ctx *c, int64_t n, int64_t n_halo, const std::vect
   int canon_len = 0, canon_m1 = -1;
   bool cn = pr && c->opt_spmv_dict >= 4 && 2 * n_bnd_groups <= n_groups && (n_bnd_groups == 0 || c->opt_spmv_mixed != 0);
   std::vector<char> bnd_pack;
+  std::vector<uint8_t> rec_idx;     // format 4: the row-record index and its table (empty: more than 256 distinct words)
+  std::vector<uint64_t> rec_words;
   if (cn) {
     // the distinct offsets and who precedes whom in some row; a common order = a linear extension of that relation
     int64_t dist[8];
@@ -395,6 +397,24 @@ static int build_op(storm_hip_ctx *c, int64_t n, int64_t n_halo, const std::vect
     }
     });
     timer.lap("canonical order + records");
+    // The row-record index: a lattice has a few dozen distinct row words (the interior class, walls, edges, corners);
+    // one byte per row naming the word in a table of them is what the tiled and marching kernels read (option
+    // spmv_record_index).  The 8-byte records stay: every other reader of the operator takes them.
+    const int64_t n_words = n_groups * 2 * kWave;
+    auto word_at = [&](int64_t i) {
+      uint64_t w;
+      memcpy(&w, pair_pack.data() + (size_t)i * 8, 8);
+      return w;
+    };
+    ValueDict wd;
+    if (wd.add_all(n_words, word_at)) {
+      rec_idx.resize((size_t)n_words);
+      parallel_chunks(n_words, 1 << 16, [&](int, int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i) rec_idx[(size_t)i] = (uint8_t)wd.lookup(word_at(i));
+      });
+      rec_words = wd.values;
+    }
+    timer.lap("row-record index");
     op->canon_k = canon_len, op->canon_m1 = canon_m1;
     for (int k = 0; k < 7; ++k) op->canon_off[k] = k < canon_len ? (int)canon[k] : 0;
   }
@@ -431,6 +451,11 @@ static int build_op(storm_hip_ctx *c, int64_t n, int64_t n_halo, const std::vect
       storm_hip_op_destroy(op);
       return st3;
     }
+    if (!rec_words.empty() && ((st3 = upload(&op->d_rec_idx, rec_idx, &bytes3)) || (st3 = upload(&op->d_rec_words, rec_words, &bytes3)))) {
+      storm_hip_op_destroy(op);
+      return st3;
+    }
+    op->rec_words = (int)rec_words.size();
     if (!bnd_pack.empty() && ((st3 = upload(&op->d_bnd_pack, bnd_pack, &bytes3)) || (st3 = op_upload_slice_lists(op)))) {
       storm_hip_op_destroy(op);
       return st3;

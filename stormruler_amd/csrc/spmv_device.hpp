@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 #include "ticket_device.hpp"
 #include "ipc_device.hpp"
@@ -15,6 +17,7 @@ __device__ __forceinline__ double ld_scal2(const Scal &s) { return s.p ? (*s.p) 
 
 typedef int int2v __attribute__((ext_vector_type(2)));
 typedef double double2v __attribute__((ext_vector_type(2)));
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kExtBytes = kWave * 8;      // 512
 constexpr int kSlotBytes = kWave * 12;    // 768: one ELL slot of a slice (64 cols + 64 vals)
@@ -31,6 +34,10 @@ struct SellArgs {
   int offs_size;
   int accumulate;                         // y += alpha*M(x) (stormDivGrad's own form) instead of y = beta*x + alpha*M(x)
   int rec_by_pos = 0;                     // paired records stored in slice-LIST order (the boundary groups of a mixed operator)
+  // format 4, option spmv_record_index (the tiled and marching kernels only): row r's record is rec_words[rec_idx[r]]
+  const uint8_t *__restrict__ rec_idx = nullptr;
+  const unsigned long long *__restrict__ rec_words = nullptr;
+  int rec_words_n = 0;
 };
 
 constexpr int kDictSize = 256;
@@ -171,6 +178,65 @@ struct CgFuseArgs {
   double ca_imm, cb_imm;       // marching kernel only: alpha, beta themselves where ca / cb are null (a HOST loop's step: lazy.hip)
 };
 
+// ---- the row-record index (option spmv_record_index) -----------------------------------------------------------------
+// A lattice operator has a few dozen distinct 8-byte row words; with at most 256 of them the tiled and marching kernels
+// load one byte per row (a lane's row pair: one 2-byte load) and find the word in the block's LDS copy of the table,
+// which sits in the dynamic LDS behind the kernel's own.  Everything after the look-up is unchanged: the same word
+// reaches the same arithmetic.  RecRaw is what a lane holds between the load and the look-up.
+template <bool IDX>
+using RecRaw = typename std::conditional<IDX, unsigned, u64x2>::type;
+__device__ __forceinline__ void rec_table_fill(const SellArgs &A, unsigned long long *words_sh) {  // before the first barrier
+  for (int i = threadIdx.x; i < A.rec_words_n; i += kBlock) words_sh[i] = A.rec_words[i];
+}
+template <bool IDX>
+__device__ __forceinline__ RecRaw<IDX> rec_load(const SellArgs &A, uint32_t rc) {  // the records of rows rc, rc + 1 (rc even)
+  if constexpr (IDX) return __builtin_nontemporal_load(reinterpret_cast<const unsigned short *>(A.rec_idx + rc));
+  else return __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>(A.pack + (size_t)(rc << 3)));
+}
+template <bool IDX>
+__device__ __forceinline__ u64x2 rec_word(RecRaw<IDX> v, const unsigned long long *words_sh) {  // after the barrier
+  if constexpr (IDX) return u64x2{words_sh[v & 0xffu], words_sh[v >> 8]};
+  else return v;
+}
+
+// One row pair of a lattice apply, y = beta c + alpha (sum_k w_k (xg_k - c) + ext c) over the slots in the common order
+// (-b, -a, -1, +1, +a, +b): spmv_canon_kernel's operands and rounding (beta c rounded on its own, then the two FMAs its
+// expression contracts to).  The marching step kernel and the residual recompute (solvers.hip)
+// both call it: their z cannot drift apart.
+__device__ __forceinline__ double2v lattice_pair_apply(const double *dict_sh, u64x2 w, const double2v (&xg)[6], double2v c,
+                                                       double alpha, double beta) {
+  double acc_a = 0.0, acc_b = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const unsigned ba = (unsigned)(w.x >> (8 * (k + 1))) & 0xffu, bb = (unsigned)(w.y >> (8 * (k + 1))) & 0xffu;
+    acc_a += *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ba) * (xg[k].x - c.x);
+    acc_b += *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + bb) * (xg[k].y - c.y);
+  }
+  const double ext_a = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ((unsigned)w.x & 0xffu));
+  const double ext_b = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ((unsigned)w.y & 0xffu));
+  double2v yi;
+  yi.x = __builtin_fma(alpha, __builtin_fma(ext_a, c.x, acc_a), beta * c.x);
+  yi.y = __builtin_fma(alpha, __builtin_fma(ext_b, c.y, acc_b), beta * c.y);
+  return yi;
+}
+// The six neighbours of a lane's row pair c in a marching kernel: the planes below / above from registers, the +-a lines
+// and the line ends from the LDS copy `buf` of the plane (the pair sits at buf[at]), the +-1 rows from the next lanes.
+__device__ __forceinline__ void march_neighbours(const double *buf, int at, int a, int lane, double2v below, double2v above,
+                                                 double2v c, double2v (&xg)[6]) {
+  xg[0] = below, xg[5] = above;
+  xg[1] = *reinterpret_cast<const double2v *>(&buf[at - a]);
+  xg[4] = *reinterpret_cast<const double2v *>(&buf[at + a]);
+  double el = 0.0;
+  if (lane == 0) el = buf[at - 1];
+  if (lane == kWave - 1) el = buf[at + 2];
+  const double left = dpp_shift<0x138>(c.y);   // wave_shr:1 -- lane i receives lane i - 1
+  const double right = dpp_shift<0x130>(c.x);  // wave_shl:1 -- lane i receives lane i + 1
+  xg[2].x = lane == 0 ? el : left;
+  xg[2].y = c.x;
+  xg[3].x = c.y;
+  xg[3].y = lane == kWave - 1 ? el : right;
+}
+
 // ---- the fused CG step, marching in z ------------------------------------------------------------------------------
 // spmv_canon_tile_kernel<FUSE> forms p' = r + beta p for its tile's halo rows and outer planes from THEIR r and p: with
 // tiles two planes deep that is one extra row of r and p per row, and with ~128 tiles per XCD in flight those rows no
@@ -179,8 +245,9 @@ struct CgFuseArgs {
 // being applied sits in the lane's registers (each plane's p, r, x, record are loaded exactly once, prefetched one
 // plane ahead), the +-a / +-1 neighbours come from an LDS copy of the current plane (three buffers in rotation, one
 // barrier per plane), and only the two planes bounding the block's chunk are loaded for their p' alone.
-//   reads  p, r, x, records (32 B/row) + the +-a halo lines (r, p; adjacent tiles of the same XCD march in step) + 2 / zc_planes planes
-//   writes x, p', z (24 B/row)
+//   reads  p, r, x, records (32 B/row; 25 with the row-record index) + the +-a halo lines (r, p; adjacent tiles of the same
+//          XCD march in step) + 2 / zc_planes planes
+//   writes x, p', z (24 B/row; 16 where the residual recompute forms z again and the kernel gets z_out = null)
 // Arithmetic per row exactly spmv_canon_kernel's; x += alpha p and p' = r + beta p exactly cg_xp_kernel's.
 struct MarchArgs {
   CanonTileArgs T;   // a, b, tiles_per_plane, per_xcd, max_gather, reverse, plane_end (= number of planes)
@@ -223,6 +290,8 @@ int spmv_tail_run(const storm_hip_op *op, Scal alpha, const double *x, double *y
 // spmv_lattice.hip: the z-marching fused CG step (its own grid: n_blocks marching blocks + the sending blocks of S)
 int spmv_march_run(const storm_hip_op *op, const MarchArgs &M, int n_blocks, Scal alpha, Scal beta, const double *x, double *y,
                    const DotArgs &dot, const int *done, const CgFuseArgs &cgf, const IpcSendArgs &S);  // (cgf.x == null: no x update)
+// spmv_lattice.hip: SellArgs of a tiled / marching launch over all rows (the row-record index where option and operator allow)
+SellArgs lattice_args(const storm_hip_op *op);
 // spmv.hip: diagonal of beta I + alpha M; spmv_build.hip calls nothing of the kernels.
 
 // ---- geometry shared by dispatch and launchers -----------------------------------------------------------------------
@@ -252,6 +321,8 @@ static inline SellArgs paired_args(const RangeLaunch &L, int *width) {
   if (boundary_of_mixed(L)) {  // the groups that read halo columns: format-3 records of their own, in list order
     A.pack = op->d_bnd_pack, A.rec_by_pos = 1;
     *width = op->bnd_width;
+  } else if (op->ctx->opt_spmv_record_index != 0 && op->rec_words > 0) {
+    A.rec_idx = op->d_rec_idx, A.rec_words = reinterpret_cast<const unsigned long long *>(op->d_rec_words), A.rec_words_n = op->rec_words;
   }
   return A;
 }

@@ -6,7 +6,7 @@
 
 namespace storm {
 
-template <bool DOT, bool WLOAD, int TZ, int HL, bool FUSE = false>
+template <bool DOT, bool WLOAD, int TZ, int HL, bool FUSE, bool IDX>
 __global__ __launch_bounds__(kBlock) void spmv_canon_tile_kernel(SellArgs A, CanonTileArgs T, Scal alpha_s, Scal beta_s,
                                                                  const double *__restrict__ x, double *__restrict__ y,
                                                                  DotArgs dot, const int *done, IpcSendArgs S, CgFuseArgs F) {
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(kBlock) void spmv_canon_tile_kernel(SellArgs A, Can
   const char *xb = reinterpret_cast<const char *>(x);
   const char *xg_base = xb - (size_t)kVecGuard * 8;
   char *yb = reinterpret_cast<char *>(y);
-  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+  unsigned long long *words_sh = reinterpret_cast<unsigned long long *>(tile_sh + TZ * ldw);  // (IDX: the word table)
 
   const double dict_word = A.dict[lane & 31];
   // ---- everything this wave reads from memory, issued back to back: own rows first (the LDS copy waits for them only)
@@ -103,13 +103,13 @@ __global__ __launch_bounds__(kBlock) void spmv_canon_tile_kernel(SellArgs A, Can
       halo[i].x = __builtin_fma(cg_b, halo[i].x, rv.x), halo[i].y = __builtin_fma(cg_b, halo[i].y, rv.y);
     }
   }
-  u64x2 vw[TZ][2];
+  RecRaw<IDX> vw[TZ][2];
   double2v wi[WLOAD ? TZ : 1][2];
 #pragma unroll
   for (int t = 0; t < TZ; ++t)
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      vw[t][g] = __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>(A.pack + (size_t)(rc[t][g] << 3)));
+      vw[t][g] = rec_load<IDX>(A, rc[t][g]);
       if (WLOAD) wi[t][g] = *reinterpret_cast<const double2v *>(reinterpret_cast<const char *>(dot.w) + (size_t)(rc[t][g] << 3));
     }
   double2v xlo[2], xhi[2];  // the planes below the first and above the last one of the tile
@@ -129,6 +129,7 @@ __global__ __launch_bounds__(kBlock) void spmv_canon_tile_kernel(SellArgs A, Can
   }
   // ---- the LDS copy of the tile's x (own rows + halo rows), one barrier
   if (lane < 32) dict_sh[lane] = dict_word;  // every wave stores the same words
+  if (IDX) rec_table_fill(A, words_sh);
 #pragma unroll
   for (int t = 0; t < TZ; ++t)
 #pragma unroll
@@ -158,15 +159,16 @@ __global__ __launch_bounds__(kBlock) void spmv_canon_tile_kernel(SellArgs A, Can
       xg[2].y = xi[t][g].x;
       xg[3].x = xi[t][g].y;
       xg[3].y = lane == kWave - 1 ? el : right;
+      const u64x2 w = rec_word<IDX>(vw[t][g], words_sh);
       double acc_a = 0.0, acc_b = 0.0;
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
-        const unsigned ba = (unsigned)(vw[t][g].x >> (8 * (k + 1))) & 0xffu, bb = (unsigned)(vw[t][g].y >> (8 * (k + 1))) & 0xffu;
+        const unsigned ba = (unsigned)(w.x >> (8 * (k + 1))) & 0xffu, bb = (unsigned)(w.y >> (8 * (k + 1))) & 0xffu;
         acc_a += *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ba) * (xg[k].x - xi[t][g].x);
         acc_b += *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + bb) * (xg[k].y - xi[t][g].y);
       }
-      const double ext_a = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ((unsigned)vw[t][g].x & 0xffu));
-      const double ext_b = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ((unsigned)vw[t][g].y & 0xffu));
+      const double ext_a = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ((unsigned)w.x & 0xffu));
+      const double ext_b = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ((unsigned)w.y & 0xffu));
       // (spelled out: beta x rounded on its own, then the two FMAs the plain kernel's expression contracts to --
       //  `(accumulate ? y : beta x) + alpha (acc + ext x)` -- so that both kernels round alike)
       double2v yi;
@@ -215,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void spmv_canon_tile_kernel(SellArgs A, Can
   }
 }
 
-template <int HLP>  // HLP: halo pairs per thread and plane: ceil(a / 256)
+template <int HLP, bool IDX>  // HLP: halo pairs per thread and plane: ceil(a / 256); IDX: the row-record index
 __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, MarchArgs M, Scal alpha_s, Scal beta_s,
                                                                const double *__restrict__ p_in, double *__restrict__ z_out,
                                                                DotArgs dot, const int *done, CgFuseArgs F, IpcSendArgs S) {
@@ -252,14 +254,15 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
   const uint32_t last_row = (uint32_t)(A.n_rows - 1);
   const char *pb = reinterpret_cast<const char *>(p_in), *rb = reinterpret_cast<const char *>(F.r);
   const char *pg_base = pb - (size_t)kVecGuard * 8, *rg_base = rb - (size_t)kVecGuard * 8;
-  typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+  unsigned long long *words_sh = reinterpret_cast<unsigned long long *>(tile_sh + 3 * ldw);  // (IDX: the word table)
   const double dict_word = A.dict[lane & 31];
   if (lane < 32) dict_sh[lane] = dict_word;  // every wave stores the same words; the first barrier below covers them
+  if (IDX) rec_table_fill(A, words_sh);
 
   // what is in flight for ONE plane: the own rows' p, r, x and record, and this thread's share of the halo lines
   struct Flight {
     double2v p[2], r[2], x[2], hp[HLP], hr[HLP];
-    u64x2 w[2];
+    RecRaw<IDX> w[2];
     uint32_t rc[2];
     bool va[2], vb[2];
     int hat[HLP];
@@ -279,7 +282,7 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
       f.r[g] = *reinterpret_cast<const double2v *>(rg_base + (size_t)((uint32_t)gi << 3));
       if (own) {
         f.x[g] = __builtin_nontemporal_load(reinterpret_cast<const double2v *>(reinterpret_cast<const char *>(F.x) + (size_t)(f.rc[g] << 3)));
-        f.w[g] = __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>(A.pack + (size_t)(f.rc[g] << 3)));
+        f.w[g] = rec_load<IDX>(A, f.rc[g]);
       }
     }
 #pragma unroll
@@ -349,7 +352,7 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
   }
 
   double2v pm[2], pc[2], pn[2];  // p' of the plane behind / at / ahead IN MARCHING ORDER
-  u64x2 wc[2];
+  RecRaw<IDX> wc[2];
   uint32_t rcc[2];
   bool vac[2], vbc[2];
   Flight fl;
@@ -368,7 +371,7 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
   for (int s = 0; s < nz; ++s) {
     const int zp = plane(s);
     const bool next_own = s + 1 < nz;
-    u64x2 wn[2];
+    RecRaw<IDX> wn[2];
     uint32_t rcn[2];
     bool van[2], vbn[2];
     consume(next_own, fl, pn, lds_of(plane(s + 1)));
@@ -383,33 +386,13 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
       if (!applies) break;
       const int at = a + 256 * wave + 128 * g + 2 * lane;
       double2v xg[6];
-      xg[0] = down ? pn[g] : pm[g], xg[5] = down ? pm[g] : pn[g];  // the planes below / above, whichever way the block marches
-      xg[1] = *reinterpret_cast<const double2v *>(&buf[at - a]);
-      xg[4] = *reinterpret_cast<const double2v *>(&buf[at + a]);
-      double el = 0.0;
-      if (lane == 0) el = buf[at - 1];
-      if (lane == kWave - 1) el = buf[at + 2];
-      const double left = dpp_shift<0x138>(pc[g].y);
-      const double right = dpp_shift<0x130>(pc[g].x);
-      xg[2].x = lane == 0 ? el : left;
-      xg[2].y = pc[g].x;
-      xg[3].x = pc[g].y;
-      xg[3].y = lane == kWave - 1 ? el : right;
-      double acc_a = 0.0, acc_b = 0.0;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const unsigned ba = (unsigned)(wc[g].x >> (8 * (k + 1))) & 0xffu, bb = (unsigned)(wc[g].y >> (8 * (k + 1))) & 0xffu;
-        acc_a += *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ba) * (xg[k].x - pc[g].x);
-        acc_b += *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + bb) * (xg[k].y - pc[g].y);
+      march_neighbours(buf, at, a, lane, down ? pn[g] : pm[g], down ? pm[g] : pn[g], pc[g], xg);  // (below / above, whichever way the block marches)
+      double2v yi = lattice_pair_apply(dict_sh, rec_word<IDX>(wc[g], words_sh), xg, pc[g], alpha, beta);
+      if (z_out != nullptr) {  // (null: the residual recompute forms z again, solvers.hip cg_r_recompute_kernel)
+        double2v *yp = reinterpret_cast<double2v *>(reinterpret_cast<char *>(z_out) + (size_t)(rcc[g] << 3));
+        if (vbc[g]) *yp = yi;
+        else if (vac[g]) z_out[rcc[g]] = yi.x;
       }
-      const double ext_a = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ((unsigned)wc[g].x & 0xffu));
-      const double ext_b = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(dict_sh) + ((unsigned)wc[g].y & 0xffu));
-      double2v yi;
-      yi.x = __builtin_fma(alpha, __builtin_fma(ext_a, pc[g].x, acc_a), beta * pc[g].x);
-      yi.y = __builtin_fma(alpha, __builtin_fma(ext_b, pc[g].y, acc_b), beta * pc[g].y);
-      double2v *yp = reinterpret_cast<double2v *>(reinterpret_cast<char *>(z_out) + (size_t)(rcc[g] << 3));
-      if (vbc[g]) *yp = yi;
-      else if (vac[g]) z_out[rcc[g]] = yi.x;
       yi.x = vac[g] ? yi.x : 0.0;
       yi.y = vbc[g] ? yi.y : 0.0;
       dot_a += pc[g].x * yi.x + pc[g].y * yi.y;
@@ -525,19 +508,24 @@ static bool launch_tile(const RangeLaunch &L, SellArgs A) {
     return false;
   const int tz = canon_tile_planes(op);
   const int hl_need = (tz * T.a + kBlock - 1) / kBlock;
-  const size_t lds = sizeof(double) * (size_t)tz * (size_t)(kTileRun + 2 * T.a) + (size_t)op->ctx->opt_spmv_tile_lds_pad;
+  // (the row-record index: its word table behind the tile's x in the dynamic LDS)
+  const size_t lds = sizeof(double) * (size_t)tz * (size_t)(kTileRun + 2 * T.a) + sizeof(uint64_t) * (size_t)A.rec_words_n +
+                     (size_t)op->ctx->opt_spmv_tile_lds_pad;
   const bool wload = DOT && dot.w != nullptr && dot.w != x;
-#define TILE_GO3(WL_, TZ_, HL_)                                                                                              \
-  hipExtLaunchKernelGGL((spmv_canon_tile_kernel<DOT, WL_, TZ_, HL_>), dim3(nb), dim3(kBlock), lds, st, ev0, ev1, 0, A, T, alpha, \
-                        beta, x, y, dot, done, S, CgFuseArgs{})
-#define TILE_GO2(TZ_, HL_)                                                                                                   \
-  do {                                                                                                                       \
-    if (cg_fuse != nullptr) {                                                                                                \
-      if constexpr (DOT)                                                                                                     \
-        hipExtLaunchKernelGGL((spmv_canon_tile_kernel<true, false, TZ_, HL_, true>), dim3(nb), dim3(kBlock), lds, st, ev0, ev1, \
-                              0, A, T, alpha, beta, x, y, dot, done, S, *cg_fuse);                                            \
-    } else if (wload) TILE_GO3(true, TZ_, HL_);                                                                              \
-    else TILE_GO3(false, TZ_, HL_);                                                                                          \
+#define TILE_GO4(WL_, TZ_, HL_, FU_, IX_, CGF_)                                                                             \
+  hipExtLaunchKernelGGL((spmv_canon_tile_kernel<DOT, WL_, TZ_, HL_, FU_, IX_>), dim3(nb), dim3(kBlock), lds, st, ev0, ev1, 0, A, \
+                        T, alpha, beta, x, y, dot, done, S, CGF_)
+#define TILE_GO3(WL_, TZ_, HL_, FU_, CGF_)                                 \
+  do {                                                                     \
+    if (A.rec_idx != nullptr) TILE_GO4(WL_, TZ_, HL_, FU_, true, CGF_);   \
+    else TILE_GO4(WL_, TZ_, HL_, FU_, false, CGF_);                        \
+  } while (0)
+#define TILE_GO2(TZ_, HL_)                                               \
+  do {                                                                   \
+    if (cg_fuse != nullptr) {                                            \
+      if constexpr (DOT) TILE_GO3(false, TZ_, HL_, true, *cg_fuse);      \
+    } else if (wload) TILE_GO3(true, TZ_, HL_, false, CgFuseArgs{});     \
+    else TILE_GO3(false, TZ_, HL_, false, CgFuseArgs{});                 \
   } while (0)
 #define TILE_GO(TZ_)                       \
   do {                                     \
@@ -551,7 +539,15 @@ static bool launch_tile(const RangeLaunch &L, SellArgs A) {
 #undef TILE_GO
 #undef TILE_GO2
 #undef TILE_GO3
+#undef TILE_GO4
   return true;
+}
+
+SellArgs lattice_args(const storm_hip_op *op) {
+  SellArgs A{op->d_pack, op->d_slice_off, op->n_rows, op->uniform_width, 0, op->d_dict, op->dict_size, op->d_offs, op->offs_size, 0};
+  if (op->ctx->opt_spmv_record_index != 0 && op->rec_words > 0)
+    A.rec_idx = op->d_rec_idx, A.rec_words = reinterpret_cast<const unsigned long long *>(op->d_rec_words), A.rec_words_n = op->rec_words;
+  return A;
 }
 
 bool spmv_tile_run(const RangeLaunch &L) {
@@ -574,15 +570,21 @@ int spmv_march_run(const storm_hip_op *op, const MarchArgs &M, int n_blocks, Sca
     ev0 = c->prof_events[c->prof_used], ev1 = c->prof_events[c->prof_used + 1];
     c->prof_used += 2;
   }
-  SellArgs A{op->d_pack, op->d_slice_off, op->n_rows, op->uniform_width, 0, op->d_dict, op->dict_size, op->d_offs, op->offs_size, 0};
-  const size_t lds = sizeof(double) * 3 * (size_t)(kTileRun + 2 * M.T.a);
+  // (a partitioned operator's march applies to its interior planes only, whose rows the index covers too)
+  const SellArgs A = lattice_args(op);
+  const size_t lds = sizeof(double) * 3 * (size_t)(kTileRun + 2 * M.T.a) + sizeof(uint64_t) * (size_t)A.rec_words_n;
   const int nb = n_blocks + S.sp.n_blocks;
-#define MARCH_GO(HLP_)                                                                                                \
-  hipExtLaunchKernelGGL((cg_step_march_kernel<HLP_>), dim3(nb), dim3(kBlock), lds, c->stream, ev0, ev1, 0, A, M, alpha, \
+#define MARCH_GO(HLP_, IX_)                                                                                                 \
+  hipExtLaunchKernelGGL((cg_step_march_kernel<HLP_, IX_>), dim3(nb), dim3(kBlock), lds, c->stream, ev0, ev1, 0, A, M, alpha, \
                         beta, x, y, dot, done, cgf, S)
   STORM_REQUIRE(cgf.x != nullptr, "spmv: the marching step updates x");
-  if (M.T.a <= kBlock) MARCH_GO(1);
-  else MARCH_GO(2);
+  if (M.T.a <= kBlock) {
+    if (A.rec_idx != nullptr) MARCH_GO(1, true);
+    else MARCH_GO(1, false);
+  } else {
+    if (A.rec_idx != nullptr) MARCH_GO(2, true);
+    else MARCH_GO(2, false);
+  }
 #undef MARCH_GO
   HIP_TRY(hipGetLastError());
   return STORM_HIP_OK;
