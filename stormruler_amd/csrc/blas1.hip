@@ -11,6 +11,7 @@
 
 #include "common.hpp"
 #include "blas1_device.hpp"
+#include "solver_device.hpp"
 #include "ticket_device.hpp"
 
 namespace storm {
@@ -354,16 +355,6 @@ __global__ __launch_bounds__(kBlock) void lin3_kernel(int64_t n, double *y, cons
 
 // ---- reductions -------------------------------------------------------------------------
 
-// Sum over the 256 threads of a block, fixed order; result valid in thread 0.
-__device__ __forceinline__ double block_sum(double v, double *lds4) {
-  v = wave_sum_down(v);  // (the __shfl_down tree's order and bits, without the LDS crossbar: wave_device.hpp)
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  __syncthreads();  // lds4 may still be read by a previous call
-  if (lane == 0) lds4[wave] = v;
-  __syncthreads();
-  return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-}
-
 template <int KB>
 __global__ __launch_bounds__(kBlock) void multi_dot_kernel(int64_t n, const double *__restrict__ a,
                                                            DotPtrs bs, double *__restrict__ partials,
@@ -420,39 +411,37 @@ __global__ __launch_bounds__(kBlock) void reduce_final_kernel(const double *__re
                                                               const int *done) {
   if (done && *done) return;
   __shared__ double lds4[4];
-  const double *p = partials + (int64_t)blockIdx.x * nblocks;
-  double v = 0.0;
-#pragma unroll 8
-  for (int i = threadIdx.x; i < nblocks; i += kBlock) v += p[i];
-  const double s = block_sum(v, lds4);
+  const double s = block_fold(partials + (int64_t)blockIdx.x * nblocks, nblocks, lds4);
   if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 // First pass when a kernel left many partials: kStage2 blocks per array fold it to kStage2 values.
-__global__ __launch_bounds__(kBlock) void reduce_stage1_plain_kernel(const double *__restrict__ partials,
-                                                                     int nblocks, double *__restrict__ out,
-                                                                     const int *done) {
+// (done == null: runs regardless)
+__global__ __launch_bounds__(kBlock) void reduce_stage1_kernel(const double *__restrict__ partials,
+                                                               int nblocks, double *__restrict__ out,
+                                                               const int *done) {
   if (done && *done) return;
   __shared__ double lds4[4];
   const int j = blockIdx.y, g = blockIdx.x;
   const int chunk = (nblocks + gridDim.x - 1) / gridDim.x;
   const int i0 = g * chunk, i1 = min(i0 + chunk, nblocks);
-  const double *p = partials + (int64_t)j * nblocks;
-  double v = 0.0;
-  for (int i = i0 + threadIdx.x; i < i1; i += kBlock) v += p[i];
-  const double s = block_sum(v, lds4);
+  const double s = block_fold(partials + (int64_t)j * nblocks, i0, i1, lds4);
   if (threadIdx.x == 0) out[j * gridDim.x + g] = s;
+}
+
+int k_reduce_stage1(storm_hip_ctx *c, const double **partials, int *nblocks, int k, const int *done) {
+  if (*nblocks <= kSinglePassPartials) return STORM_HIP_OK;
+  hipLaunchKernelGGL(reduce_stage1_kernel, dim3(kStage2, k), dim3(kBlock), 0, c->stream, *partials, *nblocks,
+                     c->d_partials2, done);
+  HIP_TRY(hipGetLastError());
+  *partials = c->d_partials2;
+  *nblocks = kStage2;
+  return STORM_HIP_OK;
 }
 
 int k_reduce_final(storm_hip_ctx *c, const double *partials, int nblocks, int k, double *d_out,
                    const int *done) {
-  if (nblocks > kSinglePassPartials) {
-    hipLaunchKernelGGL(reduce_stage1_plain_kernel, dim3(kStage2, k), dim3(kBlock), 0, c->stream, partials,
-                       nblocks, c->d_partials2, done);
-    HIP_TRY(hipGetLastError());
-    partials = c->d_partials2;
-    nblocks = kStage2;
-  }
+  STORM_TRY(k_reduce_stage1(c, &partials, &nblocks, k, done));
   hipLaunchKernelGGL(reduce_final_kernel, dim3(k), dim3(kBlock), 0, c->stream, partials, nblocks,
                      d_out, done);
   HIP_TRY(hipGetLastError());
@@ -829,7 +818,7 @@ int storm_hip_multi_dot_begin(const storm_hip_vec *a, const storm_hip_vec *const
   slot.k = k;
   slot.ready = false;
   // one rank, one launch: the kernel's last block leaves the sums in pinned host memory; _end polls them
-  const bool direct = a->n_owned > 0 && c->comm == nullptr && c->opt_host_result != 0 && c->opt_ticket_reduce != 0 &&
+  const bool direct = a->n_owned > 0 && c->comm == nullptr && c->opt_ticket_reduce != 0 &&
                       k <= kDotChunk && c->api_done == nullptr;
   if (direct) {
     STORM_TRY(k_multi_dot_host(c, a->d, ptrs, k, a->n_owned, c->d_scalars, nullptr, c->d_result_words + 16 * s, tag));

@@ -32,8 +32,8 @@ __device__ __forceinline__ void nt_dispatch(int nt, Body &&body) {  // bit 0 of 
   else body(std::false_type{});
 }
 
-// KB sums at once, ONE pair of barriers: the same wave trees and the same (w0 + w1) + (w2 + w3) as block_sum, so the same
-// bits; sums[j] valid in every thread.
+// KB sums at once, ONE pair of barriers: the same wave trees and the same (w0 + w1) + (w2 + w3) as block_sum256, so the
+// same bits; sums[j] valid in every thread.
 template <int KB>
 __device__ __forceinline__ void block_sum_multi(const double (&v)[KB], double (*lds)[4], double (&sums)[KB]) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;

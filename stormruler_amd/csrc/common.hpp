@@ -142,7 +142,6 @@ struct storm_hip_ctx {
     bool ready = false;   // value[] holds the sums already (the ordinary road computed them in _begin)
     double value[storm::kMaxMulti] = {};
   } result_ring[storm::kResultRing];
-  static constexpr int64_t opt_host_result = 1;        // 0: device scalars + hipMemcpyAsync + hipStreamSynchronize
   storm::SolverState *d_state = nullptr;
   storm::SolverState *h_state = nullptr;  // pinned staging copy of the state
   unsigned long long *h_done_ring = nullptr;  // pinned, written by the device's step kernels (solver_device.hpp advance())
@@ -204,7 +203,6 @@ struct storm_hip_ctx {
   int64_t opt_blas1_nt = 1;  // non-temporal loads/stores in the streaming kernels: 0 never, 1 for vectors of at least blas1_nt_rows rows, 2 always
   static constexpr int64_t opt_blas1_nt_rows = (int64_t)6 << 20;  // (48 MiB per vector: beyond, a solver's vectors no longer stay in the 256 MiB Infinity Cache between kernels)
   static constexpr int64_t opt_graph = 0;     // replay CG / BiCGStab iterations from a captured hipGraph: measured slower than eager launches (profiles/r01_notes.md), off
-  static constexpr int64_t opt_fuse_mgs = 1;  // GMRES/MGS on one rank, <= 2048 blocks: each step folds the previous step's partials itself (no final-reduction launch in between)
   static constexpr int64_t opt_coop_mgs_min_rows = 0;  // ... from this many rows on (0: always; with two steps per synchronisation point the chain is no slower than a launch per step even on small meshes)
   int64_t opt_coop_mgs = 1;             // GMRES: the Gram-Schmidt chain of an Arnoldi step as one cooperative kernel (latency.hip)
   int64_t opt_latency_publish = 1;      // ... its rows published with awaited atomic exchanges (0: write-through stores, ordered by their acknowledgement)
@@ -248,8 +246,6 @@ struct storm_hip_ctx {
   int64_t opt_cg_march = 8;   // ... as blocks of 1024 rows marching through this many planes (0: tiles, spmv_canon_tile planes deep); 256^3, us per CG iteration: tiles 239, 8 planes 230, 16 234, 32 236, 64 237 (profiles/r03k)
   int64_t opt_cg_residual_march = 1;  // fused CG step, one rank, unsplit lattice operator: r -= alpha z by a kernel that recomputes z = A p' from p' in cg_r_kernel's row order (solvers.hip cg_r_recompute_kernel: the same bits), so z is never stored nor read back (0: cg_r_kernel streams z)
   int64_t opt_cg_fuse = 1;   // fused CG, one rank, tiled format-4 operator: the SpMV kernel ends the previous iteration (x += alpha p, p = r + beta p) itself
-  static constexpr int64_t opt_fold_pz = 1;   // CG, one rank, > 8192 SpMV partials: cg_r_kernel folds the first-pass partials of <p,z> itself (one launch fewer)
-  static constexpr int64_t opt_fuse_dot = 1;  // 0: reductions after an SpMV run as separate kernels (A/B knob)
   // Vector storage released by vec_destroy, kept for the next vec_create of the same size: a solve
   // allocates its work vectors on entry and frees them on return (the reference re-assigns them in
   // every init, SolverCg.hpp:57-59); hipMalloc + hipFree of three 134 MB vectors cost ~7 ms per solve.
@@ -408,6 +404,9 @@ int k_dot_partials(storm_hip_ctx *c, const double *a, const double *b, int64_t n
                    const int *done);
 int k_reduce_final(storm_hip_ctx *c, const double *partials, int nblocks, int k, double *d_out,
                    const int *done);
+// More than kSinglePassPartials partials per sum: the first pass folds each of the k arrays to kStage2 values in
+// c->d_partials2 and points *partials / *nblocks there (fewer: nothing to do).
+int k_reduce_stage1(storm_hip_ctx *c, const double **partials, int *nblocks, int k, const int *done);
 
 // context.hip: a work vector with only its guard, halo tail and padding zeroed (the solver writes the owned rows first)
 int vec_create_work(const storm_hip_vec *like, storm_hip_vec **out);

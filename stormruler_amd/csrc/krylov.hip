@@ -133,47 +133,18 @@ __device__ inline void exec_prog(const SProg &p, double *S, SolverState *st) {
   }
 }
 
-// Final pass of k simultaneous reductions (out.idx[j] = register of sum j) + the scalar program behind them.  On the
-// peer-window transport (use_ipc) the block also exchanges its sums with the other ranks in between: one launch.
-__global__ __launch_bounds__(kBlock) void reduce_prog_kernel(const double *__restrict__ partials, int nblocks, int k,
-                                                             RedOut out, double *S, SolverState *st, SProg prog,
-                                                             const int *done, IpcDev w, int use_ipc) {
-  // (`done` is the same decision on every rank, and the transport's all-reduce epoch is advanced by the device, by the
-  //  all-reduces that run: skipping here keeps the ranks in step)
-  if (done && *done) return;
-  __shared__ double lds4[4];
-  __shared__ double vals[kMaxMulti];
-  for (int j = 0; j < k; ++j) {
-    const double *p = partials + (int64_t)j * nblocks;
-    double v = 0.0;
-#pragma unroll 8
-    for (int i = threadIdx.x; i < nblocks; i += kBlock) v += p[i];
-    const double sum = block_sum256(v, lds4);
-    if (threadIdx.x == 0) vals[j] = sum;
+// The epilogue of reduce_finish_kernel (solver_device.hpp) for the engine: the scalar program behind the sums.
+struct ProgEpi {
+  SProg prog;
+  double *S;
+  SolverState *st;
+  __device__ void operator()() const {
+    if (prog.n > 0) {
+      __threadfence();
+      exec_prog(prog, S, st);
+    }
   }
-  if (use_ipc) ipc_allreduce_block(w, vals, k);
-  else __syncthreads();
-  if ((int)threadIdx.x < k) S[out.idx[threadIdx.x]] = vals[threadIdx.x];
-  __syncthreads();
-  if (threadIdx.x == 0 && prog.n > 0) {
-    __threadfence();
-    exec_prog(prog, S, st);
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void reduce_stage1_kernel2(const double *__restrict__ partials, int nblocks,
-                                                                double *__restrict__ out, const int *done) {
-  if (done && *done) return;
-  __shared__ double lds4[4];
-  const int j = blockIdx.y, g = blockIdx.x;
-  const int chunk = (nblocks + gridDim.x - 1) / gridDim.x;
-  const int i0 = g * chunk, i1 = min(i0 + chunk, nblocks);
-  const double *p = partials + (int64_t)j * nblocks;
-  double v = 0.0;
-  for (int i = i0 + threadIdx.x; i < i1; i += kBlock) v += p[i];
-  const double sum = block_sum256(v, lds4);
-  if (threadIdx.x == 0) out[j * gridDim.x + g] = sum;
-}
+};
 
 // A scalar program alone; with nscatter > 0 first S[out.idx[j]] = S[scr + j] (results of an all-reduce).
 __global__ void sprog_kernel(double *S, SolverState *st, SProg prog, int nscatter, RedOut out, int scr,
@@ -801,28 +772,14 @@ struct KrylovEngine {
       }
       pend = PEND_NONE, red_pending = false;
     } else if (red_pending) {
-      const double *partials = c->d_partials;
-      int nb = red_nb;
-      if (nb > kSinglePassPartials) {
-        hipLaunchKernelGGL(reduce_stage1_kernel2, dim3(kStage2, red_k), dim3(kBlock), 0, c->stream, partials, nb,
-                           c->d_partials2, dp);
-        partials = c->d_partials2, nb = kStage2;
-      }
-      IpcDev w{};
-      const bool ipc = c->comm != nullptr && comm_ipc_next(c, &w);
-      if (c->comm == nullptr || ipc) {
-        hipLaunchKernelGGL(reduce_prog_kernel, dim3(1), dim3(kBlock), 0, c->stream, partials, nb, red_k, red_out, S,
-                           d_st, prog, dp, w, (int)ipc);
-      } else {
-        RedOut scr{};
-        for (int j = 0; j < red_k; ++j) scr.idx[j] = R_SCR + j;
-        SProg none{};
-        hipLaunchKernelGGL(reduce_prog_kernel, dim3(1), dim3(kBlock), 0, c->stream, partials, nb, red_k, scr, S, d_st,
-                           none, dp, w, 0);
-        const int st = comm_allreduce_sum(c, S + R_SCR, red_k);
-        if (st != STORM_HIP_OK) fail(st);
+      OutPtrs<kMaxMulti> out{}, scr{};  // (RCCL: the rank's sums go to the all-reduce slots; sprog_kernel moves them to their registers)
+      for (int j = 0; j < red_k; ++j) out.p[j] = S + red_out.idx[j], scr.p[j] = S + R_SCR + j;
+      const int st = k_reduce_finish(c, c->d_partials, red_nb, red_k, out, dp, ProgEpi{prog, S, d_st}, scr, [&]() -> int {
+        STORM_TRY(comm_allreduce_sum(c, S + R_SCR, red_k));
         hipLaunchKernelGGL(sprog_kernel, dim3(1), dim3(1), 0, c->stream, S, d_st, prog, red_k, red_out, (int)R_SCR, dp);
-      }
+        return STORM_HIP_OK;
+      });
+      if (st != STORM_HIP_OK) fail(st);
       red_pending = false;
     } else if (prog.n > 0) {
       hipLaunchKernelGGL(sprog_kernel, dim3(1), dim3(1), 0, c->stream, S, d_st, prog, 0, RedOut{}, 0, dp);
@@ -1037,7 +994,7 @@ struct KrylovEngine {
   // y = A(x)  AND  reg_wy = <w, y>, reg_yy = <y, y> (register < 0: not wanted): the stencil SpMV's fused epilogue
   // when the operator is native and has no CSR tail, separate reductions otherwise.
   void apply_dots(V yv, const storm_hip_vec *xv, int reg_wy, const storm_hip_vec *wv, int reg_yy = -1) {
-    const bool fusable = op_fn == nullptr && op != nullptr && op->tail_rows == 0 && c->opt_fuse_dot != 0 && n > 0 &&
+    const bool fusable = op_fn == nullptr && op != nullptr && op->tail_rows == 0 && n > 0 &&
                          reg_wy >= 0;
     if (!fusable) {
       apply(yv, xv);

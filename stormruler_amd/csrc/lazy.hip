@@ -251,7 +251,7 @@ int fetch_sum(storm_hip_ctx *c, const double *d_value, double *result) {
 // marching kernel takes: the library's fused CG step.  p' goes to the spare vector, whose storage p's handle takes over.
 // false: not that shape (nothing launched, q untouched).
 bool try_cg_step(storm_hip_ctx *c, std::vector<LazyStmt> &q, const double *a, const double *b, double *result, int *status) {
-  if (q.size() < 3 || c->opt_fuse_dot == 0 || c->opt_cg_fuse == 0 || c->opt_lazy < 2) return false;  // (lazy_statements = 2)
+  if (q.size() < 3 || c->opt_cg_fuse == 0 || c->opt_lazy < 2) return false;  // (lazy_statements = 2)
   const LazyStmt &ap = q[q.size() - 1], &sp = q[q.size() - 2], &sx = q[q.size() - 3];
   if (ap.kind != 1 || sp.kind != 0 || sx.kind != 0) return false;
   const int64_t n = ap.n;
@@ -333,7 +333,7 @@ int lazy_push_apply(const storm_hip_op *op, double alpha, double beta, const dou
 bool lazy_try_dot(storm_hip_ctx *c, const double *a, const double *b, int64_t n, double *result, int *status) {
   *status = STORM_HIP_OK;
   if (c->lazy_q.empty()) return false;
-  const bool direct = c->comm == nullptr && c->opt_host_result != 0 && c->opt_ticket_reduce != 0 && c->api_done == nullptr &&
+  const bool direct = c->comm == nullptr && c->opt_ticket_reduce != 0 && c->api_done == nullptr &&
                       c->result_ring[kLazySlot].tag == 0;
   const LazyStmt last = c->lazy_q.back();
   if (!direct || last.n != n || (a != last.y && b != last.y)) {
@@ -365,7 +365,7 @@ bool lazy_try_dot(storm_hip_ctx *c, const double *a, const double *b, int64_t n,
   if (*status != STORM_HIP_OK) return true;
   const double *w = (a == last.y) ? b : a;
   const bool yy = (w == last.y);
-  if (last.op->tail_rows != 0 || c->opt_fuse_dot == 0) {  // (no fused epilogue for operators with a CSR tail)
+  if (last.op->tail_rows != 0) {  // (no fused epilogue for operators with a CSR tail)
     *status = launch_apply(c, last);
     return false;
   }

@@ -1,9 +1,11 @@
 // Device-side pieces shared by the solver translation units (solvers.hip: the fused CG / BiCGStab / GMRES
 // loops of a stencil operator; krylov.hip: the general Krylov engine): the reference's scalar helpers and the
-// body of IterativeSolver::solve's loop, evaluated on the device against a SolverState.
+// body of IterativeSolver::solve's loop, evaluated on the device against a SolverState -- and the fold and final
+// pass every reduction of the library ends with (blas1.hip's too).
 #pragma once
 
 #include "common.hpp"
+#include "ipc_device.hpp"
 #include "wave_device.hpp"
 
 namespace storm {
@@ -82,6 +84,63 @@ __device__ __forceinline__ double block_sum256(double v, double *lds4) {
   if (lane == 0) lds4[wave] = v;
   __syncthreads();
   return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+
+// The block's sum of p[i0 .. i1): lane t adds p[i0 + t], p[i0 + t + 256], ... in ascending order into ONE accumulator,
+// then block_sum256.  Every final pass and every in-kernel fold of partials sums through here: the variants of a solver
+// are compared to the bit, and this order is what they share.
+__device__ __forceinline__ double block_fold(const double *__restrict__ p, int i0, int i1, double *lds4) {
+  double v = 0.0;
+#pragma unroll 8
+  for (int i = i0 + threadIdx.x; i < i1; i += kBlock) v += p[i];
+  return block_sum256(v, lds4);
+}
+__device__ __forceinline__ double block_fold(const double *__restrict__ p, int n, double *lds4) {
+  return block_fold(p, 0, n, lds4);
+}
+
+// Where the k sums of a final pass go; K: the most it takes (a kernel argument -- the solvers' final pass runs every
+// iteration, and carries 4)
+template <int K>
+struct OutPtrs {
+  double *p[K];
+};
+
+// Final pass of k simultaneous reductions + the scalar epilogue behind them: one block folds partials[j * nblocks ..],
+// on the peer-window transport (use_ipc) exchanges its sums with the other ranks itself (ipc_device.hpp), stores sum j
+// into *out.p[j] and runs epi() -- a scalar step (solvers.hip) or a scalar program (krylov.hip) -- in thread 0.
+template <class Epi, int K>
+__global__ __launch_bounds__(kBlock) void reduce_finish_kernel(const double *__restrict__ partials, int nblocks, int k,
+                                                               OutPtrs<K> out, const int *done, IpcDev w, int use_ipc, Epi epi) {
+  // (`done` is the same decision on every rank and the transport's all-reduce epoch is advanced by the device, by the
+  //  all-reduces that run: skipping keeps the ranks in step)
+  if (done && *done) return;
+  __shared__ double lds4[4];
+  __shared__ double vals[K];
+  for (int j = 0; j < k; ++j) {
+    const double sum = block_fold(partials + (int64_t)j * nblocks, nblocks, lds4);
+    if (threadIdx.x == 0) vals[j] = sum;
+  }
+  if (use_ipc) ipc_allreduce_block(w, vals, k);
+  else __syncthreads();
+  if ((int)threadIdx.x < k) *out.p[threadIdx.x] = vals[threadIdx.x];
+  __syncthreads();
+  if (threadIdx.x == 0) epi();
+}
+
+// partials (k arrays of nblocks) -> *out.p[j] -> epi, the same way for every solver: the first pass if there are more
+// than kSinglePassPartials; then, on one rank and on the peer-window transport, ONE launch.  Over RCCL the launch stores
+// this rank's sums through `local` and runs no epilogue; rccl_tail() enqueues the all-reduce and the epilogue.
+template <class Epi, int K, class Tail>
+int k_reduce_finish(storm_hip_ctx *c, const double *partials, int nblocks, int k, const OutPtrs<K> &out, const int *done,
+                    const Epi &epi, const OutPtrs<K> &local, Tail rccl_tail) {
+  STORM_TRY(k_reduce_stage1(c, &partials, &nblocks, k, done));
+  IpcDev w{};
+  const bool one = c->comm == nullptr || comm_ipc_next(c, &w);
+  hipLaunchKernelGGL((reduce_finish_kernel<Epi, K>), dim3(1), dim3(kBlock), 0, c->stream, partials, nblocks, k, one ? out : local,
+                     done, w, (int)(c->comm != nullptr && one), one ? epi : Epi{});
+  HIP_TRY(hipGetLastError());
+  return one ? STORM_HIP_OK : rccl_tail();
 }
 
 }  // namespace storm

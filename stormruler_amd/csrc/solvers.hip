@@ -93,56 +93,21 @@ __device__ void do_step(int kind, SolverState *st, GmresDev g) {
   }
 }
 
-struct OutSlots {
-  double *p[4];
+// The epilogue of reduce_finish_kernel (solver_device.hpp) for the fused solvers: a scalar step (STEP_NONE: none).
+struct StepEpi {
+  int step;
+  SolverState *st;
+  GmresDev g;
+  __device__ void operator()() const {
+    if (step != STEP_NONE) do_step(step, st, g);
+  }
 };
 
-// Final pass of up to 4 simultaneous reductions + the scalar step.  On one rank, and on the peer-window transport
-// (use_ipc: the block exchanges its sums with the other ranks itself, ipc_device.hpp), that is ONE launch.
-__global__ __launch_bounds__(kBlock) void reduce_step_kernel(const double *__restrict__ partials, int nblocks,
-                                                             int k, OutSlots out, int step, SolverState *st,
-                                                             GmresDev g, bool force, IpcDev w, int use_ipc) {
-  // (`done` is the same decision on every rank and the transport's all-reduce epoch is advanced by the device, by the
-  //  all-reduces that run: skipping keeps the ranks in step)
-  if (!force && st->done) return;
-  __shared__ double lds4[4];
-  __shared__ double vals[4];
-  for (int j = 0; j < k; ++j) {
-    const double *p = partials + (int64_t)j * nblocks;
-    double v = 0.0;
-#pragma unroll 8
-    for (int i = threadIdx.x; i < nblocks; i += kBlock) v += p[i];
-    const double sum = block_sum256(v, lds4);
-    if (threadIdx.x == 0) vals[j] = sum;
-  }
-  if (use_ipc) ipc_allreduce_block(w, vals, k);
-  else __syncthreads();
-  if ((int)threadIdx.x < k) *out.p[threadIdx.x] = vals[threadIdx.x];
-  __syncthreads();
-  if (step != STEP_NONE && threadIdx.x == 0) do_step(step, st, g);
-}
-
-// First pass of a two-pass final reduction (used when a kernel left > 4096 partials, e.g. the
-// 65 536 per-block partials of a 256^3 SpMV): kStage2 blocks fold the k arrays to kStage2 each.
-__global__ __launch_bounds__(kBlock) void reduce_stage1_kernel(const double *__restrict__ partials, int nblocks,
-                                                               double *__restrict__ out, const SolverState *st,
-                                                               bool force) {
-  if (!force && st->done) return;
-  __shared__ double lds4[4];
-  const int j = blockIdx.y, g = blockIdx.x;
-  const int chunk = (nblocks + gridDim.x - 1) / gridDim.x;
-  const int i0 = g * chunk, i1 = min(i0 + chunk, nblocks);
-  const double *p = partials + (int64_t)j * nblocks;
-  double v = 0.0;
-  for (int i = i0 + threadIdx.x; i < i1; i += kBlock) v += p[i];
-  const double sum = block_sum256(v, lds4);
-  if (threadIdx.x == 0) out[j * gridDim.x + g] = sum;
-}
-
-// The same first pass, finished in the kernel (ticket_device.hpp): the block that draws the last ticket folds the
-// kStage2 block sums and leaves the total in *out -- the consumer (cg_r_kernel) reads one scalar instead of folding
-// kStage2 partials in every one of its 8 192 blocks before its first load.
-// use_ipc (peer-window transport): the finishing wave also exchanges the sum with the other ranks (ipc_allreduce_wave).
+// The first pass of NV sums (partials[j * nblocks + i]), finished in the kernel (ticket_device.hpp): the block that draws
+// the last ticket folds the kStage2 block sums and leaves the totals in out[0 .. NV) -- the consumer (cg_r_kernel) reads
+// one scalar instead of folding kStage2 partials in every one of its 8 192 blocks before its first load.
+// use_ipc (peer-window transport): the finishing wave also exchanges the sums with the other ranks (ipc_allreduce_wave).
+template <int NV>
 __global__ __launch_bounds__(kBlock) void reduce_stage1_ticket_kernel(const double *__restrict__ partials, int nblocks,
                                                                       double *__restrict__ out, const SolverState *st,
                                                                       TicketArgs tickets, IpcDev w, int use_ipc) {
@@ -151,37 +116,13 @@ __global__ __launch_bounds__(kBlock) void reduce_stage1_ticket_kernel(const doub
   const int g = blockIdx.x;
   const int chunk = (nblocks + gridDim.x - 1) / gridDim.x;
   const int i0 = g * chunk, i1 = min(i0 + chunk, nblocks);
-  double v = 0.0;
-  for (int i = i0 + threadIdx.x; i < i1; i += kBlock) v += partials[i];
-  const double sum = block_sum256(v, lds4);
+  double mine[NV], total[NV];
+  for (int j = 0; j < NV; ++j) mine[j] = block_fold(partials + (int64_t)j * nblocks, i0, i1, lds4);
   if (threadIdx.x >= kWave) return;
-  const double mine[1] = {sum};
-  double total[1];
-  if (ticket_reduce_wave0<1>(tickets, mine, 1, (unsigned)g, gridDim.x, total)) {
-    if (use_ipc) ipc_allreduce_wave<1>(w, total, 1);
-    if (threadIdx.x == 0) *out = total[0];
-  }
-}
-
-// ... two sums at once (BiCGStab's <t,s>, <t,t> on the peer-window transport): partials[j * nblocks + i], results in out0 / out1.
-__global__ __launch_bounds__(kBlock) void reduce_stage1_ticket2_kernel(const double *__restrict__ partials, int nblocks,
-                                                                       double *__restrict__ out0, double *__restrict__ out1,
-                                                                       const SolverState *st, TicketArgs tickets, IpcDev w, int use_ipc) {
-  if (st->done) return;
-  __shared__ double lds4[4];
-  const int g = blockIdx.x;
-  const int chunk = (nblocks + gridDim.x - 1) / gridDim.x;
-  const int i0 = g * chunk, i1 = min(i0 + chunk, nblocks);
-  double v0 = 0.0, v1 = 0.0;
-  for (int i = i0 + threadIdx.x; i < i1; i += kBlock) v0 += partials[i], v1 += partials[nblocks + i];
-  const double s0 = block_sum256(v0, lds4);
-  const double s1 = block_sum256(v1, lds4);
-  if (threadIdx.x >= kWave) return;
-  const double mine[2] = {s0, s1};
-  double total[2];
-  if (ticket_reduce_wave0<2>(tickets, mine, 2, (unsigned)g, gridDim.x, total)) {
-    if (use_ipc) ipc_allreduce_wave<2>(w, total, 2);
-    if (threadIdx.x == 0) *out0 = total[0], *out1 = total[1];
+  if (ticket_reduce_wave0<NV>(tickets, mine, NV, (unsigned)g, gridDim.x, total)) {
+    if (use_ipc) ipc_allreduce_wave<NV>(w, total, NV);
+    if (threadIdx.x == 0)
+      for (int j = 0; j < NV; ++j) out[j] = total[j];
   }
 }
 
@@ -261,6 +202,43 @@ __global__ __launch_bounds__(kBlock) void init_residual_kernel(int64_t n, double
   if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
+// The reduction code of cg_r_kernel and cg_r_recompute_kernel: a residual kernel must form alpha and sum <r,r> exactly
+// as the other does.  Prologue: alpha = safe_divide(gamma, <p,z>), with <p,z> folded from pz_partials by every block
+// (the same n_pz values in the same order, hence the same alpha) or read from the slab; block 0 stores both.
+__device__ __forceinline__ double cg_r_alpha(SolverState *st, const double *__restrict__ pz_partials, int n_pz, double *lds4) {
+  double pz;
+  if (pz_partials) {
+    pz = block_fold(pz_partials, n_pz, lds4);
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_PZ] = pz;
+  } else {
+    pz = st->s[S_PZ];
+  }
+  const double alpha = safe_divide(st->s[S_GAMMA], pz);
+  if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_ALPHA] = alpha;  // for cg_xp_kernel / the next step kernel
+  return alpha;
+}
+// Epilogue: block bx's partial of <r,r> into partials[bx] (no tickets), or <r,r> finished here (ticket_device.hpp) and
+// the scalar step of SolverCg.hpp:110-125 with the convergence rule in the last block: no final-pass launch.
+__device__ __forceinline__ void cg_r_finish(SolverState *st, double acc, unsigned bx, double *__restrict__ partials,
+                                            const TicketArgs &tickets, const IpcDev &w, int use_ipc, double *lds4) {
+  const double s = block_sum256(acc, lds4);
+  if (tickets.cnt == nullptr) {
+    if (threadIdx.x == 0) partials[bx] = s;
+    return;
+  }
+  if (threadIdx.x >= kWave) return;
+  const double mine[1] = {s};
+  double total[1];
+  if (ticket_reduce_wave0<1>(tickets, mine, 1, bx, gridDim.x, total)) {
+    if (use_ipc == 1) ipc_allreduce_wave<1>(w, total, 1);  // the global <r,r>: the same bits on every rank
+    if (threadIdx.x == 0) {
+      st->s[S_GAMMA_NEW] = total[0];
+      // (use_ipc == 2: this rank's sum only -- the host enqueues the all-reduce and the step behind this kernel)
+      if (use_ipc != 2) do_step(STEP_CG_RR, st, GmresDev{});
+    }
+  }
+}
+
 // CG iteration, vector part, in two kernels around the <r,r> reduction (SolverCg.hpp:97-123):
 //   cg_r_kernel : alpha = safe_divide(gamma, <p,z>);  r -= alpha z;  partial <r,r>
 //   cg_xp_kernel: x += alpha p;  p = r + beta p
@@ -280,17 +258,7 @@ __global__ __launch_bounds__(kBlock) void cg_r_kernel(int64_t n, SolverState *st
   // `reverse`: the blocks sweep the rows from the far end (see the sweep-direction note in storm_hip_solve_cg);
   // block bx still owns the same rows and the same partial, whichever way the grid is dealt out
   const unsigned bx = reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
-  double pz;
-  if (pz_partials) {
-    double v = 0.0;
-    for (int i = threadIdx.x; i < n_pz; i += kBlock) v += pz_partials[i];
-    pz = block_sum256(v, lds4);
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_PZ] = pz;
-  } else {
-    pz = st->s[S_PZ];
-  }
-  const double alpha = safe_divide(st->s[S_GAMMA], pz);
-  if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_ALPHA] = alpha;  // for cg_xp_kernel of this iteration
+  const double alpha = cg_r_alpha(st, pz_partials, n_pz, lds4);
   double acc = 0.0;
   const int64_t n2 = n >> 1;
   double2v *r2 = reinterpret_cast<double2v *>(r);
@@ -321,24 +289,7 @@ __global__ __launch_bounds__(kBlock) void cg_r_kernel(int64_t n, SolverState *st
     r[n - 1] = vr;
     acc += vr * vr;
   }
-  const double s = block_sum256(acc, lds4);
-  if (tickets.cnt == nullptr) {
-    if (threadIdx.x == 0) partials[bx] = s;
-    return;
-  }
-  // <r, r> finishes here (ticket_device.hpp); the last block runs the scalar step of SolverCg.hpp:110-125 and the
-  // convergence rule: no final-pass launch
-  if (threadIdx.x >= kWave) return;
-  const double mine[1] = {s};
-  double total[1];
-  if (ticket_reduce_wave0<1>(tickets, mine, 1, bx, gridDim.x, total)) {
-    if (use_ipc == 1) ipc_allreduce_wave<1>(w, total, 1);  // the global <r,r>: the same bits on every rank
-    if (threadIdx.x == 0) {
-      st->s[S_GAMMA_NEW] = total[0];
-      // (use_ipc == 2: this rank's sum only -- the host enqueues the all-reduce and the step behind this kernel)
-      if (use_ipc != 2) do_step(STEP_CG_RR, st, GmresDev{});
-    }
-  }
+  cg_r_finish(st, acc, bx, partials, tickets, w, use_ipc, lds4);
 }
 
 // The residual recompute (option cg_residual_march): cg_r_kernel for the fused CG step on one rank, with z = A p'
@@ -363,17 +314,7 @@ __global__ __launch_bounds__(kBlock) void cg_r_recompute_kernel(int64_t n, Solve
   if (IDX) rec_table_fill(A, words_sh);
   __syncthreads();
   const unsigned bx = reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;  // (as cg_r_kernel)
-  double pz;
-  if (pz_partials) {
-    double v = 0.0;
-    for (int i = threadIdx.x; i < n_pz; i += kBlock) v += pz_partials[i];
-    pz = block_sum256(v, lds4);
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_PZ] = pz;
-  } else {
-    pz = st->s[S_PZ];
-  }
-  const double alpha = safe_divide(st->s[S_GAMMA], pz);
-  if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_ALPHA] = alpha;  // for the next step kernel
+  const double alpha = cg_r_alpha(st, pz_partials, n_pz, lds4);
   const double op_alpha = ld_scal2(alpha_s), op_beta = ld_scal2(beta_s);
   const int64_t a = T.a, b = T.b, mg = T.max_gather;
   const char *pg = reinterpret_cast<const char *>(p) - (size_t)kVecGuard * 8;
@@ -430,17 +371,8 @@ __global__ __launch_bounds__(kBlock) void cg_r_recompute_kernel(int64_t n, Solve
     }
   }
   // (an odd last row: cg_r_kernel's tail -- never here, the recompute takes operators with an even row count)
-  const double s = block_sum256(acc, lds4);
-  // <r, r> finishes here as in cg_r_kernel: the last block runs the scalar step of SolverCg.hpp:110-125
-  if (threadIdx.x >= kWave) return;
-  const double mine[1] = {s};
-  double total[1];
-  if (ticket_reduce_wave0<1>(tickets, mine, 1, bx, gridDim.x, total)) {
-    if (threadIdx.x == 0) {
-      st->s[S_GAMMA_NEW] = total[0];
-      do_step(STEP_CG_RR, st, GmresDev{});
-    }
-  }
+  // (<r, r> finishes here as in cg_r_kernel: the recompute always runs with tickets)
+  cg_r_finish(st, acc, bx, nullptr, tickets, IpcDev{}, 0, lds4);
 }
 
 // Whether the residual recompute takes iteration k > 0 of the fused CG loop: one rank, an unsplit operator with an even
@@ -650,9 +582,7 @@ __global__ __launch_bounds__(kBlock) void mgs_step_kernel(int64_t n, const int *
   __shared__ double lds4[4];
   double hv;
   if (in_partials) {
-    double v = 0.0;
-    for (int i = threadIdx.x; i < n_in; i += kBlock) v += in_partials[i];
-    hv = block_sum256(v, lds4);
+    hv = block_fold(in_partials, n_in, lds4);
     if (blockIdx.x == 0 && threadIdx.x == 0) *h_store = hv;
   } else {
     hv = *h;
@@ -955,45 +885,24 @@ struct Driver {
 
   // partials -> slots (+ all-reduce over ranks) -> scalar step
   int finish(int nblocks, int k, const int *slots, int step, bool force = false) {
-    OutSlots out{};
-    double *contiguous = slot(slots[0]);
-    bool contig = true;
+    OutPtrs<4> out{};
+    bool contiguous = true;  // (RCCL: the k slots all-reduced by one call)
     for (int j = 0; j < k; ++j) {
       out.p[j] = slot(slots[j]);
-      contig &= (slots[j] == slots[0] + j);
+      contiguous &= (slots[j] == slots[0] + j);
     }
-    return finish_ptrs(nblocks, k, out, contig ? contiguous : nullptr, step, force);
-  }
-  int finish_ptrs(int nblocks, int k, OutSlots out, double *contiguous, int step, bool force = false) {
-    const double *partials = c->d_partials;
-    if (nblocks > kSinglePassPartials) {
-      hipLaunchKernelGGL(reduce_stage1_kernel, dim3(kStage2, k), dim3(kBlock), 0, c->stream, c->d_partials,
-                         nblocks, c->d_partials2, st, force);
-      HIP_TRY(hipGetLastError());
-      partials = c->d_partials2;
-      nblocks = kStage2;
-    }
-    IpcDev w{};
-    const bool ipc = c->comm != nullptr && comm_ipc_next(c, &w);
-    if (c->comm == nullptr || ipc) {
-      hipLaunchKernelGGL(reduce_step_kernel, dim3(1), dim3(kBlock), 0, c->stream, partials, nblocks, k,
-                         out, step, st, g, force, w, (int)ipc);
-      HIP_TRY(hipGetLastError());
+    return k_reduce_finish(c, c->d_partials, nblocks, k, out, force ? nullptr : done, StepEpi{step, st, g}, out, [&]() -> int {
+      if (contiguous) {
+        STORM_TRY(comm_allreduce_sum(c, out.p[0], k));
+      } else {
+        for (int j = 0; j < k; ++j) STORM_TRY(comm_allreduce_sum(c, out.p[j], 1));
+      }
+      if (step != STEP_NONE) {
+        hipLaunchKernelGGL(step_kernel, dim3(1), dim3(1), 0, c->stream, step, st, g, force);
+        HIP_TRY(hipGetLastError());
+      }
       return STORM_HIP_OK;
-    }
-    hipLaunchKernelGGL(reduce_step_kernel, dim3(1), dim3(kBlock), 0, c->stream, partials, nblocks, k, out,
-                       (int)STEP_NONE, st, g, force, w, 0);
-    HIP_TRY(hipGetLastError());
-    if (contiguous) {
-      STORM_TRY(comm_allreduce_sum(c, contiguous, k));
-    } else {
-      for (int j = 0; j < k; ++j) STORM_TRY(comm_allreduce_sum(c, out.p[j], 1));
-    }
-    if (step != STEP_NONE) {
-      hipLaunchKernelGGL(step_kernel, dim3(1), dim3(1), 0, c->stream, step, st, g, force);
-      HIP_TRY(hipGetLastError());
-    }
-    return STORM_HIP_OK;
+    });
   }
 
   // Option ticket_verify: <a, b0> (and <a, b1>) once more by the two-launch path (per-block partials, then one block
@@ -1039,7 +948,7 @@ struct Driver {
     if (out1 >= 0) sd.out[1] = slot(out1);
     sd.ticketed_out = ticketed;
     if (ticketed) *ticketed = 0;
-    const bool want = (dot_w != nullptr || dot_yy) && c->opt_fuse_dot != 0;
+    const bool want = dot_w != nullptr || dot_yy;
     if (!want && nblocks) *nblocks = 0;
     return spmv_launch(op, host_scal(alpha), host_scal(beta), x, y, want ? &sd : nullptr,
                        predicated ? done : nullptr);
@@ -1264,8 +1173,7 @@ int gmres_orthogonalize(storm_hip_ctx *c, int64_t n, const SolverState *st, cons
     return STORM_HIP_OK;
   }
   if (gram_schmidt == 0) {
-    const bool fold_in_consumer = c->comm == nullptr && nbv <= 2048 && 2 * (int64_t)nbv <= c->partials_capacity &&
-                                  c->opt_fuse_mgs != 0;
+    const bool fold_in_consumer = c->comm == nullptr && nbv <= 2048 && 2 * (int64_t)nbv <= c->partials_capacity;
     if (fold_in_consumer) {
       // partials ping-pong between two halves of the workspace: step i folds what step i-1 wrote
       double *cur = c->d_partials, *nxt = c->d_partials + nbv;
@@ -1428,7 +1336,7 @@ int solve_cg_body(const FusedSolveArgs &args) {
   const bool tick = c->opt_ticket_reduce != 0 && (c->comm == nullptr || ipc) && nbv <= kTicketGroup * kTicketMaxGroups;
   // (<p,z> inside the SpMV only where it replaces a whole final-pass launch: with more per-wave partials than one
   // pass folds, the first pass + the fold inside cg_r cost what the ticket tail would add to the SpMV)
-  const bool tick_spmv = tick && !ipc && (4 * (int64_t)spmv_grid_blocks(op) <= kSinglePassPartials || c->opt_fold_pz == 0);
+  const bool tick_spmv = tick && !ipc && 4 * (int64_t)spmv_grid_blocks(op) <= kSinglePassPartials;
   // The fused step (one rank, tiled format-4 operator): iteration k's SpMV kernel first ENDS iteration k - 1 --
   // x += alpha p, p' = r + beta p -- on the rows it loads anyway and applies the operator to p': x and p are no longer
   // streamed by a kernel of their own (cg_xp).  p ping-pongs between two vectors (a tile's old p is another tile's
@@ -1437,7 +1345,7 @@ int solve_cg_body(const FusedSolveArgs &args) {
   // (on RCCL too, round 4: there the reductions keep their all-reduce between partials and step -- no tickets --, the
   //  step kernel reads alpha, beta and the iteration counter from the slab exactly as cg_xp_kernel does)
   const bool rccl = c->comm != nullptr && comm_is_rccl(c);
-  const bool fuse_step = c->opt_cg_fuse != 0 && c->opt_fuse_dot != 0 && spmv_can_fuse_cg(op) &&
+  const bool fuse_step = c->opt_cg_fuse != 0 && spmv_can_fuse_cg(op) &&
                          (rccl ? true : ((c->comm == nullptr || ipc) && tick && !tick_spmv));
   // RCCL: the local sums still finish inside the kernels that produce them (tickets) -- the library all-reduce and the
   // scalar step follow as launches of their own; two small launches per iteration fewer than partials + final pass
@@ -1477,22 +1385,20 @@ int solve_cg_body(const FusedSolveArgs &args) {
       STORM_TRY(k_multi_dot(c, p, bs, 1, n, d.slot(S_PZ), d.done));
       if (c->comm != nullptr) STORM_TRY(comm_allreduce_sum(c, d.slot(S_PZ), 1));
     } else if (rtick && (int64_t)nb + kStage2 <= c->partials_capacity) {
-      hipLaunchKernelGGL(reduce_stage1_ticket_kernel, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
+      hipLaunchKernelGGL(reduce_stage1_ticket_kernel<1>, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
                          d.slot(S_PZ), d.st, TicketArgs{c->d_tickets, c->d_partials + nb, c->d_ticket_sums}, ipc_w, 0);
       HIP_TRY(hipGetLastError());
       STORM_TRY(comm_allreduce_sum(c, d.slot(S_PZ), 1));
-    } else if (tick && (nb > kSinglePassPartials || ipc) && c->opt_fold_pz != 0 && (int64_t)nb + kStage2 <= c->partials_capacity) {
+    } else if (tick && (nb > kSinglePassPartials || ipc) && (int64_t)nb + kStage2 <= c->partials_capacity) {
       // many partials, one rank: ONE small launch folds them and finishes the sum itself (tickets); cg_r_kernel reads
       // <p,z> from the slab and starts streaming at once.  (The block sums go behind the SpMV's partials.)
-      hipLaunchKernelGGL(reduce_stage1_ticket_kernel, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
+      hipLaunchKernelGGL(reduce_stage1_ticket_kernel<1>, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
                          d.slot(S_PZ), d.st, TicketArgs{c->d_tickets, c->d_partials + nb, c->d_ticket_sums}, ipc_w, (int)ipc);
       HIP_TRY(hipGetLastError());
-    } else if (c->comm == nullptr && nb > kSinglePassPartials && c->opt_fold_pz != 0) {
+    } else if (c->comm == nullptr && nb > kSinglePassPartials) {
       // ... without tickets: the first pass here, the fold of its kStage2 results inside cg_r_kernel
-      hipLaunchKernelGGL(reduce_stage1_kernel, dim3(kStage2, 1), dim3(kBlock), 0, c->stream, c->d_partials, nb,
-                         c->d_partials2, d.st, false);
-      HIP_TRY(hipGetLastError());
-      pz_partials = c->d_partials2;
+      pz_partials = c->d_partials;
+      STORM_TRY(k_reduce_stage1(c, &pz_partials, &nb, 1, d.done));
     } else {
       const int slots[1] = {S_PZ};
       STORM_TRY(d.finish(nb, 1, slots, STEP_NONE));
@@ -1630,14 +1536,14 @@ int solve_bicgstab_body(const FusedSolveArgs &args) {
     bool alpha_in_kernel = ticketed != 0;  // <rt,v> is in the slab; bicg_update forms alpha itself
     if (alpha_in_kernel) {
     } else if (ipc_tick && nb > 0 && (int64_t)nb + kStage2 <= c->partials_capacity) {
-      hipLaunchKernelGGL(reduce_stage1_ticket_kernel, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
+      hipLaunchKernelGGL(reduce_stage1_ticket_kernel<1>, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
                          d.slot(S_RTV), d.st, TicketArgs{c->d_tickets, c->d_partials + nb, c->d_ticket_sums}, ipc_w, 1);
       HIP_TRY(hipGetLastError());
       alpha_in_kernel = true;
     } else if (rccl_tick && nb > 0) {
       // ONE launch folds the per-wave partials (tickets), the all-reduce follows; alpha is formed by its consumers
       if ((int64_t)nb + kStage2 <= c->partials_capacity) {
-        hipLaunchKernelGGL(reduce_stage1_ticket_kernel, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
+        hipLaunchKernelGGL(reduce_stage1_ticket_kernel<1>, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
                            d.slot(S_RTV), d.st, TicketArgs{c->d_tickets, c->d_partials + nb, c->d_ticket_sums}, IpcDev{}, 0);
         HIP_TRY(hipGetLastError());
         STORM_TRY(comm_allreduce_sum(c, d.slot(S_RTV), 1));
@@ -1674,8 +1580,8 @@ int solve_bicgstab_body(const FusedSolveArgs &args) {
     if (omega_in_kernel) {
     } else if (rccl_tick && nb > 0) {
       if (2 * (int64_t)nb + 2 * kStage2 <= c->partials_capacity) {
-        hipLaunchKernelGGL(reduce_stage1_ticket2_kernel, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
-                           d.slot(S_TR), d.slot(S_TT), d.st, TicketArgs{c->d_tickets, c->d_partials + 2 * (size_t)nb, c->d_ticket_sums},
+        hipLaunchKernelGGL(reduce_stage1_ticket_kernel<2>, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
+                           d.slot(S_TR), d.st, TicketArgs{c->d_tickets, c->d_partials + 2 * (size_t)nb, c->d_ticket_sums},
                            IpcDev{}, 0);
         HIP_TRY(hipGetLastError());
         STORM_TRY(comm_allreduce_sum(c, d.slot(S_TR), 2));
@@ -1685,8 +1591,8 @@ int solve_bicgstab_body(const FusedSolveArgs &args) {
       }
       omega_in_kernel = rccl_end = true;
     } else if (ipc_tick && nb > 0 && 2 * (int64_t)nb + 2 * kStage2 <= c->partials_capacity) {
-      hipLaunchKernelGGL(reduce_stage1_ticket2_kernel, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
-                         d.slot(S_TR), d.slot(S_TT), d.st, TicketArgs{c->d_tickets, c->d_partials + 2 * (size_t)nb, c->d_ticket_sums},
+      hipLaunchKernelGGL(reduce_stage1_ticket_kernel<2>, dim3(kStage2), dim3(kBlock), 0, c->stream, c->d_partials, nb,
+                         d.slot(S_TR), d.st, TicketArgs{c->d_tickets, c->d_partials + 2 * (size_t)nb, c->d_ticket_sums},
                          ipc_w, 1);
       HIP_TRY(hipGetLastError());
       omega_in_kernel = true;
