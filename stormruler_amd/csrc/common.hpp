@@ -276,6 +276,7 @@ struct storm_hip_ctx {
   // diagnostics: which path the solves took (storm_hip_ctx_get_counter)
   int64_t n_resident_solves = 0, n_latency_solves = 0, n_throughput_solves = 0, n_engine_solves = 0, n_cg_fused_steps = 0;
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
+  int64_t n_mgs_chain_steps = 0, n_mgs_quad_steps = 0;  // Gram-Schmidt steps run as a chain kernel (latency.hip); ... as mgs_chain_quad_kernel
   // communicator
   storm::Comm *comm = nullptr;
   int n_ranks = 1, rank = 0;

@@ -246,6 +246,8 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "engine_solves")) *value = c->n_engine_solves;
   else if (!strcmp(key, "cg_fused_steps")) *value = c->n_cg_fused_steps;
   else if (!strcmp(key, "cg_residual_marches")) *value = c->n_cg_residual_marches;
+  else if (!strcmp(key, "mgs_chain_steps")) *value = c->n_mgs_chain_steps;
+  else if (!strcmp(key, "mgs_quad_steps")) *value = c->n_mgs_quad_steps;
   else if (!strcmp(key, "lazy_fused_dots")) *value = c->n_lazy_fused_dots;
   else if (!strcmp(key, "lazy_fused_pairs")) *value = c->n_lazy_fused_pairs;
   else if (!strcmp(key, "lazy_apply_dots")) *value = c->n_lazy_apply_dots;

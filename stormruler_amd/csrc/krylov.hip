@@ -1861,6 +1861,7 @@ int storm_hip_krylov_solve(storm_hip_krylov *k, const storm_hip_vec *b, storm_hi
                           (k->method == STORM_HIP_CG || k->method == STORM_HIP_BICGSTAB ||
                            (k->method == STORM_HIP_GMRES && params->num_inner_iterations < kMaxMulti));
   if (fused_path) return krylov_solve_engine(k, b, x, params, result, history, pre_applies);  // (has its own fallback)
+  ++c->n_engine_solves;
   const int st = coop_solve_with_fallback(c, x, run_engine_body, &a, &fb);
   if (st == STORM_HIP_OK) result->path_fallback = fb;
   return st;

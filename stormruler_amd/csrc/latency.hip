@@ -1219,7 +1219,7 @@ int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w
                          const ChainApply *apply, bool *applied) {
   *taken = false;
   if (applied) *applied = false;
-  bool with_apply = false;
+  bool with_apply = false, quad = false;
   // (a step of the chain costs half an all-reduce, ~2.5 us, whatever the size; the kernel-per-step path costs a launch,
   //  ~3.5 us, or 32 B/row of HBM traffic, whichever is more -- measured, us per inner iteration, per-step vs chained:
   //  step.1 83..106 vs 74.5, 32^3 84..109 vs 72, 64^3 91..106 vs 93, 128^3 248 vs 147)
@@ -1282,7 +1282,7 @@ int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w
         HIP_TRY(hipMalloc((void **)&c->d_quad_slots, bytes));
         HIP_TRY(hipMemsetAsync(c->d_quad_slots, 0, bytes, c->stream));
       }
-      fn = qf, dyn_lds = quad_lds, threads = kQuadThreads, blocks = (qsubs_total + sv - 1) / sv;
+      fn = qf, dyn_lds = quad_lds, threads = kQuadThreads, blocks = (qsubs_total + sv - 1) / sv, quad = true;
     } else {
       with_apply = false;
     }
@@ -1340,6 +1340,7 @@ int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w
   void *args[] = {&a};
   *taken = coop_launch(c, fn, (unsigned)blocks, args, dyn_lds, threads);
   if (!*taken) c->lat_seq -= (unsigned long long)k + 2;
+  else ++c->n_mgs_chain_steps, c->n_mgs_quad_steps += quad;
   if (applied) *applied = formed || (*taken && with_apply);
   return STORM_HIP_OK;
 }
