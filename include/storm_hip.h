@@ -290,6 +290,11 @@ int storm_hip_op_create_csr(storm_hip_ctx *ctx, int64_t n_rows, int64_t n_halo,
  *   cg_fuse (1), cg_march (8), cg_march_fill (2048): the SpMV launch of a tiled format-4 operator ends the previous CG
  *              iteration (x += alpha p, p = r + beta p) itself, as blocks marching through this many planes (0: tiles), fewer
  *              planes per block on small lattices so that the grid holds about cg_march_fill blocks (0: as given);
+ *   cg_residual_march (1), cg_residual_planes (1), cg_residual_chunk (16), cg_residual_fill (512): on one rank that loop's
+ *              r -= alpha z recomputes z = A p from p instead of reading a stored z back (the same bits); by blocks that
+ *              own a 2 048-row run of a plane and march through cg_residual_chunk planes where every plane is whole such
+ *              runs (fewer planes on small lattices: about cg_residual_fill blocks; 0: as given), else -- and with
+ *              cg_residual_planes 0 -- by gathers in the streaming kernel's grid;
  *   fused_reduce (1), lin_fuse (1), ticket_reduce (1): engine reductions finished by the partials kernel's last block; two
  *              consecutive vector statements as one pass; fused-loop reductions finished inside the producing kernels;
  *   nontemporal (1), blas1_nt (1): non-temporal record / y traffic of the SpMV; of the BLAS-1 and solver kernels (0 never,

@@ -245,6 +245,9 @@ struct storm_hip_ctx {
   int64_t opt_cg_march_alternate = 1;  // odd z-chunks of the marching step kernel march downwards (spmv.hip MarchArgs::alternate)
   int64_t opt_cg_march = 8;   // ... as blocks of 1024 rows marching through this many planes (0: tiles, spmv_canon_tile planes deep); 256^3, us per CG iteration: tiles 239, 8 planes 230, 16 234, 32 236, 64 237 (profiles/r03k)
   int64_t opt_cg_residual_march = 1;  // fused CG step, one rank, unsplit lattice operator: r -= alpha z by a kernel that recomputes z = A p' from p' in cg_r_kernel's row order (solvers.hip cg_r_recompute_kernel: the same bits), so z is never stored nor read back (0: cg_r_kernel streams z)
+  int64_t opt_cg_residual_planes = 1;  // ... by blocks that own a 2 048-row run of a plane and march over planes (solvers.hip cg_r_planes_kernel: cg_r_kernel's partials, plane by plane; lattices of whole 2 048-row runs per plane) instead of gathering the +-a / +-b neighbours (0: cg_r_recompute_kernel everywhere)
+  int64_t opt_cg_residual_chunk = 16;  // ... planes per block (2 .. 32); the two planes bounding a chunk are read again: + 2 / chunk of 8 B/row
+  int64_t opt_cg_residual_fill = 512;  // ... fewer planes per block on smaller lattices, so that the grid holds about this many blocks (0: cg_residual_chunk as given)
   int64_t opt_cg_fuse = 1;   // fused CG, one rank, tiled format-4 operator: the SpMV kernel ends the previous iteration (x += alpha p, p = r + beta p) itself
   // Vector storage released by vec_destroy, kept for the next vec_create of the same size: a solve
   // allocates its work vectors on entry and frees them on return (the reference re-assigns them in
@@ -276,6 +279,7 @@ struct storm_hip_ctx {
   // diagnostics: which path the solves took (storm_hip_ctx_get_counter)
   int64_t n_resident_solves = 0, n_latency_solves = 0, n_throughput_solves = 0, n_engine_solves = 0, n_cg_fused_steps = 0;
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
+  int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_mgs_chain_steps = 0, n_mgs_quad_steps = 0;  // Gram-Schmidt steps run as a chain kernel (latency.hip); ... as mgs_chain_quad_kernel
   // communicator
   storm::Comm *comm = nullptr;

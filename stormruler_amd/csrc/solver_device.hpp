@@ -77,13 +77,16 @@ __device__ inline void gmres_givens_update(SolverState *st, GmresDev g, int k, d
 #undef H_
 }
 
+// (the second half on its own: a kernel that forms several block sums before it meets a barrier -- solvers.hip
+//  cg_r_planes_kernel -- keeps lane 0's wave_sum_down values of each and folds them here afterwards: the same bits)
+__device__ __forceinline__ double block_sum256_of_waves(const double *lds4) { return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]); }
 __device__ __forceinline__ double block_sum256(double v, double *lds4) {
   v = wave_sum_down(v);  // (the __shfl_down tree's order and bits, without the LDS crossbar: wave_device.hpp)
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) lds4[wave] = v;
   __syncthreads();
-  return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+  return block_sum256_of_waves(lds4);
 }
 
 // The block's sum of p[i0 .. i1): lane t adds p[i0 + t], p[i0 + t + 256], ... in ascending order into ONE accumulator,

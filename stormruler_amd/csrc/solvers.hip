@@ -403,6 +403,205 @@ static int cg_r_recompute_run(const storm_hip_op *op, int nbv, Scal alpha, Scal 
   return STORM_HIP_OK;
 }
 
+// The residual recompute MARCHING over planes (option cg_residual_planes): the same r and the same <r,r> bits as the two
+// kernels above, without the gathers.  At these sizes cg_r_kernel's grid is one trip per block, so its block bx owns rows
+// [2048 bx, 2048 bx + 2048): with b % 2048 == 0 a run of ONE plane.  A block here owns run yt of the plane and a chunk of
+// planes, and forms, plane by plane, what cg_r_kernel's block bx' = plane * (b / 2048) + yt forms: thread t holds pairs
+// t + 256 u (u = 0 .. 3) of p' and r, sums them into one accumulator in cg_r_kernel's order, and the block's sum of the
+// plane is partial bx'.  p' of the planes behind and ahead stays in registers while the march advances, the +-a lines and
+// the +-1 rows at the wave ends come from an LDS copy of the plane (the run and a rows on either side; two buffers in
+// rotation, one barrier per plane), so every row of p' is loaded once -- plus the halo lines (2 a / 2048 of a plane,
+// adjacent runs of one XCD march in step) and the two planes that bound the chunk.  Loads run one plane ahead of the
+// plane whose neighbours they are, two ahead of the plane being applied.
+//   The per-plane sums stay in the block (each wave's wave_sum_down value in LDS: block_sum256 without its barriers) and
+// are published when the chunk ends, all at once, through ticket_reduce_wave0_slots with cg_r_kernel's block count: one
+// atomic round trip per plane inside the march would serialise it.
+//   168 VGPRs and 41 KB of LDS at a = 256 (49 KB at a = 512): three blocks per CU.  At 256^3 the 512 blocks of 16 planes
+// are ONE round of two blocks per CU (32 planes, one block per CU: the same time; 8 planes, two rounds: 1.2 % slower), so
+// every block pays the start's round trips: the first planes are requested before anything is waited for.
+struct ResidualPlanesArgs {
+  int a, b;
+  int runs_per_plane;  // b / 2048
+  int per_xcd;         // runs_per_plane / 8 when that divides (adjacent runs on one XCD, as the step kernel's tiles), else 0
+  int planes;          // n / b
+  int nz;              // planes per block
+  int max_gather;      // largest guard-relative index a 16-byte load may start at
+};
+constexpr int kResidualMaxChunk = 32;  // planes per block at most (the per-plane sums: one lane of wave 0 each)
+template <int HLP, bool IDX>  // HLP: halo pairs per thread and plane: ceil(a / 256); IDX: the row-record index
+__global__ __launch_bounds__(kBlock) void cg_r_planes_kernel(SolverState *st, double *__restrict__ r, const double *__restrict__ p,
+                                                             SellArgs A, ResidualPlanesArgs G, Scal alpha_s, Scal beta_s,
+                                                             const double *__restrict__ pz_partials, int n_pz, int reverse,
+                                                             TicketArgs tickets) {
+  const int done = st->done;  // (tested behind the first loads: in a grid of one round every block pays the start's round trips)
+  __shared__ double lds4[4];
+  __shared__ double dict_sh[32];
+  __shared__ double wave_part[kResidualMaxChunk * (kBlock / kWave)];
+  extern __shared__ __attribute__((aligned(16))) double plane_sh[];  // [2][a + 2048 + a], then (IDX) the word table
+  const int a = G.a, b = G.b;
+  const int ldw = kStreamBlockElems + 2 * a;
+  unsigned long long *words_sh = reinterpret_cast<unsigned long long *>(plane_sh + 2 * ldw);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bidx = reverse ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+  int zc, yt;
+  if (G.per_xcd > 0) {
+    const int xcd = bidx & (kNumXcd - 1), j = bidx >> 3;
+    zc = j / G.per_xcd;
+    yt = xcd * G.per_xcd + (j - zc * G.per_xcd);
+  } else {
+    zc = bidx / G.runs_per_plane;
+    yt = bidx - zc * G.runs_per_plane;
+  }
+  const int z_begin = zc * G.nz, z_end = min(z_begin + G.nz, G.planes), nz = z_end - z_begin;
+  // (the blocks are dealt out from the far end under `reverse`, where the step kernel stopped; each still marches
+  //  upwards: a downward march measured 0.2 % slower at 256^3)
+  auto plane = [&](int s) { return z_begin + s; };  // s = -1 and s = nz: the planes next to the chunk
+  const int p0 = yt * kStreamBlockElems;
+  const char *pg = reinterpret_cast<const char *>(p) - (size_t)kVecGuard * 8;
+  double2v *r2 = reinterpret_cast<double2v *>(r);
+
+  // p' of one plane in flight: the own four pairs and this thread's share of the halo lines
+  struct Flight {
+    double2v p[kUnroll], hp[HLP];
+  };
+  int hat[HLP], hjj[HLP];  // where the thread's halo pairs sit in the LDS copy (-1: none), and in the plane
+#pragma unroll
+  for (int i = 0; i < HLP; ++i) {
+    const int h = (int)threadIdx.x + kBlock * i;  // pair h of the plane's a halo pairs
+    hjj[i] = 2 * h < a ? 2 * h - a : kStreamBlockElems + 2 * h - a;
+    hat[i] = h < a ? a + hjj[i] : -1;
+  }
+  auto load_p = [&](int64_t row) {  // guard-relative and clamped: a plane below the first / above the last has weight 0
+    int64_t gi = row + kVecGuard;
+    gi = gi < 0 ? 0 : (gi > (int64_t)G.max_gather ? (int64_t)G.max_gather : gi);
+    return *reinterpret_cast<const double2v *>(pg + (size_t)gi * 8);
+  };
+  auto issue_p = [&](int zp, bool own, Flight &f) {
+    const int64_t row0 = (int64_t)zp * b + p0;
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) f.p[u] = load_p(row0 + 2 * ((int)threadIdx.x + kBlock * u));
+#pragma unroll
+    for (int i = 0; i < HLP; ++i) {
+      f.hp[i] = double2v{0.0, 0.0};
+      if (own && hat[i] >= 0) f.hp[i] = load_p(row0 + hjj[i]);
+    }
+  };
+  auto issue_rw = [&](int zp, double2v (&vr)[kUnroll], RecRaw<IDX> (&w)[kUnroll]) {  // (an own plane: every row exists)
+    const int64_t row0 = (int64_t)zp * b + p0;
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int64_t row = row0 + 2 * ((int)threadIdx.x + kBlock * u);
+      vr[u] = r2[row >> 1];
+      w[u] = rec_load<IDX>(A, (uint32_t)row);
+    }
+  };
+
+  Flight cur, nxt, fl;
+  double2v pm[kUnroll], vr[kUnroll];
+  RecRaw<IDX> w[kUnroll];
+  issue_p(plane(-1), false, fl);
+#pragma unroll
+  for (int u = 0; u < kUnroll; ++u) pm[u] = fl.p[u];
+  issue_p(plane(0), true, cur);
+  issue_rw(plane(0), vr, w);
+  issue_p(plane(1), 1 < nz, nxt);
+  if (threadIdx.x < 32) dict_sh[threadIdx.x] = A.dict[threadIdx.x];
+  if (IDX) rec_table_fill(A, words_sh);
+  if (done) return;
+  const double alpha = cg_r_alpha(st, pz_partials, n_pz, lds4);
+  const double op_alpha = ld_scal2(alpha_s), op_beta = ld_scal2(beta_s);
+  // (the first barrier of the march covers dict_sh and the word table)
+  for (int s = 0; s < nz; ++s) {
+    const int zp = plane(s);
+    double *buf = plane_sh + (s & 1) * ldw;
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) *reinterpret_cast<double2v *>(&buf[a + 2 * ((int)threadIdx.x + kBlock * u)]) = cur.p[u];
+#pragma unroll
+    for (int i = 0; i < HLP; ++i)
+      if (hat[i] >= 0) *reinterpret_cast<double2v *>(&buf[hat[i]]) = cur.hp[i];
+    double2v vrn[kUnroll];
+    RecRaw<IDX> wn[kUnroll];
+    if (s + 2 <= nz) issue_p(plane(s + 2), s + 2 < nz, fl);
+    if (s + 1 < nz) issue_rw(plane(s + 1), vrn, wn);
+    __syncthreads();  // the LDS copy of plane zp is complete; the other buffer is free once every wave is past this point
+    const int64_t i0 = (((int64_t)zp * b + p0) >> 1) + threadIdx.x;  // cg_r_kernel's `base` of block zp * runs_per_plane + yt
+    double acc = 0.0;
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int at = a + 2 * ((int)threadIdx.x + kBlock * u);
+      double2v xg[6];
+      march_neighbours(buf, at, a, lane, pm[u], nxt.p[u], cur.p[u], xg);
+      const double2v vz = lattice_pair_apply(dict_sh, rec_word<IDX>(w[u], words_sh), xg, cur.p[u], op_alpha, op_beta);
+      // cg_r_kernel's statements, verbatim
+      vr[u] -= alpha * vz;
+      r2[i0 + u * kBlock] = vr[u];
+      acc += vr[u].x * vr[u].x;
+      acc += vr[u].y * vr[u].y;
+    }
+    acc = wave_sum_down(acc);
+    if (lane == 0) wave_part[s * (kBlock / kWave) + wave] = acc;
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) pm[u] = cur.p[u], vr[u] = vrn[u], w[u] = wn[u];
+    cur = nxt, nxt = fl;
+  }
+  __syncthreads();
+  if (threadIdx.x >= kWave) return;
+  // lane s: cg_r_kernel's block of plane(s) -- its block_sum256 value, its partial slot, its ticket
+  const bool on = lane < nz;
+  const double mine = on ? block_sum256_of_waves(wave_part + lane * (kBlock / kWave)) : 0.0;
+  const unsigned bxv = on ? (unsigned)(plane(lane) * G.runs_per_plane + yt) : 0u;
+  double total;
+  if (ticket_reduce_wave0_slots(tickets, mine, on, bxv, (unsigned)(G.planes * G.runs_per_plane), &total) && threadIdx.x == 0) {
+    st->s[S_GAMMA_NEW] = total;
+    do_step(STEP_CG_RR, st, GmresDev{});
+  }
+}
+
+// Whether the plane march takes the residual recompute: whole planes of whole 2 048-row runs (cg_r_kernel's blocks do not
+// straddle planes), one trip per cg_r_kernel block, and two LDS copies of a plane's run within a block's 64 KiB.
+static bool cg_r_planes_geometry(const storm_hip_op *op, ResidualPlanesArgs *G, int *n_blocks) {
+  storm_hip_ctx *c = op->ctx;
+  CanonTileArgs T;
+  int nbt = 0;
+  if (c->opt_cg_residual_planes == 0 || !canon_tile_geometry(op, &T, &nbt)) return false;
+  const int64_t n = op->n_rows;
+  if (T.b % kStreamBlockElems != 0 || n % T.b != 0 || n / kStreamBlockElems > kMaxStreamBlocks) return false;
+  if ((int64_t)sizeof(double) * 2 * (kStreamBlockElems + 2 * T.a) + (int64_t)sizeof(uint64_t) * op->rec_words > 60 * 1024) return false;
+  G->a = T.a, G->b = T.b, G->max_gather = T.max_gather;
+  G->runs_per_plane = T.b / kStreamBlockElems;
+  G->per_xcd = (G->runs_per_plane % kNumXcd == 0 && c->opt_spmv_xcd_remap != 0) ? G->runs_per_plane / kNumXcd : 0;
+  G->planes = (int)(n / T.b);
+  // (option cg_residual_chunk is the chunk of a large lattice; a smaller one marches fewer planes per block so that the
+  //  grid still holds about cg_residual_fill blocks, as cg_march_geometry does for the step kernel)
+  const int64_t zc = std::min<int64_t>(std::max<int64_t>(c->opt_cg_residual_chunk, 2), kResidualMaxChunk);
+  const int64_t want = c->opt_cg_residual_fill;
+  const int64_t fill = want > 0 ? (int64_t)G->planes * G->runs_per_plane / want : zc;
+  G->nz = (int)std::min<int64_t>(std::min<int64_t>(zc, std::max<int64_t>(2, fill)), G->planes);
+  *n_blocks = ((G->planes + G->nz - 1) / G->nz) * G->runs_per_plane;
+  return true;
+}
+static int cg_r_planes_run(const storm_hip_op *op, const ResidualPlanesArgs &G, int n_blocks, Scal alpha, Scal beta, const double *p,
+                           SolverState *st, double *r, const double *pz_partials, int n_pz, int reverse) {
+  storm_hip_ctx *c = op->ctx;
+  const SellArgs A = lattice_args(op);
+  const size_t lds = sizeof(double) * 2 * (size_t)(kStreamBlockElems + 2 * G.a) + sizeof(uint64_t) * (size_t)A.rec_words_n;
+  const TicketArgs tk{c->d_tickets, c->d_partials, c->d_ticket_sums};
+#define PLANES_GO(HLP_, IX_)                                                                                                   \
+  hipLaunchKernelGGL((cg_r_planes_kernel<HLP_, IX_>), dim3(n_blocks), dim3(kBlock), lds, c->stream, st, r, p, A, G, alpha, beta, \
+                     pz_partials, n_pz, reverse, tk)
+  if (G.a <= kBlock) {
+    if (A.rec_idx != nullptr) PLANES_GO(1, true);
+    else PLANES_GO(1, false);
+  } else {
+    if (A.rec_idx != nullptr) PLANES_GO(2, true);
+    else PLANES_GO(2, false);
+  }
+#undef PLANES_GO
+  HIP_TRY(hipGetLastError());
+  return STORM_HIP_OK;
+}
+
 // Five streams (3 loads, 2 stores): measured best with ONE 16-byte access per stream and thread in flight
 // (tools/cg_kernels_bench.hip at 256^3: U = 1 105.6 us, U = 2 108.2, U = 4 111.4 -- and U = 8 615 us: a wave that
 // holds too many loads in flight stalls the memory pipeline), unlike the 2- and 3-stream kernels (U = 4).
@@ -1357,6 +1556,11 @@ int solve_cg_body(const FusedSolveArgs &args) {
   //  0's plain apply writes z for cg_r_kernel)
   const bool r_march = fuse_step && !rccl && cg_r_recompute_applies(op, tick);
   if (r_march) ++c->n_cg_residual_marches;
+  // (... marching over planes where the lattice allows, cg_r_planes_kernel; else cg_r_kernel's grid with gathers)
+  ResidualPlanesArgs r_planes_args;
+  int r_planes_blocks = 0;
+  const bool r_planes = r_march && cg_r_planes_geometry(op, &r_planes_args, &r_planes_blocks);
+  if (r_planes) ++c->n_cg_residual_plane_marches;
   int64_t last_enqueued = -1;
   auto enqueue_iteration = [&]() -> int {
     const int q = fuse_step ? 0 : sweep ? (int)(cur_it & 1) : 0;  // (fused: the step kernel forward, cg_r backward, always)
@@ -1404,7 +1608,10 @@ int solve_cg_body(const FusedSolveArgs &args) {
       STORM_TRY(d.finish(nb, 1, slots, STEP_NONE));
     }
     // r -= alpha z; gamma = <r,r>                     SolverCg.hpp:97,99,115
-    if (r_march_now) {
+    if (r_march_now && r_planes) {
+      STORM_TRY(cg_r_planes_run(op, r_planes_args, r_planes_blocks, host_scal(alpha), host_scal(beta), p, d.st, r, pz_partials,
+                                (int)kStage2, sweep ? 1 - q : 0));
+    } else if (r_march_now) {
       STORM_TRY(cg_r_recompute_run(op, nbv, host_scal(alpha), host_scal(beta), p, d.st, r, pz_partials, (int)kStage2, sweep ? 1 - q : 0));
     } else {
       hipLaunchKernelGGL(cg_r_kernel, dim3(nbv), dim3(kBlock), 0, c->stream, n, d.st, r, z, c->d_partials,

@@ -59,6 +59,36 @@ __device__ __forceinline__ double ticket_wave_sum(double v) {
   return wave_sum_all(v);  // (= the xor butterfly's value in every lane, bit for bit: wave_device.hpp)
 }
 
+// The top fold, by the wave that drew the last top-level ticket: total[j] = the sum of the ng group sums of value j, in
+// all lanes.
+template <int KMAX>
+__device__ __forceinline__ void ticket_fold_groups(const TicketArgs &t, int k, unsigned ng, double (&total)[KMAX]) {
+  const unsigned lane = threadIdx.x & (kWave - 1);
+  // lane i takes groups i, i + 64, ... in ascending order (the order of the sums is fixed); four groups per lane and
+  // value are loaded before the first is added
+  constexpr int kAhead = KMAX <= 4 ? 4 : 2;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) total[j] = 0.0;
+  for (unsigned i0 = lane; i0 < ng; i0 += kWave * kAhead) {
+    double v[KMAX][kAhead];
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j)
+#pragma unroll
+      for (int u = 0; u < kAhead; ++u) {
+        const unsigned i = i0 + u * kWave;
+        v[j][u] = 0.0;
+        if (j < k && i < ng) v[j][u] = __hip_atomic_load(t.part2 + (size_t)j * ng + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j)
+#pragma unroll
+      for (int u = 0; u < kAhead; ++u)
+        if (i0 + u * kWave < ng) total[j] += v[j][u];
+  }
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) total[j] = ticket_wave_sum(total[j]);
+}
+
 // Wave 0 of every block calls this (all 64 lanes) with the block's partials `mine[0 .. k)` (k <= KMAX).
 // Returns true in wave 0 of exactly one block, the last to arrive, with total[j] valid in all lanes.
 template <int KMAX>
@@ -99,29 +129,87 @@ __device__ __forceinline__ bool ticket_reduce_wave0(const TicketArgs &t, const d
   }
   go = __shfl(go, 0, kWave);
   if (!go) return false;
-  // lane i takes groups i, i + 64, ... in ascending order (the order of the sums is fixed); four groups per lane and
-  // value are loaded before the first is added
-  constexpr int kAhead = KMAX <= 4 ? 4 : 2;
-#pragma unroll
-  for (int j = 0; j < KMAX; ++j) total[j] = 0.0;
-  for (unsigned i0 = lane; i0 < ng; i0 += kWave * kAhead) {
-    double v[KMAX][kAhead];
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j)
-#pragma unroll
-      for (int u = 0; u < kAhead; ++u) {
-        const unsigned i = i0 + u * kWave;
-        v[j][u] = 0.0;
-        if (j < k && i < ng) v[j][u] = __hip_atomic_load(t.part2 + (size_t)j * ng + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j)
-#pragma unroll
-      for (int u = 0; u < kAhead; ++u)
-        if (i0 + u * kWave < ng) total[j] += v[j][u];
+  ticket_fold_groups<KMAX>(t, k, ng, total);
+  return true;
+}
+
+// ticket_reduce_wave0 for a block that stands for SEVERAL virtual blocks of a grid of nb (a marching kernel that forms,
+// plane by plane, the partials a one-trip streaming kernel's blocks would have formed): every lane of wave 0 that is `on`
+// holds the partial `mine` of virtual block bxv (one value per block; the lanes' bxv all differ).  The partials are published by all
+// lanes at once, then every group takes ONE ticket draw for all the slots this block owns in it ("old + count == group
+// size" is the last), and the group sums and the top fold are ticket_reduce_wave0's: the same values in the same
+// order, whichever hardware block formed them.  Round trips to memory do not grow with the number of slots: every
+// step is issued for all its lanes (or, the group loads, four groups) at a time.
+__device__ __forceinline__ bool ticket_reduce_wave0_slots(const TicketArgs &t, double mine, bool on, unsigned bxv, unsigned nb,
+                                                          double *total) {
+  const unsigned lane = threadIdx.x & (kWave - 1);
+  const unsigned g = bxv / kTicketGroup, ng = (nb + kTicketGroup - 1) / kTicketGroup;
+  const unsigned gsize = (nb - g * kTicketGroup) < (unsigned)kTicketGroup ? (nb - g * kTicketGroup) : (unsigned)kTicketGroup;
+  if (on) {
+    const double v[1] = {mine};
+    ticket_publish<1>(t.part1 + bxv, nb, v, 1);
   }
+  // the lowest lane of every group draws for all of the block's slots in it
+  int count = 0;
+  bool leader = false;
+  for (unsigned long long rest = __ballot(on); rest != 0ull;) {
+    const int first = __ffsll((long long)rest) - 1;
+    const unsigned long long same = __ballot(on && g == (unsigned)__shfl((int)g, first, kWave));
+    if ((int)lane == first) leader = true, count = __popcll(same);
+    rest &= ~same;
+  }
+  int go = 0;
+  if (leader) {
+    int *c = t.cnt + (size_t)(1 + g) * kTicketStride;
+    if (__hip_atomic_fetch_add(c, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + count == (int)gsize) {
+      __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      go = 1;
+    }
+  }
+  // the groups this block completed: their sums (ticket_reduce_wave0's loads and wave sum) into the drawing lanes
+  unsigned long long fin = __ballot(go != 0);
+  if (fin == 0ull) return false;
+  const int n_fin = __popcll(fin);
+  double gsum = 0.0;
+  while (fin != 0ull) {
+    int at[4];
+    double gp[4];
 #pragma unroll
-  for (int j = 0; j < KMAX; ++j) total[j] = ticket_wave_sum(total[j]);
+    for (int j = 0; j < 4; ++j) {
+      at[j] = fin != 0ull ? __ffsll((long long)fin) - 1 : -1;
+      if (at[j] >= 0) fin &= fin - 1ull;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      gp[j] = 0.0;
+      if (at[j] >= 0) {
+        const unsigned gj = (unsigned)__shfl((int)g, at[j], kWave), nj = (unsigned)__shfl((int)gsize, at[j], kWave);
+        if (lane < nj)
+          gp[j] = __hip_atomic_load(t.part1 + (size_t)gj * kTicketGroup + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double sj = ticket_wave_sum(gp[j]);
+      if ((int)lane == at[j]) gsum = sj;
+    }
+  }
+  if (go) {
+    const double v[1] = {gsum};
+    ticket_publish<1>(t.part2 + g, ng, v, 1);
+  }
+  go = 0;
+  if (lane == 0) {
+    if (__hip_atomic_fetch_add(t.cnt, n_fin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + n_fin == (int)ng) {
+      __hip_atomic_store(t.cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      go = 1;
+    }
+  }
+  go = __shfl(go, 0, kWave);
+  if (!go) return false;
+  double tot[1];
+  ticket_fold_groups<1>(t, 1, ng, tot);
+  *total = tot[0];
   return true;
 }
 
