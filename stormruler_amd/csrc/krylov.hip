@@ -1698,7 +1698,7 @@ int begin_solve(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
   if (k->method == STORM_HIP_BICGSTAB_L || k->method == STORM_HIP_IDRS)
     STORM_REQUIRE(k->inner <= 48, "krylov: num_inner_iterations = %d too large for this method (<= 48)", k->inner);
   if (k->method == STORM_HIP_IDRS)
-    STORM_REQUIRE(c->comm == nullptr, "krylov: IDR(s) draws its shadow space with fill_randomly, single rank only");
+    STORM_REQUIRE(c->n_ranks == 1, "krylov: IDR(s) draws its shadow space with fill_randomly, single rank only");
   k->reset_prog(), k->red_pending = false;
   k->dp = nullptr;
   k->applies = k->pre_applies = 0;

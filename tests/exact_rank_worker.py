@@ -5,7 +5,8 @@ box (integer stencil coefficients, tests/exact_ref.py) and connects the host-sta
 STORM_TRANSPORT=ipc, the peer-window transport.  On integer data every all-reduce is exact whatever its order, so each
 rank must reproduce the closed forms of the whole box: the global <b,b>, <b,z> and z = A b bitwise, CG's x1 =
 fl(fl(rr/pz) * b_local) bitwise, history[0] bitwise and history[1] of CG, BiCGStab and GMRES(30) within the derived
-tolerance -- on fp64 records and on format 4 (mixed records on a slab)."""
+tolerance -- on fp64 records and on format 4 (mixed records on a slab).  On the host-staged transport the engine's CGS
+and TFQMR also run to K = 2 against exact_ref.Pins of the whole box."""
 import json
 import math
 import os
@@ -36,6 +37,17 @@ def _solve(ctx, cls, mat, b, n, n_halo, counted=True, **knobs):
     return s, x.to_numpy(), ctx.counter("cg_fused_steps") - before[1]
 
 
+def _engine_solve(ctx, cls, mat, b, n, n_halo, iters):
+    s = cls()
+    s.num_iterations, s.absolute_error_tolerance, s.relative_error_tolerance = iters, 0.0, 0.0
+    s.record_history = True
+    x = api.DeviceVector(ctx, n, n_halo)
+    before = ctx.counter("engine_solves")
+    s.solve(x, b, api.HipStencilOperator(mat, -1.0, 0.0))
+    assert ctx.counter("engine_solves") == before + 1 and s.iteration == iters and s.path_fallback == 0
+    return s
+
+
 def main():
     nx, ny, nzl = (int(v) for v in sys.argv[1:4])
     dist.init_process_group("gloo")
@@ -59,6 +71,12 @@ def main():
     b_loc = b_glob[loc.global_id[:n]]
     z_loc = er.int_apply(shape, b_glob, k0, k1)
     report = {"rank": rank, "world": world, "nbrs": [int(r) for r in plan.nbr_rank], "fused": {}, "history": {}}
+    pins = {}
+    if transport == "host":  # the engine's CGS and TFQMR to K = 2 against the exact reference of the whole box
+        from oracle import oracle
+
+        g, basis = er.unit_box(mesh, *shape), er.Basis(shape, b_glob)
+        pins = {kind: er.Pins(oracle, g, shape, b_glob, kind, fs=fs, basis=basis) for kind in ("cgs", "tfqmr")}
 
     ctx.set_option("spmv_canon_tile_min_rows", 0)  # (the lattice kernels on slabs this small)
     for fmt in (0, 4):
@@ -90,6 +108,11 @@ def main():
         assert er.close(s.history[1], fs.gmres_h1, fs.gmres_tol), ("gmres h1", fmt, s.history[1], fs.gmres_h1)
         report["history"][f"gmres{fmt}"] = [float(v) for v in s.history]
         assert math.isfinite(s.history[1])
+        for kind, cls in (("cgs", api.CgsSolver), ("tfqmr", api.TfqmrSolver)):
+            if kind in pins:
+                s = _engine_solve(ctx, cls, mat, b, n, n_halo, pins[kind].K)
+                pins[kind].check(s.history, f"{kind} rank {rank} format {fmt}")
+                report["history"][f"{kind}{fmt}"] = [float(v) for v in s.history]
         mat.close()
     ctx.sync()
     td.barrier()  # nobody unmaps / frees a peer window another rank's kernels may still write to

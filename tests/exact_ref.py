@@ -9,9 +9,15 @@ With x0 = 0 and r0 = b, the first iteration of CG, GMRES(m) and BiCGStab has clo
 (``first_step``); the residual norms after it are held to a tolerance derived from the data and the fold depth
 (``tolerance``), never tuned to an observed error.
 
+The engine's other methods -- CGS, TFQMR(1), BiCGStab(l), IDR(s), Richardson, and the Jacobi-preconditioned solves --
+are restated from the reference's headers on coefficient columns over the integer Krylov chain, in Fractions or
+high-precision decimals (``Space`` and the method functions); ``Pins`` turns their exact histories into the values and
+tolerances the tests assert.
+
 Plain module, not a conftest: the tests import it by name.
 """
 import math
+from decimal import Decimal, localcontext
 from fractions import Fraction
 
 import numpy as np
@@ -32,6 +38,28 @@ def int_apply(shape, x, k0=0, k1=None):
     k1 = nz if k1 is None else k1
     v = np.asarray(x, dtype=np.int64).reshape(nz, ny, nx)
     assert int(np.abs(v).max(initial=0)) * 12 < (1 << 62)
+    return _stencil(v)[k0:k1].reshape(-1)
+
+
+def exact_apply(shape, x):
+    """``(-L) x`` of the whole unit box for an object array (Python ints, Fractions, Decimals): no range limit."""
+    nx, ny, nz = shape
+    return _stencil(np.asarray(x, dtype=object).reshape(nz, ny, nx)).reshape(-1)
+
+
+def int_diagonal(shape):
+    """The diagonal of ``-L`` on the unit box: per axis 2, plus 1 for every wall the cell touches (6 ... 9, or more
+    on a box one cell thick)."""
+    nx, ny, nz = shape
+    d = np.zeros((nz, ny, nx), np.int64)
+    for ax, n in ((2, nx), (1, ny), (0, nz)):
+        i = np.arange(n)
+        w = 2 + (i == 0) + (i == n - 1)
+        d += w.reshape([n if a == ax else 1 for a in range(3)])
+    return d.reshape(-1)
+
+
+def _stencil(v):
     out = np.zeros_like(v)
     for ax in range(3):
         n = v.shape[ax]
@@ -47,7 +75,7 @@ def int_apply(shape, x, k0=0, k1=None):
         first[ax], last[ax] = 0, n - 1
         out[tuple(first)] += 2 * v[tuple(first)]  # a wall: ghost value 0 at half the distance, weight 2
         out[tuple(last)] += 2 * v[tuple(last)]
-    return out[k0:k1].reshape(-1)
+    return out
 
 
 def int_vector(n, seed, lo=-1000, hi=1000):
@@ -99,10 +127,10 @@ def fold_depth(n):
     return 64 + -(-nblocks // 256)
 
 
-def tolerance(n, magnitude, h1_sq):
+def tolerance(n, magnitude, h1_sq, c=16):
     """Relative tolerance of a residual norm h1 after one iteration, from the data and the fold depth:
 
-        tol = 2^-53 * (D + 16 * sqrt(M) / h1)
+        tol = 2^-53 * (D + c * sqrt(M) / h1),   c = 16 for the three closed forms below
 
     h1^2 is the fold of the squares of the residual's computed elements: the fold adds at most D roundings of
     relative size 2^-53 to h1^2 (half that to h1).  Each element r_i is a combination of terms -- b and a z for CG
@@ -115,7 +143,7 @@ def tolerance(n, magnitude, h1_sq):
     At or below 1e-12 on every case the tests use (asserted): a dropped or doubled
     row moves these values by ~1/n, orders of magnitude more."""
     q = Fraction(magnitude) / Fraction(h1_sq)
-    tol = (fold_depth(n) + 16.0 * math.sqrt(float(q))) * 2.0 ** -53
+    tol = (fold_depth(n) + c * math.sqrt(float(q))) * 2.0 ** -53
     assert tol <= 1e-12, f"tolerance {tol:.3e} above 1e-12: the case cannot separate a dropped row from rounding"
     return tol
 
@@ -160,3 +188,780 @@ class FirstStep:
 
 def close(value, exact, tol):
     return abs(value - exact) <= tol * exact
+
+
+# ---- the Krylov methods in coefficient form -------------------------------------------------------------------------
+#
+# With x0 = 0 every vector CGS, TFQMR, BiCGStab(l), IDR(s), Richardson, CG and GMRES form lies in the span of a chain
+# of integer vectors: W_0 = b, W_{t+1} = A W_t without a preconditioner; with the Jacobi preconditioner P = diag(dinv)
+# the chain alternates W_{t+1} = D' W_t (t even) and A W_t (t odd), D' = 2^56 dinv an integer diagonal (fl(1/d) is a
+# dyadic rational for d in {6, 7, 8, 9}), so that P W_t = 2^-56 W_{t+1}.  A vector is its coefficient column over the
+# chain (plus, for IDR(s), over its fixed dyadic shadow vectors); applying A or P shifts the column by one place, and
+# <u, v> = c_u^T G c_v with the Gram matrix G of the chain formed exactly in Python integers.  The method bodies below
+# restate the reference's init / iterate on such columns (the header lines are cited on every statement); the scalars
+# are Fractions where the method is rational and decimals of PREC digits where it takes a square root.  They are
+# written against a small vector interface (``b``, ``zero``, ``A``, ``P``, ``dot``, ``fixed``), so the same bodies run
+# on ``Space`` (coefficient columns) and ``ElemSpace`` (every element a Fraction / decimal, the brute force).
+
+PRE_SHIFT = 56  # 2^56 * fl(1/d) is an integer for d in {6, 7, 8, 9} (1/9 has the finest last place, 2^-56)
+PREC = 80  # decimal digits wherever a method takes a square root
+
+
+def _dec(q):
+    """A Fraction (or int) as a decimal of the current context: one rounding at 10^-PREC relative."""
+    if isinstance(q, Decimal):
+        return q
+    q = Fraction(q)
+    return Decimal(q.numerator) / Decimal(q.denominator)
+
+
+def _mul(a, b):
+    if isinstance(a, Decimal) != isinstance(b, Decimal):
+        return _dec(a) * _dec(b)
+    return a * b
+
+
+def _add(a, b):
+    if isinstance(a, Decimal) != isinstance(b, Decimal):
+        return _dec(a) + _dec(b)
+    return a + b
+
+
+def _sdiv(x, y):
+    """safe_divide (MathUtils.hpp:50-52)."""
+    return 0 * x if y == 0 else x / y
+
+
+class Vec:
+    """A vector as its coefficient column {chain index (>= 0) or fixed vector (< 0): coefficient}."""
+    __slots__ = ("c",)
+
+    def __init__(self, c):
+        self.c = c
+
+    def _comb(self, o, sign):
+        c = dict(self.c)
+        for k, v in o.c.items():
+            c[k] = _add(c[k], sign * v) if k in c else sign * v
+        return Vec(c)
+
+    def __add__(self, o):
+        return self._comb(o, 1)
+
+    def __sub__(self, o):
+        return self._comb(o, -1)
+
+    def __rmul__(self, a):
+        return Vec({k: _mul(a, v) for k, v in self.c.items()})
+
+    def __truediv__(self, a):
+        return Vec({k: _dec(v) / a if isinstance(a, Decimal) else v / a for k, v in self.c.items()})
+
+
+def _limbs(a, bits):
+    """Signed limbs of an int64 vector: a = sum_k 2^(bits k) limb_k, |limb_k| < 2^bits."""
+    s, m = np.sign(a), np.abs(a)
+    out = []
+    while True:
+        out.append(s * (m & ((1 << bits) - 1)))
+        m = m >> bits
+        if not m.any():
+            return out
+
+
+def big_dot(u, v):
+    """<u, v> as a Python int for integer vectors of any size: object arrays directly, int64 by limbs small enough that
+    no int64 partial sum can wrap."""
+    if u.dtype == object or v.dtype == object:
+        return int(np.dot(u.astype(object), v.astype(object)))
+    bits = (62 - max(1, u.size).bit_length()) // 2
+    lu, lv = _limbs(u, bits), _limbs(v, bits)
+    return sum(int(np.dot(a, b)) << (bits * (i + j)) for i, a in enumerate(lu) for j, b in enumerate(lv))
+
+
+class Basis:
+    """The integer chain of one problem (shape, b, optional Jacobi dinv), grown on demand, and its Gram entries,
+    cached: one per problem serves every method, side and number type."""
+
+    def __init__(self, shape, b, dinv=None):
+        self.shape, self.n = tuple(shape), int(np.asarray(b).size)
+        self.pre = dinv is not None
+        if self.pre:
+            dinv = np.asarray(dinv, np.float64)
+            assert np.array_equal(dinv, 1.0 / int_diagonal(shape)), "dinv is not fl(1 / diag(A))"
+            dp = dinv * 2.0 ** PRE_SHIFT  # exact: a power-of-two scaling
+            assert np.all(dp == np.floor(dp)) and dp.max() < 2.0 ** 62
+            self.dp = dp.astype(np.int64).astype(object)
+            self.W = [np.asarray(b, np.int64).astype(object)]
+        else:
+            self.W = [np.asarray(b, np.int64)]
+        self.R = []  # fixed dyadic vectors: (integer numerators as objects, common power-of-two denominator)
+        self._fixed, self._g = {}, {}
+
+    def grow(self, t):
+        while len(self.W) <= t:
+            w = self.W[-1]
+            if self.pre and len(self.W) % 2 == 1:
+                self.W.append(self.dp * w)
+            elif w.dtype == object:
+                self.W.append(exact_apply(self.shape, w))
+            else:
+                self.W.append(int_apply(self.shape, w))  # (asserts that int64 holds it)
+
+    def fixed(self, values):
+        """Register a fixed fp64 vector (a dyadic rational per element); returns its key (the same for the same bits)."""
+        values = np.ascontiguousarray(values, np.float64)
+        if values.tobytes() not in self._fixed:
+            ratios = [float(v).as_integer_ratio() for v in values]
+            den = max(d for _, d in ratios)
+            self.R.append((np.array([p * (den // d) for p, d in ratios], dtype=object), den))
+            self._fixed[values.tobytes()] = -len(self.R)
+        return self._fixed[values.tobytes()]
+
+    def _vec(self, k):
+        if k >= 0:
+            self.grow(k)
+            return self.W[k], 1
+        return self.R[-1 - k]
+
+    def gram(self, i, j):
+        key = (min(i, j), max(i, j))
+        if key not in self._g:
+            (u, du), (v, dv) = self._vec(i), self._vec(j)
+            self._g[key] = Fraction(big_dot(u, v), du * dv)
+        return self._g[key]
+
+    def last_row(self, k):
+        u, d = self._vec(k)
+        return Fraction(int(u[-1]), d)
+
+
+class Space:
+    """The coefficient-form vectors of a Basis.  ``drop_at``: the ordinal of one dot product (counted from 1 in call
+    order) that leaves the last row out -- the defect a lost partial sum would make."""
+
+    def __init__(self, basis, decimal=False):
+        self.basis, self.decimal = basis, decimal
+        self.one = Decimal(1) if decimal else Fraction(1)
+        self.ndots, self.drop_at = 0, None
+
+    def b(self):
+        return Vec({0: self.one})
+
+    def zero(self):
+        return Vec({})
+
+    def A(self, v):
+        for k in v.c:
+            assert k >= 0 and (not self.basis.pre or k % 2 == 1), "A applies to chain vectors of the other kind"
+        return Vec({k + 1: c for k, c in v.c.items()})
+
+    def P(self, v):
+        assert self.basis.pre
+        for k in v.c:
+            assert k >= 0 and k % 2 == 0, "P applies to chain vectors of the other kind"
+        s = Fraction(1, 1 << PRE_SHIFT)
+        return Vec({k + 1: _mul(c, s) for k, c in v.c.items()})
+
+    def fixed(self, values):
+        return Vec({self.basis.fixed(values): self.one})
+
+    def dot(self, u, v):
+        self.ndots += 1
+        drop = self.ndots == self.drop_at
+        s = 0
+        for i, ci in u.c.items():
+            for j, cj in v.c.items():
+                g = self.basis.gram(i, j)
+                if drop:
+                    g -= self.basis.last_row(i) * self.basis.last_row(j)
+                s += _mul(_mul(ci, cj), g)
+        return _dec(s) if self.decimal else Fraction(s)
+
+    def magnitude(self, v):
+        """M: the sum of the squared norms of the terms c_t W_t that form v."""
+        return sum((_mul(_mul(c, c), self.basis.gram(k, k)) for k, c in v.c.items()), 0)
+
+    def materialize(self, v):
+        """The exact elements of a vector with Fraction coefficients, each rounded once to fp64."""
+        den = 1
+        for k, c in v.c.items():
+            den = math.lcm(den, Fraction(c).denominator * self.basis._vec(k)[1])
+        acc = np.zeros(self.basis.n, dtype=object)
+        for k, c in v.c.items():
+            u, d = self.basis._vec(k)
+            acc = acc + int(Fraction(c) * den / d) * u.astype(object)
+        return np.array([int(a) / den for a in acc])
+
+
+class ElemSpace:
+    """The same interface with every element held exactly (Fraction) or in PREC-digit decimals: the brute force."""
+
+    def __init__(self, shape, b, dinv=None, decimal=False):
+        self.shape, self.decimal = tuple(shape), decimal
+        conv = _dec if decimal else Fraction
+        with localcontext() as ctx:
+            ctx.prec = PREC
+            self._b = np.array([conv(int(v)) for v in b], dtype=object)
+            self._dinv = None if dinv is None else np.array([conv(Fraction(float(v))) for v in dinv], dtype=object)
+        self.ndots, self.drop_at = 0, None
+
+    def b(self):
+        return self._b.copy()
+
+    def zero(self):
+        return np.zeros(self._b.size, dtype=object)
+
+    def A(self, v):
+        return exact_apply(self.shape, v)
+
+    def P(self, v):
+        return self._dinv * v
+
+    def fixed(self, values):
+        conv = _dec if self.decimal else Fraction
+        return np.array([conv(Fraction(float(x))) for x in values], dtype=object)
+
+    def dot(self, u, v):
+        self.ndots += 1
+        n = u.size - (1 if self.ndots == self.drop_at else 0)
+        s = sum((u[i] * v[i] for i in range(n)), 0)
+        return _dec(s) if self.decimal else Fraction(s)
+
+
+class Run:
+    """What a method restated on a space gives: the exact squares of history[0..K] (``hist_sq``), x_K, and per
+    history entry the vectors whose norms formed it (``feeds``: the floor of the tolerance reads their terms)."""
+
+    def __init__(self, hist_sq, x, feeds):
+        self.hist_sq, self.x, self.feeds = hist_sq, x, feeds
+
+    @property
+    def history(self):
+        with localcontext() as ctx:
+            ctx.prec = PREC
+            return [float(_dec(h).sqrt()) for h in self.hist_sq]
+
+
+def _ops(sp, side):
+    """``s <- op(y)`` with its intermediate z, as every method writes it: left P(z <- A y), right A(z <- P y)."""
+    def op(y):
+        if side == "left":
+            z = sp.A(y)
+            return sp.P(z), z
+        if side == "right":
+            z = sp.P(y)
+            return sp.A(z), z
+        return sp.A(y), None
+    return op
+
+
+def cgs(sp, K, side=None, defect=None):
+    """SolverCgs.hpp:57-174.  ``defect`` (the separation tests only): "stale_beta" forms beta from the rho of the
+    previous pass alone, "shadow_r" takes r for r~ in the shadow dots."""
+    b = sp.b()
+    r = b  # :80 (x0 = 0)
+    if side == "left":
+        r = sp.P(r)  # :81-84
+    rt = r  # :85
+    shadow = (lambda: r) if defect == "shadow_r" else (lambda: rt)
+    rho = sp.dot(rt, r)  # :86
+    x, hist, feeds = sp.zero(), [rho], [[r]]
+    for it in range(K):
+        if it == 0:
+            u = r  # :113-115
+            p = u
+        else:
+            rho_bar, rho = rho, sp.dot(shadow(), r)  # :117-118
+            beta = _sdiv(rho_bar if defect == "stale_beta" else rho, rho_bar)  # :119
+            u = r + beta * q  # :120
+            p = u + beta * (q + beta * p)  # :121
+        if side == "left":
+            q = sp.A(p)  # :136
+            v = sp.P(q)
+        elif side == "right":
+            q = sp.P(p)  # :137
+            v = sp.A(q)
+        else:
+            v = sp.A(p)  # :138
+        alpha = _sdiv(rho, sp.dot(shadow(), v))  # :139
+        q = u - alpha * v  # :140
+        v = u + q  # :141
+        if side == "left":
+            x = x + alpha * v  # :160-162
+            u = sp.A(v)
+            v = sp.P(u)
+            r = r - alpha * v
+        elif side == "right":
+            u = sp.P(v)  # :164-166
+            v = sp.A(u)
+            x = x + alpha * u
+            r = r - alpha * v
+        else:
+            u = sp.A(v)  # :168-170
+            x = x + alpha * v
+            r = r - alpha * u
+        hist.append(sp.dot(r, r))  # :173
+        feeds.append([r])
+    return Run(hist, x, feeds)
+
+
+def tfqmr(sp, K, side=None, l1=False, defect=None):
+    """SolverTfqmr.hpp:44-209 (``l1``: TFQMR1).  Rational throughout in the squares: tau^2, omega^2 and the rotation's
+    cs^2 = tau^2 / (tau^2 + omega^2), sn^2 = omega^2 / (tau^2 + omega^2) (sym_ortho, MathUtils.hpp:165-179); only the
+    history takes a root.  ``defect`` as for ``cgs``."""
+    op = _ops(sp, side)
+    d = x = sp.zero()  # :74-78 (x0 = 0: d = x = 0 for both variants)
+    y = sp.b()  # :79
+    if side == "left":
+        y = sp.P(y)  # :80-83
+    u = y  # :84
+    rt = u  # :85
+    shadow = (lambda: u) if defect == "shadow_r" else (lambda: rt)
+    rho = sp.dot(rt, u)  # :86
+    tau2 = rho
+    hist, feeds = [tau2], [[u]]
+    for it in range(K):
+        if it == 0:
+            s, z = op(y)  # :128-130
+            v = s  # :131
+        else:
+            rho_bar, rho = rho, sp.dot(shadow(), u)  # :133-134
+            beta = _sdiv(rho_bar if defect == "stale_beta" else rho, rho_bar)  # :135
+            v = s + beta * v  # :136
+            y = u + beta * y  # :137
+            s, z = op(y)  # :138-140
+            v = s + beta * v  # :141
+        alpha = _sdiv(rho, sp.dot(shadow(), v))  # :173
+        fed = []
+        for m in (0, 1):
+            u = u - alpha * s  # :175
+            d = d + alpha * (z if side == "right" else y)  # :176
+            om2 = sp.dot(u, u)  # :177
+            fed.append(u)
+            if l1:
+                if om2 < tau2:  # :178-179
+                    tau2, x = om2, d
+            else:
+                h2 = tau2 + om2  # :181-184
+                cs2, sn2 = (tau2 / h2, om2 / h2) if h2 > 0 else (sp.one, 0 * sp.one)
+                tau2 = om2 * cs2
+                x = x + cs2 * d
+                d = sn2 * d
+            if m == 0:
+                y = y - alpha * v  # :187
+                s, z = op(y)  # :188-190
+        hist.append(tau2 if l1 else tau2 * (2 * it + 3))  # :202-206
+        feeds.append(fed)
+    return Run(hist, x, feeds)
+
+
+def bicgstab_l(sp, K, l, pre=False, defect=None):
+    """SolverBiCgStab.hpp:194-375, BiCGStab(l); a preconditioner is always applied on the left (:226-229, :275-279,
+    :295-299).  ``defect`` as for ``cgs``."""
+    b = sp.b()
+    r, u = [b] + [sp.zero()] * l, [sp.zero()] * (l + 1)  # :208-211, :224-225 (x0 = 0)
+    if pre:
+        r[0] = sp.P(r[0])  # :226-229
+    rt = r[0]  # :230
+    shadow = (lambda: r[0]) if defect == "shadow_r" else (lambda: rt)
+    rho = sp.dot(rt, r[0])  # :231
+    x, hist, feeds = sp.zero(), [rho], [[r[0]]]
+    alpha = None
+
+    def apply(v):
+        return sp.P(sp.A(v)) if pre else sp.A(v)
+
+    tau, sigma, gbar, gam, gbb = {}, {}, {}, {}, {}
+    for it in range(K):
+        j = it % l  # Solver.hpp:239
+        if it == 0:
+            u[0] = r[0]  # :265-266
+        else:
+            rho_bar, rho = rho, sp.dot(shadow(), r[j])  # :268-269
+            beta = _sdiv(alpha * (rho_bar if defect == "stale_beta" else rho), rho_bar)  # :270
+            for i in range(j + 1):
+                u[i] = r[i] - beta * u[i]  # :271-273
+        u[j + 1] = apply(u[j])  # :275-279
+        alpha = _sdiv(rho, sp.dot(shadow(), u[j + 1]))  # :280
+        for i in range(j + 1):
+            r[i] = r[i] - alpha * u[i + 1]  # :281-283
+        x = x + alpha * u[0]  # :294
+        r[j + 1] = apply(r[j])  # :295-299
+        if j == l - 1:
+            for jj in range(1, l + 1):  # :313-322
+                for i in range(1, jj):
+                    tau[i, jj] = _sdiv(sp.dot(r[i], r[jj]), sigma[i])
+                    r[jj] = r[jj] - tau[i, jj] * r[i]
+                sigma[jj] = sp.dot(r[jj], r[jj])
+                gbar[jj] = _sdiv(sp.dot(r[0], r[jj]), sigma[jj])
+            omega = gam[l] = gbar[l]  # :339
+            rho = rho * -omega
+            for jj in range(l - 1, 0, -1):  # :340-345
+                gam[jj] = gbar[jj]
+                for i in range(jj + 1, l + 1):
+                    gam[jj] = gam[jj] - tau[jj, i] * gam[i]
+            for jj in range(1, l):  # :346-351
+                gbb[jj] = gam[jj + 1]
+                for i in range(jj + 1, l):
+                    gbb[jj] = gbb[jj] + tau[jj, i] * gam[i + 1]
+            x = x + gam[1] * r[0]  # :364-366
+            r[0] = r[0] - gbar[l] * r[l]
+            u[0] = u[0] - gam[l] * u[l]
+            for jj in range(1, l):  # :367-371
+                x = x + gbb[jj] * r[jj]
+                r[0] = r[0] - gbar[jj] * r[jj]
+                u[0] = u[0] - gam[jj] * u[jj]
+        hist.append(sp.dot(r[0], r[0]))  # :374
+        feeds.append([r[0]])
+    return Run(hist, x, feeds)
+
+
+def richardson(sp, K, omega, pre=False):
+    """SolverRichardson.hpp:51-96: the preconditioner, if any, acts on the residual (left) whatever the side."""
+    b = sp.b()
+    x, r = sp.zero(), b  # :65 (x0 = 0)
+    if pre:
+        r = sp.P(r)  # :66-69
+    hist, feeds = [sp.dot(r, r)], [[r]]  # :71
+    for _ in range(K):
+        x = x + omega * r  # :88
+        r = b - sp.A(x)  # :89
+        if pre:
+            r = sp.P(r)  # :90-93
+        hist.append(sp.dot(r, r))  # :95
+        feeds.append([r])
+    return Run(hist, x, feeds)
+
+
+def cg(sp, K, pre=False):
+    """SolverCg.hpp:54-126; the preconditioner has no side (z = P r)."""
+    b = sp.b()
+    x, r = sp.zero(), b  # :73 (x0 = 0)
+    if pre:
+        z = sp.P(r)  # :74-77
+        p = z
+        gamma = sp.dot(r, z)
+    else:
+        p = r  # :79-80
+        gamma = sp.dot(r, r)
+    hist, feeds = [sp.dot(r, r) if pre else gamma], [[r]]  # :83
+    for _ in range(K):
+        z = sp.A(p)  # :96
+        alpha = _sdiv(gamma, sp.dot(p, z))  # :97
+        x = x + alpha * p  # :98
+        r = r - alpha * z  # :99
+        gamma_bar = gamma  # :110
+        if pre:
+            z = sp.P(r)  # :111-113
+            gamma = sp.dot(r, z)
+        else:
+            gamma = sp.dot(r, r)  # :115
+        beta = _sdiv(gamma, gamma_bar)  # :122
+        p = (z if pre else r) + beta * p  # :123
+        hist.append(sp.dot(r, r) if pre else gamma)  # :125
+        feeds.append([r])
+    return Run(hist, x, feeds)
+
+
+def _root(v):
+    return _dec(v).sqrt()
+
+
+def idrs(sp, K, s, shadow=(), side=None):
+    """SolverIdrs.hpp:62-283, IDR(s), in decimals (p_0 = r / |r| and the normalisations take roots); every dot is
+    exact before its one conversion.  ``shadow``: the s - 1 fp64 vectors fill_randomly draws for p_1 ... p_{s-1}."""
+    op = _ops(sp, side)
+    with localcontext() as ctx:
+        ctx.prec = PREC
+        r = sp.b()  # :94 (x0 = 0)
+        if side == "left":
+            r = sp.P(r)  # :95-98
+        phi, gamma, mu = [Decimal(0)] * s, [Decimal(0)] * s, {}
+        phi[0] = _root(sp.dot(r, r))  # :99
+        x, hist, feeds = sp.zero(), [phi[0] * phi[0]], [[r]]
+        g, u, p = [sp.zero()] * s, [sp.zero()] * s, [None] * s
+        omega = None
+        for it in range(K):
+            k = it % s  # Solver.hpp:239
+            if k == 0:
+                if it == 0:
+                    omega = mu[0, 0] = Decimal(1)  # :131
+                    p[0] = r / phi[0]  # :132
+                    for i in range(1, s):  # :133-141
+                        mu[i, i], phi[i] = Decimal(1), Decimal(0)
+                        p[i] = sp.fixed(shadow[i - 1])
+                        for j in range(i):
+                            mu[i, j] = Decimal(0)
+                            p[i] = p[i] - _dec(sp.dot(p[i], p[j])) * p[j]
+                        p[i] = p[i] / _root(sp.dot(p[i], p[i]))
+                else:
+                    for i in range(s):  # :143-145
+                        phi[i] = _dec(sp.dot(p[i], r))
+            for i in range(k, s):  # :167-173
+                gamma[i] = phi[i]
+                for j in range(k, i):
+                    gamma[i] -= mu[i, j] * gamma[j]
+                gamma[i] /= mu[i, i]
+            v = r - gamma[k] * g[k]  # :195
+            for i in range(k + 1, s):
+                v = v - gamma[i] * g[i]  # :196-198
+            if side == "right":
+                v = sp.P(v)  # :199-202
+            u[k] = omega * v + gamma[k] * u[k]  # :203
+            for i in range(k + 1, s):
+                u[k] = u[k] + gamma[i] * u[i]  # :204-206
+            g[k] = sp.P(sp.A(u[k])) if side == "left" else sp.A(u[k])  # :207-211
+            for i in range(k):  # :221-226
+                a = _sdiv(_dec(sp.dot(p[i], g[k])), mu[i, i])
+                u[k] = u[k] - a * u[i]
+                g[k] = g[k] - a * g[i]
+            for i in range(k, s):
+                mu[i, k] = _dec(sp.dot(p[i], g[k]))  # :234-236
+            beta = _sdiv(phi[k], mu[k, k])  # :244
+            x = x + beta * u[k]  # :245
+            r = r - beta * g[k]  # :246
+            for i in range(k + 1, s):
+                phi[i] -= beta * mu[i, k]  # :254-256
+            if k == s - 1:
+                v, z = op(r)  # :272-274
+                omega = _sdiv(_dec(sp.dot(v, r)), _dec(sp.dot(v, v)))  # :276-277
+                x = x + omega * (z if side == "right" else r)  # :278
+                r = r - omega * v  # :279
+            hist.append(_dec(sp.dot(r, r)))  # :282
+            feeds.append([r])
+    return Run(hist, x, feeds)
+
+
+def fgmres(sp, K, m):
+    """SolverGmres.hpp:51-249 with Flexible = true: a preconditioner is applied on the right whatever the side
+    (:69-70, :125-130), z_k = P q_k kept per k (:152-153), x += sum beta_i z_i at the end of a cycle (:237-240)."""
+    with localcontext() as ctx:
+        ctx.prec = PREC
+        b = sp.b()
+        x = sp.zero()
+        q, z, H, cs, sn, beta = [None] * (m + 1), [None] * m, {}, [None] * m, [None] * m, [Decimal(0)] * (m + 1)
+        hist, feeds = [], []
+        for it in range(K + 1):
+            if it == 0 or it % m == 0:  # outer_init (:82-88) and inner_init (:110-116) alike
+                q[0] = b - sp.A(x) if it else b
+                beta[0] = _root(sp.dot(q[0], q[0]))
+                if it == 0:
+                    hist.append(beta[0] * beta[0])
+                    feeds.append([q[0]])
+                q[0] = q[0] / beta[0]
+            if it == K:
+                break
+            k = it % m
+            z[k] = sp.P(q[k])  # :152-153
+            w = sp.A(z[k])
+            for i in range(k + 1):  # :157-160
+                H[i, k] = _dec(sp.dot(w, q[i]))
+                w = w - H[i, k] * q[i]
+            H[k + 1, k] = _root(sp.dot(w, w))  # :161
+            q[k + 1] = w / H[k + 1, k]  # :162
+            for i in range(k):  # :176-180
+                chi = cs[i] * H[i, k] + sn[i] * H[i + 1, k]
+                H[i + 1, k] = -sn[i] * H[i, k] + cs[i] * H[i + 1, k]
+                H[i, k] = chi
+            rr = (H[k, k] ** 2 + H[k + 1, k] ** 2).sqrt()  # :181, MathUtils.hpp:165-179
+            cs[k], sn[k] = (H[k, k] / rr, H[k + 1, k] / rr) if rr > 0 else (Decimal(1), Decimal(0))
+            H[k, k] = cs[k] * H[k, k] + sn[k] * H[k + 1, k]  # :182-183
+            H[k + 1, k] = Decimal(0)
+            beta[k + 1], beta[k] = -sn[k] * beta[k], cs[k] * beta[k]  # :189
+            hist.append(beta[k + 1] * beta[k + 1])  # :191
+            feeds.append([w])
+            if k == m - 1:  # inner_finalize, :207-240
+                for i in range(k, -1, -1):
+                    for j in range(i + 1, k + 1):
+                        beta[i] -= H[i, j] * beta[j]
+                    beta[i] /= H[i, i]
+                for i in range(k + 1):
+                    x = x + beta[i] * z[i]
+    return Run(hist, x, feeds)
+
+
+# ---- what the tests pin, and how tightly -----------------------------------------------------------------------------
+
+DECIMAL_METHODS = ("idrs", "fgmres")
+OMEGA = Fraction(1, 32)  # Richardson's relaxation_factor in the pins: 2^-5 keeps every x_k and r_k dyadic
+TOL_CAP = 1e-10  # a measured tolerance above this could not tell a dropped row (~1/n) from rounding
+
+
+def iterations(method, param, pre):
+    """K, the iterations pinned: two for CGS, TFQMR(1), Richardson and every preconditioned case; the whole first
+    cycle of BiCGStab(l) with its MR part (one more for l = 2); s + 1 for IDR(s), which reaches the next cycle's dots."""
+    if pre or method in ("cgs", "tfqmr", "tfqmr1", "richardson", "cg", "fgmres"):
+        return 2
+    return param + 1 if method == "idrs" or param == 2 else param
+
+
+def shadow_vectors(oracle, n, s):
+    """p_1 ... p_{s-1} of IDR(s): fill_randomly's sequence from a fresh generator, n values each in turn."""
+    oracle.rng_reset()
+    return [oracle.fill_randomly(n) for _ in range(s - 1)]
+
+
+def exact_run(sp, method, param, K, side=None, shadow=()):
+    """The method restated on a space (``Space`` or ``ElemSpace``, decimal for DECIMAL_METHODS); ``side`` None: no
+    preconditioner, else the space's dinv on that side (or the method's own)."""
+    pre = side is not None
+    if method == "cgs":
+        return cgs(sp, K, side)
+    if method in ("tfqmr", "tfqmr1"):
+        return tfqmr(sp, K, side, l1=method == "tfqmr1")
+    if method == "bicgstabl":
+        return bicgstab_l(sp, K, param, pre=pre)
+    if method == "idrs":
+        return idrs(sp, K, param, shadow, side)
+    if method == "richardson":
+        return richardson(sp, K, OMEGA, pre=pre)
+    if method == "cg":
+        return cg(sp, K, pre=pre)
+    if method == "fgmres":
+        return fgmres(sp, K, param)
+    raise ValueError(method)
+
+
+# c of the floor rule at history[1], no preconditioner, from the statements that touch the vector since r0 (fp64, no
+# fma contraction): a statement a u + b v rounds an element at most twice, an apply of a non-integer vector at most 13
+# times (7 products, 6 sums), a scalar once per division or root; an error that then passes through an apply grows by
+# at most ||A|| <= 12 (row sums of |A| on the unit box).
+#   CGS     v = A p exact (p = b); alpha 1; q = u - alpha v 2; v = u + q 1; u = A v 13 + 12 (2 + 1 + 1);
+#           r = r - alpha u 2 + 1                                                                        -> 64
+#   TFQMR1  s = A y exact; alpha 1; u -= alpha s 2 + 1; y -= alpha v 2 + 1, s = A y 13 + 12 * 3;
+#           u -= alpha s 2 + 1 on top of the first 3                                                       -> 54
+#   TFQMR   the same and the rotation's hypot, divisions and product, 5                                   -> 59
+#   IDR(s)  phi_0 = |r| 1; p_0 = r / phi_0 1; mu_00 = <p_0, g_0>, beta = phi_0 / mu_00 2 (g_0 = A r exact);
+#   s > 1   r -= beta g_0 2 + 1                                                                            -> 7
+#   IDR(1)  then v = A r 13 + 12 * 7; omega 1; r -= omega v 2 + 7                                          -> 107
+#   Richardson: every vector exact (``richardson_integers``)                                               -> 0
+# Later iterations and the preconditioned cases repeat these statements: c_k = k c_1 (+ 4k + 1 with the elementwise
+# products of a preconditioner) is their floor; there the measured error of the oracle decides (``Pins``).
+C1 = {"cgs": 64, "tfqmr": 59, "tfqmr1": 54, "idrs": 7, "idrs1": 107, "richardson": 0, "bicgstabl": 64, "cg": 16,
+      "fgmres": 32}
+
+
+def _c(method, param, k, pre):
+    c1 = C1["idrs1" if method == "idrs" and param == 1 else method]
+    return k * c1 + (4 * k + 1 if pre else 0)
+
+
+def floor_tol(n, ratio, c):
+    """2^-53 (D + c sqrt(M) / h): ``tolerance`` with the ratio sqrt(M) / h given."""
+    return (fold_depth(n) + c * ratio) * 2.0 ** -53
+
+
+def oracle_histories(oracle, g, b, method, param, K, side=None, dinv=None):
+    """history[0..K] of the CPU oracle on the same data, in both of its arithmetic variants."""
+    out = {}
+    bf = np.asarray(b, np.float64)
+    for variant in ("strict", "fma"):
+        op = oracle.StencilOperator(g, -1.0, 0.0, variant=variant)
+        pre = None if dinv is None else oracle.DiagOperator(dinv, variant=variant)
+        common = dict(num_iterations=K, abs_tol=0.0, rel_tol=0.0, variant=variant)
+        if method == "fgmres":
+            r, _ = oracle.solve_gmres_pre(op, pre, bf, side=side, flexible=True, num_inner_iterations=param, **common)
+        else:
+            kw = {}
+            if method in ("bicgstabl", "idrs"):
+                kw["num_inner_iterations"] = param
+            if method == "richardson":
+                kw["relaxation_factor"] = float(OMEGA)
+            if method == "idrs":
+                oracle.rng_reset(variant)
+            if pre is not None:
+                kw.update(pre=pre, side=side)
+            r = oracle.solve(method, op, bf, **common, **kw)
+        assert r.history.size == K + 1, (method, r.history)
+        out[variant] = r.history
+    return out
+
+
+class Pins:
+    """history[0..K] of one case with the tolerance of every entry (None: bitwise).
+
+    - history[0] where r0 is b itself: sqrt of an exact integer sum, bitwise.
+    - history[1] without a preconditioner: CGS, TFQMR(1), IDR(s) by the floor rule (c from ``C1``), at most 1e-12;
+      Richardson bitwise (``richardson_integers``); BiCGStab(l) by the closed forms of ``FirstStep`` (CG's |r1| for
+      l >= 2, BiCGStab's for l = 1).
+    - everything else: tol_k = max(floor_k, 16 e_k), e_k the larger relative distance of the oracle's two variants
+      from the exact value.  The device folds its dots in a tree of depth D ~ 65 where the oracle adds in a chain of
+      n terms, so its reduction error is not the larger; what differs is the rounding pattern of the vector statements
+      and where an fma contracts, and 16 times one sample of that error covers another pattern.  Every tol_k is at
+      most TOL_CAP (asserted: a condition on the case, not a measurement)."""
+
+    def __init__(self, oracle, g, shape, b, method, param=None, side=None, fs=None, K=None, basis=None):
+        b = np.asarray(b, np.int64)
+        pre = side is not None
+        self.n, self.method, self.param, self.side = b.size, method, param, side
+        self.K = K = iterations(method, param, pre) if K is None else K
+        dinv = 1.0 / int_diagonal(shape) if pre else None
+        basis = basis or Basis(shape, b, dinv)
+        assert basis.pre == pre
+        shadow = shadow_vectors(oracle, b.size, param) if method == "idrs" else ()
+        sp = Space(basis, decimal=method in DECIMAL_METHODS)
+        run = exact_run(sp, method, param, K, side, shadow)
+        self.run = run
+        self.exact = exact = run.history
+        hist = oracle_histories(oracle, g, b, method, param, K, side, dinv)
+        self.oracle = hist
+        self.e = [max(abs(h[k] - exact[k]) / exact[k] for h in hist.values()) for k in range(K + 1)]
+        fs = fs or FirstStep(Sums(shape, b))
+        self.tol, self.rule = [], []
+        for k in range(K + 1):
+            ratio = max(math.sqrt(float(_dec(sp.magnitude(v)) / _dec(sp.dot(v, v)))) for v in run.feeds[k])
+            floor = floor_tol(self.n, ratio, _c(method, param, k, pre))
+            if k == 0 and run.feeds[0][0].c == {0: 1}:
+                assert exact[0] == fs.h0
+                self.tol.append(None), self.rule.append("exact")
+            elif k == 1 and not pre and method == "richardson":
+                h1 = richardson_h1(shape, b)
+                assert close(h1, exact[1], 1e-15)
+                exact[1] = h1
+                self.tol.append(None), self.rule.append("exact")
+            elif k == 1 and not pre and method == "bicgstabl":
+                h1, tol = (fs.cg_h1, fs.cg_tol) if param >= 2 else (fs.bicgstab_h1, fs.bicgstab_tol)
+                assert close(exact[1], h1, 1e-15)
+                self.tol.append(tol), self.rule.append("closed form")
+            elif k == 1 and not pre and method in ("cgs", "tfqmr", "tfqmr1", "idrs"):
+                assert floor <= 1e-12, f"{method}: floor {floor:.3e} above 1e-12"
+                self.tol.append(floor), self.rule.append(f"floor c={_c(method, param, k, pre)}")
+            else:
+                tol = max(floor, 16 * self.e[k])
+                assert tol <= TOL_CAP, f"{method}({param}) {side}: tol_{k} = {tol:.3e} above the cap {TOL_CAP}"
+                self.tol.append(tol), self.rule.append("16 e_k" if tol > floor else "floor")
+
+    def check(self, history, label=""):
+        """Assert a history against the pins; returns the ratios |h - exact| / (exact e_k)."""
+        assert len(history) == self.K + 1, (label, history)
+        ratios = []
+        for k, (h, x, tol) in enumerate(zip(history, self.exact, self.tol)):
+            if tol is None:
+                assert h == x, f"{label} history[{k}] = {h!r}, exact {x!r} (bitwise)"
+            else:
+                assert close(h, x, tol), f"{label} history[{k}] = {h!r}, exact {x!r}: rel {abs(h - x) / x:.3e} > tol " \
+                                         f"{tol:.3e} ({self.rule[k]})"
+            ratios.append(abs(h - x) / (x * self.e[k]) if self.e[k] > 0 else (0.0 if h == x else math.inf))
+        return ratios
+
+
+def richardson_integers(shape, b, k):
+    """Richardson with omega = 2^-5 in integers: X = 32^k x_k and R = 32^k r_k.  With |X| and every partial sum of A X
+    below 2^53 (asserted, from row sums of |A| <= 12), every statement x += omega r, r = b - A x is exact in any order
+    and with any fma: x_k = X / 32^k to the bit."""
+    b = np.asarray(b, np.int64)
+    X, R = np.zeros_like(b), b.copy()
+    for j in range(k):
+        X = 32 * X + R  # 32^(j+1) x_{j+1} = 32 (32^j x_j) + 32^j r_j
+        assert int(np.abs(X).max()) * 12 < EXACT
+        R = (32 ** (j + 1)) * b - int_apply(shape, X)  # 32^(j+1) (b - A x_{j+1})
+        assert int(np.abs(R).max()) < EXACT
+    return X, R
+
+
+def richardson_h1(shape, b):
+    """history[1] of Richardson with omega = 2^-5: sum (32 r_1)^2 below 2^53 (exact_dot), so <r_1, r_1> is exact at
+    its scale 2^-10 and its root correctly rounded -- bitwise."""
+    _, R = richardson_integers(shape, b, 1)
+    return math.sqrt(exact_dot(R, R) / 1024.0)

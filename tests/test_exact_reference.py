@@ -1,6 +1,8 @@
 """The exact references of tests/exact_ref.py, checked where no GPU is needed: the integer operator against the CPU
 oracle's stencil, the closed forms of the first Krylov iteration against a Fraction brute force and against
-``oracle.solve(..., num_iterations=1)`` in both of its arithmetic variants."""
+``oracle.solve(..., num_iterations=1)`` in both of its arithmetic variants; the coefficient-form restatement of every
+engine method against an elementwise brute force, its tolerances against their caps and the oracle on the GPU tests'
+own data, and the size of the defects those tolerances must see."""
 import math
 from fractions import Fraction
 
@@ -123,10 +125,20 @@ def test_closed_forms_against_the_oracle_solvers(env, shape, variant):
         assert er.close(r.history[1], fs.gmres_h1, fs.gmres_tol)
     r = one("bicgstab")
     assert er.close(r.history[1], fs.bicgstab_h1, fs.bicgstab_tol)
-    for kind in ("cgs", "tfqmr", "idrs", "bicgstabl"):
-        if kind == "idrs":
-            oracle.rng_reset(variant)
-        one(kind)
+    basis = er.Basis(shape, b)
+    for kind in ("cgs", "tfqmr"):
+        pins = er.Pins(oracle, g, shape, b, kind, fs=fs, K=1, basis=basis)
+        pins.check(one(kind).history, f"{kind} {variant}")
+    # IDR(s > 1) at k = 0 and BiCGStab(l >= 2) at j = 0 (here s = l = 50, the oracle's default) end their first
+    # iteration on CG's r1: beta = phi_0 / <p_0, A r> = rr / pz (SolverIdrs.hpp:132, :244-246), and r_0 - alpha u_1
+    # with u_1 = A b, alpha = rr / pz (SolverBiCgStab.hpp:275-283).  IDR's floor (c = 7, er.C1) on CG's terms
+    oracle.rng_reset(variant)
+    r = one("idrs")
+    a = Fraction(fs.s.rr, fs.s.pz)
+    assert er.close(r.history[1], fs.cg_h1, er.tolerance(fs.s.n, fs.s.rr + a * a * fs.s.zz, a * a * fs.s.zz - fs.s.rr,
+                                                         c=er.C1["idrs"]))
+    r = one("bicgstabl")
+    assert er.close(r.history[1], fs.cg_h1, fs.cg_tol)
 
 
 def test_a_dropped_row_is_far_outside_the_tolerance(env):
@@ -141,3 +153,146 @@ def test_a_dropped_row_is_far_outside_the_tolerance(env):
     assert s.rr / short != fs.cg_alpha
     a = Fraction(s.rr) / Fraction(short)
     assert not er.close(math.sqrt(float(a * a * s.zz - s.rr)), fs.cg_h1, fs.cg_tol)
+
+
+# ---- the Krylov methods in coefficient form (exact_ref.Space) ----------------------------------------------------------
+
+SMALL = (64, 48, 40)  # the shapes and data of tests/test_gpu_exact_first_step.py
+ODD = (37, 21, 19)
+ENGINE = [("cgs", None), ("tfqmr", None), ("tfqmr1", None), ("richardson", None), ("bicgstabl", 1),
+          ("bicgstabl", 2), ("bicgstabl", 3), ("idrs", 1), ("idrs", 2), ("idrs", 4)]
+JACOBI = [("cg", None), ("cgs", None), ("tfqmr", None), ("idrs", 2), ("fgmres", 1), ("fgmres", 30),
+          ("richardson", None), ("bicgstabl", 2)]
+FIXED_SIDE = {"richardson": "left", "bicgstabl": "left", "fgmres": "right"}  # what these methods do whatever pre_side
+BRUTE = [(m, p, None) for m, p in ENGINE + [("cg", None)]] + \
+        [(m, p, side) for m, p in JACOBI for side in ("left", "right") if FIXED_SIDE.get(m, side) == side]
+
+
+def _mid(m, p):
+    return m + ("" if p is None else str(p))
+
+
+_gpu_data = {}
+
+
+def _gpu_case(env, shape):
+    """The GPU tests' problem: the unit box, b = int_vector(n, 31), one Basis per preconditioning."""
+    oracle, mesh = env
+    if shape not in _gpu_data:
+        g = er.unit_box(mesh, *shape)
+        b = er.int_vector(g.n_cells, 31)
+        _gpu_data[shape] = (g, b, er.FirstStep(er.Sums(shape, b)),
+                            {False: er.Basis(shape, b), True: er.Basis(shape, b, 1.0 / er.int_diagonal(shape))})
+    return _gpu_data[shape]
+
+
+@pytest.mark.parametrize("shape", BOXES + [(5, 1, 3)])
+def test_integer_diagonal_is_the_operator_diagonal(shape):
+    n = shape[0] * shape[1] * shape[2]
+    d = er.int_diagonal(shape)
+    assert all(int(er.int_apply(shape, np.eye(n, dtype=np.int64)[i])[i]) == d[i] for i in range(n))
+
+
+@pytest.mark.parametrize("method,param,side", BRUTE, ids=[f"{_mid(m, p)}-{s}" for m, p, s in BRUTE])
+def test_coefficient_form_against_a_brute_force(method, param, side):
+    """Every method's statements run once on coefficient columns over the integer chain (Gram matrix, shifts, the
+    2^-56 scale of D') and once elementwise in Fractions / PREC-digit decimals on a tiny box: the same history and
+    x_K (exactly where rational; to 1e-60 where decimal).  IDR(s) takes fixed dyadic shadow vectors; the Jacobi cases
+    run the preconditioner on both sides of the comparison."""
+    shape = (4, 3, 3)
+    n = 36
+    b = er.int_vector(n, 7)
+    dinv = 1.0 / er.int_diagonal(shape) if side else None
+    rng = np.random.default_rng(11)
+    shadow = [rng.integers(1, 1 << 20, n) / float(1 << 21) for _ in range(3)]  # dyadic, as fill_randomly's are
+    K = er.iterations(method, param, side is not None) + 1
+    dec = method in er.DECIMAL_METHODS
+    sp = er.Space(er.Basis(shape, b, dinv), decimal=dec)
+    el = er.ElemSpace(shape, b, dinv, decimal=dec)
+
+    coef = er.exact_run(sp, method, param, K, side, shadow)
+    brute = er.exact_run(el, method, param, K, side, shadow)
+    assert len(coef.hist_sq) == len(brute.hist_sq) == K + 1
+    if not dec:
+        assert coef.hist_sq == brute.hist_sq
+        assert np.array_equal(sp.materialize(coef.x), np.array([float(v) for v in brute.x]))
+        return
+    from decimal import localcontext
+
+    with localcontext() as ctx:
+        ctx.prec = er.PREC
+        for c, e in zip(coef.hist_sq, brute.hist_sq):
+            assert abs(c - e) <= abs(e) * er._dec(Fraction(1, 10 ** 60))
+        xc = sum((er._dec(c) * sp.basis.W[k].astype(object) for k, c in coef.x.c.items()), np.zeros(n, dtype=object))
+        scale = max(abs(v) for v in brute.x)
+        assert max(abs(a - e) for a, e in zip(xc, brute.x)) <= scale * er._dec(Fraction(1, 10 ** 60))
+
+
+@pytest.mark.parametrize("shape", [SMALL, ODD], ids=["small", "odd"])
+def test_richardson_is_exact_in_integers(env, shape):
+    """omega = 2^-5: the coefficient form's x_k, materialised, is 32^-k times the integer iteration, k = 1 ... 4, and
+    history[1] is the root of an exact sum (every bound asserted inside richardson_integers)."""
+    g, b, _, bases = _gpu_case(env, shape)
+    sp = er.Space(bases[False])
+    run = er.richardson(sp, 4, er.OMEGA)
+    for k in range(1, 5):
+        X, R = er.richardson_integers(shape, b, k)
+        assert np.array_equal(sp.materialize(er.richardson(sp, k, er.OMEGA).x), X / 32.0 ** k)
+        assert run.hist_sq[k] == Fraction(er.big_dot(R, R), 4 ** (5 * k))
+    assert run.history[1] == er.richardson_h1(shape, b)
+
+
+GPU_CASES = [(m, p, None) for m, p in ENGINE] + \
+            [(m, p, side) for m, p in JACOBI for side in ("left", "right") if FIXED_SIDE.get(m, side) == side]
+
+
+@pytest.mark.parametrize("shape", [SMALL, ODD], ids=["small", "odd"])
+@pytest.mark.parametrize("method,param,side", GPU_CASES, ids=[f"{_mid(m, p)}-{s}" for m, p, s in GPU_CASES])
+def test_the_oracle_lies_within_the_pins(env, shape, method, param, side):
+    """Every case of the GPU tests: its tolerances at or below their caps (1e-12 for the floor rule at history[1],
+    TOL_CAP for the measured ones -- asserted as Pins is built), and both oracle variants inside them."""
+    oracle, _ = env
+    g, b, fs, bases = _gpu_case(env, shape)
+    pins = er.Pins(oracle, g, shape, b, method, param, side, fs=fs, basis=bases[side is not None])
+    for variant, hist in pins.oracle.items():
+        pins.check(list(hist), f"{_mid(method, param)} {side} {variant}")
+
+
+@pytest.mark.parametrize("shape", [SMALL, ODD], ids=["small", "odd"])
+def test_tfqmr1_meets_cgs_on_these_data(env, shape):
+    """On these data TFQMR1's minimum takes the omega after the second half-step -- CGS's residual -- in both
+    iterations pinned: a cross-pin that holds for this b (shown here), not in general."""
+    _, _, _, bases = _gpu_case(env, shape)
+    sp = er.Space(bases[False])
+    assert er.tfqmr(sp, 2, l1=True).hist_sq == er.cgs(sp, 2).hist_sq
+
+
+@pytest.mark.parametrize("method,param", [("cgs", None), ("tfqmr", None), ("bicgstabl", 2)],
+                         ids=["cgs", "tfqmr", "bicgstabl2"])
+def test_a_defect_at_iteration_2_is_far_outside_the_tolerance(env, method, param):
+    """What the later pins are for: at history[2] on SMALL, each of one dropped row in one dot of the second
+    iteration, a beta formed from the previous pass's rho alone (the register read before this pass writes it), and
+    r~ replaced by r moves the exact value by more than 100 times its tolerance."""
+    oracle, _ = env
+    g, b, fs, bases = _gpu_case(env, SMALL)
+    pins = er.Pins(oracle, g, SMALL, b, method, param, fs=fs, basis=bases[False])
+    tol, exact = pins.tol[2], pins.exact[2]
+
+    def run(K, defect=None, drop_at=None):
+        sp = er.Space(bases[False])
+        sp.drop_at = drop_at
+        if method == "bicgstabl":
+            return er.bicgstab_l(sp, K, param, defect=defect), sp
+        return {"cgs": er.cgs, "tfqmr": er.tfqmr}[method](sp, K, defect=defect), sp
+
+    assert run(2)[0].history[2] == exact
+    _, first = run(1)  # (first.ndots: the dots of the first iteration)
+    # the two dots that form the second iteration's coefficients: rho = <r~, r> and <r~, v> (<r~, u_2> for BiCGStab(l)).
+    # (The dots of BiCGStab(l)'s MR part are not held here: the MR coefficients minimise |r_0|, so a small error in
+    # them moves the norm only to second order.)
+    for at in (first.ndots + 1, first.ndots + 2):
+        h = run(2, drop_at=at)[0].history[2]
+        assert abs(h - exact) > 100 * tol * exact, ("dropped row", at, h, exact, tol)
+    for defect in ("stale_beta", "shadow_r"):
+        h = run(2, defect=defect)[0].history[2]
+        assert abs(h - exact) > 100 * tol * exact, (defect, h, exact, tol)

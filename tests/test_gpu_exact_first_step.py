@@ -6,6 +6,8 @@ correct path, so:
     CG x1                == fl(fl(rr / pz) * b_i), bitwise, every element: the whole <p,z> and <r,r> reduction of
                             iteration 0, whatever grid, fold or format produced it
     CG / GMRES / BiCGStab history[1]  within a tolerance derived from the data and the fold depth (<= 1e-12)
+    the engine's CGS, TFQMR(1), Richardson, BiCGStab(l), IDR(s) and Jacobi-preconditioned solves: history[0..K]
+                            against the exact coefficient-form reference (exact_ref.Pins)
 Each case asserts the path it is meant to reach from the context's path counters and the operator's stats; the
 comment names the <p,z> branch of the fused CG loop (solvers.hip, storm_hip_solve_cg) it takes."""
 import math
@@ -35,7 +37,8 @@ def env():
 
 
 DEFAULTS = (("resident_path", 1), ("latency_path", 1), ("generic_solvers", 0), ("ticket_reduce", 1), ("coop_mgs", 1),
-            ("spmv_record_index", 1), ("spmv_dict", 4), ("ell_cap", 0), ("lazy_statements", 0), ("test_disable", 0))
+            ("spmv_record_index", 1), ("spmv_dict", 4), ("ell_cap", 0), ("lazy_statements", 0), ("test_disable", 0),
+            ("fused_reduce", 1), ("lin_fuse", 1))
 
 
 @pytest.fixture(autouse=True)
@@ -284,6 +287,143 @@ def test_gmres_first_step(env, fmt, m, chain):
 
 
 # ---- the engine's other methods -------------------------------------------------------------------------------------------
+#
+# CGS, TFQMR, TFQMR1, Richardson, BiCGStab(l), IDR(s) (krylov.hip) and the preconditioned engine solves against the
+# coefficient-form restatement of the reference's headers (tests/exact_ref.py, ``Pins``): history[0] bitwise wherever
+# r0 is b, Richardson (omega = 2^-5) bitwise in x_k and history[1], history[1] of the rest by the floor rule or the
+# closed forms, every later or preconditioned entry within max(floor, 16 e_k) of the exact value, e_k the oracle's own
+# distance from it.  Each case prints |h - exact| / (exact e_k) per entry ("ratio" lines).
+
+CLASSES = {"cgs": "CgsSolver", "tfqmr": "TfqmrSolver", "tfqmr1": "Tfqmr1Solver", "richardson": "RichardsonSolver",
+           "bicgstabl": "BiCgStabLSolver", "idrs": "IdrsSolver", "cg": "CgSolver", "fgmres": "FgmresSolver"}
+ENGINE_METHODS = [("cgs", None), ("tfqmr", None), ("tfqmr1", None), ("richardson", None), ("bicgstabl", 1),
+                  ("bicgstabl", 2), ("bicgstabl", 3), ("idrs", 1), ("idrs", 2), ("idrs", 4)]
+# each format once with the defaults, each engine option once against the lattice format
+ENGINE_CONFIGS = [("lattice", {}), ("lattice8", {}), ("fp64", {}), ("tail", {}), ("lattice", {"fused_reduce": 0}),
+                  ("lattice", {"lin_fuse": 0}), ("lattice", {"ticket_reduce": 0})]
+
+_bases, _pins_cache = {}, {}
+
+
+def _method_id(m):
+    return m[0] + ("" if m[1] is None else str(m[1]))
+
+
+def _pins(mesh, shape, kind, param, side=None):
+    from oracle import oracle
+
+    key = (shape, kind, param, side)
+    if key not in _pins_cache:
+        g, b_h, fs = _problem(mesh, shape)
+        bkey = (shape, side is not None)
+        if bkey not in _bases:
+            _bases[bkey] = er.Basis(shape, b_h, 1.0 / er.int_diagonal(shape) if side is not None else None)
+        _pins_cache[key] = er.Pins(oracle, g, shape, b_h, kind, param, side, fs=fs, basis=_bases[bkey])
+    return _pins_cache[key]
+
+
+def _knobs(kind, param):
+    if kind in ("bicgstabl", "idrs", "fgmres"):
+        return {"num_inner_iterations": param}
+    if kind == "richardson":
+        return {"relaxation_factor": float(er.OMEGA)}
+    return {}
+
+
+def _report(label, pins, ratios):
+    print(f"ratio {label}: " + " ".join(f"{r:.2f}" for r in ratios) + "   tol " +
+          " ".join("bitwise" if t is None else f"{t:.1e}" for t in pins.tol))
+
+
+@pytest.mark.parametrize("shape", [SMALL, ODD], ids=["small", "odd"])
+@pytest.mark.parametrize("case", ENGINE_CONFIGS, ids=lambda c: c[0] + "".join(f"-{k}{v}" for k, v in c[1].items()))
+@pytest.mark.parametrize("method", ENGINE_METHODS, ids=_method_id)
+def test_engine_methods_against_the_exact_reference(env, method, case, shape):
+    """history[0..K] of every engine method pinned (K from er.iterations), plus: Richardson's x_k bitwise for
+    k = 1 ... 4 and its history[1] bitwise; BiCGStab(l >= 2)'s x after one iteration is CG's x1, bitwise."""
+    api, mesh, ctx = env
+    kind, param = method
+    fmt, opts = case
+    g, b_h, fs = _problem(mesh, shape)
+    pins = _pins(mesh, shape, kind, param)
+    mat = _matrix(api, ctx, g, fmt)
+    for k, v in opts.items():
+        ctx.set_option(k, v)
+    cls = getattr(api, CLASSES[kind])
+    label = f"{_method_id(method)} {fmt} {opts} {shape}"
+    api.rng_reset()
+    s, x, path = _solve(api, ctx, cls, mat, b_h, iters=pins.K, **_knobs(kind, param))
+    _only(path, "engine_solves")
+    assert s.history[0] == fs.h0
+    _report(label, pins, pins.check(s.history, label))
+    if kind == "bicgstabl" and param >= 2:
+        s, x, _ = _solve(api, ctx, cls, mat, b_h, iters=1, **_knobs(kind, param))
+        assert np.array_equal(x, fs.cg_x1(b_h)), f"x1: {np.count_nonzero(x != fs.cg_x1(b_h))} elements differ"
+    if kind == "richardson":
+        for k in range(1, 5):
+            X, _ = er.richardson_integers(shape, b_h, k)
+            s, x, path = _solve(api, ctx, cls, mat, b_h, iters=k, **_knobs(kind, param))
+            _only(path, "engine_solves")
+            want = X / 32.0 ** k  # exact: |X| < 2^53
+            assert np.array_equal(x, want), f"x_{k}: {np.count_nonzero(x != want)} elements differ"
+            if k == 1:
+                assert s.history[1] == er.richardson_h1(shape, b_h), (s.history[1], er.richardson_h1(shape, b_h))
+    mat.close()
+
+
+@pytest.mark.parametrize("method", [("cgs", None), ("bicgstabl", 2)], ids=_method_id)
+def test_engine_methods_many_partials(env, method):
+    """256 x 256 x 258: more partials than one pass folds, in every engine reduction.  (The reference's chain of
+    this box is not kept beyond the test: about 1 GB.)"""
+    from oracle import oracle
+
+    api, mesh, ctx = env
+    kind, param = method
+    g, b_h, fs = _problem(mesh, BIG)
+    pins = er.Pins(oracle, g, BIG, b_h, kind, param, fs=fs)
+    mat = _matrix(api, ctx, g, "lattice")
+    s, x, path = _solve(api, ctx, getattr(api, CLASSES[kind]), mat, b_h, iters=pins.K, **_knobs(kind, param))
+    _only(path, "engine_solves")
+    label = f"{_method_id(method)} lattice BIG"
+    _report(label, pins, pins.check(s.history, label))
+    mat.close()
+
+
+JACOBI_METHODS = [("cg", None), ("cgs", None), ("tfqmr", None), ("idrs", 2), ("fgmres", 1), ("fgmres", 30),
+                  ("richardson", None), ("bicgstabl", 2)]
+# the side the reference applies the preconditioner on whatever pre_side says: Richardson (SolverRichardson.hpp:66-69,
+# :90-93) and BiCGStab(l) (SolverBiCgStab.hpp:226-229) always on the left, FGMRES (SolverGmres.hpp:125-130) always on
+# the right; CG (SolverCg.hpp:74-77) has no side
+FIXED_SIDE = {"richardson": "left", "bicgstabl": "left", "fgmres": "right"}
+
+
+@pytest.mark.parametrize("lin_fuse", [1, 0])
+@pytest.mark.parametrize("side", ["left", "right"])
+@pytest.mark.parametrize("method", JACOBI_METHODS, ids=_method_id)
+@pytest.mark.parametrize("shape", [SMALL, ODD], ids=["small", "odd"])
+def test_engine_methods_with_jacobi(env, shape, method, side, lin_fuse):
+    """api.JacobiPreconditioner on either side, lin_fuse on and off (for CG it switches the fused pre_dots pass,
+    z = P r with <r,z> and <r,r>): history[0..2] against the reference restated with P = diag(fl(1/d))."""
+    api, mesh, ctx = env
+    kind, param = method
+    g, b_h, fs = _problem(mesh, shape)
+    mat = _matrix(api, ctx, g, "lattice")
+    d = api.DeviceVector(ctx, g.n_cells)
+    mat.diagonal(-1.0, 0.0, d, invert=True)
+    assert np.array_equal(d.to_numpy(), 1.0 / er.int_diagonal(shape))  # the dinv the reference is restated with
+    pins = _pins(mesh, shape, kind, param, FIXED_SIDE.get(kind, side))
+    if kind == "cg":
+        ctx.set_option("generic_solvers", 1)
+    ctx.set_option("lin_fuse", lin_fuse)
+    knobs = dict(_knobs(kind, param), pre_op=api.JacobiPreconditioner(),
+                 pre_side=api.PreconditionerSide.Left if side == "left" else api.PreconditionerSide.Right)
+    api.rng_reset()
+    s, _, path = _solve(api, ctx, getattr(api, CLASSES[kind]), mat, b_h, iters=pins.K, **knobs)
+    _only(path, "engine_solves")
+    label = f"{_method_id(method)} jacobi-{side} lin_fuse{lin_fuse} {shape}"
+    _report(label, pins, pins.check(s.history, label))
+    mat.close()
+
 
 @pytest.mark.parametrize("cls", ["CgsSolver", "TfqmrSolver", "Tfqmr1Solver", "IdrsSolver", "BiCgStabLSolver"])
 def test_engine_methods_initial_residual(env, cls):
@@ -325,6 +465,12 @@ def test_cg_first_step_over_rccl(fused):
         s, _, path = _solve(api, ctx, api.GmresSolver, mat, b_h, num_inner_iterations=30)
         assert s.history[0] == fs.h0
         assert er.close(s.history[1], fs.gmres_h1, fs.gmres_tol), (s.history[1], fs.gmres_h1)
+        for kind, param in (("cgs", None), ("idrs", 2)):  # the engine's methods, every sum through the all-reduce
+            pins = _pins(mesh, SMALL, kind, param)
+            api.rng_reset()
+            s, _, path = _solve(api, ctx, getattr(api, CLASSES[kind]), mat, b_h, iters=pins.K, **_knobs(kind, param))
+            _only(path, "engine_solves")
+            pins.check(s.history, f"{kind} rccl_fused {fused}")
         mat.close()
     finally:
         ctx.close()

@@ -2,7 +2,8 @@
 
 Exact integers make the order of every all-reduce irrelevant, so on the slab partition of a unit-spacing box each rank
 must reproduce the whole box's closed forms: x1 bitwise on its own rows, history[0] bitwise and history[1] within the
-derived tolerance, and the same history on every rank.  World 2 on the host-staged transport; world 3 on the
+derived tolerance, and the same history on every rank.  World 2 on the host-staged transport (with the engine's CGS
+and TFQMR to K = 2 against the exact reference of the whole box, exact_ref.Pins); world 3 on the
 peer-window transport, where the fused CG finishes <p,z> with reduce_stage1_ticket_kernel<1> exchanging its sum itself
 (the `ipc` branch of storm_hip_solve_cg) and cg_r_kernel finishes <r,r> through the window.  At most 4 processes with
 the GPU open: the ranks and this one."""
@@ -39,6 +40,8 @@ def test_first_step_pins_on_every_rank(world, dims, transport, tmp_path):
     for r in reports:
         assert len(r["nbrs"]) == (1 if r["rank"] in (0, world - 1) else 2)
         assert r["history"] == reports[0]["history"]  # every rank: the same bits
+        if transport == "host":
+            assert all(f"{kind}{fmt}" in r["history"] for kind in ("cgs", "tfqmr") for fmt in (0, 4))
     if transport == "ipc":
         # the peer-window transport keeps the fused step on format 4 (the ticketed finishes, ipc branch)
         assert all(r["fused"]["cg4"] == 1 for r in reports), [r["fused"] for r in reports]
