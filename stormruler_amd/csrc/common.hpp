@@ -146,9 +146,7 @@ struct storm_hip_ctx {
   storm::SolverState *h_state = nullptr;  // pinned staging copy of the state
   unsigned long long *h_done_ring = nullptr;  // pinned, written by the device's step kernels (solver_device.hpp advance())
   unsigned long long *d_done_ring = nullptr;  // device pointer to the same memory
-  std::vector<hipEvent_t> ev_ring;            // (option poll_events = 1: a marker behind every iteration, the r02 form; created on first use)
   std::vector<storm::KrylovRes> krylov_free;   // krylov.hip: resources of destroyed engines, reused by the next create
-  static constexpr int64_t opt_poll_events = 0;
   unsigned long long ring_gen = 0;            // generation of the current solve's ring words (state_init draws the next one)
   // options
   int64_t opt_ell_cap = 0;
@@ -166,15 +164,11 @@ struct storm_hip_ctx {
   // XCDs' streams run.  A chooser that counted cross-XCD columns per operator was written and removed: it picks 8 - 32 there.
   int64_t opt_spmv_xcd_remap_sell = 64;
   int64_t opt_nt = 1;
-  static constexpr int64_t opt_sweep_alternate = 1;   // fused CG: consecutive kernels sweep the rows in opposite directions (2: and without non-temporal hints)
-  int stream_reverse = 0;            // ... and the same for the next elementwise kernel
+  int stream_reverse = 0;            // set around an elementwise kernel by the solver: deal the blocks out from the far end (consecutive kernels sweep the rows in opposite directions)
   int spmv_reverse = 0;              // set around a format-4 SpMV launch by the solver: deal the tiles out from the far end
-  static constexpr int64_t opt_spmv_canon_groups = 2; // format-4 / 5 kernel: 128-row groups per wavefront (1 or 2)
-  static constexpr int64_t opt_spmv_tile_lds_pad = 0;   // A/B knob: extra dynamic LDS per block of the tiled kernel (fewer resident tiles per CU)
-  int64_t opt_spmv_canon_tile_min_rows = (int64_t)1 << 20;  // ... for operators of at least this many rows
+  int64_t opt_spmv_canon_tile_min_rows = (int64_t)1 << 20;  // the tiled format-4 kernel for operators of at least this many rows
   int64_t opt_spmv_record_index = 1;  // format 4 with <= 256 distinct 8-byte row words: the tiled and marching kernels read one byte per row into a table of them (storm_hip_op::d_rec_idx) instead of the word (0: the 8-byte records)
   int64_t opt_spmv_canon_tile = 2;   // format 4 on a lattice (offsets -b,-a,-1,+1,+a,+b): tiles of 1024 rows x this many planes (2, or 4) with the +-a / +-1 neighbours from LDS and the +-b ones from registers; 0 = the plain kernel.  Measured at 256^3 (profiles/r03f, r03g): CG step 242 (2 planes) / 247 (4) us per iteration, BiCGStab 496 / 510
-  static constexpr int64_t opt_vec_contiguous = 0;     // vectors in physically contiguous device memory (hipDeviceMallocContiguous)
   int64_t opt_mgs_steps = 4;          // throughput-path Gram-Schmidt: steps per pass over w (2: mgs_pair_kernel; 3, 4: mgs_multi_kernel)
   int64_t opt_resident_early = 1;    // resident CG: the residual's surface published under the all-reduce that yields beta (res_halo MODE 2; behind the block's own arrival at that all-reduce): bitwise the same solve, 7 - 12 % faster (128^3: 16.8 -> 15.4 us per iteration)
   int64_t opt_resident_apply_cache = 1;  // resident path: a pair of rows' coefficients stay in registers from plane to plane while the weight words do not change (0: decoded per plane; the same bits)
@@ -185,10 +179,8 @@ struct storm_hip_ctx {
   int64_t opt_coop_mgs_alternate = 1;  // ... the chain's vector order alternates with k: ascending / descending (test_disable bit 256: off)
   int64_t opt_coop_mgs_xcd_runs = 1;  // ... the chain's blocks own ONE contiguous run of row chunks per XCD (test_disable bit 128: off)
   int64_t opt_coop_mgs_apply = 1;    // ... with the operator apply in front of it done by the chain kernel itself (format-4 lattice operators)
-  static constexpr int64_t opt_coop_mgs_pairs = 1;    // cooperative Gram-Schmidt chain: two steps per synchronisation point
-  static constexpr int64_t opt_coop_dense = 1;        // the multi-step Gram-Schmidt chain's all-reduce with dense value-major slots (0: the two-level form; 2: the resident kernels too)
-  int64_t opt_coop_mgs_quad = 1;     // ... FOUR steps per synchronisation point (blocks of 512 threads; <= 2^21 rows)
-  char *d_quad_slots = nullptr;      // ... its all-reduce slots (ten values each)
+  int64_t opt_coop_mgs_quad = 1;     // ... FOUR steps per synchronisation point instead of two (blocks of 512 threads; <= 2^21 rows)
+  char *d_quad_slots = nullptr;      // ... the dense granules of its all-reduce (ten values)
   int64_t opt_coop_mgs_lds = 1;      // ... with the next pair of basis vectors fetched by LDS-DMA into a ring (<= 2^21 rows)
   int64_t opt_spmv_mixed = 1;        // partitioned operators: format 4 for the groups that read no halo column, format 3 for the rest
   int64_t opt_profile_spmv = 0;
@@ -200,10 +192,7 @@ struct storm_hip_ctx {
   int64_t n_lazy_fused_dots = 0, n_lazy_fused_pairs = 0, n_lazy_apply_dots = 0, n_lazy_cg_steps = 0;
   storm_hip_vec *lazy_spare = nullptr;  // where a fused CG step writes the new direction (lazy.hip: try_cg_step)
   int64_t opt_profile_comm = 0;       // RCCL transport: stamp kernels around the halo exchange and the all-reduces (comm.hip comm_profile_*)
-  int64_t opt_blas1_nt = 1;  // non-temporal loads/stores in the streaming kernels: 0 never, 1 for vectors of at least blas1_nt_rows rows, 2 always
-  static constexpr int64_t opt_blas1_nt_rows = (int64_t)6 << 20;  // (48 MiB per vector: beyond, a solver's vectors no longer stay in the 256 MiB Infinity Cache between kernels)
-  static constexpr int64_t opt_graph = 0;     // replay CG / BiCGStab iterations from a captured hipGraph: measured slower than eager launches (profiles/r01_notes.md), off
-  static constexpr int64_t opt_coop_mgs_min_rows = 0;  // ... from this many rows on (0: always; with two steps per synchronisation point the chain is no slower than a launch per step even on small meshes)
+  int64_t opt_blas1_nt = 1;  // non-temporal loads/stores in the streaming kernels: 0 never, 1 for vectors of at least kBlas1NtRows rows, 2 always
   int64_t opt_coop_mgs = 1;             // GMRES: the Gram-Schmidt chain of an Arnoldi step as one cooperative kernel (latency.hip)
   int64_t opt_latency_publish = 1;      // ... its rows published with awaited atomic exchanges (0: write-through stores, ordered by their acknowledgement)
   int64_t opt_coop_plain = 1;           // the cooperative kernels by ordinary launches (latency.hip coop_launch; 0: hipLaunchCooperativeKernel)
@@ -215,10 +204,8 @@ struct storm_hip_ctx {
   int64_t opt_latency_path = 1;         // small operators: CG as one cooperative persistent kernel (latency.hip)
   // resident.hip: lattice operators as one persistent kernel per solve, every block owning a box of the lattice
   int64_t opt_resident_path = 1;
-  static constexpr int64_t opt_resident_min_rows = 0;            // ... from this many rows on (below: the latency path, where it applies)
   int64_t opt_resident_max_rows = (int64_t)1 << 22;
   int64_t opt_resident_planes = 0;              // ... exactly this many planes per block (0: the fewest that cover the lattice with one block per CU)
-  static constexpr int64_t opt_resident_max_planes = 12;         // ... with at most this many planes per block (registers)
   char *d_res_exch = nullptr;                   // its exchange buffer: one 16-byte granule per row (grown on demand)
   int64_t res_exch_rows = 0;
   int64_t opt_resident_profile = 0;             // the kernels time their phases (storm_hip_ctx_get_counter "resident_phase_max_k" / "_mean_k", ticks of 10 ns)
@@ -237,9 +224,6 @@ struct storm_hip_ctx {
   int64_t opt_comm_wait_seconds = 120;  // RCCL transport, flag hand-offs: how long a one-thread waiter polls before it gives up (STORM_HIP_E_COMM from the next checked call; the first 4 exchanges of a communicator, inside which RCCL connects its peers: at least 180 s).  A cross-stream event waits for ever; a kernel must not, but a rank that builds an operator or reads a mesh between two solves may well be tens of seconds late
   int64_t opt_rccl_flag_wait = 1;       // RCCL: the boundary rows wait for a flag in device memory set behind the exchange, not for a cross-stream event (comm.hip)
   int64_t opt_rccl_early_halo = 1;      // RCCL, BiCGStab: the halo of s / p' leaves before the kernel that forms the vector runs (rows to send formed by a small kernel)
-  static constexpr int64_t opt_ipc_bicg_ticket = 1;      // peer windows, BiCGStab: sums finished by tickets and exchanged by the finishing block (as CG does)
-  static constexpr int64_t opt_ipc_fused = 1;            // peer-window transport: the interior launch sends, the boundary launch reads the window (0: stand-alone send / receive-copy kernels)
-  static constexpr int64_t opt_ipc_streams = 2;          // peer-window halo exchange: 2 = on the comm stream beside the interior rows, 1 = on the compute stream around them
   int64_t opt_generic_solvers = 0;  // 1: storm_hip_krylov_solve never takes the fused CG / BiCGStab / GMRES loops (A/B knob)
   int64_t opt_cg_march_fill = 2048;    // ... fewer planes per block on smaller lattices, so that the grid holds about this many blocks (0: cg_march as given)
   int64_t opt_cg_march_alternate = 1;  // odd z-chunks of the marching step kernel march downwards (spmv.hip MarchArgs::alternate)
@@ -264,11 +248,6 @@ struct storm_hip_ctx {
   };
   std::vector<VecArena> arenas;
   int64_t opt_vec_arena = 1;            // 0: every vector an allocation of its own
-  static constexpr int64_t opt_vec_arena_contiguous = 1; // arenas in physically contiguous memory (hipDeviceMallocContiguous)
-  static constexpr int64_t opt_cg_roles = 8;             // solve_cg_body: permutation of the work vectors' roles over their arena slots (A/B knob; 24 permutations at 256^3: 4 505 - 4 570 it/s, profiles/r05z_roles.txt)
-  static constexpr int64_t opt_vec_arena_slots = 8;
-  static constexpr int64_t opt_vec_arena_max_bytes = (int64_t)64 << 30;  // all arenas of a context together; beyond: vectors allocated one by one
-  static constexpr int64_t opt_vec_arena_skew_kib = 0;   // pitch = the vector rounded up to 2 MiB + this
   size_t pool_bytes = 0;
   int64_t opt_pool_bytes = (int64_t)16 << 30;
   std::vector<hipEvent_t> prof_events;  // pairs (start, stop), grown on demand
@@ -381,8 +360,10 @@ static inline int stream_blocks(int64_t n) {
 }
 
 // Non-temporal accesses for a streaming kernel over n rows?  (blas1_device.hpp: nt_dispatch)
+// (48 MiB per vector: beyond, a solver's vectors no longer stay in the 256 MiB Infinity Cache between kernels)
+constexpr int64_t kBlas1NtRows = (int64_t)6 << 20;
 static inline int stream_nt(const storm_hip_ctx *c, int64_t n) {
-  return (c->opt_blas1_nt == 2 || (c->opt_blas1_nt == 1 && n >= c->opt_blas1_nt_rows)) ? 1 : 0;
+  return (c->opt_blas1_nt == 2 || (c->opt_blas1_nt == 1 && n >= kBlas1NtRows)) ? 1 : 0;
 }
 
 // blas1.hip -- all asynchronous on ctx->stream, owned rows only.
@@ -429,9 +410,8 @@ int state_init(storm_hip_ctx *c, SolverState *d_state, double abs_tol, double re
 // (1-based) as ONE self-validating word (i << 1 | done) into a pinned ring (solver_device.hpp advance()); the host,
 // `lag` iterations ahead, polls the word -- no marker in the stream: an event recorded behind every iteration is a
 // barrier with a system-scope release between two kernels, 5.9 us per CG iteration at 256^3
-// (profiles/r03t_event_gap.txt).  ring_post / ring_wait: option poll_events = 1 brings the markers back.
-int ring_post(storm_hip_ctx *c, std::vector<hipEvent_t> &events, int64_t it);
-int ring_wait(storm_hip_ctx *c, std::vector<hipEvent_t> &events, volatile unsigned long long *ring, int64_t it, bool *stop);  // (words of c->ring_gen only)
+// (profiles/r03t_event_gap.txt).
+int ring_wait(storm_hip_ctx *c, volatile unsigned long long *ring, int64_t it, bool *stop);  // (words of c->ring_gen only)
 
 // spmv.hip
 // y = beta*x + alpha*M x over slices [s0, s1); when dot_w != null also writes

@@ -89,7 +89,6 @@ int storm_hip_ctx_destroy(storm_hip_ctx *c) {
   if (c->lazy_spare) (void)storm_hip_vec_destroy(c->lazy_spare), c->lazy_spare = nullptr;
   (void)hipDeviceSynchronize();
   comm_destroy(c);
-  for (auto &ev : c->ev_ring) (void)hipEventDestroy(ev);
   for (auto &r : c->krylov_free) {
     if (r.S) (void)hipFree(r.S);
     (void)hipFree(r.d_st);
@@ -363,19 +362,8 @@ extern "C" int storm_hip_vec_create(storm_hip_ctx *c, int64_t n_owned, int64_t n
   return vec_create_impl(c, n_owned, n_halo, out, kZeroAll);
 }
 namespace storm {
-int ring_post(storm_hip_ctx *c, std::vector<hipEvent_t> &events, int64_t it) {
-  if (c->opt_poll_events == 0) return STORM_HIP_OK;
-  while (events.size() < (size_t)kStateRing) {
-    hipEvent_t ev;
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    events.push_back(ev);
-  }
-  HIP_TRY(hipEventRecord(events[(size_t)(it % kStateRing)], c->stream));
-  return STORM_HIP_OK;
-}
-
 // The verdict of iteration index `it` (0-based; the device counts from 1).
-int ring_wait(storm_hip_ctx *c, std::vector<hipEvent_t> &events, volatile unsigned long long *ring, int64_t it, bool *stop) {
+int ring_wait(storm_hip_ctx *c, volatile unsigned long long *ring, int64_t it, bool *stop) {
   volatile unsigned long long *w = ring + it % kStateRing;
   const unsigned long long want = (unsigned long long)(it + 1);
   const unsigned long long gen = c->ring_gen & 0xfffffull;
@@ -388,11 +376,6 @@ int ring_wait(storm_hip_ctx *c, std::vector<hipEvent_t> &events, volatile unsign
     return false;
   };
   *stop = false;
-  if (c->opt_poll_events != 0 && events.size() == (size_t)kStateRing) {  // (the option switched on mid-solve: poll)
-    HIP_TRY(hipEventSynchronize(events[(size_t)(it % kStateRing)]));
-    (void)posted(stop);
-    return STORM_HIP_OK;
-  }
   for (unsigned long spin = 1;; ++spin) {
     if (posted(stop)) return STORM_HIP_OK;
     if ((spin & 0x3ffful) == 0) {
@@ -498,7 +481,7 @@ static bool in_arena(const storm_hip_ctx *c, const void *p) {
 // Give pooled storage back to the driver (an allocation failed, or the pool budget shrank; the caller has synchronised
 // the stream): every vector allocated by itself, and every ARENA whose slots are all back in the pool -- an arena with a
 // slot still in use stays, with its free slots pooled.  pool_bytes counts the stand-alone vectors only: arena slots have
-// the arenas' own budget (vec_arena_max_bytes) and must not crowd the others out of the pool.
+// the arenas' own budget (arena_take: kArenaMaxBytes) and must not crowd the others out of the pool.
 static void pool_release(storm_hip_ctx *c) {
   std::vector<int> pooled(c->arenas.size(), 0);
   auto arena_of = [&](const void *p) {
@@ -534,10 +517,11 @@ static double *arena_take(storm_hip_ctx *c, size_t bytes) {
   // 256^3 CG (tools/arena_sweep.py, vectors of 128 MiB + 288 B): 130, 131, 133, 134, 138, 142 MiB apart 4 500 - 4 550
   // it/s; 132 and 136 MiB apart -- multiples of 4 MiB; 132 MiB is where separate hipMalloc calls put them -- 4 360 - 4 380.
   constexpr size_t kMiB = (size_t)1 << 20;
+  constexpr int kArenaSlots = 8;                       // vectors of the first arena of a size class
+  constexpr size_t kArenaMaxBytes = (size_t)64 << 30;  // all arenas of a context together; beyond: vectors allocated one by one
   size_t pitch = (bytes + 4 * kMiB - 1) / (4 * kMiB) * (4 * kMiB);  // a multiple of 4 MiB
   pitch = pitch - 2 * kMiB >= bytes ? pitch - 2 * kMiB : pitch + 2 * kMiB;
-  pitch += (size_t)c->opt_vec_arena_skew_kib * 1024;
-  int slots = (int)std::max<int64_t>(2, c->opt_vec_arena_slots);
+  int slots = kArenaSlots;
   for (auto &a : c->arenas) {
     if (a.bytes != bytes || a.pitch != pitch) continue;
     if (a.used < a.slots) return reinterpret_cast<double *>(a.base + (size_t)(a.used++) * pitch);
@@ -547,11 +531,11 @@ static double *arena_take(storm_hip_ctx *c, size_t bytes) {
   if (slots < 2) return nullptr;
   size_t held = 0;
   for (const auto &h : c->arenas) held += (size_t)h.slots * h.pitch;
-  if (held + (size_t)slots * pitch > (size_t)c->opt_vec_arena_max_bytes) return nullptr;  // (many sizes in one context: enough reserved)
+  if (held + (size_t)slots * pitch > kArenaMaxBytes) return nullptr;  // (many sizes in one context: enough reserved)
   storm_hip_ctx::VecArena a;
   a.bytes = bytes, a.pitch = pitch, a.slots = slots, a.used = 1;
   const size_t total = (size_t)slots * pitch;
-  if (c->opt_vec_arena_contiguous == 0 || hipExtMallocWithFlags((void **)&a.base, total, hipDeviceMallocContiguous) != hipSuccess) {
+  if (hipExtMallocWithFlags((void **)&a.base, total, hipDeviceMallocContiguous) != hipSuccess) {
     (void)hipGetLastError();
     if (hipMalloc((void **)&a.base, total) != hipSuccess) {
       (void)hipGetLastError();
@@ -593,21 +577,13 @@ static int vec_create_impl(storm_hip_ctx *c, int64_t n_owned, int64_t n_halo, st
       break;
     }
   }
-  // (option vec_contiguous: physically contiguous storage -- the largest page-table fragments the driver can give)
-  auto device_malloc = [&](double **p) {
-    if (c->opt_vec_contiguous != 0 && bytes >= ((size_t)1 << 21)) {
-      if (hipExtMallocWithFlags((void **)p, bytes, hipDeviceMallocContiguous) == hipSuccess) return hipSuccess;
-      (void)hipGetLastError();
-    }
-    return hipMalloc(p, bytes);
-  };
   if (base == nullptr) base = arena_take(c, bytes);
   if (base == nullptr) {
-    e = device_malloc(&base);
+    e = hipMalloc(&base, bytes);
     if (e != hipSuccess && !c->pool.empty()) {  // give the pooled storage back and retry
       (void)hipStreamSynchronize(c->stream);
       pool_release(c);
-      e = device_malloc(&base);
+      e = hipMalloc(&base, bytes);
     }
   }
   if (e != hipSuccess) {

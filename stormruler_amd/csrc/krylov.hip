@@ -591,7 +591,6 @@ struct KrylovEngine {
   // device state (own: solves may nest, e.g. a solver used as another solver's preconditioner)
   SolverState *d_st = nullptr, *h_st = nullptr;
   unsigned long long *h_ring = nullptr, *d_ring = nullptr;
-  std::vector<hipEvent_t> ev;
   double *S = nullptr;
   int S_cap = 0, S_top = 0;
   double *d_history = nullptr;
@@ -634,7 +633,7 @@ struct KrylovEngine {
   // Sweep directions (see storm_hip_solve_cg): every streaming statement deals its blocks out from the end of the
   // rows where the previous one stopped -- what the Infinity Cache still holds.  Same rows and slots per block.
   int sweep_dir = 1;
-  int flip() { return (c->opt_sweep_alternate != 0) ? (sweep_dir ^= 1) : 0; }
+  int flip() { return sweep_dir ^= 1; }
   int stream_flags() { return stream_nt(c, n) | (flip() << 1); }
   // per-method vectors and registers
   V p = nullptr, q = nullptr, r = nullptr, rt = nullptr, t = nullptr, u = nullptr, v = nullptr, y = nullptr, z = nullptr,
@@ -1779,7 +1778,6 @@ int storm_hip_krylov_destroy(storm_hip_krylov *k) {
   (void)hipSetDevice(k->c->device);
   (void)hipStreamSynchronize(k->c->stream);
   release_work(k);
-  for (auto &e : k->ev) (void)hipEventDestroy(e);
   if (k->c->krylov_free.size() < 8) {  // (the stream is idle: nothing reads these any more)
     k->c->krylov_free.push_back(KrylovRes{k->d_st, k->h_st, k->h_ring, k->d_ring, k->S, k->S_cap});
   } else {
@@ -1891,11 +1889,10 @@ static int krylov_solve_engine(storm_hip_krylov *k, const storm_hip_vec *b, stor
     k->it_enqueued = it + 1;
     k->applies_after.push_back(k->applies);
     k->pre_after.push_back(k->pre_applies);
-    // post a marker behind this iteration; look at the verdict of iteration it - lag
-    st = ring_post(c, k->ev, it);
-    if (st == STORM_HIP_OK && it >= k->lag) {
+    // look at the verdict of iteration it - lag
+    if (it >= k->lag) {
       bool stop = false;
-      st = ring_wait(c, k->ev, k->h_ring, it - k->lag, &stop);
+      st = ring_wait(c, k->h_ring, it - k->lag, &stop);
       if (stop) break;
     }
   }

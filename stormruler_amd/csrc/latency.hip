@@ -551,7 +551,8 @@ struct MgsArgs {
   MgsGivens givens;  // st == nullptr: the caller applies the rotations
   long long *prof;   // option resident_profile: [gridDim.x][8] ticks per phase of this launch (diagnostic)
   char *quad_slots;  // mgs_chain_quad_kernel: all-reduce slots of kQuadSlotStride bytes (two-level form) / dense granules
-  int dense;         // ... the flat all-reduce with dense value-major slots instead of the two-level one
+  int dense;         // ... the flat all-reduce with dense value-major slots instead of the two-level one: always 1 (the A/B is decided;
+                     // the argument stays because without it mgs_chain_quad_kernel<4, 3> is allocated 238 / 222 VGPRs instead of 211 / 196)
   int prefetch;      // ... with the next group's vectors requested between its halves (S <= 4)
   int xcd_runs;      // ... and the blocks' chunks of rows dealt out in ONE contiguous run per XCD (see the kernel)
   int descend;       // ... the basis vectors taken in the order k, k - 1, ..., 0 (odd k: see the kernel)
@@ -1223,8 +1224,7 @@ int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w
   // (a step of the chain costs half an all-reduce, ~2.5 us, whatever the size; the kernel-per-step path costs a launch,
   //  ~3.5 us, or 32 B/row of HBM traffic, whichever is more -- measured, us per inner iteration, per-step vs chained:
   //  step.1 83..106 vs 74.5, 32^3 84..109 vs 72, 64^3 91..106 vs 93, 128^3 248 vs 147)
-  if (c->opt_coop_mgs == 0 || c->coop_disabled != 0 || c->comm != nullptr || n < c->opt_coop_mgs_min_rows ||
-      k + 1 > kMgsMaxVectors || c->opt_profile_spmv != 0)
+  if (c->opt_coop_mgs == 0 || c->coop_disabled != 0 || c->comm != nullptr || k + 1 > kMgsMaxVectors || c->opt_profile_spmv != 0)
     return STORM_HIP_OK;
   const int64_t n_slices = (n + kWave - 1) / kWave;
   int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(std::min(c->num_cus, 256), (n_slices + kLatWaves - 1) / kLatWaves));
@@ -1240,8 +1240,8 @@ int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w
   //  32^3 43.0 / 43.5 / 48.3, 64^3 60.5 / 51.1 / 55.2, 128^3 104.5 / 106.3 / 100.0 -- profiles/r04p_gmres_chain_ab.jsonl; with the
   //  dense flat all-reduce the triples / quadruples take 38.9 / 52.6 / 97.2 and are the default wherever they fit;
   //  options coop_mgs_quad: 0 off, else on; coop_mgs_lds: 0 never, 1 where the quadruples are off, 2 always)
-  if ((c->opt_coop_mgs_lds == 2 || (c->opt_coop_mgs_lds == 1 && c->opt_coop_mgs_quad == 0 && n >= ((int64_t)1 << 17))) && c->opt_coop_mgs_pairs != 0 &&
-      sub >= 1 && sub <= 4) {
+  if ((c->opt_coop_mgs_lds == 2 || (c->opt_coop_mgs_lds == 1 && c->opt_coop_mgs_quad == 0 && n >= ((int64_t)1 << 17))) && sub >= 1 &&
+      sub <= 4) {
     const int sv = sub <= 1 ? 1 : sub <= 2 ? 2 : 4;
     fn = sv == 1 ? (const void *)mgs_chain_lds_kernel<1> : sv == 2 ? (const void *)mgs_chain_lds_kernel<2> : (const void *)mgs_chain_lds_kernel<4>;
     dyn_lds = sizeof(double) * 2 * (size_t)sv * kMgsSub;
@@ -1253,7 +1253,7 @@ int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w
   unsigned threads = kLatBlock;
   const int64_t qsubs_total = (n + kQuadSub - 1) / kQuadSub;
   const int qsub = (int)((qsubs_total + cus - 1) / cus);
-  if (c->opt_coop_mgs_quad != 0 && c->opt_coop_mgs_pairs != 0 && qsub >= 1 && qsub <= 8) {
+  if (c->opt_coop_mgs_quad != 0 && qsub >= 1 && qsub <= 8) {
     const int sv = qsub <= 1 ? 1 : qsub <= 2 ? 2 : qsub <= 4 ? 4 : 8;
     // (eight or sixteen rows per thread and FOUR vectors of them do not fit 256 registers beside the all-reduce: three there)
     // the operator applied inside the kernel: format-4 records with the six common offsets of a 3-D lattice numbering,
@@ -1270,7 +1270,7 @@ int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w
     // eight row pairs per thread: the next group's vectors through LDS (mgs_chain_quad_kernel<8, 3, APPLY, true>)
     size_t quad_lds = 0;
     // (with the apply only: the kernel that reads w instead has no registers left for the first vector -- 65 spills)
-    const bool lds_pf = sv == 8 && with_apply && c->opt_coop_dense != 0 && c->opt_coop_mgs_prefetch != 0 && c->opt_coop_mgs_lds_prefetch != 0;
+    const bool lds_pf = sv == 8 && with_apply && c->opt_coop_mgs_prefetch != 0 && c->opt_coop_mgs_lds_prefetch != 0;
     if (lds_pf) {
       qf = (const void *)mgs_chain_quad_kernel<8, 3, true, true>;
       quad_lds = sizeof(double) * 2 * 8 * (size_t)kQuadSub;
@@ -1306,14 +1306,14 @@ int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w
   for (int i = k + 1; i < kMgsMaxVectors; ++i) a.q[i] = q[0];
   a.w = w, a.H = H, a.norm2_out = norm2_out, a.n_rows = n, a.n_slices = n_slices, a.k = k, a.m = m;
   a.normalise = normalise ? 1 : 0;
-  a.pairs = (c->opt_coop_mgs_pairs != 0 && need <= 8) ? 1 : 0;  // (16 slices per wave + a third basis vector: spills)
+  a.pairs = need <= 8 ? 1 : 0;  // (16 slices per wave + a third basis vector: spills)
   a.seq_base = (1ull << 31) | (c->lat_seq & 0x7fffffffull);  // bit 31: never the tag of a CG solve (those count from 1)
   c->lat_seq += (unsigned long long)k + 2;
   a.slots = c->d_lat_slots, a.done = done;
   a.givens = (givens != nullptr && normalise && c->opt_coop_mgs != 2) ? *givens  // (coop_mgs = 2: A/B, rotations by the caller)
                                                                         : MgsGivens{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   a.quad_slots = c->d_quad_slots;
-  a.dense = (int)(c->opt_coop_dense != 0);
+  a.dense = 1;  // (see MgsArgs)
   a.prefetch = (int)(c->opt_coop_mgs_prefetch != 0);
   a.xcd_runs = (int)(c->opt_coop_mgs_xcd_runs != 0);
   a.descend = (int)(c->opt_coop_mgs_alternate != 0 && (k & 1) != 0);

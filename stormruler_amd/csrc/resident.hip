@@ -69,7 +69,6 @@ struct ResArgs {
   size_t exch_half;
   size_t exch_stride;   // a second exchange buffer this many bytes on (BiCGStab's early publish: one per travelling vector)
   char *slots;         // all-reduce slots, kLatSlotStride bytes per (block, parity)
-  char *dense;         // ... or (non-null) dense value-major granules: co_allreduce_dense, coop_device.hpp
   int *gave_up;        // the latency path's flag (lat_check_gave_up)
   long long *prof;     // option resident_profile: [gridDim.x][8] ticks of the 100 MHz counter per phase of the loop, summed over the solve
   unsigned long long *cnt;  // [0] all-reduce sequence number, [1] exchange sequence number: carried from solve to solve
@@ -143,10 +142,6 @@ __device__ __forceinline__ void res_allreduce_wait(double (&s)[NV], const ResArg
 }
 template <int NV>
 __device__ __forceinline__ void res_allreduce(double (&s)[NV], const ResArgs &A, unsigned long long seq, double *lds) {
-  if (A.dense) {  // one 16-byte load per thread and poll, whole lines
-    co_allreduce_dense<NV, kResWaves>(s, A.dense, A.gave_up, seq, lds);
-    return;
-  }
   res_allreduce_arrive<NV>(s, A, seq, lds);
   res_allreduce_wait<NV>(s, A, seq, lds);
 }
@@ -538,7 +533,7 @@ template <int TZ, bool XREG>
 __global__ __launch_bounds__(kResThreads) void res_cg_kernel(ResArgs A) {
   extern __shared__ __attribute__((aligned(16))) double P[];  // [TZ][a + kResRun + a]
   __shared__ double dict_sh[32];
-  __shared__ double red[2 * 256 + 16];  // (co_allreduce_dense: NV x 256 polled values + the results)
+  __shared__ double red[2 * kResWaves];  // (res_allreduce: NV <= 2 values per wave)
   const ResBox B0 = res_box<TZ>(A);
   ResBox B = B0;
   SolverState *st = A.st;
@@ -627,9 +622,8 @@ __global__ __launch_bounds__(kResThreads) void res_cg_kernel(ResArgs A) {
       // the surface of the new residual travels under the all-reduce below; the neighbours form p' = r + beta p on it --
       // BEHIND the block's own arrival at that all-reduce (in front of it every block arrives late by the time the
       // surface's stores take to drain: 2.7 -> 5.2 us for the all-reduce at 128^3)
-      const bool split = early && A.dense == nullptr;
-      if (split) res_allreduce_arrive<1>(acc, A, seq + 1, red);
       if (early) {
+        res_allreduce_arrive<1>(acc, A, seq + 1, red);
         const unsigned rtag = (unsigned)xseq;
 #pragma unroll
         for (int t = 0; t < TZ; ++t) res_publish_pair(A, B, t, r[t], rtag);
@@ -643,8 +637,8 @@ __global__ __launch_bounds__(kResThreads) void res_cg_kernel(ResArgs A) {
       //  surfaces this early costs the all-reduce more than it saves behind it -- 16.9 against 15.4 us per iteration;
       //  64^3, one plane per box: 8.4 against 9.2)
       constexpr bool kFetchUnderAllreduce = TZ <= 2;
-      if (split && kFetchUnderAllreduce) res_halo2_fetch<TZ>(A, B, (unsigned)xseq, hv, hat);
-      if (split) res_allreduce_wait<1>(acc, A, seq, red);
+      if (early && kFetchUnderAllreduce) res_halo2_fetch<TZ>(A, B, (unsigned)xseq, hv, hat);
+      if (early) res_allreduce_wait<1>(acc, A, seq, red);
       else res_allreduce<1>(acc, A, seq, red);
       lap(5);  // the second all-reduce
       const double gamma_bar = gamma;
@@ -682,7 +676,7 @@ __global__ __launch_bounds__(kResThreads) void res_cg_kernel(ResArgs A) {
       if (!go_on) break;
       if (early) {
         if (__hip_atomic_load(A.gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        if (split && TZ <= 2) res_halo2_finish<TZ>(A, B, P, (unsigned)xseq, hv, hat, &lo, &hi, beta);
+        if (TZ <= 2) res_halo2_finish<TZ>(A, B, P, (unsigned)xseq, hv, hat, &lo, &hi, beta);
         else if (!halo_first) res_halo<TZ, 2>(A, B, P, (unsigned)xseq, nullptr, &lo, &hi, beta);
         continue;
       }
@@ -719,7 +713,7 @@ template <int TZ, bool XLDS>
 __global__ __launch_bounds__(kResThreads) void res_bicgstab_kernel(ResArgs A) {
   extern __shared__ __attribute__((aligned(16))) double P[];  // [TZ][a + kResRun + a] (+ XLDS: [TZ][kResRun], x of the own rows, private to its thread)
   __shared__ double dict_sh[32];
-  __shared__ double red[2 * 256 + 16];  // (co_allreduce_dense: NV x 256 polled values + the results)
+  __shared__ double red[2 * kResWaves];  // (res_allreduce: NV <= 2 values per wave)
   const ResBox B0 = res_box<TZ>(A);
   ResBox B = B0;
   SolverState *st = A.st;
@@ -943,7 +937,7 @@ template <int TZ, bool XLDS>
 __global__ __launch_bounds__(kResThreads) void res_bicgstab_early_kernel(ResArgs A) {
   extern __shared__ __attribute__((aligned(16))) double P[];  // the copy, [XLDS: x of the own rows,] Hr, Hp, Hv
   __shared__ double dict_sh[32];
-  __shared__ double red[2 * 256 + 16];
+  __shared__ double red[2 * kResWaves];
   const ResBox B0 = res_box<TZ>(A);
   ResBox B = B0;
   SolverState *st = A.st;
@@ -1153,14 +1147,14 @@ static bool res_geometry(const storm_hip_op *op, ResGeometry *G, bool bicgstab =
   if (o[0] != -b || o[1] != -a || o[2] != -1 || o[3] != 1) return false;
   if (a < 2 || a > 512 || (a & 1) || (b & 1) || b < 2 * a) return false;
   const int64_t n = op->n_rows;
-  if (n < c->opt_resident_min_rows || n > c->opt_resident_max_rows) return false;
+  if (n > c->opt_resident_max_rows) return false;
   const int64_t nplanes = (n + b - 1) / b, nsec = (b + kResRun - 1) / kResRun;
   const int cus = std::min(c->num_cus, 256);
   if (nsec > cus) return false;
   const int variants[] = {1, 2, 3, 4, 6, 8, 12};
   for (int tz : variants) {
     if (c->opt_resident_planes > 0 && tz != c->opt_resident_planes) continue;  // (tests: a given depth, ragged last chunks)
-    if (tz > kResMaxPlanes || tz > c->opt_resident_max_planes || (bicgstab && tz > kResMaxPlanesBicg)) break;
+    if (tz > kResMaxPlanes || (bicgstab && tz > kResMaxPlanesBicg)) break;
     const int64_t blocks = nsec * ((nplanes + tz - 1) / tz);
     const size_t lds = sizeof(double) * (size_t)tz * (size_t)(kResRun + 2 * a);
     if (blocks > cus || lds > (size_t)150 * 1024) continue;
@@ -1242,7 +1236,7 @@ int res_solve(bool bicgstab, const storm_hip_op *op, double alpha, double beta, 
     c->res_exch_rows = op->n_rows + 2;
   }
   if (c->d_res_slots == nullptr) {
-    const size_t bytes = (size_t)2 * 256 * kLatSlotStride + 256 + (size_t)2 * kDenseMaxValues * 256 * 16;  // flat slots, counters, dense granules
+    const size_t bytes = (size_t)2 * 256 * kLatSlotStride + 256;  // flat slots, counters
     HIP_TRY(hipMalloc((void **)&c->d_res_slots, bytes));
     HIP_TRY(hipMemsetAsync(c->d_res_slots, 0, bytes, c->stream));
   }
@@ -1252,10 +1246,9 @@ int res_solve(bool bicgstab, const storm_hip_op *op, double alpha, double beta, 
   A.exch = c->d_res_exch, A.exch_half = (exch_half + 255) / 256 * 256, A.exch_stride = exch_stride, A.slots = c->d_res_slots;
   A.gave_up = reinterpret_cast<int *>(c->d_lat_slots + (size_t)2 * 256 * kLatSlotStride);
   A.cnt = reinterpret_cast<unsigned long long *>(c->d_res_slots + (size_t)2 * 256 * kLatSlotStride);
-  // (measured A/B, CG us per iteration with the dense form / the 64-byte slots: 64^3 10.0 / 8.9, 128^3 16.9 / 15.8 -- with ONE
-  //  or two values the extra barrier and the trip through LDS cost more than the fewer requests save; the Gram-Schmidt
-  //  chains, six and ten values, are the dense form's case.  coop_dense = 2 forces it here, for that A/B.)
-  A.dense = c->opt_coop_dense == 2 ? c->d_res_slots + (size_t)2 * 256 * kLatSlotStride + 256 : nullptr;
+  // (the 64-byte slots and not co_allreduce_dense's granules -- measured A/B, CG us per iteration with the dense form / the
+  //  64-byte slots: 64^3 10.0 / 8.9, 128^3 16.9 / 15.8 -- with ONE or two values the extra barrier and the trip through LDS
+  //  cost more than the fewer requests save; the Gram-Schmidt chains, six and ten values, are the dense form's case)
   A.early_publish = (int)(c->opt_resident_early != 0);
   A.apply_cache = (int)(c->opt_resident_apply_cache != 0);
   A.halo_interleave = (int)(c->opt_resident_halo_interleave != 0);

@@ -154,7 +154,6 @@ __global__ void step_kernel(int step, SolverState *st, GmresDev g, bool force) {
 
 // ---- fused vector kernels ------------------------------------------------------------------------
 // Same streaming shape as blas1.hip: one trip per thread, kUnroll x 16 bytes per stream in flight.
-static inline int vec_blocks(const storm_hip_ctx *, int64_t n) { return stream_blocks(n); }
 
 #define STORM_STREAM_FOR(base, n2) \
   for (int64_t base = (int64_t)blockIdx.x * (kBlock * kUnroll) + threadIdx.x; base < (n2); \
@@ -1170,13 +1169,12 @@ static int prepare_state(Driver &d, const storm_hip_solver_params *p, double *hi
   return STORM_HIP_OK;
 }
 
-// Post a status snapshot for iteration `it`; returns true in *stop when the snapshot of
-// iteration it - lag says the device is done.
+// Iteration `it` is enqueued; returns true in *stop when the word the device posted for
+// iteration it - lag says it is done.
 static int post_and_poll(Driver &d, int64_t it, bool *stop) {
   storm_hip_ctx *c = d.c;
-  STORM_TRY(ring_post(c, c->ev_ring, it));
   *stop = false;
-  if (it >= d.lag) STORM_TRY(ring_wait(c, c->ev_ring, c->h_done_ring, it - d.lag, stop));
+  if (it >= d.lag) STORM_TRY(ring_wait(c, c->h_done_ring, it - d.lag, stop));
   return STORM_HIP_OK;
 }
 
@@ -1245,39 +1243,6 @@ struct VecPool {  // work vectors: re-assigned (zeroed) on every solve like Solv
   }
 };
 
-// A launch-bound inner loop replayed from a hipGraph: one iteration's kernels are captured once
-// (their arguments never change -- every scalar is read from the device slab) and replayed per
-// iteration, which cuts the host cost of ~8 launches to one.  Not used with a communicator (RCCL
-// calls and the comm-stream fork stay eager) nor while per-launch profiling events are recorded.
-struct IterationGraph {
-  hipGraphExec_t exec = nullptr;
-  ~IterationGraph() {
-    if (exec) (void)hipGraphExecDestroy(exec);
-  }
-  template <class F>
-  int capture(storm_hip_ctx *c, int64_t iterations, F &&enqueue) {
-    if (c->opt_graph == 0 || c->comm != nullptr || c->opt_profile_spmv != 0 || iterations < 8) return STORM_HIP_OK;
-    HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    const int st = enqueue();
-    hipGraph_t graph = nullptr;
-    const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-    if (st != STORM_HIP_OK || e != hipSuccess || graph == nullptr) {  // fall back to eager launches
-      if (graph) (void)hipGraphDestroy(graph);
-      (void)hipGetLastError();
-      return st != STORM_HIP_OK ? st : STORM_HIP_OK;
-    }
-    if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr, (void)hipGetLastError();
-    (void)hipGraphDestroy(graph);
-    return STORM_HIP_OK;
-  }
-  template <class F>
-  int launch_or(storm_hip_ctx *c, F &&enqueue) {
-    if (exec == nullptr) return enqueue();
-    HIP_TRY(hipGraphLaunch(exec, c->stream));
-    return STORM_HIP_OK;
-  }
-};
-
 static int64_t applies_cg(int64_t it, int64_t) { return 1 + it; }
 static int64_t applies_bicg(int64_t it, int64_t) { return 1 + 2 * it; }
 static int64_t applies_gmres(int64_t it, int64_t m) { return 1 + it + (it + m - 1) / m; }
@@ -1324,7 +1289,7 @@ int gmres_orthogonalize(storm_hip_ctx *c, int64_t n, const SolverState *st, cons
     if (c->comm != nullptr) STORM_TRY(comm_allreduce_sum(c, norm2_out, 1));
     return STORM_HIP_OK;
   }
-  if (gram_schmidt == 0 && c->comm == nullptr && c->opt_ticket_reduce != 0 && c->opt_coop_mgs_pairs != 0) {
+  if (gram_schmidt == 0 && c->comm == nullptr && c->opt_ticket_reduce != 0) {
     // two steps per pass (mgs_pair_kernel): ceil((k + 1) / 2) + 1 launches for the k + 1 basis vectors
     const int nbp = (int)std::min<int64_t>(std::max<int64_t>(1, ((n >> 1) + kBlock - 1) / kBlock),
                                            std::min<int64_t>(32768, c->partials_capacity / 3));
@@ -1501,13 +1466,12 @@ int solve_cg_body(const FusedSolveArgs &args) {
   // (r: the init apply; p: init_residual's copy; z: the first SpMV -- all before any read; the fused step's second p)
   const bool may_fuse_step = c->opt_cg_fuse != 0 && spmv_can_fuse_cg(op);
   STORM_TRY(pool.make(x, may_fuse_step ? 4 : 3, false));
-  // (option cg_roles: which of the four work vectors -- consecutive slots of the context's arena -- plays p, r, z and the
-  //  second direction vector: the k-th permutation of (0, 1, 2, 3) in lexicographic order; an A/B knob for placement)
-  int role[4] = {0, 1, 2, 3};
-  for (int64_t k = 0; k < c->opt_cg_roles % 24; ++k) std::next_permutation(role, role + 4);
-  if (!may_fuse_step) role[0] = 0, role[1] = 1, role[2] = 2;
+  // (which of the four work vectors -- consecutive slots of the context's arena -- plays p, r, z and the second direction
+  //  vector is a matter of placement: the 24 assignments at 256^3 gave 4 505 - 4 570 it/s, profiles/r05z_roles.txt)
+  static const int kRolesFused[4] = {1, 2, 0, 3}, kRolesPlain[3] = {0, 1, 2};
+  const int *role = may_fuse_step ? kRolesFused : kRolesPlain;
   double *p = pool.v[v0 + role[0]]->d, *r = pool.v[v0 + role[1]]->d, *z = pool.v[v0 + role[2]]->d;
-  const int nbv = vec_blocks(c, n);
+  const int nbv = stream_blocks(n);
 
   // init: r = b - A x; p = r; gamma = <r,r>          SolverCg.hpp:75-85
   int nb = 0;
@@ -1524,9 +1488,8 @@ int solve_cg_body(const FusedSolveArgs &args) {
   // Sweep directions.  The 256 MB Infinity Cache still holds the END of what the previous kernel streamed (a read
   // served from it runs ~18 % faster than from HBM, tools/mall_probe.hip), so every kernel starts where its
   // predecessor stopped: iteration k even -- SpMV forward, cg_r backward, cg_xp forward; k odd -- the mirror image.
-  // Blocks keep their rows and their partial slots: the same bits either way.
-  const bool sweep = c->opt_sweep_alternate != 0;  // (per rank: with a communicator too)
-  const int nt_stream = (int)(stream_nt(c, n) != 0 && !(sweep && c->opt_sweep_alternate == 2));
+  // Blocks keep their rows and their partial slots: the same bits either way.  (Per rank: with a communicator too.)
+  const int nt_stream = stream_nt(c, n);
   // Reductions that finish inside the kernels producing their partials (ticket_device.hpp), one rank: an iteration
   // is then three launches -- SpMV (+ <p,z>), cg_r (+ <r,r>, beta, the convergence rule), cg_xp.
   // (on the peer-window transport too: the block that finishes a reduction exchanges its sum with the other ranks itself)
@@ -1563,7 +1526,7 @@ int solve_cg_body(const FusedSolveArgs &args) {
   if (r_planes) ++c->n_cg_residual_plane_marches;
   int64_t last_enqueued = -1;
   auto enqueue_iteration = [&]() -> int {
-    const int q = fuse_step ? 0 : sweep ? (int)(cur_it & 1) : 0;  // (fused: the step kernel forward, cg_r backward, always)
+    const int q = fuse_step ? 0 : (int)(cur_it & 1);  // (fused: the step kernel forward, cg_r backward, always)
     // z = A p, <p,z>                                  SolverCg.hpp:96-97
     c->spmv_reverse = q;
     int pz_done = 0;  // <p,z> finished inside the SpMV kernel (tickets): cg_r reads it from the slab
@@ -1610,12 +1573,12 @@ int solve_cg_body(const FusedSolveArgs &args) {
     // r -= alpha z; gamma = <r,r>                     SolverCg.hpp:97,99,115
     if (r_march_now && r_planes) {
       STORM_TRY(cg_r_planes_run(op, r_planes_args, r_planes_blocks, host_scal(alpha), host_scal(beta), p, d.st, r, pz_partials,
-                                (int)kStage2, sweep ? 1 - q : 0));
+                                (int)kStage2, 1 - q));
     } else if (r_march_now) {
-      STORM_TRY(cg_r_recompute_run(op, nbv, host_scal(alpha), host_scal(beta), p, d.st, r, pz_partials, (int)kStage2, sweep ? 1 - q : 0));
+      STORM_TRY(cg_r_recompute_run(op, nbv, host_scal(alpha), host_scal(beta), p, d.st, r, pz_partials, (int)kStage2, 1 - q));
     } else {
       hipLaunchKernelGGL(cg_r_kernel, dim3(nbv), dim3(kBlock), 0, c->stream, n, d.st, r, z, c->d_partials,
-                         nt_stream, pz_partials, (int)kStage2, sweep ? 1 - q : 0,
+                         nt_stream, pz_partials, (int)kStage2, 1 - q,
                          (tick || rtick) ? TicketArgs{c->d_tickets, c->d_partials, c->d_ticket_sums} : TicketArgs{nullptr, nullptr, nullptr},
                          ipc_w, rtick ? 2 : (int)(ipc && tick));
       HIP_TRY(hipGetLastError());
@@ -1694,7 +1657,7 @@ int solve_bicgstab_body(const FusedSolveArgs &args) {
   //  452 against 445 us per iteration at 256^3; profiles/experiments/r08_pruned_experiments.patch)
   STORM_TRY(pool.make(x, 5, false));  // (r, rt: init; p: the copy of iteration 0; v, t: the SpMVs -- all before any read)
   double *p = pool.v[v0]->d, *r = pool.v[v0 + 1]->d, *rt = pool.v[v0 + 2]->d, *t = pool.v[v0 + 3]->d, *v = pool.v[v0 + 4]->d;
-  const int nbv = vec_blocks(c, n);
+  const int nbv = stream_blocks(n);
   const int nbv2 = nbv;  // second half-step: one access per stream in flight, four trips per thread
   int nb = 0;
 
@@ -1709,9 +1672,8 @@ int solve_bicgstab_body(const FusedSolveArgs &args) {
   }
   // Sweep directions as in storm_hip_solve_cg: every streaming kernel starts at the end of the rows where its
   // predecessor stopped (what the Infinity Cache still holds); blocks keep their rows and partial slots.
-  const bool sweep = c->opt_sweep_alternate != 0 && c->opt_graph == 0;
   int dir = 1;
-  auto flip = [&]() -> int { return sweep ? (dir ^= 1) : 0; };
+  auto flip = [&]() -> int { return dir ^= 1; };
   // ... and reductions finished in-kernel (see storm_hip_solve_cg): five launches per iteration instead of eleven.
   const bool tick = c->opt_ticket_reduce != 0 && c->comm == nullptr && nbv <= kTicketGroup * kTicketMaxGroups;
   const TicketArgs no_tickets{nullptr, nullptr, nullptr}, tickets{c->d_tickets, c->d_partials, c->d_ticket_sums};
@@ -1719,7 +1681,7 @@ int solve_bicgstab_body(const FusedSolveArgs &args) {
   // it with the other ranks (ipc_device.hpp); the update kernels form alpha / omega themselves and the second half-step's
   // last block all-reduces |r|^2, <rt, r> and runs the scalar step -- as on one rank, plus two small launches per iteration.
   IpcDev ipc_w{};
-  const bool ipc_tick = c->opt_ticket_reduce != 0 && c->opt_ipc_bicg_ticket != 0 && c->comm != nullptr && comm_ipc_next(c, &ipc_w) &&
+  const bool ipc_tick = c->opt_ticket_reduce != 0 && c->comm != nullptr && comm_ipc_next(c, &ipc_w) &&
                         nbv <= kTicketGroup * kTicketMaxGroups;
   // RCCL: the halo of the vector an update kernel is about to form leaves BEFORE that kernel (comm.hip)
   const bool early_halo = c->comm != nullptr && comm_is_rccl(c) && c->opt_rccl_early_halo != 0 && op->halo.n_nbrs > 0;
@@ -1841,15 +1803,13 @@ int solve_bicgstab_body(const FusedSolveArgs &args) {
     STORM_TRY(st_p);
     return enqueue_rest();
   };
-  IterationGraph graph;
-  STORM_TRY(graph.capture(c, params->num_iterations - 1, enqueue_iteration));
   for (int64_t it = 0; it < params->num_iterations; ++it) {
     bi_it = it;
     if (it == 0) {
       STORM_TRY(k_copy(c, p, r, n, d.done));  // :114
       STORM_TRY(enqueue_rest());
     } else {
-      STORM_TRY(graph.launch_or(c, enqueue_iteration));
+      STORM_TRY(enqueue_iteration());
     }
     bool stop = false;
     STORM_TRY(post_and_poll(d, it, &stop));
@@ -1891,7 +1851,7 @@ int solve_gmres_body(const FusedSolveArgs &args) {
   HIP_TRY(hipMemsetAsync(d_gm, 0, sizeof(double) * gm_doubles, c->stream));
   d.g = GmresDev{d_gm, d_gm + (size_t)(m + 1) * m, d_gm + (size_t)(m + 1) * m + (m + 1),
                  d_gm + (size_t)(m + 1) * m + (m + 1) + m, m};
-  const int nbv = vec_blocks(c, n);
+  const int nbv = stream_blocks(n);
   int nb = 0;
 
   // q0 = b - A x; beta0 = |q0|; q0 /= beta0        (outer_init :82-88 and inner_init :110-116)

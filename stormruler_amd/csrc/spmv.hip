@@ -126,7 +126,7 @@ bool spmv_can_fuse_cg(const storm_hip_op *op) {
   MarchArgs M;
   // ... or on RCCL: the boundary planes of p' are packed by a small kernel and travel on the comm stream under the march
   return op->halo.n_nbrs > 0 && op->d_bnd_pack != nullptr && op->tail_rows == 0 &&
-         ((comm_is_ipc(op->ctx) && op->ctx->opt_ipc_fused != 0) || (comm_is_rccl(op->ctx) && op->ctx->opt_rccl_fused != 0)) &&
+         (comm_is_ipc(op->ctx) || (comm_is_rccl(op->ctx) && op->ctx->opt_rccl_fused != 0)) &&
          op->n_boundary > 0 && cg_march_geometry(op, &M, &nb, true);
 }
 
@@ -154,7 +154,7 @@ int spmv_launch(const storm_hip_op *op, Scal alpha, Scal beta, const double *x, 
   const bool split = exchange || op->d_bnd_pack != nullptr;
   DotArgs dot{nullptr, nullptr, 0, 0, 0};
   // peer-window transport + paired records: the fused form of the exchange (IpcFused)
-  const bool fuse_x = exchange && comm_is_ipc(c) && op->pair != 0 && c->opt_ipc_fused != 0 && op->n_boundary > 0;
+  const bool fuse_x = exchange && comm_is_ipc(c) && op->pair != 0 && op->n_boundary > 0;
   IpcFused fx;
   if (fuse_x) STORM_TRY(comm_ipc_exchange(op, &fx.w, &fx.sp, &fx.rp));
   const int nbi_tile = split ? interior_blocks(op, accumulate, 0) : -1;  // (send blocks carry no partials)

@@ -296,14 +296,14 @@ SellArgs lattice_args(const storm_hip_op *op);
 
 // ---- geometry shared by dispatch and launchers -----------------------------------------------------------------------
 // 128-row groups per wave of the format-4 / 5 kernel.
-static inline int canon_groups(const storm_hip_op *op) { return op->ctx->opt_spmv_canon_groups == 2 ? 2 : 1; }
+constexpr int kCanonGroups = 2;
 // Slices per wave: SPW for the uniform-width value-dictionary kernel, 1 otherwise.
 static inline int op_spw(const storm_hip_op *op) {
   if (op->pair) return 1;  // a "slice" of a format-3 operator is a 128-row group, one per wave
   return (op->dict_size > 0 && op->uniform_width > 0) ? (int)op->spw : 1;
 }
 static inline int blocks_for(const storm_hip_op *op, int64_t n_launch_slices, bool boundary_of_mixed = false) {
-  const int64_t per_block = (kBlock / kWave) * ((op->pair >= 2 && !boundary_of_mixed) ? canon_groups(op) : op_spw(op));
+  const int64_t per_block = (kBlock / kWave) * ((op->pair >= 2 && !boundary_of_mixed) ? kCanonGroups : op_spw(op));
   return (int)((n_launch_slices + per_block - 1) / per_block);
 }
 // the launch over the boundary groups of a mixed operator (format-3 records of their own, in list order)

@@ -509,8 +509,7 @@ static bool launch_tile(const RangeLaunch &L, SellArgs A) {
   const int tz = canon_tile_planes(op);
   const int hl_need = (tz * T.a + kBlock - 1) / kBlock;
   // (the row-record index: its word table behind the tile's x in the dynamic LDS)
-  const size_t lds = sizeof(double) * (size_t)tz * (size_t)(kTileRun + 2 * T.a) + sizeof(uint64_t) * (size_t)A.rec_words_n +
-                     (size_t)op->ctx->opt_spmv_tile_lds_pad;
+  const size_t lds = sizeof(double) * (size_t)tz * (size_t)(kTileRun + 2 * T.a) + sizeof(uint64_t) * (size_t)A.rec_words_n;
   const bool wload = DOT && dot.w != nullptr && dot.w != x;
 #define TILE_GO4(WL_, TZ_, HL_, FU_, IX_, CGF_)                                                                             \
   hipExtLaunchKernelGGL((spmv_canon_tile_kernel<DOT, WL_, TZ_, HL_, FU_, IX_>), dim3(nb), dim3(kBlock), lds, st, ev0, ev1, 0, A, \

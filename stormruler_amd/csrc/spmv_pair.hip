@@ -271,20 +271,13 @@ static void launch_canon(const RangeLaunch &L, SellArgs A) {
     const int span = kNumXcd * group;
     C.xcd_full = (nb / span) * span;
   }
-#define CANON_GO2(K_, M1_, G_)                                                                                       \
-  hipExtLaunchKernelGGL((spmv_canon_kernel<DOT, K_, M1_, G_>), dim3(nb), dim3(kBlock), 0, st, ev0, ev1, 0, A, C, alpha, \
-                      beta, x, y, slice_list, n_launch, dot, done)
-#define CANON_GO(K_, M1_)                                      \
-  do {                                                         \
-  const bool two = canon_groups(op) == 2;                    \
-  if (two) CANON_GO2(K_, M1_, 2);                            \
-  else CANON_GO2(K_, M1_, 1);                                \
-  } while (0)
+#define CANON_GO(K_, M1_)                                                                                                     \
+  hipExtLaunchKernelGGL((spmv_canon_kernel<DOT, K_, M1_, kCanonGroups>), dim3(nb), dim3(kBlock), 0, st, ev0, ev1, 0, A, C, alpha, \
+                        beta, x, y, slice_list, n_launch, dot, done)
   if (op->canon_k == 6) CANON_GO(6, 2);
   else if (op->canon_k == 4) CANON_GO(4, 1);
   else CANON_GO(2, 0);
 #undef CANON_GO
-#undef CANON_GO2
 }
 
 bool spmv_canon_run(const RangeLaunch &L) {
