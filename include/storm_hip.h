@@ -143,14 +143,38 @@ int storm_hip_vec_get(const storm_hip_vec *v, int64_t row, double *value);
  * One call per Bittern expression statement the solver bodies execute
  * (overload census); each is one kernel over the owned rows.
  * Reference loops: Bittern/MatrixAlgorithms.hpp:58-81 (matrix_for_each),
- * :162-205 (reduce).  Reductions return the sum over all ranks. */
+ * :162-205 (reduce).  Reductions return the sum over all ranks.
+ *
+ * Rounding.  The library is built with -ffp-contract=on: a product may be fused into the addition that consumes it,
+ * within one expression.  WHICH evaluation of the reference's expression an entry point gives is part of its contract,
+ * the same on every row (the odd last row included), for every size, under every blas1_nt setting and with
+ * lazy_statements 0 or 1 (tests/test_gpu_exact_statements.py; fl = one rounding, fma(a, b, c) = fl(a b + c) with the
+ * product exact).  ONE EXCEPTION, lazy_statements = 2 (which the host loops of Storm.hpp / api.py switch on): where
+ * `x += a p; p <<= r + b p; z = A p; <p, z>` leaves as the fused CG step of a lattice operator (see that option below),
+ * storm_hip_xpay IS fma(b, y, x) -- one rounding, as the library's device loop computes it -- not the form of this table
+ * (storm_hip_axpy is fma(a, x, y) either way):
+ *     fill, copy, scale, div_scalar, vmul                    one operation, correctly rounded
+ *     vdiv                                                   fl(fl(s a) / b);  a == NULL: fl(s / b)
+ *     axpbz(y, a, x, b, z)                                   fma(a, x, fl(b z)): the FIRST product is the fused one
+ *       with b == 0 and z the same vector as x               fl(a x) -- `y <<= a * x`: -0, +-inf as a * x gives them
+ *     axpy(y, a, x)   = axpbz(y, a, x, 1, y)                 fma(a, x, y)
+ *     xpay(y, x, b)   = axpbz(y, 1, x, b, y)                 fl(x + fl(b y)): NOT fma(b, y, x)
+ *     lin3(y, r, s, a, x, b, z)                              fma(s, fma(a, x, fl(b z)), r)
+ *     bicgstab_p(p, r, beta, omega, v)                       fma(beta, fma(-omega, v, p), r)
+ *     vmul_add(y, s, a, b)                                   fma(s, fl(a b), y)
+ *     multi_axpy(y, coefs, xs, k)                            y = fma(coefs[j], xs[j], y) for j = 0 .. k - 1 in turn
+ *     map                                                    every operation rounded on its own (see below)
+ * So BiCGStab's p through storm_hip_lin3(p, r, beta, 1, p, -omega, v) -- fma(beta, fl(p + fl(-omega v)), r) -- and through
+ * storm_hip_bicgstab_p differ in the last place on about one row in eleven: a caller who wants the bits of one must
+ * call that one. */
 int storm_hip_fill(storm_hip_vec *y, double value);                        /* fill_with(y, v)   Solver.hpp:281 */
 int storm_hip_copy(storm_hip_vec *y, const storm_hip_vec *x);              /* y <<= x           MatrixAlgorithms.hpp:120-124 */
 int storm_hip_scale(storm_hip_vec *y, double s);                           /* y *= s            MatrixTarget.hpp:96-99 */
 int storm_hip_div_scalar(storm_hip_vec *y, double s);                      /* y /= s            MatrixTarget.hpp:101-105, SolverGmres.hpp:88 */
 int storm_hip_axpy(storm_hip_vec *y, double a, const storm_hip_vec *x);    /* y += a*x (a<0: y -= |a|*x)  SolverCg.hpp:98-99 */
 int storm_hip_xpay(storm_hip_vec *y, const storm_hip_vec *x, double b);    /* y <<= x + b*y     SolverCg.hpp:123 */
-/* y <<= a*x + b*z  (covers r <<= b - r, Operator.hpp:98; y may alias x or z) */
+/* y <<= a*x + b*z  (covers r <<= b - r, Operator.hpp:98; y may alias x or z).  b == 0 with z the same vector as x is
+ * the one-term statement `y <<= a * x`: x is streamed once. */
 int storm_hip_axpbz(storm_hip_vec *y, double a, const storm_hip_vec *x, double b, const storm_hip_vec *z);
 /* p <<= r + beta*(p - omega*v)   SolverBiCgStab.hpp:119 */
 int storm_hip_bicgstab_p(storm_hip_vec *p, const storm_hip_vec *r, double beta, double omega,
@@ -205,7 +229,7 @@ int storm_hip_multi_dot(const storm_hip_vec *a, const storm_hip_vec *const *bs, 
  * _begin + _end.  (With a communicator, or k > 8, _begin computes the sums and _end returns them.) */
 int storm_hip_multi_dot_begin(const storm_hip_vec *a, const storm_hip_vec *const *bs, int k, int *request);
 int storm_hip_multi_dot_end(storm_hip_ctx *ctx, int request, double *out);
-/* y += sum_i coefs[i] * xs[i]  (SolverGmres.hpp:233-236 batched) */
+/* y += sum_i coefs[i] * xs[i]  (SolverGmres.hpp:233-236 batched).  No xs[i] may be y (refused); they may repeat. */
 int storm_hip_multi_axpy(storm_hip_vec *y, const double *coefs, const storm_hip_vec *const *xs, int k);
 
 /* ---- operators -----------------------------------------------------------

@@ -99,6 +99,15 @@ struct AxpbzF {
   __device__ void prepare() { av = ld_scal(a), bv = ld_scal(b); }
   __device__ double operator()(double, double x0, double x1) const { return av * x0 + bv * x1; }
 };
+// y = a*x0: the one-term statement `y <<= a * x` (a x + 0 x is NaN for x = +-inf and +0 for a < 0, x = +0)
+struct ScaleXF {
+  static constexpr bool reads_y = false;
+  static constexpr int nin = 1;
+  Scal a;
+  double av;
+  __device__ void prepare() { av = ld_scal(a); }
+  __device__ double operator()(double, double x0, double) const { return av * x0; }
+};
 // p = r + beta*(p - omega*v)     SolverBiCgStab.hpp:119
 struct BicgPF {
   static constexpr bool reads_y = true;
@@ -686,8 +695,11 @@ int storm_hip_xpay(storm_hip_vec *y, const storm_hip_vec *x, double b) {
 int storm_hip_axpbz(storm_hip_vec *y, double a, const storm_hip_vec *x, double b, const storm_hip_vec *z) {
   STORM_TRY(check_pair(y, x, "axpbz"));
   STORM_TRY(check_pair(y, z, "axpbz"));
-  if (lazy_on(y->ctx)) return lazy_push_lin(y->ctx, y, a, x->d, b, z->d, 2, y->n_owned);
+  // `y <<= a * x` arrives as a x + 0 x (Storm.hpp, api.py): one term, one stream, fl(a x) for every x
+  const bool one_term = b == 0.0 && z->d == x->d;
+  if (lazy_on(y->ctx)) return lazy_push_lin(y->ctx, y, a, x->d, b, z->d, one_term ? 1 : 2, y->n_owned);
   STORM_TRY(lazy_sync(y->ctx));
+  if (one_term) return launch_ew(y->ctx, y->n_owned, EwPtrs{y->d, x->d, nullptr}, ScaleXF{host_scal(a), 0.0}, y->ctx->api_done);
   return k_axpbz(y->ctx, y->d, host_scal(a), x->d, host_scal(b), z->d, y->n_owned, y->ctx->api_done);
 }
 
@@ -904,6 +916,8 @@ int storm_hip_multi_axpy(storm_hip_vec *y, const double *coefs, const storm_hip_
   const double *ptrs[kMaxMulti];
   for (int j = 0; j < k; ++j) {
     STORM_TRY(check_pair(y, xs[j], "multi_axpy"));
+    // (the kernel loads a chunk's x_j before it updates y, and a second chunk sees the first one's y)
+    STORM_REQUIRE(xs[j]->d != y->d, "multi_axpy: xs[%d] aliases y", j);
     ptrs[j] = xs[j]->d;
   }
   STORM_TRY(lazy_sync(y->ctx));

@@ -6,7 +6,10 @@
 // _axpbz) and storm_hip_op_apply are NOT launched when called: they wait, in program order, for the call that needs
 // their result.  When that call is a reduction over a vector the LAST waiting statement writes, the reduction rides in
 // that statement's kernel:
-//     x += alpha p;  r -= alpha z;  <r, r>       ONE pass: both updates and the sum (lazy_lin_kernel<2, true>)
+//     x += alpha p;  r -= alpha z;  <r, r>       the sum rides with `r -= alpha z` (lazy_lin_kernel<1, true>); x += alpha p,
+//                                                which neither it nor the sum depends on, keeps waiting (lazy_try_dot)
+//     x += alpha p;  r -= x;  <r, r>             a statement that reads what the one before it writes: ONE pass, both
+//                                                updates and the sum (lazy_lin_kernel<2, true>)
 //     z = A p;  <p, z>                           the apply with its fused-dot epilogue (spmv_launch with SpmvDot)
 //     x += alpha p;  [r -= alpha z;  <r, r>;]  p <<= r + beta p;  z = A p;  <p, z>
 //                                                on a lattice operator the library's own fused CG step

@@ -965,3 +965,395 @@ def richardson_h1(shape, b):
     its scale 2^-10 and its root correctly rounded -- bitwise."""
     _, R = richardson_integers(shape, b, 1)
     return math.sqrt(exact_dot(R, R) / 1024.0)
+
+
+# ---- the vector statements --------------------------------------------------------------------------------------------
+#
+# The elementwise half of BLAS-1 (fill, copy, *=, /=, +=, x + b y, a x + b z, r + s (a x + b z), BiCGStab's p, vmul,
+# vmul_add, vdiv, multi_axpy) in two models.
+#
+# Integer model (``INT_STATEMENTS``): integer vectors, coefficients integers or dyadic fractions, divisors powers of
+# two.  Every value is k / 2^s with |k| < 2^53 (``Dyadic``, asserted on every product and every sum), so every product
+# and every sum is exact in fp64, every contraction choice gives the same bits, and a kernel is compared BITWISE
+# whatever the compiler did.  The vectors depend on the row index (``stmt_vector``), so a shifted, swapped or repeated
+# block cannot reproduce the expected vector.
+#
+# Rounding forms (``REAL_STATEMENTS``): on real-valued data a statement has a finite list of admissible evaluations of
+# the reference's expression under "a product may be fused into the addition that consumes it".  Each form is a named
+# vector of correctly rounded fp64 values: unfused steps are numpy's (one IEEE operation per ufunc, nothing contracts),
+# fused ones come from exact integer ratios (``fma``: int / int is correctly rounded in CPython).  ``classify`` names the
+# forms a result equals on EVERY element.
+
+SENTINEL = -1.0e300  # pre-fill of a target: no statement below produces it
+
+
+def stmt_vector(n, seed):
+    """int_vector plus (row mod 1999): integers in [-1000, 2998] that depend on the row index."""
+    return int_vector(n, seed) + (np.arange(n, dtype=np.int64) % 1999)
+
+
+def pow2_vector(n, seed):
+    """Divisors for vdiv: 1, 2, 4 or 8, by row and seed."""
+    return np.int64(1) << ((np.arange(n, dtype=np.int64) + seed) % 4)
+
+
+class Dyadic:
+    """k / 2^s elementwise (k int64, |k| < 2^53): an fp64 value exactly.  Products and sums assert the bound on their
+    result at the finer of the two scales, which covers every operand of every evaluation order.  A zero carries the
+    sign IEEE arithmetic gives it (``neg0``: the rows that are -0; None: none) -- the same for every contraction choice,
+    since the products are exact: (-0.25) * 0 is -0, and a sum is -0 only where both terms are."""
+
+    def __init__(self, k, s=0, neg0=None):
+        self.k = np.asarray(k, dtype=np.int64)
+        self.s = int(s)
+        self.neg0 = neg0
+        assert self.mag() < EXACT, f"|k| reaches 2^53 ({self.mag()})"
+
+    @classmethod
+    def of(cls, c):
+        """A scalar coefficient: an integer or a dyadic fraction."""
+        q = Fraction(c)
+        s = q.denominator.bit_length() - 1
+        assert q.denominator == 1 << s, f"{c!r} is not dyadic"
+        return cls(q.numerator, s)
+
+    def mag(self):
+        return int(np.abs(self.k).max(initial=0))
+
+    def _negative(self):
+        return (self.k < 0) if self.neg0 is None else ((self.k < 0) | self.neg0)
+
+    def __mul__(self, o):
+        assert self.mag() * o.mag() < EXACT, "a product reaches 2^53"
+        k = self.k * o.k
+        neg0 = (k == 0) & (self._negative() ^ o._negative())
+        return Dyadic(k, self.s + o.s, neg0 if neg0.any() else None)
+
+    def __add__(self, o):
+        s = max(self.s, o.s)
+        assert (self.mag() << (s - self.s)) + (o.mag() << (s - o.s)) < EXACT, "a sum reaches 2^53"
+        neg0 = None if self.neg0 is None or o.neg0 is None else self.neg0 & o.neg0
+        return Dyadic((self.k << (s - self.s)) + (o.k << (s - o.s)), s, neg0)
+
+    def over_pow2(self, b):
+        """Elementwise quotient by powers of two (positive int64)."""
+        b = np.asarray(b, dtype=np.int64)
+        assert b.size == 0 or (int(b.min()) > 0 and not int(np.bitwise_and(b, b - 1).max()))
+        top = int(b.max(initial=1))
+        return self * Dyadic(top // b, top.bit_length() - 1)
+
+    def value(self):
+        v = np.ldexp(self.k.astype(np.float64), -self.s)
+        if self.neg0 is not None:
+            v[np.broadcast_to(self.neg0, v.shape)] = -0.0
+        return v
+
+
+def _d(v):
+    return v if isinstance(v, Dyadic) else (Dyadic(v) if isinstance(v, np.ndarray) else Dyadic.of(v))
+
+
+def int_axpbz(a, x, b, z):
+    return _d(a) * _d(x) + _d(b) * _d(z)
+
+
+def int_lin3(r, s, a, x, b, z):
+    return _d(r) + _d(s) * int_axpbz(a, x, b, z)
+
+
+def int_multi_axpy(y, coefs, xs):
+    acc = _d(y)
+    for c, x in zip(coefs, xs):  # ascending j: the kernel's order, every partial sum asserted
+        acc = acc + _d(c) * _d(x)
+    return acc
+
+
+# coefficients of the integer model: integers and dyadic fractions of both signs
+I_FILL, I_SCALE, I_DIV, I_A1, I_AXPY, I_XPAY = 7.0, -0.25, 4.0, -0.25, 0.5, 3.0
+I_A, I_B, I_S, I_BETA, I_OMEGA, I_VS, I_VD = 3.0, -0.25, 0.5, -0.25, 3.0, 0.5, 3.0
+MAP_CONSTS = (3.0,)  # the fixed storm_hip_map program: y <<= 3 x0 + x1 * y  (RPN: x0 c0 * x1 y * +)
+
+
+def multi_coefs_int(k):
+    return [(0.5, -0.25, 3.0, -1.0, 2.0)[j % 5] for j in range(k)]
+
+
+# name -> (number of vectors, the target's old value first; f(vectors) -> Dyadic).  The divisors of vdiv are the LAST vector.
+INT_STATEMENTS = {
+    "fill": (1, lambda v: Dyadic.of(I_FILL) * Dyadic(np.ones_like(v[0]))),
+    "copy": (2, lambda v: _d(v[1])),
+    "scale": (1, lambda v: _d(I_SCALE) * _d(v[0])),
+    "div_scalar": (1, lambda v: _d(v[0]) * Dyadic.of(1 / Fraction(I_DIV))),
+    "scaled_copy": (2, lambda v: _d(I_A1) * _d(v[1])),
+    "axpy": (2, lambda v: int_axpbz(I_AXPY, v[1], 1, v[0])),
+    "xpay": (2, lambda v: int_axpbz(1, v[1], I_XPAY, v[0])),
+    "axpbz": (3, lambda v: int_axpbz(I_A, v[1], I_B, v[2])),
+    "lin3": (4, lambda v: int_lin3(v[1], I_S, I_A, v[2], I_B, v[3])),
+    "bicgstab_p": (3, lambda v: int_lin3(v[1], I_BETA, 1, v[0], -I_OMEGA, v[2])),
+    "vmul_add": (3, lambda v: _d(v[0]) + _d(I_VS) * (_d(v[1]) * _d(v[2]))),
+    "vmul": (3, lambda v: _d(v[1]) * _d(v[2])),
+    "vdiv": (3, lambda v: (_d(I_VD) * _d(v[1])).over_pow2(v[2])),
+    "vdiv_scalar": (2, lambda v: (_d(I_VD) * Dyadic(np.ones_like(v[1]))).over_pow2(v[1])),
+    "map": (3, lambda v: _d(MAP_CONSTS[0]) * _d(v[1]) + _d(v[2]) * _d(v[0])),
+}
+MULTI_KS = (1, 2, 3, 4, 5, 8, 9, 19, 64)  # every multi_axpy_kernel<KB> unroll class (1-2, 3-4, 5-8) and the chunk boundary
+for _k in MULTI_KS:
+    INT_STATEMENTS[f"multi_axpy{_k}"] = (_k + 1, lambda v, _k=_k: int_multi_axpy(v[0], multi_coefs_int(_k), v[1:]))
+DIVISOR_LAST = ("vdiv", "vdiv_scalar")
+
+
+def int_operands(name, n, seed=0, distinct=None, make=stmt_vector):
+    """The int64 vectors of a statement of the integer model (target first), each from its own seed.  ``distinct``:
+    at most so many different INPUT vectors, repeated in turn (a long multi_axpy on long vectors; 4 is coprime to the
+    period of its coefficients).  ``make(n, seed)`` builds a vector (a caller may cache)."""
+    count = INT_STATEMENTS[name][0]
+    vecs = [make(n, 101 + 7 * seed + (j if distinct is None or j == 0 else 1 + (j - 1) % distinct)) for j in range(count)]
+    if name in DIVISOR_LAST:
+        vecs[-1] = pow2_vector(n, seed)
+    return vecs
+
+
+def int_result(name, vecs):
+    """The exact result as fp64; ``vecs`` may repeat an array (aliasing)."""
+    return INT_STATEMENTS[name][1](vecs).value()
+
+
+# ---- rounding forms -----------------------------------------------------------------------------------------------------
+
+
+def fma(a, x, t):
+    """One element of fma(a, x, t): the exact a x + t rounded once (IEEE, overflow and special values included)."""
+    a, x, t = float(a), float(x), float(t)
+    if not (math.isfinite(a) and math.isfinite(x)):
+        with np.errstate(all="ignore"):
+            return float(np.float64(a) * np.float64(x) + np.float64(t))  # (the product is +-inf or NaN exactly)
+    if not math.isfinite(t):
+        return t  # a finite product, however large, plus +-inf or NaN
+    (an, ad), (xn, xd), (tn, td) = a.as_integer_ratio(), x.as_integer_ratio(), t.as_integer_ratio()
+    num, den = an * xn * td + tn * ad * xd, ad * xd * td  # the exact a x + t (the denominators are powers of two)
+    if num == 0:
+        return a * x + t  # a x = -t exactly: the float expression is exact and carries the IEEE sign of the zero
+    try:
+        return num / den  # int / int is correctly rounded in CPython, subnormal results included
+    except OverflowError:
+        return math.inf if num > 0 else -math.inf
+
+
+def vfma(a, x, t):
+    """fma elementwise; scalars broadcast."""
+    a, x, t = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(x, np.float64), np.asarray(t, np.float64))
+    out = np.empty(a.shape, np.float64)
+    flat = out.reshape(-1)
+    for i, (ai, xi, ti) in enumerate(zip(a.reshape(-1).tolist(), x.reshape(-1).tolist(), t.reshape(-1).tolist())):
+        flat[i] = fma(ai, xi, ti)
+    return out
+
+
+def _unit(c):
+    return c == 1.0 or c == -1.0  # fma(+-1, x, t) == fl(+-x + t): the fused form is the unfused one by construction
+
+
+def forms_axpbz(a, x, b, z):
+    """a x + b z: ``none`` fl(fl(a x) + fl(b z)); ``fuse_x`` fma(a, x, fl(b z)); ``fuse_z`` fma(b, z, fl(a x)).  A form
+    that is another one by construction (a coefficient +-1) is left out."""
+    a, b = np.float64(a), np.float64(b)
+    with np.errstate(all="ignore"):
+        ax, bz = a * x, b * z
+        forms = {"none": ax + bz}
+    if not _unit(a):
+        forms["fuse_x"] = vfma(a, x, bz)
+    if not _unit(b):
+        forms["fuse_z"] = vfma(b, z, ax)
+    return forms
+
+
+def forms_outer(r, s, inner):
+    """r + s t for every form t of the inner sum: ``<inner>/none`` fl(r + fl(s t)), ``<inner>/fused`` fma(s, t, r)."""
+    s = np.float64(s)
+    forms = {}
+    for name, t in inner.items():
+        with np.errstate(all="ignore"):
+            forms[f"{name}/none"] = r + s * t
+        if not _unit(s):
+            forms[f"{name}/fused"] = vfma(s, t, r)
+    return forms
+
+
+def forms_lin3(r, s, a, x, b, z):
+    return forms_outer(r, s, forms_axpbz(a, x, b, z))
+
+
+def forms_vmul_add(y, s, a, b):
+    with np.errstate(all="ignore"):
+        return forms_outer(y, s, {"prod": a * b})  # (the inner product feeds a product: never fused)
+
+
+def forms_multi_axpy(y, coefs, xs):
+    """All k steps fused, or none, in ascending j -- straight through the chunk boundary at k = 9."""
+    none, fused = np.array(y, np.float64), np.array(y, np.float64)
+    for c, x in zip(coefs, xs):
+        with np.errstate(all="ignore"):
+            none = none + np.float64(c) * x
+        fused = vfma(c, x, fused)
+    return {"none": none, "fused": fused}
+
+
+def _one(value):
+    return {"exact": value}
+
+
+# the non-dyadic coefficients of the rounding-form fixtures
+R_FILL, R_SCALE, R_DIV, R_A1, R_AXPY, R_XPAY = 0.3, 0.3, 0.7, -0.3, 0.3, 0.7
+R_A, R_B, R_S, R_BETA, R_OMEGA, R_VS, R_VD = 0.75, -1.25, 0.3, 0.3, 0.7, 0.3, 0.3
+
+
+def multi_coefs_real(k):
+    return [0.3 + 0.07 * j for j in range(k)]
+
+
+def _np(f):
+    def g(v):
+        with np.errstate(all="ignore"):
+            return _one(f(v))
+    return g
+
+
+# name -> (number of vectors, target first; f(vectors) -> {form: fp64 vector})
+REAL_STATEMENTS = {
+    "fill": (1, _np(lambda v: np.full_like(v[0], R_FILL))),
+    "copy": (2, _np(lambda v: v[1].copy())),
+    "scale": (1, _np(lambda v: v[0] * np.float64(R_SCALE))),
+    "div_scalar": (1, _np(lambda v: v[0] / np.float64(R_DIV))),
+    "scaled_copy": (2, _np(lambda v: np.float64(R_A1) * v[1])),
+    "axpy": (2, lambda v: forms_axpbz(R_AXPY, v[1], 1.0, v[0])),
+    "xpay": (2, lambda v: forms_axpbz(1.0, v[1], R_XPAY, v[0])),
+    "axpbz": (3, lambda v: forms_axpbz(R_A, v[1], R_B, v[2])),
+    "lin3": (4, lambda v: forms_lin3(v[1], R_S, R_A, v[2], R_B, v[3])),
+    "bicgstab_p": (3, lambda v: forms_lin3(v[1], R_BETA, 1.0, v[0], -R_OMEGA, v[2])),
+    "vmul_add": (3, lambda v: forms_vmul_add(v[0], R_VS, v[1], v[2])),
+    "vmul": (3, _np(lambda v: v[1] * v[2])),
+    "vdiv": (3, _np(lambda v: (np.float64(R_VD) * v[1]) / v[2])),
+    "vdiv_scalar": (2, _np(lambda v: np.float64(R_VD) / v[1])),
+    "map": (3, _np(lambda v: np.float64(MAP_CONSTS[0]) * v[1] + v[2] * v[0])),  # (every operation a statement: no fusing)
+}
+for _k in MULTI_KS:
+    REAL_STATEMENTS[f"multi_axpy{_k}"] = (_k + 1, lambda v, _k=_k: forms_multi_axpy(v[0], multi_coefs_real(_k), v[1:]))
+
+REAL_ROWS = (1, 3, 2049, 4096, 100003)
+# multi_axpy at 100 003 rows costs k exact fmas per row: one width per unroll class there (1, 3) and the chunk
+# boundary (9); the other widths stay at the sizes up to 4096
+REAL_LONG_NAMES = tuple(n for n in REAL_STATEMENTS if not n.startswith("multi_axpy") or int(n[10:]) in (1, 3, 9))
+
+
+def real_rows(name):
+    return REAL_ROWS if name in REAL_LONG_NAMES else REAL_ROWS[:-1]
+
+
+def forms_differ(forms):
+    """All forms pairwise different on every element of (short) vectors."""
+    vals = list(forms.values())
+    return all(bool(np.all(bits(vals[i]) != bits(vals[j]))) for i in range(len(vals)) for j in range(i))
+
+
+_REAL_CACHE = {}
+
+
+def real_operands(name, n):
+    """Standard-normal vectors of a statement (target first), seeded by the statement and the size, and their forms.
+    The LAST row is redrawn from the same stream until every two forms differ on it: the odd tail of a kernel (and the
+    only row of a one-row vector) then always tells the forms apart -- the seed chosen so that the condition of
+    tests/test_exact_reference.py holds."""
+    key = (name, n)
+    if key not in _REAL_CACHE:
+        count, fn = REAL_STATEMENTS[name]
+        rng = np.random.default_rng([sorted(REAL_STATEMENTS).index(name), n])
+        vecs = [rng.standard_normal(n) for _ in range(count)]
+        for _ in range(100000):
+            tail = [v[-1:] for v in vecs]
+            if forms_differ(fn(tail)):
+                break
+            for v in vecs:
+                v[-1] = rng.standard_normal()
+        else:
+            raise AssertionError(f"{name}: no last row separates the forms")
+        _REAL_CACHE[key] = (vecs, fn(vecs))
+    return _REAL_CACHE[key]
+
+
+def bits(a):
+    """fp64 values as their bit patterns, every NaN as one pattern."""
+    a = np.ascontiguousarray(a, np.float64)
+    b = a.view(np.uint64).copy()
+    b[np.isnan(a)] = np.uint64(0x7ff8000000000000)
+    return b
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and bool(np.array_equal(bits(a), bits(b)))
+
+
+def classify(got, forms):
+    """The names of the forms that ``got`` equals, bit for bit, on EVERY element."""
+    return [name for name, value in forms.items() if same_bits(got, value)]
+
+
+def differing_share(forms):
+    """{(form, form): share of the elements on which the two differ} for every pair of forms."""
+    names = list(forms)
+    return {(p, q): float(np.mean(bits(forms[p]) != bits(forms[q]))) if forms[p].size else 0.0
+            for i, p in enumerate(names) for q in names[:i]}
+
+
+# Operand aliasings the header allows ("y may alias x or z", "y may alias any operand", "may alias a or b"): operand i
+# of the statement (target first, INT_STATEMENTS' order) is vector ALIASINGS[name][..][i].
+_THREE = [(0, 0, 2), (0, 1, 0), (0, 1, 1), (0, 0, 0)]  # y is x; y is z; x is z; all three
+ALIASINGS = {
+    "copy": [(0, 0)],
+    "axpbz": _THREE,
+    "bicgstab_p": _THREE,
+    "vmul": _THREE,
+    "vmul_add": _THREE,
+    "vdiv": _THREE,
+    "lin3": [(0, 0, 2, 3), (0, 1, 0, 3), (0, 1, 2, 0), (0, 1, 2, 2), (0, 0, 2, 2), (0, 0, 0, 0)],
+}
+
+
+def aliased_operands(name, n, amap, seed=0, make=stmt_vector):
+    """int_operands with operand i taken from vector amap[i] (a divisor vector stays a vector of powers of two)."""
+    base = int_operands(name, n, seed, make=make)
+    if name in DIVISOR_LAST:
+        base[-1] = make(n, 99 + seed)
+        base[amap[-1]] = pow2_vector(n, seed)
+    return [base[i] for i in amap]
+
+
+# ---- the loop shape of the streaming kernels, as a model ------------------------------------------------------------------
+#
+# Which rows ew_kernel (and lin3_kernel, multi_axpy_kernel, map_kernel, lazy_lin_kernel: the same shape) writes: pairs of
+# rows i < n >> 1 in a grid-stride loop over min(ceil(n / 2048), 32768) blocks of 1024 pairs, and the odd last row by
+# thread 0 of block 0.  With ``mutation`` one line of it is edited -- the edits a test of these kernels must catch;
+# tests/test_exact_reference.py shows at which of the GPU tests' row counts each one changes the result.
+STMT_SMALL_ROWS = (1, 2, 3, 2047, 2048, 2049, 4097, 12345)
+STMT_BIG_ROWS = ((1 << 26) - 3, 1 << 26, (1 << 26) + 1, (1 << 26) + 2, (1 << 26) + 2049, (1 << 27) + 2051)
+MAX_STREAM_BLOCKS = 32768  # kMaxStreamBlocks (common.hpp)
+LOOP_MUTATIONS = ("dropped_pair", "tail_guard_block_1", "one_trip")
+
+
+def loop_model(result, before, mutation=None):
+    """What the target holds after the kernel: ``result`` on the rows the loop writes, ``before`` elsewhere.
+    dropped_pair: `n2 = (n >> 1) - 1`; tail_guard_block_1: the tail guard `bx == 0` changed to `bx == 1`; one_trip: the
+    grid-stride `for` turned into an `if`."""
+    assert mutation is None or mutation in LOOP_MUTATIONS
+    n = result.size
+    out = before.copy()
+    if n == 0:
+        return out
+    grid = min(max(1, -(-n // STREAM_BLOCK)), MAX_STREAM_BLOCKS)
+    n2 = (n >> 1) - (1 if mutation == "dropped_pair" else 0)
+    pairs = max(0, min(n2, grid * (STREAM_BLOCK // 2)) if mutation == "one_trip" else n2)
+    out[:2 * pairs] = result[:2 * pairs]
+    tail_block = 1 if mutation == "tail_guard_block_1" else 0
+    if (n & 1) and tail_block < grid:
+        out[n - 1] = result[n - 1]
+    return out

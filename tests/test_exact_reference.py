@@ -296,3 +296,222 @@ def test_a_defect_at_iteration_2_is_far_outside_the_tolerance(env, method, param
     for defect in ("stale_beta", "shadow_r"):
         h = run(2, defect=defect)[0].history[2]
         assert abs(h - exact) > 100 * tol * exact, (defect, h, exact, tol)
+
+
+# ---- the vector statements -------------------------------------------------------------------------------------------
+
+F = Fraction
+
+
+def _brute_multi(coefs):
+    return lambda v: [v[0][i] + sum(F(c) * x[i] for c, x in zip(coefs, v[1:])) for i in range(len(v[0]))]
+
+
+def _each(f):
+    return lambda v: [f(*row) for row in zip(*v)]
+
+
+# every statement of the integer model restated on Fractions, element by element, from the header's formula
+BRUTE = {
+    "fill": _each(lambda y: F(er.I_FILL)),
+    "copy": _each(lambda y, x: x),
+    "scale": _each(lambda y: y * F(er.I_SCALE)),
+    "div_scalar": _each(lambda y: y / F(er.I_DIV)),
+    "scaled_copy": _each(lambda y, x: F(er.I_A1) * x),
+    "axpy": _each(lambda y, x: y + F(er.I_AXPY) * x),
+    "xpay": _each(lambda y, x: x + F(er.I_XPAY) * y),
+    "axpbz": _each(lambda y, x, z: F(er.I_A) * x + F(er.I_B) * z),
+    "lin3": _each(lambda y, r, x, z: r + F(er.I_S) * (F(er.I_A) * x + F(er.I_B) * z)),
+    "bicgstab_p": _each(lambda p, r, v: r + F(er.I_BETA) * (p - F(er.I_OMEGA) * v)),
+    "vmul_add": _each(lambda y, a, b: y + F(er.I_VS) * (a * b)),
+    "vmul": _each(lambda y, a, b: a * b),
+    "vdiv": _each(lambda y, a, b: F(er.I_VD) * a / b),
+    "vdiv_scalar": _each(lambda y, b: F(er.I_VD) / b),
+    "map": _each(lambda y, x0, x1: F(er.MAP_CONSTS[0]) * x0 + x1 * y),
+}
+for _k in er.MULTI_KS:
+    BRUTE[f"multi_axpy{_k}"] = _brute_multi(er.multi_coefs_int(_k))
+
+
+def _fractions(vecs):
+    return [[F(int(e)) for e in v] for v in vecs]
+
+
+def test_every_statement_has_both_models_and_a_brute_force():
+    assert set(BRUTE) == set(er.INT_STATEMENTS) == set(er.REAL_STATEMENTS)
+
+
+@pytest.mark.parametrize("name", sorted(er.INT_STATEMENTS))
+def test_integer_statement_model_matches_fractions(name):
+    for n in (1, 2, 7, 64):
+        maps = [tuple(range(er.INT_STATEMENTS[name][0]))] + er.ALIASINGS.get(name, [])
+        for amap in maps:
+            vecs = er.aliased_operands(name, n, amap, seed=n)
+            got = er.int_result(name, vecs)
+            exact = BRUTE[name](_fractions(vecs))
+            assert got.dtype == np.float64 and [F(float(g)) for g in got] == exact, (name, n, amap)
+            assert not np.any(got == er.SENTINEL)
+
+
+def test_integer_model_refuses_data_that_could_round():
+    big = np.full(4, 1 << 40, np.int64)
+    with pytest.raises(AssertionError):
+        er.int_result("vmul", [big, big, big])  # 2^80
+    with pytest.raises(AssertionError):
+        er.int_axpbz(0.3, np.array([3]), 1, np.array([1]))  # fl(0.3) is k / 2^54: its multiples need more than 53 bits
+    with pytest.raises(AssertionError):
+        er.Dyadic(np.array([3])).over_pow2(np.array([6]))
+    top = np.full(4, (1 << 52) + 1, np.int64)
+    with pytest.raises(AssertionError):
+        er.int_axpbz(1, top, 1, top)  # the sum reaches 2^53
+
+
+def test_integer_model_signs_its_zeros_as_ieee_does():
+    """(-0.25) * 0 is -0, (-0) + (+0) is +0, (-0) + (-0) is -0: whatever a kernel fuses, the products are exact and the
+    zero's sign is the same -- the model must give it, bit for bit."""
+    x = np.array([0, 0, 5, -5, 0, 3], np.int64)
+    z = np.array([0, 7, 0, 0, -2, 3], np.int64)
+    xf, zf = x.astype(np.float64), z.astype(np.float64)
+    for a, b in ((-0.25, 3.0), (-0.25, -0.5), (0.5, -3.0), (2.0, 0.5)):
+        assert er.same_bits(er.int_axpbz(a, x, b, z).value(), a * xf + b * zf), (a, b)
+        assert er.same_bits((er.Dyadic.of(a) * er.Dyadic(x)).value(), a * xf)
+        assert er.same_bits((er.Dyadic(x) * er.Dyadic(z)).value(), xf * zf)
+        assert er.same_bits(er.int_lin3(z, a, b, x, a, z).value(), zf + a * (b * xf + a * zf))
+        assert er.same_bits((er.Dyadic.of(a) * er.Dyadic(x)).over_pow2(np.array([1, 2, 4, 8, 1, 2])).value(),
+                            a * xf / np.array([1.0, 2.0, 4.0, 8.0, 1.0, 2.0]))
+    assert np.signbit(er.int_result("scale", [x])).tolist() == [True, True, True, False, True, True]
+
+
+def test_statement_vectors_depend_on_the_row():
+    v = er.stmt_vector(12345, 3)
+    for shift in (1, 2, 256, 2048):
+        assert not np.array_equal(v[shift:], v[:-shift])
+    assert not np.array_equal(v[:2048], v[2048:4096])
+
+
+def test_fma_is_the_exactly_rounded_sum():
+    rng = np.random.default_rng(5)
+    for _ in range(3000):
+        a, x, t = (rng.standard_normal(3) * 10.0 ** rng.integers(-4, 5, 3)).tolist()
+        assert er.fma(a, x, t) == float(F(a) * F(x) + F(t))
+    big, tiny, inf = 1.7976931348623157e308, 5e-324, math.inf
+    assert er.fma(big, 2.0, -big) == big  # no overflow where fl(a x) overflows
+    assert er.fma(big, 2.0, 0.0) == inf and er.fma(-big, 2.0, 0.0) == -inf
+    assert er.fma(big, 2.0, -inf) == -inf and math.isnan(er.fma(inf, 0.0, 1.0)) and math.isnan(er.fma(inf, 1.0, -inf))
+    assert er.fma(tiny, 0.5, 0.0) == 0.0 and er.fma(tiny, 0.75, 0.0) == tiny  # ties to even; subnormal results
+    assert math.copysign(1.0, er.fma(-1.0, 0.0, 0.0)) == 1.0 and math.copysign(1.0, er.fma(-1.0, 0.0, -0.0)) == -1.0
+
+
+def test_unfused_forms_are_one_rounding_per_operation():
+    """numpy's a * x + b * z against Fractions rounded after every operation, and the single-form statements."""
+    rnd = lambda q: float(q)  # noqa: E731
+    (y, x, z), forms = er.real_operands("axpbz", 2049)
+    want = [rnd(F(rnd(F(er.R_A) * F(xi))) + F(rnd(F(er.R_B) * F(zi)))) for xi, zi in zip(x[:300].tolist(), z[:300].tolist())]
+    assert forms["none"][:300].tolist() == want
+    (y,), forms = er.real_operands("div_scalar", 2049)
+    assert forms["exact"][:300].tolist() == [rnd(F(yi) / F(er.R_DIV)) for yi in y[:300].tolist()]
+    (y, a, b), forms = er.real_operands("vdiv", 2049)
+    assert forms["exact"][:300].tolist() == [rnd(F(rnd(F(er.R_VD) * F(ai))) / F(bi)) for ai, bi in zip(a[:300].tolist(), b[:300].tolist())]
+
+
+@pytest.mark.parametrize("name", sorted(er.REAL_STATEMENTS))
+def test_rounding_forms_are_told_apart_by_the_fixtures(name):
+    """The condition that makes `classify` mean something on the GPU tests' own data: every two admissible forms of a
+    statement differ on at least 1 % of the rows, and on the LAST row of every odd-length fixture (the kernels' scalar
+    tail).  Without it a result could "identify" a form by accident."""
+    for n in er.real_rows(name):
+        vecs, forms = er.real_operands(name, n)
+        assert all(v.shape == (n,) for v in forms.values())
+        for (p, q), share in er.differing_share(forms).items():
+            assert share >= 0.01, (name, n, p, q, share)
+            if n & 1:
+                assert er.bits(forms[p])[-1] != er.bits(forms[q])[-1], (name, n, p, q)
+        for p in forms:
+            assert er.classify(forms[p], forms) == [p]
+
+
+def test_form_lists_are_the_admissible_evaluations():
+    assert list(er.real_operands("axpbz", 3)[1]) == ["none", "fuse_x", "fuse_z"]
+    assert list(er.real_operands("axpy", 3)[1]) == ["none", "fuse_x"]  # (b = 1: fuse_z is `none` by construction)
+    assert list(er.real_operands("xpay", 3)[1]) == ["none", "fuse_z"]
+    assert sorted(er.real_operands("lin3", 3)[1]) == sorted(f"{i}/{o}" for i in ("none", "fuse_x", "fuse_z") for o in ("none", "fused"))
+    assert sorted(er.real_operands("bicgstab_p", 3)[1]) == sorted(f"{i}/{o}" for i in ("none", "fuse_z") for o in ("none", "fused"))
+    assert list(er.real_operands("vmul_add", 3)[1]) == ["prod/none", "prod/fused"]
+    assert list(er.real_operands("multi_axpy9", 3)[1]) == ["none", "fused"]
+
+
+def _mutations(good, other, n):
+    """Wrong results a kernel with a wrong bound, stride or tail would leave (n odd, more than two blocks)."""
+    blk = er.STREAM_BLOCK
+    m = {}
+    m["dropped last row"] = good.copy()
+    m["dropped last row"][-1] = er.SENTINEL
+    m["shifted by one double2"] = np.concatenate([good[2:], good[:2]])
+    m["block written twice"] = good.copy()
+    m["block written twice"][blk:2 * blk] = good[:blk]
+    m["tail from another form"] = good.copy()
+    m["tail from another form"][-1] = other[-1]
+    m["one ulp off"] = good.copy()
+    m["one ulp off"][n // 2] = np.nextafter(good[n // 2], np.inf)
+    return m
+
+
+def test_mutations_are_caught():
+    n = 2 * er.STREAM_BLOCK + 1
+    (y, x, z), forms = er.real_operands("axpbz", 2049)
+    rng = np.random.default_rng(9)
+    vecs = [np.concatenate([rng.standard_normal(n - 2049), v]) for v in (y, x, z)]  # (the tuned last row stays last)
+    forms = er.REAL_STATEMENTS["axpbz"][1](vecs)
+    for what, bad in _mutations(forms["fuse_x"], forms["fuse_z"], n).items():
+        assert er.classify(bad, forms) == [], what
+    ivecs = er.int_operands("axpbz", n)
+    good = er.int_result("axpbz", ivecs)
+    other = er.int_result("axpbz", [ivecs[0], ivecs[2], ivecs[1]])
+    assert er.same_bits(good, good.copy())
+    for what, bad in _mutations(good, other, n).items():
+        assert not er.same_bits(bad, good), what
+
+
+def test_loop_edits_are_caught_at_the_row_counts_the_gpu_tests_use():
+    """The four one-line kernel edits a test of the streaming kernels must catch, on the model of their loop
+    (er.loop_model) and on the GPU tests' own row counts and comparisons -- which comparison catches which:
+      n2 = (n >> 1) - 1         the bitwise integer comparison, at EVERY size of two rows or more (the last pair keeps the
+                                sentinel, or the old value of a target the statement reads);
+      tail guard bx == 1        the integer comparison at the odd sizes whose grid is ONE block (1, 3, 2047): with two
+                                blocks or more block 1 exists and writes the tail, so 2049, 4097, 12345 and the odd
+                                2^26-class sizes cannot see it -- which is why the small odd sizes are in the list;
+      grid-stride for -> if     the integer comparison at 2^26 + 2, 2^26 + 2049 (and 2^27 + 2051, not modelled here for
+                                its memory): rows of the second trip keep the sentinel.  NOT at 2^26 + 1: its one row
+                                beyond the first trip is the odd tail, which block 0 writes outside the loop -- the
+                                first row of the second trip is row 2^26 of a vector of 2^26 + 2, the size this model
+                                added to the list;
+      AxpbzF's operands swapped the form test: classify gives [fuse_z] where the table says fuse_x, for axpbz, and
+                                [none] instead of [fuse_x] for axpy (y += a x); xpay's two forms swap likewise; the
+                                integer comparison cannot see it, by construction."""
+    caught = {m: [] for m in er.LOOP_MUTATIONS}
+    for n in er.STMT_SMALL_ROWS + er.STMT_BIG_ROWS[:5]:
+        # `fill` on a sentinel target (a statement that does not read its target) and `scale` (one that does)
+        for result, before in ((np.full(n, er.I_FILL), np.full(n, er.SENTINEL)),) + \
+                (((lambda y: (er.I_SCALE * y, y))(er.stmt_vector(n, 3).astype(np.float64)),) if n <= 12345 else ()):
+            assert np.array_equal(er.loop_model(result, before), result), n
+            for m in er.LOOP_MUTATIONS:
+                same = np.array_equal(er.loop_model(result, before, m), result)
+                if not same and n not in caught[m]:
+                    caught[m].append(n)
+                if n <= 12345:  # both statements agree on where the edit shows
+                    assert same == (n not in caught[m]), (m, n)
+    big = list(er.STMT_BIG_ROWS[:5])
+    assert caught["dropped_pair"] == [n for n in er.STMT_SMALL_ROWS if n >= 2] + big
+    assert caught["tail_guard_block_1"] == [1, 3, 2047]
+    assert caught["one_trip"] == [(1 << 26) + 2, (1 << 26) + 2049]
+    # the swapped functor: a * x0 + b * x1 fuses its FIRST product, so b * x1 + a * x0 is the form fuse_z
+    for name, swapped in (("axpbz", "fuse_z"), ("axpy", "none"), ("xpay", "fuse_z")):
+        for n in er.real_rows(name):
+            vecs, forms = er.real_operands(name, n)
+            if name == "axpbz":
+                got = er.forms_axpbz(er.R_B, vecs[2], er.R_A, vecs[1])["fuse_x"]
+            elif name == "axpy":
+                got = er.forms_axpbz(1.0, vecs[0], er.R_AXPY, vecs[1])["none"]  # fma(1, y, fl(a x))
+            else:
+                got = er.forms_axpbz(er.R_XPAY, vecs[0], 1.0, vecs[1])["fuse_x"]  # fma(b, y, fl(1 x))
+            assert er.classify(got, forms) == [swapped], (name, n)
