@@ -139,6 +139,23 @@ int storm_hip_vec_context(const storm_hip_vec *v, storm_hip_ctx **ctx);
  * `Field::operator()(row, col)`, Feathers/Field.hpp:104-111. */
 int storm_hip_vec_get(const storm_hip_vec *v, int64_t row, double *value);
 
+/* ---- block vectors ---------------------------------------------------------
+ * `Field<Mesh, Index, Value, NumVars>` with NumVars > 1 (Feathers/Field.hpp:56-79: shape [num_entities, NumVars], every
+ * cell stores a Vec<Value, NumVars>; the playground's CellField<Mesh, real_t, 5>, Playground.cpp:217-218).  No handle
+ * type of its own: a block of k columns over n cells IS a storm_hip_vec with n_owned = n * k and n_halo = 0, element
+ * (i, j) at i * k + j -- the reference's layout.  1 <= k <= 8.  Upload, download, fill, copy, scale and every other
+ * elementwise entry point work on it as on any vector, and storm_hip_dot over two blocks is the reference's
+ * dot_product over all NumVars components (MatrixAlgorithms.hpp:310-317).  Single rank only: a vector with halo rows or
+ * a context with a communicator is refused with STORM_HIP_E_UNSUPPORTED. */
+/* Strided copy between column j of a block and a plain n-vector: `Field::operator()(row, j)` for every row,
+ * Feathers/Field.hpp:104-111. */
+int storm_hip_block_get_column(const storm_hip_vec *X, int k, int j, storm_hip_vec *v);
+int storm_hip_block_set_column(storm_hip_vec *X, int k, int j, const storm_hip_vec *v);
+/* out[j] = <A_j, B_j>, j < k: dot_product (MatrixAlgorithms.hpp:310-317) column by column. */
+int storm_hip_block_dot(const storm_hip_vec *A, const storm_hip_vec *B, int k, double *out);
+/* Y_j = fma(a[j], X_j, Y_j), j < k: `y += a * x` (SolverCg.hpp:98) with one coefficient per column.  X and Y must not alias. */
+int storm_hip_block_axpy(storm_hip_vec *Y, const double *a, const storm_hip_vec *X, int k);
+
 /* ---- BLAS-1 --------------------------------------------------------------
  * One call per Bittern expression statement the solver bodies execute
  * (overload census); each is one kernel over the owned rows.
@@ -363,7 +380,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *ctx, const char *key, int64_t value)
 /* Which path the solves of this context took so far (no reference counterpart: a diagnostic of this library; the
  * reference logs one line per solve, Solver.hpp:144-145).  Keys: "resident_solves" (csrc/resident.hip),
  * "latency_solves" (csrc/latency.hip: one cooperative kernel per solve), "throughput_solves" (a kernel per statement,
- * fused loops of csrc/solvers.hip), "engine_solves" (csrc/krylov.hip), "cg_fused_steps" (solves whose CG step rode in
+ * fused loops of csrc/solvers.hip), "engine_solves" (csrc/krylov.hip), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "cg_fused_steps" (solves whose CG step rode in
  * the SpMV launch), "lazy_fused_dots" / "lazy_fused_pairs" / "lazy_apply_dots" / "lazy_cg_steps" / "lazy_waiting" (option
  * lazy_statements: reductions that rode in a statement's kernel, pairs of statements that left as one pass, applies that
  * left with a fused dot, fused CG steps, statements waiting now).  On the peer-window transport, where the time of the exchanges went (ticks of 10 ns of the device's
@@ -478,6 +495,15 @@ int storm_hip_op_set_halo(storm_hip_op *op, int n_nbrs, const int32_t *nbr_rank,
 int storm_hip_op_apply(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *x,
                        storm_hip_vec *y);
 
+/* `Operator::mul(y, x)` (Solvers/Operator.hpp:74) on a block of k columns (see "block vectors"): Y_j = beta X_j +
+ * alpha M(X_j) for every column, the operator's records streamed ONCE -- by bytes 96 + 16 k per row instead of 112 k.
+ * Column j of Y is, bit for bit, what storm_hip_op_apply gives for column j of X.  X and Y must not alias.  Needs
+ * fp64 records (an operator built with option spmv_dict = 0; with or without a CSR tail): an operator in a compact
+ * record format, one with a halo plan, or a context with a communicator returns STORM_HIP_E_UNSUPPORTED.  Sizes that
+ * are not n_rows * k, k outside 1..8 and aliasing return STORM_HIP_E_INVALID. */
+int storm_hip_op_apply_block(const storm_hip_op *op, double alpha, double beta, int k, const storm_hip_vec *X,
+                             storm_hip_vec *Y);
+
 /* d_i = diagonal entry i of beta*I + alpha*M; with invert != 0 its safe inverse (0 -> 0,
  * Crow/MathUtils.hpp:54-58).  What `Preconditioner::build(x, b, op)` (Preconditioner.hpp:70-72) of a
  * Jacobi preconditioner needs from the operator. */
@@ -548,6 +574,19 @@ int storm_hip_solve_bicgstab(const storm_hip_op *op, double alpha, double beta, 
 int storm_hip_solve_gmres(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *b,
                           storm_hip_vec *x, const storm_hip_solver_params *params,
                           storm_hip_solver_result *result, double *history);    /* SolverGmres.hpp:41-255 */
+
+/* k independent CG solves A x_j = b_j on the columns of a block (see "block vectors"): SolverCg.hpp:54-126 per column,
+ * the convergence rule of Solver.hpp:116-147 per column, the operator's records streamed once per iteration for all
+ * columns (storm_hip_op_apply_block; the same operators are refused).  Every column has its own gamma, alpha, beta,
+ * residual norms and done flag on the device; the statements are rounded as storm_hip_solve_cg's kernel-per-statement
+ * loop rounds them (fma(alpha, p, x), fma(-alpha, z, r), fma(beta, p, r)).  A column that has converged -- or left at
+ * once by abs_tol > 0 && |r0| < abs_tol -- is frozen: its x keeps the value of the iteration where it stopped, its
+ * `iterations` stays there, and nothing it holds reaches another column.  results[k]; histories: NULL or
+ * k * (num_iterations + 1) doubles, column j's residual norms at histories[j * (num_iterations + 1) ...] (entry 0 =
+ * initial; iterations + 1 norms, zeros behind them).  Counted by "block_solves" (storm_hip_ctx_get_counter). */
+int storm_hip_solve_cg_block(const storm_hip_op *op, double alpha, double beta, int k, const storm_hip_vec *B,
+                             storm_hip_vec *X, const storm_hip_solver_params *params,
+                             storm_hip_solver_result *results, double *histories);
 
 /* ---- the general Krylov engine ---------------------------------------------
  * Every solver of Solvers/  for ANY operator, device-resident:

@@ -616,6 +616,58 @@ private:
   storm_hip_mesh* _h = nullptr;
 };
 
+/// `Field<Mesh, Index, Value, NumVars>` with NumVars = k > 1 (Feathers/Field.hpp:56-79): k interleaved columns over n
+/// cells, element (i, j) at i k + j, 1 <= k <= 8.  It IS a DeviceVector of n k elements: every vector statement,
+/// dot_product and norm_2 work on it (over all columns, as Bittern's do on such a field).
+class DeviceBlockVector : public DeviceVector {
+public:
+  DeviceBlockVector() = default;
+  DeviceBlockVector(const Context& ctx, std::size_t n, std::size_t k) : DeviceVector(ctx, n * k, 0), _k{k} {
+    if (k < 1 || k > 8) throw std::invalid_argument("DeviceBlockVector: k outside [1, 8]");
+  }
+  DeviceBlockVector(DeviceBlockVector&& o) noexcept : DeviceVector(std::move(o)), _k{o._k} {}
+  DeviceBlockVector& operator=(DeviceBlockVector&& o) noexcept {
+    DeviceVector::operator=(std::move(o));
+    _k = o._k;
+    return *this;
+  }
+
+  /// Field::assign(other, copy): a new zero-initialised block shaped like `other`.
+  void assign(const DeviceBlockVector& other, bool copy = true) {
+    DeviceVector::assign(other, copy);
+    _k = other._k;
+  }
+  /// Field::shape() = {N, NumVars}  (Field.hpp:77-79)
+  std::array<std::size_t, 2> shape() const { return {DeviceVector::size() / _k, _k}; }
+  std::size_t num_cells() const { return shape()[0]; }
+  std::size_t num_vars() const noexcept { return _k; }
+  /// Field::operator()(row, col) (Field.hpp:104-111): a host proxy, one blocking 8-byte copy per call.
+  real_t operator()(std::size_t row, std::size_t col) const { return DeviceVector::operator()(row * _k + col); }
+
+  /// Column j as / from a plain n-vector (strided copies on the device).
+  void get_column(std::size_t j, DeviceVector& v) const {
+    detail::check(storm_hip_block_get_column(handle(), (int)_k, (int)j, v.handle()));
+  }
+  void set_column(std::size_t j, const DeviceVector& v) {
+    detail::check(storm_hip_block_set_column(handle(), (int)_k, (int)j, v.handle()));
+  }
+
+private:
+  std::size_t _k = 1;
+};
+
+/// out[j] = <A_j, B_j>: dot_product (MatrixAlgorithms.hpp:310-317) column by column.
+inline std::vector<real_t> block_dot(const DeviceBlockVector& a, const DeviceBlockVector& b) {
+  std::vector<real_t> out(a.num_vars());
+  detail::check(storm_hip_block_dot(a.handle(), b.handle(), (int)a.num_vars(), out.data()));
+  return out;
+}
+/// Y_j = fma(coefs[j], X_j, Y_j): `y += a * x` with one coefficient per column.
+inline void block_axpy(DeviceBlockVector& y, const std::vector<real_t>& coefs, const DeviceBlockVector& x) {
+  if (coefs.size() != y.num_vars()) throw std::invalid_argument("block_axpy: one coefficient per column");
+  detail::check(storm_hip_block_axpy(y.handle(), coefs.data(), x.handle(), (int)y.num_vars()));
+}
+
 /// A = beta I + alpha M as an Operator<DeviceVector> (the caller keeps `matrix` alive, as the
 /// reference's operator lambdas capture the mesh by reference, Playground.cpp:152-167).
 class HipStencilOperator final : public Operator<DeviceVector> {
@@ -625,6 +677,12 @@ public:
   void mul(DeviceVector& y_vec, const DeviceVector& x_vec) const override {
     _matrix->apply(_alpha, _beta, x_vec, y_vec);
   }
+  /// `mul` on a block: Y_j = A X_j for every column, the operator's records streamed once; column by column the
+  /// bits of `mul`.  Needs fp64 records (a matrix built with option spmv_dict = 0).
+  void mul_block(DeviceBlockVector& y_block, const DeviceBlockVector& x_block) const {
+    detail::check(storm_hip_op_apply_block(_matrix->handle(), _alpha, _beta, (int)x_block.num_vars(), x_block.handle(),
+                                           y_block.handle()));
+  }
   const StencilMatrix& matrix() const noexcept { return *_matrix; }
   real_t alpha() const noexcept { return _alpha; }
   real_t beta() const noexcept { return _beta; }
@@ -633,6 +691,41 @@ private:
   const StencilMatrix* _matrix;
   real_t _alpha, _beta;
 };
+
+/// What one column of a block solve reports: the fields of IterativeSolver (Solver.hpp:66-72) after `solve`.
+struct BlockColumnResult {
+  std::size_t iteration = 0;
+  real_t absolute_error = 0.0, relative_error = 0.0, initial_error = 0.0;
+  bool converged = false;
+  std::vector<real_t> history;  // with record_history: iteration + 1 residual norms
+};
+/// k independent CG solves A x_j = b_j on the columns of a block (storm_hip_solve_cg_block): SolverCg.hpp:54-126 and the
+/// convergence rule of Solver.hpp:116-147 per column, with the reference's knob names and defaults.
+inline std::vector<BlockColumnResult> solve_block_cg(DeviceBlockVector& x_block, const DeviceBlockVector& b_block,
+                                                     const HipStencilOperator& op, std::size_t num_iterations = 2000,
+                                                     real_t absolute_error_tolerance = 1.0e-6,
+                                                     real_t relative_error_tolerance = 1.0e-6, bool record_history = false) {
+  const std::size_t k = b_block.num_vars();
+  storm_hip_solver_params p;
+  storm_hip_solver_params_default(&p);
+  p.num_iterations = (int64_t)num_iterations;
+  p.absolute_error_tolerance = absolute_error_tolerance;
+  p.relative_error_tolerance = relative_error_tolerance;
+  std::vector<storm_hip_solver_result> res(k);
+  std::vector<real_t> hist(record_history ? k * (num_iterations + 1) : 0);
+  detail::check(storm_hip_solve_cg_block(op.matrix().handle(), op.alpha(), op.beta(), (int)k, b_block.handle(), x_block.handle(),
+                                         &p, res.data(), record_history ? hist.data() : nullptr));
+  std::vector<BlockColumnResult> out(k);
+  for (std::size_t j = 0; j < k; ++j) {
+    out[j].iteration = (std::size_t)res[j].iterations;
+    out[j].absolute_error = res[j].absolute_error, out[j].relative_error = res[j].relative_error;
+    out[j].initial_error = res[j].initial_error, out[j].converged = res[j].converged != 0;
+    if (record_history)
+      out[j].history.assign(hist.begin() + (std::ptrdiff_t)(j * (num_iterations + 1)),
+                            hist.begin() + (std::ptrdiff_t)(j * (num_iterations + 1) + out[j].iteration + 1));
+  }
+  return out;
+}
 
 // ---------------------------------------------------------------------------------------------
 #ifndef STORM_HIP_NO_SOLVERS

@@ -119,6 +119,10 @@ SIGNATURES = {
     "storm_hip_multi_dot_begin": (C.c_int, [vp, C.POINTER(vp), C.c_int, C.POINTER(C.c_int)]),
     "storm_hip_multi_dot_end": (C.c_int, [vp, C.c_int, f64p]),
     "storm_hip_multi_axpy": (C.c_int, [vp, f64p, C.POINTER(vp), C.c_int]),
+    "storm_hip_block_get_column": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+    "storm_hip_block_set_column": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+    "storm_hip_block_dot": (C.c_int, [vp, vp, C.c_int, f64p]),
+    "storm_hip_block_axpy": (C.c_int, [vp, f64p, vp, C.c_int]),
     "storm_hip_op_create_from_faces": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, i64p, i64p, f64p,
                                                  C.c_int64, i64p, f64p, f64p, C.POINTER(vp)]),
     "storm_hip_op_create_from_mesh": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int32, C.c_int64, i64p, i64p, f64p, f64p,
@@ -141,6 +145,7 @@ SIGNATURES = {
     "storm_hip_op_create_from_mesh_object": (C.c_int, [vp, vp, C.POINTER(vp)]),
     "storm_hip_mesh_destroy": (C.c_int, [vp]),
     "storm_hip_op_apply": (C.c_int, [vp, C.c_double, C.c_double, vp, vp]),
+    "storm_hip_op_apply_block": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, vp, vp]),
     "storm_hip_op_apply_add": (C.c_int, [vp, C.c_double, vp, vp]),
     "storm_hip_op_get_diagonal": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, vp]),
     "storm_hip_op_get_stats": (C.c_int, [vp, C.POINTER(OpStats)]),
@@ -152,6 +157,8 @@ SIGNATURES = {
                                            C.POINTER(SolverResult), f64p]),
     "storm_hip_solve_gmres": (C.c_int, [vp, C.c_double, C.c_double, vp, vp, C.POINTER(SolverParams),
                                         C.POINTER(SolverResult), f64p]),
+    "storm_hip_solve_cg_block": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, vp, vp, C.POINTER(SolverParams),
+                                           C.POINTER(SolverResult), f64p]),
     "storm_hip_krylov_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
     "storm_hip_krylov_destroy": (C.c_int, [vp]),
     "storm_hip_krylov_set_operator": (C.c_int, [vp, vp, C.c_double, C.c_double]),

@@ -738,6 +738,13 @@ class HipStencilOperator(Operator):
     def conj_mul(self, x_vec, y_vec):
         raise RuntimeError("`Operator::conj_mul` was not overriden")
 
+    def mul_block(self, y_block: DeviceVector, x_block: DeviceVector, k: Optional[int] = None) -> None:
+        """``Operator::mul`` on a block of ``k`` interleaved columns (:class:`BlockVector`, or any vector of ``n * k``
+        elements with ``k`` given): ``Y_j = A X_j`` for every column, the operator's records streamed once; column by
+        column the bits of :meth:`mul`.  Needs fp64 records (a matrix built with option ``spmv_dict = 0``)."""
+        k = int(k if k is not None else x_block.k)
+        check(lib.storm_hip_op_apply_block(self.matrix._h, self.alpha, self.beta, k, x_block._h, y_block._h))
+
 
 # ---------------------------------------------------------------------------------------------
 # Solvers (Solvers/Solver.hpp)
@@ -1198,3 +1205,115 @@ def solve_non_uniform(solver: Solver, x_vec: DeviceVector, b_vec: DeviceVector, 
         y_vec -= at_zero
 
     return solver.solve(x_vec, rhs, make_operator(uniform))
+
+
+# ---------------------------------------------------------------------------------------------
+# Block vectors: ``Field<Mesh, Index, Value, NumVars>`` with NumVars > 1 (Feathers/Field.hpp:56-79)
+
+
+class BlockVector(DeviceVector):
+    """``k`` interleaved columns over ``n`` cells: a :class:`DeviceVector` of ``n * k`` elements with element (i, j) at
+    ``i * k + j``, the reference's ``Field`` layout (Feathers/Field.hpp:56-79).  Every elementwise statement, ``dot_product``
+    and ``norm_2`` work on it as on any vector (over all columns, as Bittern's do on a ``NumVars`` field)."""
+
+    def __init__(self, ctx: Optional[Context] = None, n: int = 0, k: int = 1):
+        if ctx is not None and not 1 <= int(k) <= 8:
+            raise ValueError(f"BlockVector: k = {k} outside [1, 8]")
+        super().__init__(ctx, int(n) * int(k), 0)
+        self.n, self.k = int(n), int(k)
+
+    def assign(self, other: "DeviceVector", copy: bool = True) -> None:
+        super().assign(other, copy)
+        self.k = int(getattr(other, "k", 1))
+        self.n = self.n_owned // self.k
+
+    def shape(self):
+        return (self.n, self.k)  # Field::shape() = {N, NumVars}, Field.hpp:77-79
+
+    @classmethod
+    def from_numpy(cls, ctx: Context, a: np.ndarray) -> "BlockVector":  # noqa: D102 -- an (n, k) array
+        a = np.ascontiguousarray(a, np.float64)
+        if a.ndim != 2:
+            raise ValueError("BlockVector.from_numpy takes an (n, k) array")
+        v = cls(ctx, a.shape[0], a.shape[1])
+        check(lib.storm_hip_vec_upload(v._h, a.ctypes.data_as(_lib.f64p), a.size))
+        return v
+
+    def upload(self, a: np.ndarray) -> None:
+        a = np.ascontiguousarray(a, np.float64)
+        if a.shape != (self.n, self.k):
+            raise ValueError(f"BlockVector.upload: shape {a.shape}, expected {(self.n, self.k)}")
+        check(lib.storm_hip_vec_upload(self._h, a.ctypes.data_as(_lib.f64p), a.size))
+
+    def to_numpy(self, with_halo: bool = False) -> np.ndarray:
+        return super().to_numpy().reshape(self.n, self.k)
+
+    def column(self, j: int, out: Optional[DeviceVector] = None) -> DeviceVector:
+        """Column ``j`` as a plain ``n``-vector (a strided copy)."""
+        v = out if out is not None else DeviceVector(self.ctx, self.n)
+        check(lib.storm_hip_block_get_column(self._h, self.k, int(j), v._h))
+        return v
+
+    def set_column(self, j: int, v: DeviceVector) -> None:
+        check(lib.storm_hip_block_set_column(self._h, self.k, int(j), v._h))
+
+
+def block_dot(a: BlockVector, b: BlockVector) -> np.ndarray:
+    """``out[j] = <A_j, B_j>``: ``dot_product`` (MatrixAlgorithms.hpp:310-317) column by column."""
+    out = np.zeros(a.k)
+    check(lib.storm_hip_block_dot(a._h, b._h, a.k, out.ctypes.data_as(_lib.f64p)))
+    return out
+
+
+def block_axpy(y: BlockVector, coefs: Sequence[float], x: BlockVector) -> None:
+    """``Y_j = fma(coefs[j], X_j, Y_j)``: ``y += a * x`` with one coefficient per column."""
+    cf = np.ascontiguousarray(coefs, np.float64)
+    if cf.size != y.k:
+        raise ValueError(f"block_axpy: {cf.size} coefficients for {y.k} columns")
+    check(lib.storm_hip_block_axpy(y._h, cf.ctypes.data_as(_lib.f64p), x._h, y.k))
+
+
+class BlockCgSolver:
+    """``k`` independent CG solves ``A x_j = b_j`` on the columns of a block (``storm_hip_solve_cg_block``):
+    SolverCg.hpp:54-126 and the convergence rule of Solver.hpp:116-147 per column, the operator's records streamed
+    once per iteration for all columns.  The reference's knobs and defaults (Solver.hpp:66-72); after ``solve`` the
+    per-column ``iterations``, ``converged``, ``absolute_error``, ``relative_error``, ``initial_error`` (arrays of
+    ``k``) and, with ``record_history``, ``history`` (a list of ``k`` arrays, ``iterations[j] + 1`` norms each)."""
+
+    def __init__(self):
+        self.num_iterations = 2000
+        self.absolute_error_tolerance = 1.0e-6
+        self.relative_error_tolerance = 1.0e-6
+        self.check_lag = 0
+        self.record_history = False
+        self.iterations = self.converged = self.history = None
+        self.absolute_error = self.relative_error = self.initial_error = None
+        self.path_fallback = 0
+
+    def solve(self, x_block: BlockVector, b_block: BlockVector, any_op: HipStencilOperator) -> bool:
+        """True when every column converged."""
+        if not isinstance(any_op, HipStencilOperator):
+            raise TypeError("BlockCgSolver needs a HipStencilOperator")
+        k = int(b_block.k)
+        p = _lib.SolverParams()
+        lib.storm_hip_solver_params_default(C.byref(p))
+        p.num_iterations = self.num_iterations
+        p.absolute_error_tolerance = self.absolute_error_tolerance
+        p.relative_error_tolerance = self.relative_error_tolerance
+        p.check_lag = self.check_lag
+        res = (_lib.SolverResult * k)()
+        hist = np.zeros((k, self.num_iterations + 1)) if self.record_history else None
+        check(lib.storm_hip_solve_cg_block(any_op.matrix._h, any_op.alpha, any_op.beta, k, b_block._h, x_block._h, C.byref(p),
+                                           res, None if hist is None else hist.ctypes.data_as(_lib.f64p)))
+        self.iterations = np.array([r.iterations for r in res], np.int64)
+        self.converged = np.array([bool(r.converged) for r in res])
+        self.absolute_error = np.array([r.absolute_error for r in res])
+        self.relative_error = np.array([r.relative_error for r in res])
+        self.initial_error = np.array([r.initial_error for r in res])
+        self.num_applies = np.array([r.num_applies for r in res], np.int64)
+        self.path_fallback = max(r.path_fallback for r in res)
+        self.history = None if hist is None else [hist[j, : res[j].iterations + 1].copy() for j in range(k)]
+        for j in range(k):
+            _LOG.info("column %d: n_iter: %4d, abs_err: %-12e, rel_err: %-12e", j, res[j].iterations, res[j].absolute_error,
+                      res[j].relative_error)
+        return bool(self.converged.all())

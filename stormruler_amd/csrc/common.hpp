@@ -257,6 +257,7 @@ struct storm_hip_ctx {
   const int *api_done = nullptr;
   // diagnostics: which path the solves took (storm_hip_ctx_get_counter)
   int64_t n_resident_solves = 0, n_latency_solves = 0, n_throughput_solves = 0, n_engine_solves = 0, n_cg_fused_steps = 0;
+  int64_t n_block_solves = 0;  // storm_hip_solve_cg_block (block.hip)
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_mgs_chain_steps = 0, n_mgs_quad_steps = 0;  // Gram-Schmidt steps run as a chain kernel (latency.hip); ... as mgs_chain_quad_kernel
@@ -394,6 +395,20 @@ int k_reduce_final(storm_hip_ctx *c, const double *partials, int nblocks, int k,
 // c->d_partials2 and points *partials / *nblocks there (fewer: nothing to do).
 int k_reduce_stage1(storm_hip_ctx *c, const double **partials, int *nblocks, int k, const int *done);
 
+// context.hip: grow the reduction workspace (d_partials) to `need` doubles; waits for the stream when it has to
+int partials_reserve(storm_hip_ctx *c, int64_t need);
+// GO(K) for the compile-time column count K = k of a block vector (1 .. 8)
+#define STORM_K_SWITCH(k, GO) \
+  switch (k) {                \
+    case 1: GO(1); break;     \
+    case 2: GO(2); break;     \
+    case 3: GO(3); break;     \
+    case 4: GO(4); break;     \
+    case 5: GO(5); break;     \
+    case 6: GO(6); break;     \
+    case 7: GO(7); break;     \
+    default: GO(8); break;    \
+  }
 // context.hip: a work vector with only its guard, halo tail and padding zeroed (the solver writes the owned rows first)
 int vec_create_work(const storm_hip_vec *like, storm_hip_vec **out);
 // ... `count` of them, their edges zeroed by ONE launch (a memset is a launch of its own with ~10 us in front of it:
@@ -444,6 +459,12 @@ int spmv_grid_blocks(const storm_hip_op *op);
 bool spmv_can_fuse_cg(const storm_hip_op *op);
 bool spmv_can_march(const storm_hip_op *op);  // the z-marching kernel applies to an unsplit launch of this operator
 int op_upload_slice_lists(storm_hip_op *op);
+// Block vectors (k interleaved columns, element (i, j) at i k + j): Y_j = beta X_j + alpha M(X_j) with the records streamed
+// once (spmv_block.hip).  pz_partials != null: per-wave partials of <X_j, Y_j> go to pz_partials[j * *n_partials + wave]
+// (operators without a CSR tail; with one *n_partials = 0 and the caller forms the sums itself).
+int spmv_block_launch(const storm_hip_op *op, double alpha, double beta, int k, const double *X, double *Y,
+                      double *pz_partials, int *n_partials, const int *done);
+int spmv_block_check(const storm_hip_op *op, int k, const storm_hip_vec *X, const storm_hip_vec *Y, const char *what);
 
 // latency.hip
 int op_make_latency_copy(storm_hip_op *op, int64_t n, int64_t n_halo, const std::vector<int64_t> &row_ptr,

@@ -246,6 +246,7 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "latency_solves")) *value = c->n_latency_solves;
   else if (!strcmp(key, "throughput_solves")) *value = c->n_throughput_solves;
   else if (!strcmp(key, "engine_solves")) *value = c->n_engine_solves;
+  else if (!strcmp(key, "block_solves")) *value = c->n_block_solves;
   else if (!strcmp(key, "cg_fused_steps")) *value = c->n_cg_fused_steps;
   else if (!strcmp(key, "cg_residual_marches")) *value = c->n_cg_residual_marches;
   else if (!strcmp(key, "cg_residual_plane_marches")) *value = c->n_cg_residual_plane_marches;
@@ -389,6 +390,19 @@ int ring_wait(storm_hip_ctx *c, volatile unsigned long long *ring, int64_t it, b
       __builtin_ia32_pause();
     }
   }
+}
+
+// Grow the reduction workspace to `need` doubles (an operator with more SpMV blocks than any before it; a block solve's
+// per-column partials).  Waits for the stream: a kernel may still be reading the old buffer.
+int partials_reserve(storm_hip_ctx *c, int64_t need) {
+  if (need <= c->partials_capacity) return STORM_HIP_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  double *bigger = nullptr;
+  HIP_TRY(hipMalloc(&bigger, sizeof(double) * (size_t)need));
+  (void)hipFree(c->d_partials);
+  c->d_partials = bigger;
+  c->partials_capacity = need;
+  return STORM_HIP_OK;
 }
 
 // A solver's WORK vector whose owned rows the solver writes before it reads them (CG's r, p, z; BiCGStab's r, rt, p, v,

@@ -330,6 +330,16 @@ int storm_hip_op_apply(const storm_hip_op *op, double alpha, double beta, const 
   return spmv_launch(op, host_scal(alpha), host_scal(beta), x->d, y->d, nullptr, op->ctx->api_done);
 }
 
+// The block apply's dispatch: fp64 records go to spmv_block.hip, every other format and every partitioned operator is
+// refused (spmv_block_check names the reason).
+int storm_hip_op_apply_block(const storm_hip_op *op, double alpha, double beta, int k, const storm_hip_vec *X,
+                             storm_hip_vec *Y) {
+  STORM_TRY(spmv_block_check(op, k, X, Y, "op_apply_block"));
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  STORM_TRY(lazy_sync(op->ctx));
+  return spmv_block_launch(op, alpha, beta, k, X->d, Y->d, nullptr, nullptr, op->ctx->api_done);
+}
+
 int storm_hip_op_apply_add(const storm_hip_op *op, double alpha, const storm_hip_vec *x, storm_hip_vec *y) {
   STORM_REQUIRE(op && x && y, "op_apply_add: null argument");
   STORM_REQUIRE(x->ctx == op->ctx && y->ctx == op->ctx, "op_apply_add: context mismatch");

@@ -463,14 +463,7 @@ static int build_op(storm_hip_ctx *c, int64_t n, int64_t n_halo, const std::vect
     timer.lap("upload");
     op->device_bytes += bytes3;
     const int64_t need3 = 8 * ((n_slices + 3) / 4) + 16 + 2 * kMaxMulti;
-    if (need3 > c->partials_capacity) {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      double *bigger = nullptr;
-      HIP_TRY(hipMalloc(&bigger, sizeof(double) * (size_t)need3));
-      (void)hipFree(c->d_partials);
-      c->d_partials = bigger;
-      c->partials_capacity = need3;
-    }
+    STORM_TRY(partials_reserve(c, need3));
     *out = op;
     return STORM_HIP_OK;
   }
@@ -577,14 +570,7 @@ static int build_op(storm_hip_ctx *c, int64_t n, int64_t n_halo, const std::vect
   op->device_bytes = bytes;
   // fused-dot partials: two per SpMV block
   const int64_t need = 8 * ((n_slices + 3) / 4) + 16 + 2 * kMaxMulti;
-  if (need > c->partials_capacity) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    double *bigger = nullptr;
-    HIP_TRY(hipMalloc(&bigger, sizeof(double) * (size_t)need));
-    (void)hipFree(c->d_partials);
-    c->d_partials = bigger;
-    c->partials_capacity = need;
-  }
+  STORM_TRY(partials_reserve(c, need));
   *out = op;
   return STORM_HIP_OK;
 }

@@ -1,72 +1,12 @@
 // Operator apply, sliced-ELL records: formats 0 (fp64 records) and 1 / 2 of mixed width through the general kernel, and
 // the CSR tail.  Record layout: the header of spmv.hip.
-#include "spmv_device.hpp"
+#include "sell_device.hpp"
 
 namespace storm {
 
 
 
-// sum_k w_k (x[col_k] - x_i) over slots [S0, S0 + W) of a record whose slice has `width` slots
-// (W compile-time, S0 even).  Pairs are read as int2 / double2, an odd last slot unpaired.
-template <bool NT, int W>
-__device__ __forceinline__ double row_sum(const char *rec, int width, int lane, const double *__restrict__ x,
-                                          double xi, int s0 = 0) {
-  constexpr int NP = W / 2;
-  const int npair_total = width >> 1;
-  const int2v *cp2 = reinterpret_cast<const int2v *>(rec + kExtBytes) + lane + (s0 >> 1) * kWave;
-  const char *vbase = rec + kExtBytes + (int64_t)width * (kWave * 4);
-  const double2v *vp2 = reinterpret_cast<const double2v *>(vbase) + lane + (s0 >> 1) * kWave;
-  int2v c[NP > 0 ? NP : 1];
-  double2v v[NP > 0 ? NP : 1];
-  int ct = 0;
-  double vt = 0.0;
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    c[q] = NT ? __builtin_nontemporal_load(cp2 + q * kWave) : cp2[q * kWave];
-    v[q] = NT ? __builtin_nontemporal_load(vp2 + q * kWave) : vp2[q * kWave];
-  }
-  if (W & 1) {  // the slice's unpaired last slot
-    ct = ld_i<NT>(reinterpret_cast<const int *>(rec + kExtBytes + (int64_t)npair_total * (kWave * 8)) + lane);
-    vt = ld_d<NT>(reinterpret_cast<const double *>(vbase + (int64_t)npair_total * (kWave * 16)) + lane);
-  }
-  double xg[W > 0 ? W : 1];
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    xg[2 * q] = x[c[q].x];
-    xg[2 * q + 1] = x[c[q].y];
-  }
-  if (W & 1) xg[W - 1] = x[ct];
-  double acc = 0.0;
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    acc += v[q].x * (xg[2 * q] - xi);
-    acc += v[q].y * (xg[2 * q + 1] - xi);
-  }
-  if (W & 1) acc += vt * (xg[W - 1] - xi);
-  return acc;
-}
-
-// Rows wider than 8 slots: chunks of 8, then the remainder.
-template <bool NT>
-__device__ __forceinline__ double row_sum_wide(const char *rec, int width, int lane, const double *__restrict__ x,
-                                               double xi) {
-  double acc = 0.0;
-  int s0 = 0;
-  for (; s0 + 8 <= width; s0 += 8) acc += row_sum<NT, 8>(rec, width, lane, x, xi, s0);
-  switch (width - s0) {
-    case 1: acc += row_sum<NT, 1>(rec, width, lane, x, xi, s0); break;
-    case 2: acc += row_sum<NT, 2>(rec, width, lane, x, xi, s0); break;
-    case 3: acc += row_sum<NT, 3>(rec, width, lane, x, xi, s0); break;
-    case 4: acc += row_sum<NT, 4>(rec, width, lane, x, xi, s0); break;
-    case 5: acc += row_sum<NT, 5>(rec, width, lane, x, xi, s0); break;
-    case 6: acc += row_sum<NT, 6>(rec, width, lane, x, xi, s0); break;
-    case 7: acc += row_sum<NT, 7>(rec, width, lane, x, xi, s0); break;
-    default: break;
-  }
-  return acc;
-}
-
-// Value-dictionary record: columns as in row_sum, the weight of slot k is dict[byte k + 1 of iw] (LDS).
+// Value-dictionary record: columns as in row_sum_block (sell_device.hpp), the weight of slot k is dict[byte k + 1 of iw] (LDS).
 template <bool NT, int W>
 __device__ __forceinline__ double row_sum_cv(const char *rec, int width, int lane, const double *__restrict__ x,
                                              double xi, uint64_t iw, const double *dict) {
@@ -162,23 +102,13 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SellArgs A, Scal alph
       }
     } else {
     ext = ld_d<NT>(reinterpret_cast<const double *>(rec) + lane);
-    // The width is wave-uniform: dispatch to a body with the width as a compile-time constant,
-    // so all (col, val) loads of the row are issued back to back, then all gathers, then the
-    // FMAs -- no branch (and no s_waitcnt) between the gathers of one row.
-    switch (width) {
-      case 0: acc = 0.0; break;
-      case 1: acc = row_sum<NT, 1>(rec, 1, lane, x, xi); break;
-      case 2: acc = row_sum<NT, 2>(rec, 2, lane, x, xi); break;
-      case 3: acc = row_sum<NT, 3>(rec, 3, lane, x, xi); break;
-      case 4: acc = row_sum<NT, 4>(rec, 4, lane, x, xi); break;
-      case 5: acc = row_sum<NT, 5>(rec, 5, lane, x, xi); break;
-      case 6: acc = row_sum<NT, 6>(rec, 6, lane, x, xi); break;
-      case 7: acc = row_sum<NT, 7>(rec, 7, lane, x, xi); break;
-      case 8: acc = row_sum<NT, 8>(rec, 8, lane, x, xi); break;
-      default: acc = row_sum_wide<NT>(rec, width, lane, x, xi); break;
+    // (the width is wave-uniform: row_sum_any dispatches to a body with the width as a compile-time constant)
+    const double xi1[1] = {xi};
+    double acc1[1];
+    row_sum_any<NT, 1>(rec, width, lane, x, xi1, acc1);
+    acc = acc1[0];
     }
-    }
-    yi = (A.accumulate ? (valid ? y[row] : 0.0) : beta * xi) + alpha * (acc + ext * xi);
+    yi = sell_row_result(A.accumulate != 0, (A.accumulate && valid) ? y[row] : 0.0, beta, xi, alpha, acc, ext);
     if (valid && !done_flag) {
       if (NT) __builtin_nontemporal_store(yi, y + row);
       else y[row] = yi;
@@ -216,13 +146,7 @@ __global__ __launch_bounds__(kBlock) void spmv_tail_kernel(int64_t n_tail, const
   const int64_t t = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
   if (t >= n_tail) return;
   const double alpha = ld_scal2(alpha_s);
-  const int r = tail_row[t];
-  const double xi = x[r];
-  double acc = 0.0;
-  for (int64_t k = tail_ptr[t] + lane; k < tail_ptr[t + 1]; k += kWave)
-    acc += tail_val[k] * (x[tail_col[k]] - xi);
-  acc = wave_sum_down(acc);
-  if (lane == 0) y[r] += alpha * acc;
+  tail_row_add(t, tail_row[t], lane, tail_ptr, tail_col, tail_val, alpha, x, y, 1, 0);
 }
 
 template <bool NT, bool DOT, int VARIANT>

@@ -1,0 +1,514 @@
+"""Block vectors on the device: k interleaved columns in one vector (element (i, j) at i k + j), the operator apply
+that streams the records once for all columns, and the batched CG (include/storm_hip.h "block vectors").
+
+  1. layout            set_column / get_column round-trip bitwise, a downloaded block has (i, j) at i k + j
+  2. apply             mul_block == storm_hip_op_apply column by column, TO THE BIT, on every kind of fp64 operator
+  3. exact integers    mul_block and block_dot against exact integer results (tests/exact_ref.py)
+  4. first CG step     per column the three assertions of test_gpu_exact_first_step._check_cg, and exact_ref.Pins
+  5. independence      a column's solve does not depend on what the other columns hold, nor on where it sits
+  6. fixed K           per column against the CPU oracle under the rule of tests/test_gpu_fixed_k.py
+  7. uneven columns    converged solves whose columns stop at different iterations; frozen columns
+  8. coupled solve     the engine's CG over the n k block vector with mul_block as operator (Bittern's semantics)
+  9. refusals          compact record formats, halo plans, bad k, bad sizes, aliasing
+ 10. C++ driver        tests/cpp/block_driver against the Python solver
+
+Fold depth (item 4).  exact_ref.fold_depth(n) = 64 + ceil(blocks / 256) bounds the addition chain of the one-column
+kernels.  The block kernels' chain is SHORTER (csrc/block.hip: 8 cells per thread, 6 + 2 in the block, 6 + ceil(groups
+/ 64) + 6 through the tickets; <p_j, z_j>: 6 in the wave, then the same fold as the one-column loop), so FirstStep.cg_tol
+holds as it stands -- between 1.37e-14 and 1.72e-14 on these cases, asserted <= 1e-12 inside exact_ref.tolerance."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import exact_ref as er
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SMALL, ODD, BIG = (64, 48, 40), (37, 21, 19), (256, 256, 258)
+AB = ((-1.0, 0.0), (-0.3, 1.0), (1.0, 0.0))
+UNSUPPORTED, INVALID = -6, -1
+
+
+@pytest.fixture(scope="module")
+def env():
+    from oracle import oracle
+    from stormruler_amd import api, mesh
+
+    ctx = api.Context(0)
+    yield api, mesh, oracle, ctx
+    ctx.close()
+
+
+@pytest.fixture(autouse=True)
+def _defaults(env):
+    yield
+    ctx = env[3]
+    for k, v in (("spmv_dict", 4), ("ell_cap", 0), ("nontemporal", 1), ("lazy_statements", 0)):
+        ctx.set_option(k, v)
+
+
+def _fp64(ctx, build, ell_cap=0):
+    """An operator with fp64 records (spmv_dict = 0), the defaults restored afterwards as
+    test_gpu_exact_first_step._matrix does."""
+    ctx.set_option("spmv_dict", 0)
+    ctx.set_option("ell_cap", ell_cap)
+    try:
+        mat = build()
+    finally:
+        ctx.set_option("spmv_dict", 4)
+        ctx.set_option("ell_cap", 0)
+    st = mat.stats()
+    assert st["value_dictionary_size"] == 0 and st["paired_rows"] == 0
+    assert (st["tail_rows"] > 0) == (ell_cap > 0)
+    return mat
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def _neumann(mesh, g):
+    return mesh.FaceGraph(g.n_cells, 2, g.inner, g.outer, g.area, g.center, g.volume, b_center=np.zeros((0, 2)))
+
+
+def _random_csr(n, lo, hi, seed):
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng(seed)
+    rows, cols, vals = [], [], []
+    for i in range(n):
+        w = int(rng.integers(lo, hi + 1))
+        cs = rng.choice(n - 1, w, replace=False)
+        cs = cs + (cs >= i)  # no diagonal entry among them
+        rows += [i] * w
+        cols += list(cs)
+        vals += list(rng.standard_normal(w))
+    return (sp.coo_matrix((vals, (rows, cols)), shape=(n, n)) + sp.diags(4.0 + rng.random(n))).tocsr()
+
+
+def _operators(api, mesh, ctx):
+    """name -> (builder of an fp64-record StencilMatrix, n)."""
+    from stormruler_amd import io_tetgen
+
+    def box(shape):
+        g = er.unit_box(mesh, *shape)
+        return lambda: _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+
+    def jitter():
+        g = mesh.jitter_geometry(mesh.structured_box(24, 20, 18), 1.0 / 24)
+        return _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+
+    def tet():
+        pos, bf, cells = io_tetgen.tet_box(8)
+        g = io_tetgen.face_graph_from_simplices(pos, bf, np.ones(len(bf), np.int64), cells)
+        return _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+
+    def triangle(name):
+        g = _neumann(mesh, io_tetgen.read_triangle(os.path.join(ROOT, "tests", "golden", "mesh", name + ".")))
+        return lambda: _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+
+    def convdiff():
+        g = mesh.structured_box(33, 20, 17)
+        wi, wo, de = mesh.convection_diffusion_weights(g, 1e-2, (1.0, 0.5, 0.25))
+        return _fp64(ctx, lambda: api.StencilMatrix.from_face_weights(ctx, g.n_cells, g.n_halo, g.inner, g.outer, wi, wo, de))
+
+    def csr_tail():
+        a = _random_csr(3000, 2, 14, 5)  # rows longer than 8, everything beyond 3 slots in the CSR tail
+        mat = _fp64(ctx, lambda: api.StencilMatrix.from_csr(ctx, a), ell_cap=3)
+        assert mat.stats()["tail_rows"] > 0 and mat.stats()["max_row_len"] > 8
+        return mat
+
+    def csr_wide():
+        a = _random_csr(2500, 1, 19, 6)  # slices of every width, the chunk sums of rows wider than 8 included
+        mat = _fp64(ctx, lambda: api.StencilMatrix.from_csr(ctx, a))
+        assert mat.stats()["max_row_len"] > 16
+        return mat
+
+    return {"box_64x48x40": box(SMALL), "box_37x21x19": box(ODD), "jittered_box": jitter, "tetrahedra": tet,
+            "triangle_square_nb": triangle("square_nb.1"), "triangle_step": triangle("step.1"), "upwind_convdiff": convdiff,
+            "csr_tail_ell_cap_3": csr_tail, "csr_wide_rows": csr_wide}
+
+
+OPERATORS = ("box_64x48x40", "box_37x21x19", "jittered_box", "tetrahedra", "triangle_square_nb", "triangle_step",
+             "upwind_convdiff", "csr_tail_ell_cap_3", "csr_wide_rows")
+
+
+# ---- 1. layout ----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("k", range(1, 9))
+def test_columns_round_trip_and_layout(env, k):
+    api, mesh, oracle, ctx = env
+    n = 2049  # odd: ragged pairs, a ragged last block
+    rng = np.random.default_rng(k)
+    cols = [rng.standard_normal(n) for _ in range(k)]
+    X = api.BlockVector(ctx, n, k)
+    assert X.shape() == (n, k) and X.n_owned == n * k and X.n_halo == 0
+    for j in reversed(range(k)):
+        X.set_column(j, api.DeviceVector.from_numpy(ctx, cols[j]))
+    flat = api.DeviceVector.to_numpy(X)  # the plain download of the n k elements
+    for j in range(k):
+        assert np.array_equal(_bits(X.column(j).to_numpy()), _bits(cols[j])), j
+        assert np.array_equal(_bits(flat[j::k]), _bits(cols[j])), j  # (i, j) sits at i k + j
+    host = X.to_numpy()
+    assert host.shape == (n, k) and np.array_equal(_bits(host), _bits(np.stack(cols, axis=1)))
+    Y = api.BlockVector.from_numpy(ctx, host)
+    assert np.array_equal(_bits(api.DeviceVector.to_numpy(Y)), _bits(flat))
+    # the elementwise entry points work on a block unchanged
+    Y *= 2.0
+    Y += X
+    assert np.array_equal(_bits(Y.to_numpy()), _bits(2.0 * host + host))
+
+
+def test_block_axpy_is_one_fma_per_column(env):
+    api, mesh, oracle, ctx = env
+    n, k = 4099, 5
+    rng = np.random.default_rng(3)
+    x, y = rng.standard_normal((n, k)), rng.standard_normal((n, k))
+    a = rng.standard_normal(k)
+    X, Y = api.BlockVector.from_numpy(ctx, x), api.BlockVector.from_numpy(ctx, y)
+    api.block_axpy(Y, a, X)
+    want = np.stack([er.vfma(a[j], x[:, j], y[:, j]) for j in range(k)], axis=1)
+    assert np.array_equal(_bits(Y.to_numpy()), _bits(want))
+
+
+# ---- 2. apply == single apply, to the bit --------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", OPERATORS)
+def test_mul_block_equals_the_single_apply_bit_for_bit(env, name):
+    api, mesh, oracle, ctx = env
+    mat = _operators(api, mesh, ctx)[name]()
+    n = mat.stats()["n_rows"]
+    rng = np.random.default_rng(11)
+    host = rng.standard_normal((n, 8))
+    x1, y1 = api.DeviceVector(ctx, n), api.DeviceVector(ctx, n)
+    compared = 0
+    for nt in (0, 1):
+        ctx.set_option("nontemporal", nt)
+        for alpha, beta in AB:
+            op = api.HipStencilOperator(mat, alpha, beta)
+            single = []
+            for j in range(8):
+                x1.upload(host[:, j])
+                op.mul(y1, x1)
+                single.append(y1.to_numpy())
+            for k in range(1, 9):
+                X = api.BlockVector.from_numpy(ctx, host[:, :k])
+                Y = api.BlockVector(ctx, n, k)
+                op.mul_block(Y, X)
+                got = Y.to_numpy()
+                for j in range(k):
+                    assert np.array_equal(_bits(got[:, j]), _bits(single[j])), \
+                        (name, nt, alpha, beta, k, j, int(np.count_nonzero(got[:, j] != single[j])))
+                    compared += 1
+    assert compared == 2 * 3 * 36
+    mat.close()
+
+
+# ---- 3. exact integers --------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("shape", [SMALL, ODD])
+@pytest.mark.parametrize("k", [1, 3, 4, 8])
+def test_mul_block_on_integers_is_exact(env, shape, k):
+    api, mesh, oracle, ctx = env
+    g = er.unit_box(mesh, *shape)
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+    b = [er.int_vector(g.n_cells, 31 + j) for j in range(k)]
+    X = api.BlockVector.from_numpy(ctx, np.stack(b, axis=1).astype(np.float64))
+    Y = api.BlockVector(ctx, g.n_cells, k)
+    api.HipStencilOperator(mat, -1.0, 0.0).mul_block(Y, X)
+    got = Y.to_numpy()
+    for j in range(k):
+        assert np.array_equal(got[:, j], er.int_apply(shape, b[j]).astype(np.float64)), j
+    mat.close()
+
+
+@pytest.mark.parametrize("shape", [(40, 30, 17), (256, 128, 130)])
+@pytest.mark.parametrize("k", [3, 8])
+def test_block_dot_on_integers_is_exact(env, shape, k):
+    api, mesh, oracle, ctx = env
+    n = shape[0] * shape[1] * shape[2]
+    a = [er.int_vector(n, 31 + j) for j in range(k)]
+    b = [er.int_vector(n, 71 + j) for j in range(k)]
+    A = api.BlockVector.from_numpy(ctx, np.stack(a, axis=1).astype(np.float64))
+    B = api.BlockVector.from_numpy(ctx, np.stack(b, axis=1).astype(np.float64))
+    got = api.block_dot(A, B)
+    for j in range(k):
+        assert got[j] == float(er.exact_dot(a[j], b[j])), j
+    sq = api.block_dot(A, A)
+    for j in range(k):
+        assert sq[j] == float(er.exact_dot(a[j], a[j])), j
+
+
+# ---- 4. first CG step, exact --------------------------------------------------------------------------------------
+
+def _block_solve(api, ctx, mat, cols, iters, x0=None, abs_tol=0.0, rel_tol=0.0):
+    k = len(cols)
+    s = api.BlockCgSolver()
+    s.num_iterations, s.absolute_error_tolerance, s.relative_error_tolerance = iters, abs_tol, rel_tol
+    s.record_history = True
+    B = api.BlockVector.from_numpy(ctx, np.stack([np.asarray(c, np.float64) for c in cols], axis=1))
+    X = api.BlockVector(ctx, B.n, k) if x0 is None else api.BlockVector.from_numpy(ctx, x0)
+    before = ctx.counter("block_solves")
+    ok = s.solve(X, B, api.HipStencilOperator(mat, -1.0, 0.0))
+    assert ctx.counter("block_solves") == before + 1 and s.path_fallback == 0
+    return s, X.to_numpy(), ok
+
+
+FIRST_STEP = [(SMALL, 0), (SMALL, 3), (ODD, 0), (ODD, 3), (BIG, 0)]
+
+
+@pytest.mark.parametrize("shape,ell_cap", FIRST_STEP, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else f"ell_cap{v}")
+def test_block_cg_first_step_is_exact(env, shape, ell_cap):
+    api, mesh, oracle, ctx = env
+    k = 4
+    g = er.unit_box(mesh, *shape)
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g), ell_cap=ell_cap)
+    b = [er.int_vector(g.n_cells, 31 + j) for j in range(k)]
+    s, x, _ = _block_solve(api, ctx, mat, b, 1)
+    assert list(s.iterations) == [1] * k and not s.converged.any()
+    for j in range(k):
+        fs = er.FirstStep(er.Sums(shape, b[j]))
+        h = s.history[j]
+        assert h.size == 2
+        print(f"{shape} ell_cap {ell_cap} column {j}: h0 {h[0]!r} (exact {fs.h0!r}), h1 rel "
+              f"{abs(h[1] - fs.cg_h1) / fs.cg_h1:.3e} (tol {fs.cg_tol:.3e})")
+        assert h[0] == fs.h0, j
+        assert np.array_equal(x[:, j], fs.cg_x1(b[j])), (j, int(np.count_nonzero(x[:, j] != fs.cg_x1(b[j]))))
+        assert fs.cg_tol <= 1e-12
+        assert er.close(h[1], fs.cg_h1, fs.cg_tol), (j, h[1], fs.cg_h1)
+    mat.close()
+
+
+def test_block_cg_two_iterations_against_the_exact_pins(env):
+    api, mesh, oracle, ctx = env
+    k, shape = 4, SMALL
+    g = er.unit_box(mesh, *shape)
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+    b = [er.int_vector(g.n_cells, 31 + j) for j in range(k)]
+    s, _, _ = _block_solve(api, ctx, mat, b, 2)
+    for j in range(k):
+        pins = er.Pins(oracle, g, shape, b[j], "cg")
+        ratios = pins.check(list(s.history[j]), label=f"column {j}")
+        print(f"column {j}: |h - exact| / (exact e_k) = {ratios}")
+    mat.close()
+
+
+# ---- 5. columns do not see each other -------------------------------------------------------------------------------
+
+def test_a_column_does_not_see_the_others(env):
+    api, mesh, oracle, ctx = env
+    g = mesh.structured_box(40, 36, 33)
+    n = g.n_cells
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+    rng = np.random.default_rng(17)
+    b = [np.sin(0.37 * np.arange(n)), np.ones(n), rng.standard_normal(n), np.cos(0.11 * np.arange(n))]
+    junk = 1e3 * rng.standard_normal(n) + 7.0
+    s0, x0, _ = _block_solve(api, ctx, mat, b, 20)
+    s1, x1, _ = _block_solve(api, ctx, mat, [b[0], junk, junk, junk], 20)
+    s2, x2, _ = _block_solve(api, ctx, mat, [junk, 0.5 * junk, b[0], junk], 20)
+    assert s0.history[0].size == 21
+    for s, x, col in ((s1, x1, 0), (s2, x2, 2)):
+        assert np.array_equal(_bits(x[:, col]), _bits(x0[:, 0])), col
+        assert np.array_equal(_bits(s.history[col]), _bits(s0.history[0])), col
+        assert s.iterations[col] == s0.iterations[0]
+    mat.close()
+
+
+# ---- 6. fixed K against the oracle ----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("K", [5, 10, 20])
+def test_block_cg_fixed_k_against_the_oracle(env, K):
+    """The rule of tests/test_gpu_fixed_k.py, per column: max(base, 10 x the oracle's strict-vs-FMA disagreement)."""
+    api, mesh, oracle, ctx = env
+    g = mesh.structured_box(64)
+    n, c = g.n_cells, g.center
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+    cols = [np.ones(n), np.sin(3 * c[:, 0]) * np.cos(7 * c[:, 1]) * np.cos(2 * c[:, 2]), np.sin(0.37 * np.arange(n)),
+            er.int_vector(n, 31).astype(np.float64)]
+    s, x, _ = _block_solve(api, ctx, mat, cols, K)
+    base = 1e-10 if K <= 5 else 1e-9
+    for j, b in enumerate(cols):
+        ref, fma = (oracle.solve("cg", oracle.StencilOperator(g, -1.0, 0.0, variant=v), b, num_iterations=K, abs_tol=0.0,
+                                 rel_tol=0.0, variant=v) for v in ("strict", "fma"))
+        spread_h = np.abs(fma.history - ref.history).max() / np.abs(ref.history).max()
+        spread_x = np.linalg.norm(fma.x - ref.x) / np.linalg.norm(ref.x)
+        assert s.iterations[j] == ref.iterations == K
+        hist = s.history[j]
+        assert hist.shape == ref.history.shape
+        worst = np.abs(hist - ref.history).max() / np.abs(ref.history).max()
+        err = np.linalg.norm(x[:, j] - ref.x) / np.linalg.norm(ref.x)
+        print(f"K {K} column {j}: history {worst:.3e} (bound {max(base, 10 * spread_h):.3e}), x {err:.3e} "
+              f"(bound {max(base, 10 * spread_x):.3e})")
+        assert worst <= max(base, 10.0 * spread_h), (j, worst, spread_h)
+        assert err <= max(base, 10.0 * spread_x), (j, err, spread_x)
+    mat.close()
+
+
+# ---- 7. converged solves with uneven columns -------------------------------------------------------------------------
+
+def test_block_cg_converges_with_uneven_columns(env):
+    api, mesh, oracle, ctx = env
+    g = mesh.structured_box(48)
+    n, c = g.n_cells, g.center
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+    cols = [np.ones(n), np.zeros(n), np.sin(3 * c[:, 0]) * np.cos(7 * c[:, 1]) * np.cos(2 * c[:, 2]), 1e-3 * np.ones(n)]
+    s, x, ok = _block_solve(api, ctx, mat, cols, 2000, abs_tol=1e-6, rel_tol=1e-6)
+    assert ok and s.converged.all() and s.path_fallback == 0
+    assert s.iterations[1] == 0 and s.history[1].size == 1 and s.history[1][0] == 0.0
+    assert not x[:, 1].any()
+    for j in (0, 2, 3):
+        ref = oracle.solve("cg", oracle.StencilOperator(g, -1.0, 0.0), cols[j])
+        assert ref.converged
+        rel = np.linalg.norm(x[:, j] - ref.x) / np.linalg.norm(ref.x)
+        print(f"column {j}: {s.iterations[j]} iterations (oracle {ref.iterations}), |x - x_oracle| / |x_oracle| = {rel:.3e}")
+        assert abs(int(s.iterations[j]) - ref.iterations) <= 2, (j, s.iterations[j], ref.iterations)
+        assert rel <= 1e-8, (j, rel)
+        assert s.history[j].size == s.iterations[j] + 1
+    assert len(set(int(v) for v in s.iterations)) >= 3  # the columns really stop at different iterations
+    # a column that stopped at iteration m was not written afterwards: its x is that of a solve capped at m
+    last = int(s.iterations.max())
+    for j in (0, 2, 3):
+        m = int(s.iterations[j])
+        if m == last:
+            continue
+        sm, xm, _ = _block_solve(api, ctx, mat, cols, m, abs_tol=1e-6, rel_tol=1e-6)
+        assert sm.iterations[j] == m
+        assert np.array_equal(_bits(xm[:, j]), _bits(x[:, j])), j
+        assert np.array_equal(_bits(sm.history[j]), _bits(s.history[j])), j
+    mat.close()
+
+
+# ---- 8. the reference's coupled semantics ----------------------------------------------------------------------------
+
+def test_engine_cg_over_the_block_vector_is_the_coupled_solve(env):
+    """CgSolver on a FunctionalOperator whose mat_vec is mul_block: the vectors are the n k blocks and dot_product runs
+    over all columns, as Bittern's does on a NumVars field."""
+    api, mesh, oracle, ctx = env
+    g = mesh.structured_box(32)
+    n, k, K = g.n_cells, 3, 10
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+    hop = api.HipStencilOperator(mat, -1.0, 0.0)
+    op = api.make_operator(lambda y, x: hop.mul_block(y, x, k))
+    c = g.center
+    b = np.stack([np.ones(n), np.sin(3 * c[:, 0]) * np.cos(7 * c[:, 1]) * np.cos(2 * c[:, 2]), np.sin(0.37 * np.arange(n))], axis=1)
+    B = api.BlockVector.from_numpy(ctx, b)
+    X = api.BlockVector(ctx, n, k)
+    s = api.CgSolver()
+    s.record_history, s.num_iterations = True, K
+    s.absolute_error_tolerance = s.relative_error_tolerance = 0.0
+    s.solve(X, B, op)
+
+    def both(variant):
+        sop = oracle.StencilOperator(g, -1.0, 0.0, variant=variant)
+
+        def f(v):
+            v = v.reshape(n, k)
+            return np.stack([sop.apply(np.ascontiguousarray(v[:, j])) for j in range(k)], axis=1).reshape(-1)
+
+        return oracle.solve("cg", oracle.CallbackOperator(n * k, f), b.reshape(-1), num_iterations=K, abs_tol=0.0, rel_tol=0.0,
+                            variant=variant)
+
+    ref, fma = both("strict"), both("fma")
+    spread_h = np.abs(fma.history - ref.history).max() / np.abs(ref.history).max()
+    spread_x = np.linalg.norm(fma.x - ref.x) / np.linalg.norm(ref.x)
+    base = 1e-9
+    assert s.iteration == ref.iterations == K
+    worst = np.abs(np.array(s.history) - ref.history).max() / np.abs(ref.history).max()
+    err = np.linalg.norm(X.to_numpy().reshape(-1) - ref.x) / np.linalg.norm(ref.x)
+    print(f"coupled CG: history {worst:.3e}, x {err:.3e} (oracle strict vs fma {spread_h:.3e}, {spread_x:.3e})")
+    assert worst <= max(base, 10.0 * spread_h) and err <= max(base, 10.0 * spread_x)
+    mat.close()
+
+
+# ---- 9. refusals -----------------------------------------------------------------------------------------------------
+
+def _status(api, fn):
+    with pytest.raises(api._lib.StormHipError) as e:
+        fn()
+    return e.value.status, str(e.value)
+
+
+def test_refusals(env):
+    api, mesh, oracle, ctx = env
+    g = mesh.structured_box(16)
+    n = g.n_cells
+    X, Y = api.BlockVector(ctx, n, 2), api.BlockVector(ctx, n, 2)
+    solver = api.BlockCgSolver()
+    # a default-format box operator
+    compact = api.StencilMatrix.from_face_graph(ctx, g)
+    assert compact.stats()["paired_rows"] == 2
+    for call in (lambda: api.HipStencilOperator(compact).mul_block(Y, X), lambda: solver.solve(X, Y, api.HipStencilOperator(compact))):
+        status, what = _status(api, call)
+        assert status == UNSUPPORTED and "spmv_dict = 0" in what, what
+    compact.close()
+    # an operator with a halo plan
+    loc, send_idx = mesh.periodic_z_local_graph(8, 8, 8)
+    halo = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, loc))
+    halo.set_halo([0], [0, loc.n_halo], send_idx, [0, loc.n_halo])
+    Xh, Yh = api.BlockVector(ctx, loc.n_cells, 2), api.BlockVector(ctx, loc.n_cells, 2)
+    status, what = _status(api, lambda: api.HipStencilOperator(halo).mul_block(Yh, Xh))
+    assert status == UNSUPPORTED and "halo" in what, what
+    halo.close()
+    # argument errors
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+    op = api.HipStencilOperator(mat)
+    for k in (0, 9, -1):
+        assert _status(api, lambda: op.mul_block(Y, X, k))[0] == INVALID
+        assert _status(api, lambda: api._lib.check(api._lib.lib.storm_hip_block_dot(X._h, Y._h, k, (api.C.c_double * 16)())))[0] == INVALID
+    assert _status(api, lambda: op.mul_block(Y, X, 3))[0] == INVALID  # sizes are not n_rows * k
+    short = api.BlockVector(ctx, n - 1, 2)
+    assert _status(api, lambda: op.mul_block(short, X))[0] == INVALID
+    assert _status(api, lambda: op.mul_block(X, X))[0] == INVALID  # X aliases Y
+    assert _status(api, lambda: solver.solve(X, X, op))[0] == INVALID
+    v = api.DeviceVector(ctx, n)
+    assert _status(api, lambda: X.set_column(2, v))[0] == INVALID
+    assert _status(api, lambda: X.column(0, api.DeviceVector(ctx, n + 1)))[0] == INVALID
+    op.mul_block(Y, X)  # ... and the well-formed call goes through
+    mat.close()
+
+
+def test_block_entry_points_launch_what_lazy_statements_holds_back(env):
+    api, mesh, oracle, ctx = env
+    g = mesh.structured_box(16)
+    n, k = g.n_cells, 2
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+    op = api.HipStencilOperator(mat, -1.0, 0.0)
+    host = np.random.default_rng(2).standard_normal((n, k))
+    X, Y = api.BlockVector.from_numpy(ctx, host), api.BlockVector(ctx, n, k)
+    op.mul_block(Y, X)
+    eager = Y.to_numpy()
+    ctx.set_option("lazy_statements", 1)
+    X2, Y2 = api.BlockVector(ctx, n, k), api.BlockVector(ctx, n, k)
+    X2 <<= X  # waits ...
+    assert ctx.counter("lazy_waiting") == 1
+    op.mul_block(Y2, X2)  # ... until the block apply needs it
+    assert ctx.counter("lazy_waiting") == 0
+    ctx.set_option("lazy_statements", 0)
+    assert np.array_equal(_bits(Y2.to_numpy()), _bits(eager))
+    mat.close()
+
+
+# ---- 10. C++ driver --------------------------------------------------------------------------------------------------
+
+def test_cpp_block_driver_matches_the_python_solver(env):
+    api, mesh, oracle, ctx = env
+    n, k = 32, 3
+    exe = os.path.join(ROOT, "tests", "cpp", "block_driver")
+    r = subprocess.run([exe, str(n), str(k)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stderr)
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    g = mesh.structured_box(n)
+    mat = _fp64(ctx, lambda: api.StencilMatrix.from_face_graph(ctx, g))
+    i = np.arange(g.n_cells, dtype=np.int64)
+    cols = [((i * (j + 3)) % 17 - 8).astype(np.float64) for j in range(k)]
+    s, x, ok = _block_solve(api, ctx, mat, cols, 2000, abs_tol=1e-6, rel_tol=1e-6)
+    assert ok and out["converged"] == [True] * k and out["block_solves"] == 1
+    assert out["iterations"] == [int(v) for v in s.iterations], (out["iterations"], s.iterations)
+    for j in range(k):
+        assert abs(out["absolute_error"][j] - s.absolute_error[j]) <= 1e-6 * s.initial_error[j]
+        assert abs(out["true_residual"][j] - out["absolute_error"][j]) <= 1e-6 * s.initial_error[j]
+    mat.close()
