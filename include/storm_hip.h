@@ -380,7 +380,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *ctx, const char *key, int64_t value)
 /* Which path the solves of this context took so far (no reference counterpart: a diagnostic of this library; the
  * reference logs one line per solve, Solver.hpp:144-145).  Keys: "resident_solves" (csrc/resident.hip),
  * "latency_solves" (csrc/latency.hip: one cooperative kernel per solve), "throughput_solves" (a kernel per statement,
- * fused loops of csrc/solvers.hip), "engine_solves" (csrc/krylov.hip), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "cg_fused_steps" (solves whose CG step rode in
+ * fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip), "engine_solves" (csrc/krylov.hip), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "cg_fused_steps" (solves whose CG step rode in
  * the SpMV launch), "lazy_fused_dots" / "lazy_fused_pairs" / "lazy_apply_dots" / "lazy_cg_steps" / "lazy_waiting" (option
  * lazy_statements: reductions that rode in a statement's kernel, pairs of statements that left as one pass, applies that
  * left with a fused dot, fused CG steps, statements waiting now).  On the peer-window transport, where the time of the exchanges went (ticks of 10 ns of the device's

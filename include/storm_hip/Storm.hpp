@@ -1055,7 +1055,7 @@ bool solve_non_uniform(Solver<Vector>& solver, Vector& x_vec, const Vector& b_ve
 
 // ---------------------------------------------------------------------------------------------
 // The shipped solvers.  Each names its library method; the loop bodies are csrc/krylov.hip (and, for a stencil
-// operator without preconditioner, the fused kernels of csrc/solvers.hip).  They exist for DeviceVector only.
+// operator without preconditioner, the fused kernels of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip).  They exist for DeviceVector only.
 namespace detail {
 
 /// Stepping hooks of a shipped plain solver over the library's stepping calls.

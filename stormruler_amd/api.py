@@ -1046,7 +1046,7 @@ class InnerOuterIterativeSolver(IterativeSolver):
 
 
 # The shipped solvers: a method id each; their loops are csrc/krylov.hip (and, for a stencil operator without
-# preconditioner, the fused kernels of csrc/solvers.hip).
+# preconditioner, the fused kernels of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip).
 class CgSolver(IterativeSolver):
     """SolverCg.hpp:47-128."""
 

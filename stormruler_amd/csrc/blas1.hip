@@ -522,7 +522,7 @@ static int k_multi_dot_host(storm_hip_ctx *c, const double *a, const double *con
   return k_reduce_final(c, c->d_partials, nb, k, d_out, done);
 }
 
-// Per-block partials of <a, b> without the final pass (the consumer folds them: solvers.hip, fused MGS).
+// Per-block partials of <a, b> without the final pass (the consumer folds them: solver_gmres.hip, fused MGS).
 int k_dot_partials(storm_hip_ctx *c, const double *a, const double *b, int64_t n, double *partials, int nb,
                    const int *done) {
   DotPtrs ptrs;

@@ -60,7 +60,7 @@ constexpr int kSinglePassPartials = 8192;
 // alpha/beta/omega/Givens value ever visits the host (SURVEY.md section 7
 // "Reduction latency").  One instance lives in each context.
 struct SolverState {
-  double s[kSlab];          // named slots, see solvers.hip
+  double s[kSlab];          // named slots, see solver_fused.hpp
   double initial_error;
   double absolute_error;
   double relative_error;
@@ -228,8 +228,8 @@ struct storm_hip_ctx {
   int64_t opt_cg_march_fill = 2048;    // ... fewer planes per block on smaller lattices, so that the grid holds about this many blocks (0: cg_march as given)
   int64_t opt_cg_march_alternate = 1;  // odd z-chunks of the marching step kernel march downwards (spmv.hip MarchArgs::alternate)
   int64_t opt_cg_march = 8;   // ... as blocks of 1024 rows marching through this many planes (0: tiles, spmv_canon_tile planes deep); 256^3, us per CG iteration: tiles 239, 8 planes 230, 16 234, 32 236, 64 237 (profiles/r03k)
-  int64_t opt_cg_residual_march = 1;  // fused CG step, one rank, unsplit lattice operator: r -= alpha z by a kernel that recomputes z = A p' from p' in cg_r_kernel's row order (solvers.hip cg_r_recompute_kernel: the same bits), so z is never stored nor read back (0: cg_r_kernel streams z)
-  int64_t opt_cg_residual_planes = 1;  // ... by blocks that own a 2 048-row run of a plane and march over planes (solvers.hip cg_r_planes_kernel: cg_r_kernel's partials, plane by plane; lattices of whole 2 048-row runs per plane) instead of gathering the +-a / +-b neighbours (0: cg_r_recompute_kernel everywhere)
+  int64_t opt_cg_residual_march = 1;  // fused CG step, one rank, unsplit lattice operator: r -= alpha z by a kernel that recomputes z = A p' from p' in cg_r_kernel's row order (solver_cg.hip cg_r_recompute_kernel: the same bits), so z is never stored nor read back (0: cg_r_kernel streams z)
+  int64_t opt_cg_residual_planes = 1;  // ... by blocks that own a 2 048-row run of a plane and march over planes (solver_cg.hip cg_r_planes_kernel: cg_r_kernel's partials, plane by plane; lattices of whole 2 048-row runs per plane) instead of gathering the +-a / +-b neighbours (0: cg_r_recompute_kernel everywhere)
   int64_t opt_cg_residual_chunk = 16;  // ... planes per block (2 .. 32); the two planes bounding a chunk are read again: + 2 / chunk of 8 B/row
   int64_t opt_cg_residual_fill = 512;  // ... fewer planes per block on smaller lattices, so that the grid holds about this many blocks (0: cg_residual_chunk as given)
   int64_t opt_cg_fuse = 1;   // fused CG, one rank, tiled format-4 operator: the SpMV kernel ends the previous iteration (x += alpha p, p = r + beta p) itself
@@ -489,6 +489,11 @@ struct ChainApply {
 int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w, const double *const *q, int k, int m,
                          double *H, double *norm2_out, bool normalise, bool *taken, const MgsGivens *givens,
                          const ChainApply *apply = nullptr, bool *applied = nullptr);
+// solver_gmres.hip: the Gram-Schmidt step of storm_hip_solve_gmres, shared with the general engine (krylov.hip)
+int gmres_orthogonalize(storm_hip_ctx *c, int64_t n, const SolverState *st, const int *done, double *qn,
+                        const double *const *q, int k, int m, double *H, double *norm2_out, double *scratch,
+                        int gram_schmidt, bool *normalised, const MgsGivens *givens = nullptr,
+                        bool *givens_done = nullptr, const ChainApply *apply = nullptr);
 // *taken = false: no cooperative kernel ran (none fits, or the launch was refused) -- take the throughput path
 int cg_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x, double *p,
                      double *r, SolverState *d_state, bool *taken);

@@ -581,7 +581,7 @@ static int vec_create_impl(storm_hip_ctx *c, int64_t n_owned, int64_t n_halo, st
   hipError_t e = hipSuccess;
   double *base = nullptr;
   // last in, first out, order kept: a solver that releases its work vectors in the reverse order of their creation
-  // (VecPool, solvers.hip) gets every vector back in the same role next time -- until round 4 the roles permuted with
+  // (VecPool, solver_fused.hpp) gets every vector back in the same role next time -- until round 4 the roles permuted with
   // period two, and the 256^3 CG rate alternated between 4 588 and 4 660 it/s with them (tools/rate_stability.py)
   for (size_t i = c->pool.size(); i-- > 0;) {
     if (c->pool[i].first == bytes) {

@@ -1237,14 +1237,6 @@ void K::gmres_update_x(int k) {
   }
 }
 
-namespace storm {
-// solvers.hip: the Gram-Schmidt step of storm_hip_solve_gmres, shared with this engine
-int gmres_orthogonalize(storm_hip_ctx *c, int64_t n, const SolverState *st, const int *done, double *qn,
-                        const double *const *q, int k, int m, double *H, double *norm2_out, double *scratch,
-                        int gram_schmidt, bool *normalised, const MgsGivens *givens = nullptr,
-                        bool *givens_done = nullptr, const ChainApply *apply = nullptr);
-}  // namespace storm
-
 void K::init() {
   const bool P = has_pre();
   switch (method) {
@@ -1869,7 +1861,7 @@ static int krylov_solve_engine(storm_hip_krylov *k, const storm_hip_vec *b, stor
                                const storm_hip_solver_params *params, storm_hip_solver_result *result, double *history,
                                int64_t *pre_applies) {
   storm_hip_ctx *c = k->c;
-  // A stencil operator without preconditioner: CG / BiCGStab / GMRES have fused kernels (solvers.hip).
+  // A stencil operator without preconditioner: CG / BiCGStab / GMRES have fused kernels (solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip).
   if (k->op != nullptr && !k->has_pre() && c->opt_generic_solvers == 0) {
     fused_entry fused = k->method == STORM_HIP_CG         ? &storm_hip_solve_cg
                         : k->method == STORM_HIP_BICGSTAB ? &storm_hip_solve_bicgstab

@@ -1,7 +1,7 @@
 // The latency path: CG and BiCGStab for SMALL operators as ONE cooperative, persistent kernel per solve.
 //
 // The reference's own meshes have 6 000 .. 80 000 cells (tests/_data/mesh), BASELINE config 1 has 64^3 = 262 144:
-// vectors of 50 KB .. 2 MB.  The throughput path (solvers.hip) spends such an iteration on launch latency -- 7 kernels
+// vectors of 50 KB .. 2 MB.  The throughput path (solver_cg.hip and its siblings) spends such an iteration on launch latency -- 7 kernels
 // of a few microseconds each.  Here a solve is one launch (SolverCg.hpp:54-126 inside Solver.hpp:116-147):
 //
 //   * every wavefront owns a fixed set of 64-row slices for the whole solve and keeps x, r, p, z of its rows in

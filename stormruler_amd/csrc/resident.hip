@@ -2,7 +2,7 @@
 // persistent kernel per solve in which every block OWNS a box of the lattice.
 //
 // BASELINE configs 4 and 5 (and every mid-size user) live at 128^3 = 2.1 M rows.  There the throughput path
-// (solvers.hip) is three dependent launches of ~13 us each per CG iteration -- launch- and tail-bound although the
+// (solver_cg.hip) is three dependent launches of ~13 us each per CG iteration -- launch- and tail-bound although the
 // whole working set sits in the Infinity Cache -- and the latency path (latency.hip), which keeps its vectors in
 // registers, publishes EVERY row of r and p with returning atomics and gathers six neighbours per row through the
 // L2s: 235 MB of atomic / L2 traffic per iteration at 128^3, slower than the launches beyond 100^3.  On a lattice

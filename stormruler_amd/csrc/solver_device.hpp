@@ -1,5 +1,5 @@
-// Device-side pieces shared by the solver translation units (solvers.hip: the fused CG / BiCGStab / GMRES
-// loops of a stencil operator; krylov.hip: the general Krylov engine): the reference's scalar helpers and the
+// Device-side pieces shared by the solver translation units (solver_fused.hip and the unit of each loop: the fused CG /
+// BiCGStab / GMRES loops of a stencil operator; krylov.hip: the general Krylov engine): the reference's scalar helpers and the
 // body of IterativeSolver::solve's loop, evaluated on the device against a SolverState -- and the fold and final
 // pass every reduction of the library ends with (blas1.hip's too).
 #pragma once
@@ -77,7 +77,7 @@ __device__ inline void gmres_givens_update(SolverState *st, GmresDev g, int k, d
 #undef H_
 }
 
-// (the second half on its own: a kernel that forms several block sums before it meets a barrier -- solvers.hip
+// (the second half on its own: a kernel that forms several block sums before it meets a barrier -- solver_cg.hip
 //  cg_r_planes_kernel -- keeps lane 0's wave_sum_down values of each and folds them here afterwards: the same bits)
 __device__ __forceinline__ double block_sum256_of_waves(const double *lds4) { return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]); }
 __device__ __forceinline__ double block_sum256(double v, double *lds4) {
@@ -111,7 +111,7 @@ struct OutPtrs {
 
 // Final pass of k simultaneous reductions + the scalar epilogue behind them: one block folds partials[j * nblocks ..],
 // on the peer-window transport (use_ipc) exchanges its sums with the other ranks itself (ipc_device.hpp), stores sum j
-// into *out.p[j] and runs epi() -- a scalar step (solvers.hip) or a scalar program (krylov.hip) -- in thread 0.
+// into *out.p[j] and runs epi() -- a scalar step (solver_fused.hpp) or a scalar program (krylov.hip) -- in thread 0.
 template <class Epi, int K>
 __global__ __launch_bounds__(kBlock) void reduce_finish_kernel(const double *__restrict__ partials, int nblocks, int k,
                                                                OutPtrs<K> out, const int *done, IpcDev w, int use_ipc, Epi epi) {

@@ -201,7 +201,7 @@ __device__ __forceinline__ u64x2 rec_word(RecRaw<IDX> v, const unsigned long lon
 
 // One row pair of a lattice apply, y = beta c + alpha (sum_k w_k (xg_k - c) + ext c) over the slots in the common order
 // (-b, -a, -1, +1, +a, +b): spmv_canon_kernel's operands and rounding (beta c rounded on its own, then the two FMAs its
-// expression contracts to).  The marching step kernel and the residual recompute (solvers.hip)
+// expression contracts to).  The marching step kernel and the residual recompute (solver_cg.hip)
 // both call it: their z cannot drift apart.
 __device__ __forceinline__ double2v lattice_pair_apply(const double *dict_sh, u64x2 w, const double2v (&xg)[6], double2v c,
                                                        double alpha, double beta) {

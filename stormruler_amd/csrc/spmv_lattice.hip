@@ -388,7 +388,7 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
       double2v xg[6];
       march_neighbours(buf, at, a, lane, down ? pn[g] : pm[g], down ? pm[g] : pn[g], pc[g], xg);  // (below / above, whichever way the block marches)
       double2v yi = lattice_pair_apply(dict_sh, rec_word<IDX>(wc[g], words_sh), xg, pc[g], alpha, beta);
-      if (z_out != nullptr) {  // (null: the residual recompute forms z again, solvers.hip cg_r_recompute_kernel)
+      if (z_out != nullptr) {  // (null: the residual recompute forms z again, solver_cg.hip cg_r_recompute_kernel)
         double2v *yp = reinterpret_cast<double2v *>(reinterpret_cast<char *>(z_out) + (size_t)(rcc[g] << 3));
         if (vbc[g]) *yp = yi;
         else if (vac[g]) z_out[rcc[g]] = yi.x;

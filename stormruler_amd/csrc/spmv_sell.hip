@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void spmv_sell_kernel(SellArgs A, Scal alph
     // One partial per WAVE (64-lane DPP tree, lane 63 stores): no LDS, no block barrier.
     // (A per-block partial with __syncthreads cost 6 % of the kernel: every wave of a block had
     // to outlive its slowest sibling.)  The 4x longer partial arrays are folded by the two-pass
-    // final reduction in solvers.hip.
+    // final reduction in solver_fused.hip.
     double a = dot.w ? wi * yi : 0.0, b = dot.yy ? yi * yi : 0.0;
     a = wave_sum_to_lane63(a);
     if (dot.yy) b = wave_sum_to_lane63(b);

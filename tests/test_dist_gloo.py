@@ -5,7 +5,7 @@ generator, halo plans), stormruler_amd.dist (rendezvous on 127.0.0.1, id broadca
 barrier) and the exchange protocol itself (who sends which rows to whom, in which order, into which
 halo segment; reductions summed over ranks).  The local compute is done by the CPU oracle -- the
 HIP kernels need a GPU -- and the distributed CG below follows SolverCg.hpp:54-126 statement by
-statement with the same places for the halo exchange and the all-reduces as csrc/solvers.hip.
+statement with the same places for the halo exchange and the all-reduces as csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip.
 """
 import json
 import os

@@ -1,5 +1,5 @@
 """Which record format and which solver path each BASELINE.json config gets -- asserted from `storm_hip_op_stats` and the
-context's path counters, so that a refactor of the dispatch (csrc/spmv.hip's format ladder, csrc/solvers.hip's choice of
+context's path counters, so that a refactor of the dispatch (csrc/spmv.hip's format ladder, csrc/solver_cg.hip's and solver_bicgstab.hip's choice of
 resident / latency / fused / kernel-per-statement loops) cannot silently move a config off the kernels its numbers in
 bench.py and profiles/ were measured on."""
 import numpy as np

@@ -9,7 +9,8 @@ correct path, so:
     the engine's CGS, TFQMR(1), Richardson, BiCGStab(l), IDR(s) and Jacobi-preconditioned solves: history[0..K]
                             against the exact coefficient-form reference (exact_ref.Pins)
 Each case asserts the path it is meant to reach from the context's path counters and the operator's stats; the
-comment names the <p,z> branch of the fused CG loop (solvers.hip, storm_hip_solve_cg) it takes."""
+comment names the <p,z> branch of the fused CG loop (solver_cg.hip, storm_hip_solve_cg; the branches themselves:
+Driver::finish_dots, solver_fused.hip) it takes."""
 import math
 
 import numpy as np
@@ -273,7 +274,7 @@ def test_gmres_first_step(env, fmt, m, chain):
     ctx.set_option("test_disable", test_disable)
     chain_before = ctx.counter("mgs_chain_steps")
     s, _, path = _solve(api, ctx, api.GmresSolver, mat, b_h, num_inner_iterations=m)
-    # the fused GMRES loop (solvers.hip) counts no solve path; its chain steps tell the two Gram-Schmidt forms apart
+    # the fused GMRES loop (solver_gmres.hip) counts no solve path; its chain steps tell the two Gram-Schmidt forms apart
     assert path == {k: 0 for k in PATHS}, path
     assert ctx.counter("mgs_chain_steps") - chain_before == coop_mgs
     assert s.history[0] == fs.h0

@@ -5,7 +5,7 @@
     configs[2]  BiCGStab,  the same 256^3 block per GPU     355 iterations (reference summation order)
     configs[3]  GMRES(30), convection-diffusion 128^3       376 iterations
 
-Every case runs twice on the device: through the fused loops of csrc/solvers.hip (what a stencil operator gets)
+Every case runs twice on the device: through the fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip (what a stencil operator gets)
 and through the general engine of csrc/krylov.hip (`generic_solvers = 1`: what a callback operator gets).
 
 CG and GMRES reproduce the fixtures: same iteration count and operator applications, every entry of the residual

@@ -1,6 +1,6 @@
 """The latency path (csrc/latency.hip): CG and BiCGStab for small operators as one cooperative persistent kernel --
 vectors in registers, two (CG) / three (BiCGStab) all-reduce synchronisation points per iteration.  It must be
-indistinguishable from the throughput path (csrc/solvers.hip) except for rounding-level differences of the dot products: same convergence rule and
+indistinguishable from the throughput path (csrc/solver_cg.hip, solver_bicgstab.hip) except for rounding-level differences of the dot products: same convergence rule and
 counters (Solver.hpp:116-147), same iteration counts (+-1), same solutions, against the oracle too; for every
 register variant (1 / 2 / 4 / 8 slices per wavefront, records cached in registers or re-read), ragged last slices,
 rows longer than the register cache, early exits and zero iterations."""

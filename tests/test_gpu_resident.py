@@ -1,7 +1,7 @@
 """The resident path (csrc/resident.hip): CG and BiCGStab of a lattice operator as ONE persistent kernel per solve in
 which every block owns a box of the lattice -- r (BiCGStab: r, p, v) in registers, the vector the operator is applied
 to in LDS, only the boxes' surfaces exchanged (self-validating granules), two / three all-reduces per iteration.  It
-must be indistinguishable from the throughput path (csrc/solvers.hip) but for rounding-level differences of the dot
+must be indistinguishable from the throughput path (csrc/solver_cg.hip, solver_bicgstab.hip) but for rounding-level differences of the dot
 products: same convergence rule and counters (Solver.hpp:116-147), same iteration counts, histories, solutions -- for
 every depth of the boxes, ragged runs (shorter than a line, shorter than the halo), ragged last chunks of planes,
 long lines, warm starts, early exits; against the oracle too."""

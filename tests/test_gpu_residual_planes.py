@@ -1,4 +1,4 @@
-"""The plane march of the residual recompute (option `cg_residual_planes`, solvers.hip cg_r_planes_kernel): blocks that
+"""The plane march of the residual recompute (option `cg_residual_planes`, solver_cg.hip cg_r_planes_kernel): blocks that
 own a 2 048-row run of a plane and march over planes form, plane by plane, the accumulators, the block sums and the
 partial slots of cg_r_kernel's blocks and hand them to the same ticket fold.  r, <r,r> and with them every scalar of
 the solve and x are therefore the SAME BITS as with the gathering form (`cg_residual_planes` 0) and as with z stored

@@ -3,7 +3,7 @@
 * blas1_nt (csrc/blas1_device.hpp: nt_dispatch): non-temporal or plain loads and stores of the BLAS-1 / solver kernels --
   the same values, the same order of every sum: solver histories and BLAS-1 results are BITWISE equal in both modes;
   the default mode switches at 6 * 2^20 rows per vector.
-* mgs_steps (csrc/solvers.hip: mgs_pair_kernel / mgs_multi_kernel): two, three or four modified-Gram-Schmidt steps per
+* mgs_steps (csrc/solver_gmres.hip: mgs_pair_kernel / mgs_multi_kernel): two, three or four modified-Gram-Schmidt steps per
   pass over w (SolverGmres.hpp:157-161) -- the coefficients follow from bilinearity, so the histories agree to rounding,
   not bitwise.
 """

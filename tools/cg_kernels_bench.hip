@@ -1,4 +1,4 @@
-// Micro-benchmark of the two BLAS-1 kernels of a fused CG iteration (csrc/solvers.hip: cg_r_kernel, cg_xp_kernel)
+// Micro-benchmark of the two BLAS-1 kernels of a fused CG iteration (csrc/solver_cg.hip: cg_r_kernel, cg_xp_kernel)
 // in several shapes, at 256^3 doubles per vector, rotating over three buffer sets (the 256 MiB Infinity Cache must
 // not decide).  Build and run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 tools/cg_kernels_bench.hip -o /tmp/cgk && /tmp/cgk

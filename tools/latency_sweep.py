@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """CG and BiCGStab microseconds per iteration over problem sizes: the resident path (csrc/resident.hip: lattice operators, a
 box of the lattice per block), the latency path (csrc/latency.hip: any small operator, a kernel per solve) and the
-throughput path (csrc/solvers.hip: a kernel per statement) -- which one pays where?  One JSON line per size and solver;
+throughput path (csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip: a kernel per statement) -- which one pays where?  One JSON line per size and solver;
 `default_path_us_per_iteration` is what a caller gets with no option set."""
 import json
 import os

@@ -18,7 +18,7 @@ using storm::double2v;
 
 
 
-// ---- the library's own kernels (text copied from csrc/solvers.hip and csrc/blas1.hip when this tool was last edited: keep
+// ---- the library's own kernels (text copied from csrc/solver_gmres.hip and csrc/blas1.hip when this tool was last edited: keep
 // in step) ----------------------------------------------------------------------------------------------------------
 #include "ticket_device.hpp"
 #include "solver_device.hpp"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Iteration rates of the solver PATHS of this library on one MI355X (one JSON line per case, for profiles/):
 
-    fused          stencil operator, the fused kernels of csrc/solvers.hip (CG / BiCGStab / GMRES only)
+    fused          stencil operator, the fused kernels of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip (CG / BiCGStab / GMRES only)
     engine         stencil operator through the general engine of csrc/krylov.hip (`generic_solvers = 1`)
     engine-lambda  the operator handed over as a lambda through make_operator -- what the reference's only call
                    site does (Playground.cpp:151-167) -- device-resident loop, the callback only enqueues
