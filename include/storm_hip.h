@@ -336,6 +336,9 @@ int storm_hip_op_create_csr(storm_hip_ctx *ctx, int64_t n_rows, int64_t n_halo,
  *              own a 2 048-row run of a plane and march through cg_residual_chunk planes where every plane is whole such
  *              runs (fewer planes on small lattices: about cg_residual_fill blocks; 0: as given), else -- and with
  *              cg_residual_planes 0 -- by gathers in the streaming kernel's grid;
+ *   cg_pz_fold (1): the plane march also folds the step kernel's per-wave partials of <p,z> itself, under its first loads,
+ *              where one pass folds them (at most 8 192): two launches an iteration instead of three (0: a one-block launch
+ *              folds them in between).  The same bits;
  *   fused_reduce (1), lin_fuse (1), ticket_reduce (1): engine reductions finished by the partials kernel's last block; two
  *              consecutive vector statements as one pass; fused-loop reductions finished inside the producing kernels;
  *   nontemporal (1), blas1_nt (1): non-temporal record / y traffic of the SpMV; of the BLAS-1 and solver kernels (0 never,

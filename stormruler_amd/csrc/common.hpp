@@ -232,6 +232,7 @@ struct storm_hip_ctx {
   int64_t opt_cg_residual_planes = 1;  // ... by blocks that own a 2 048-row run of a plane and march over planes (solver_cg.hip cg_r_planes_kernel: cg_r_kernel's partials, plane by plane; lattices of whole 2 048-row runs per plane) instead of gathering the +-a / +-b neighbours (0: cg_r_recompute_kernel everywhere)
   int64_t opt_cg_residual_chunk = 16;  // ... planes per block (2 .. 32); the two planes bounding a chunk are read again: + 2 / chunk of 8 B/row
   int64_t opt_cg_residual_fill = 512;  // ... fewer planes per block on smaller lattices, so that the grid holds about this many blocks (0: cg_residual_chunk as given)
+  int64_t opt_cg_pz_fold = 1;  // ... and that kernel folds the step kernel's per-wave partials of <p,z> itself, under its first loads, where one pass folds them (at most kSinglePassPartials): no one-block launch between the two (0: the launch; the same bits)
   int64_t opt_cg_fuse = 1;   // fused CG, one rank, tiled format-4 operator: the SpMV kernel ends the previous iteration (x += alpha p, p = r + beta p) itself
   // Vector storage released by vec_destroy, kept for the next vec_create of the same size: a solve
   // allocates its work vectors on entry and frees them on return (the reference re-assigns them in
@@ -260,6 +261,7 @@ struct storm_hip_ctx {
   int64_t n_block_solves = 0;  // storm_hip_solve_cg_block (block.hip)
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
+  int64_t n_cg_pz_consumer_folds = 0;  // ... of those, the solves whose plane march folded <p,z> itself (option cg_pz_fold)
   int64_t n_mgs_chain_steps = 0, n_mgs_quad_steps = 0;  // Gram-Schmidt steps run as a chain kernel (latency.hip); ... as mgs_chain_quad_kernel
   // communicator
   storm::Comm *comm = nullptr;

@@ -234,6 +234,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *c, const char *key, int64_t value) {
   else if (!strcmp(key, "cg_residual_planes")) c->opt_cg_residual_planes = value;
   else if (!strcmp(key, "cg_residual_chunk")) c->opt_cg_residual_chunk = value;
   else if (!strcmp(key, "cg_residual_fill")) c->opt_cg_residual_fill = value;
+  else if (!strcmp(key, "cg_pz_fold")) c->opt_cg_pz_fold = value;
   else if (!strcmp(key, "spmv_record_index")) c->opt_spmv_record_index = value;
   else if (!strcmp(key, "blas1_nt")) c->opt_blas1_nt = value;
   else STORM_FAIL(STORM_HIP_E_INVALID, "ctx_set_option: unknown key '%s'", key);
@@ -250,6 +251,7 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "cg_fused_steps")) *value = c->n_cg_fused_steps;
   else if (!strcmp(key, "cg_residual_marches")) *value = c->n_cg_residual_marches;
   else if (!strcmp(key, "cg_residual_plane_marches")) *value = c->n_cg_residual_plane_marches;
+  else if (!strcmp(key, "cg_pz_consumer_folds")) *value = c->n_cg_pz_consumer_folds;
   else if (!strcmp(key, "mgs_chain_steps")) *value = c->n_mgs_chain_steps;
   else if (!strcmp(key, "mgs_quad_steps")) *value = c->n_mgs_quad_steps;
   else if (!strcmp(key, "lazy_fused_dots")) *value = c->n_lazy_fused_dots;

@@ -9,17 +9,28 @@ namespace storm {
 // The reduction code of cg_r_kernel and cg_r_recompute_kernel: a residual kernel must form alpha and sum <r,r> exactly
 // as the other does.  Prologue: alpha = safe_divide(gamma, <p,z>), with <p,z> folded from pz_partials by every block
 // (the same n_pz values in the same order, hence the same alpha) or read from the slab; block 0 stores both.
-__device__ __forceinline__ double cg_r_alpha(SolverState *st, const double *__restrict__ pz_partials, int n_pz, double *lds4) {
+// (Fold: block_fold of the partials, or -- cg_r_planes_kernel, whose fold's loads are in flight since block_fold_issue --
+//  block_fold_sum of them: the same sum.  Gamma: the slab's <r,r>, read here or, by that kernel, with its first loads:
+//  nothing writes it before the grid's last block has drawn its ticket)
+template <class Fold, class Gamma>
+__device__ __forceinline__ double cg_r_alpha_of(SolverState *st, bool folds, Fold fold, Gamma gamma) {
   double pz;
-  if (pz_partials) {
-    pz = block_fold(pz_partials, n_pz, lds4);
+  if (folds) {
+    pz = fold();
     if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_PZ] = pz;
   } else {
     pz = st->s[S_PZ];
   }
-  const double alpha = safe_divide(st->s[S_GAMMA], pz);
+  const double alpha = safe_divide(gamma(), pz);
   if (blockIdx.x == 0 && threadIdx.x == 0) st->s[S_ALPHA] = alpha;  // for cg_xp_kernel / the next step kernel
   return alpha;
+}
+__device__ __forceinline__ double cg_r_alpha(SolverState *st, const double *__restrict__ pz_partials, int n_pz, double *lds4) {
+  return cg_r_alpha_of(st, pz_partials != nullptr, [&] { return block_fold(pz_partials, n_pz, lds4); }, [&] { return st->s[S_GAMMA]; });
+}
+__device__ __forceinline__ double cg_r_alpha(SolverState *st, bool folds, const FoldWhole &pz_flight, int n_pz, double gamma,
+                                             double *lds4) {
+  return cg_r_alpha_of(st, folds, [&] { return block_fold_sum(pz_flight, n_pz, lds4); }, [&] { return gamma; });
 }
 // Epilogue: block bx's partial of <r,r> into partials[bx] (no tickets), or <r,r> finished here (ticket_device.hpp) and
 // the scalar step of SolverCg.hpp:110-125 with the convergence rule in the last block: no final-pass launch.
@@ -238,6 +249,7 @@ __global__ __launch_bounds__(kBlock) void cg_r_planes_kernel(SolverState *st, do
                                                              const double *__restrict__ pz_partials, int n_pz, int reverse,
                                                              TicketArgs tickets) {
   const int done = st->done;  // (tested behind the first loads: in a grid of one round every block pays the start's round trips)
+  const double gamma = st->s[S_GAMMA];  // (with it: a load behind the fold would be one more round trip in front of the march)
   __shared__ double lds4[4];
   __shared__ double dict_sh[32];
   __shared__ double wave_part[kResidualMaxChunk * (kBlock / kWave)];
@@ -310,10 +322,15 @@ __global__ __launch_bounds__(kBlock) void cg_r_planes_kernel(SolverState *st, do
   issue_p(plane(0), true, cur);
   issue_rw(plane(0), vr, w);
   issue_p(plane(1), 1 < nz, nxt);
+  // (<p,z> folded here, option cg_pz_fold: the n_pz <= kSinglePassPartials per-wave partials of the step kernel, requested
+  //  behind the planes so that they arrive under them -- no launch of one block that folds them while HBM idles)
+  const bool folds = pz_partials != nullptr;  // (block-uniform)
+  FoldWhole pz_flight;
+  if (folds) block_fold_issue(pz_partials, n_pz, pz_flight);
   if (threadIdx.x < 32) dict_sh[threadIdx.x] = A.dict[threadIdx.x];
   if (IDX) rec_table_fill(A, words_sh);
   if (done) return;
-  const double alpha = cg_r_alpha(st, pz_partials, n_pz, lds4);
+  const double alpha = cg_r_alpha(st, folds, pz_flight, n_pz, gamma, lds4);
   const double op_alpha = ld_scal2(alpha_s), op_beta = ld_scal2(beta_s);
   // (the first barrier of the march covers dict_sh and the word table)
   for (int s = 0; s < nz; ++s) {
@@ -385,12 +402,16 @@ static bool cg_r_planes_geometry(const storm_hip_op *op, ResidualPlanesArgs *G, 
   *n_blocks = ((G->planes + G->nz - 1) / G->nz) * G->runs_per_plane;
   return true;
 }
+// (rr_partials: where the kernel's <r,r> slots go -- the workspace's start, or behind pz_partials where the kernel folds the
+//  step kernel's partials itself: a block that starts late must still find them)
 static int cg_r_planes_run(const storm_hip_op *op, const ResidualPlanesArgs &G, int n_blocks, Scal alpha, Scal beta, const double *p,
-                           SolverState *st, double *r, const double *pz_partials, int n_pz, int reverse) {
+                           SolverState *st, double *r, const double *pz_partials, int n_pz, int reverse, double *rr_partials) {
   storm_hip_ctx *c = op->ctx;
+  STORM_REQUIRE(pz_partials == nullptr || n_pz <= kSinglePassPartials, "cg: the plane march folds at most %d partials of <p,z>, not %d",
+                kSinglePassPartials, n_pz);
   const SellArgs A = lattice_args(op);
   const size_t lds = sizeof(double) * 2 * (size_t)(kStreamBlockElems + 2 * G.a) + sizeof(uint64_t) * (size_t)A.rec_words_n;
-  const TicketArgs tk{c->d_tickets, c->d_partials, c->d_ticket_sums};
+  const TicketArgs tk{c->d_tickets, rr_partials, c->d_ticket_sums};
 #define PLANES_GO(HLP_, IX_)                                                                                                   \
   hipLaunchKernelGGL((cg_r_planes_kernel<HLP_, IX_>), dim3(n_blocks), dim3(kBlock), lds, c->stream, st, r, p, A, G, alpha, beta, \
                      pz_partials, n_pz, reverse, tk)
@@ -469,7 +490,8 @@ struct CgRoads {
   // The fused step (one rank, tiled format-4 operator): iteration k's SpMV kernel first ENDS iteration k - 1 --
   // x += alpha p, p' = r + beta p -- on the rows it loads anyway and applies the operator to p': x and p are no longer
   // streamed by a kernel of their own (cg_xp).  p ping-pongs between two vectors (a tile's old p is another tile's
-  // halo).  Two launches + the small first pass per iteration; the last iteration's x update runs behind the loop.
+  // halo).  Two launches + the small first pass per iteration (two where the plane march folds <p,z> itself, option
+  // cg_pz_fold); the last iteration's x update runs behind the loop.
   // (on the peer-window transport too: the marching launch also sends p' of the boundary rows, spmv.hip)
   // (on RCCL too, round 4: there the reductions keep their all-reduce between partials and step -- no tickets --, the
   //  step kernel reads alpha, beta and the iteration counter from the slab exactly as cg_xp_kernel does)
@@ -549,6 +571,7 @@ static int solve_cg_body(const FusedSolveArgs &args) {
   // Blocks keep their rows and their partial slots: the same bits either way.  (Per rank: with a communicator too.)
   const int nt_stream = stream_nt(c, n);
   int64_t last_enqueued = -1;
+  bool pz_fold_counted = false;
   auto enqueue_iteration = [&]() -> int {
     const int q = road.fuse_step ? 0 : (int)(cur_it & 1);  // (fused: the step kernel forward, cg_r backward, always)
     // z = A p, <p,z>                                  SolverCg.hpp:96-97
@@ -558,8 +581,8 @@ static int solve_cg_body(const FusedSolveArgs &args) {
     const bool r_march_now = road.r_march && cur_it > 0;
     if (road.fuse_step && cur_it > 0) {
       const CgStep step{(long long)cur_it, x, r, p_alt};  // ends iteration cur_it - 1 (SolverCg.hpp:98, :123)
-      // (<p,z>: per-wave partials for the final pass below -- finishing it inside the marching kernel by tickets was
-      //  measured for this loop and dropped; the host loop's fused step, lazy.hip, does finish it there: one launch less
+      // (<p,z>: per-wave partials for the plane march's fold or the final pass below -- finishing it inside the marching
+      //  kernel by tickets was measured for this loop and dropped; the host loop's fused step, lazy.hip, does finish it there: one launch less
       //  in front of a host wait)
       st_apply = d.apply(p, r_march_now ? nullptr : z, &nb, {.w = p, .ticketed = &pz_done}, true, &step);
       std::swap(p, p_alt);
@@ -575,11 +598,20 @@ static int solve_cg_body(const FusedSolveArgs &args) {
                                           : !tickets_now ? Driver::ROAD_PLAIN : road.ipc ? Driver::ROAD_TICKETS_IPC : Driver::ROAD_TICKETS;
     Driver::Road ran;
     const double *pz_partials = nullptr, *const pz_with[1] = {z};
-    STORM_TRY(d.finish_dots(pz_done, nb, 1, S_PZ, p, pz_with, allow, STEP_NONE, &ran, &pz_partials));
+    // (option cg_pz_fold: the plane march folds the step kernel's nb partials itself, under its first loads -- no launch in
+    //  between; its own <r,r> slots then go behind them.  One rank without tickets for <p,z>: r_march implies the first)
+    const int64_t rr_slots = road.r_planes ? (int64_t)road.planes_args.planes * road.planes_args.runs_per_plane : 0;
+    const bool pz_fold_now = c->opt_cg_pz_fold != 0 && r_march_now && road.r_planes && c->comm == nullptr && !tickets_now &&
+                             !pz_done && nb > 0 && nb <= kSinglePassPartials && nb + rr_slots <= c->partials_capacity;
+    if (pz_fold_now && !pz_fold_counted) ++c->n_cg_pz_consumer_folds, pz_fold_counted = true;
+    if (!pz_fold_now) STORM_TRY(d.finish_dots(pz_done, nb, 1, S_PZ, p, pz_with, allow, STEP_NONE, &ran, &pz_partials));
     // r -= alpha z; gamma = <r,r>                     SolverCg.hpp:97,99,115
-    if (r_march_now && road.r_planes) {
+    if (pz_fold_now) {
+      STORM_TRY(cg_r_planes_run(op, road.planes_args, road.planes_blocks, host_scal(d.alpha), host_scal(d.beta), p, d.st, r, c->d_partials,
+                                nb, 1 - q, c->d_partials + nb));
+    } else if (r_march_now && road.r_planes) {
       STORM_TRY(cg_r_planes_run(op, road.planes_args, road.planes_blocks, host_scal(d.alpha), host_scal(d.beta), p, d.st, r, pz_partials,
-                                (int)kStage2, 1 - q));
+                                (int)kStage2, 1 - q, c->d_partials));
     } else if (r_march_now) {
       STORM_TRY(cg_r_recompute_run(op, nbv, host_scal(d.alpha), host_scal(d.beta), p, d.st, r, pz_partials, (int)kStage2, 1 - q));
     } else {

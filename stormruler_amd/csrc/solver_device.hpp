@@ -92,14 +92,51 @@ __device__ __forceinline__ double block_sum256(double v, double *lds4) {
 // The block's sum of p[i0 .. i1): lane t adds p[i0 + t], p[i0 + t + 256], ... in ascending order into ONE accumulator,
 // then block_sum256.  Every final pass and every in-kernel fold of partials sums through here: the variants of a solver
 // are compared to the bit, and this order is what they share.
+// The order is written once, in fold_add: B values of a thread -- p[i], p[i + 256], ... below i1 -- are loaded by
+// fold_issue, all before the first is used, and added by fold_add in ascending order.
+template <int B>
+struct FoldFlight {
+  double v[B];
+};
+template <int B>
+__device__ __forceinline__ void fold_issue(const double *__restrict__ p, int i, int i1, FoldFlight<B> &f) {
+#pragma unroll
+  for (int j = 0; j < B; ++j) {
+    f.v[j] = 0.0;
+    if (i + kBlock * j < i1) f.v[j] = p[i + kBlock * j];
+  }
+}
+template <int B>
+__device__ __forceinline__ void fold_add(const FoldFlight<B> &f, int i, int i1, double &v) {
+#pragma unroll
+  for (int j = 0; j < B; ++j)
+    if (i + kBlock * j < i1) v += f.v[j];
+}
 __device__ __forceinline__ double block_fold(const double *__restrict__ p, int i0, int i1, double *lds4) {
   double v = 0.0;
-#pragma unroll 8
-  for (int i = i0 + threadIdx.x; i < i1; i += kBlock) v += p[i];
+  for (int i = i0 + threadIdx.x; i < i1; i += kBlock * 8) {
+    FoldFlight<8> f;
+    fold_issue(p, i, i1, f);
+    fold_add(f, i, i1, v);
+  }
   return block_sum256(v, lds4);
 }
 __device__ __forceinline__ double block_fold(const double *__restrict__ p, int n, double *lds4) {
   return block_fold(p, 0, n, lds4);
+}
+// block_fold(p, n, lds4) of at most kSinglePassPartials values in two halves, for a kernel that has loads of its own to
+// put the fold's behind (solver_cg.hip cg_r_planes_kernel): block_fold_issue requests ALL of the thread's values (32 at
+// most), block_fold_sum adds them -- fold_add's order, one accumulator from 0.0 -- and ends with block_sum256.
+constexpr int kFoldWhole = kSinglePassPartials / kBlock;
+static_assert(kFoldWhole * kBlock == kSinglePassPartials, "a whole fold holds kSinglePassPartials / kBlock values per thread");
+using FoldWhole = FoldFlight<kFoldWhole>;
+__device__ __forceinline__ void block_fold_issue(const double *__restrict__ p, int n, FoldWhole &f) {
+  fold_issue(p, (int)threadIdx.x, n, f);
+}
+__device__ __forceinline__ double block_fold_sum(const FoldWhole &f, int n, double *lds4) {
+  double v = 0.0;
+  fold_add(f, (int)threadIdx.x, n, v);
+  return block_sum256(v, lds4);
 }
 
 // Where the k sums of a final pass go; K: the most it takes (a kernel argument -- the solvers' final pass runs every
