@@ -37,6 +37,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 
 #define STORM_HIP_ABI_VERSION 6
+/* Feature-test macro, here to stay: defined (to 1) by every header that declares the two-stage operator
+ * (storm_hip_op_apply2, storm_hip_solve_cg2, storm_hip_krylov_set_operator2; HipTwoStageOperator in storm_hip/Storm.hpp),
+ * which was added within ABI 6.  A caller that must also build against an older header tests it with #ifdef. */
+#define STORM_HIP_HAS_TWO_STAGE 1
 
 enum {
   STORM_HIP_OK = 0,
@@ -517,6 +521,18 @@ int storm_hip_op_get_diagonal(const storm_hip_op *op, double alpha, double beta,
  * (:153-167).  Exchanges x's halo first when a halo plan is set.  x and y must not alias. */
 int storm_hip_op_apply_add(const storm_hip_op *op, double alpha, const storm_hip_vec *x, storm_hip_vec *y);
 
+/* The playground's operator lambda (Playground.cpp:153-167) -- two stormDivGrad calls per apply -- as ONE operator: its
+ * linear part is the two-stage operator
+ *     A x = beta2 x + alpha2 M (beta1 x + alpha1 M x),      beta1 = sigma, alpha1 = -Gamma, beta2 = 1, alpha2 = -tau.
+ * Computes t = beta1 x + alpha1 M x (the lambda's w_hat minus its constant part) and y = beta2 x + alpha2 M t.  t may be
+ * NULL (a pooled work vector is used).  y and t are, bit for bit and in every record format, what
+ *     storm_hip_op_apply(op, alpha1, beta1, x, t);  storm_hip_copy(y, x);  storm_hip_scale(y, beta2);
+ *     storm_hip_op_apply_add(op, alpha2, t, y)
+ * give.  x, t and y must be pairwise distinct (STORM_HIP_E_INVALID, as sizes that differ from the operator's).  An
+ * operator with a halo plan or a context with a communicator returns STORM_HIP_E_UNSUPPORTED. */
+int storm_hip_op_apply2(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2,
+                        const storm_hip_vec *x, storm_hip_vec *t, storm_hip_vec *y);
+
 typedef struct storm_hip_op_stats {
   int64_t n_rows, n_cols, nnz_offdiag;  /* off-diagonal entries (2F for a face graph) */
   int64_t ell_slots;                    /* stored ELL slots incl. padding */
@@ -578,6 +594,17 @@ int storm_hip_solve_gmres(const storm_hip_op *op, double alpha, double beta, con
                           storm_hip_vec *x, const storm_hip_solver_params *params,
                           storm_hip_solver_result *result, double *history);    /* SolverGmres.hpp:41-255 */
 
+/* `solve<CgSolver>(c_hat, c, lambda)`  Playground.cpp:151-167 for the linear part of the lambda, the two-stage operator
+ * A = beta2 I + alpha2 M (beta1 I + alpha1 M) of storm_hip_op_apply2: SolverCg.hpp:54-126 under the rule of
+ * Solver.hpp:116-147.  num_applies = iterations + 1 (one apply is both stages).  A small halo-free operator runs as ONE
+ * cooperative kernel per solve (csrc/latency.hip, three synchronisation points per iteration; counted by
+ * "latency_solves"), under the rules of storm_hip_solve_cg's one-kernel path (options latency_path, latency_rows;
+ * path_fallback); everything else runs the engine's CG loop with the two stages as library launches ("engine_solves").
+ * Halo plan / communicator: STORM_HIP_E_UNSUPPORTED. */
+int storm_hip_solve_cg2(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2,
+                        const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_solver_params *params,
+                        storm_hip_solver_result *result, double *history);
+
 /* k independent CG solves A x_j = b_j on the columns of a block (see "block vectors"): SolverCg.hpp:54-126 per column,
  * the convergence rule of Solver.hpp:116-147 per column, the operator's records streamed once per iteration for all
  * columns (storm_hip_op_apply_block; the same operators are refused).  Every column has its own gamma, alpha, beta,
@@ -630,6 +657,12 @@ int storm_hip_krylov_destroy(storm_hip_krylov *k);
  * kernels of storm_hip_solve_*), or a callback. */
 int storm_hip_krylov_set_operator(storm_hip_krylov *k, const storm_hip_op *op, double alpha, double beta);
 int storm_hip_krylov_set_operator_fn(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user);
+/* The two-stage operator A = beta2 I + alpha2 M (beta1 I + alpha1 M) of storm_hip_op_apply2 (the playground's lambda,
+ * Playground.cpp:153-167, without a callback): an apply is both stages as library launches, so every method and every
+ * preconditioner side works on it; CG without preconditioner runs storm_hip_solve_cg2.  Halo plan / communicator:
+ * STORM_HIP_E_UNSUPPORTED. */
+int storm_hip_krylov_set_operator2(storm_hip_krylov *k, const storm_hip_op *op, double alpha1, double beta1, double alpha2,
+                                   double beta2);
 /* pre_op / pre_side.  fn == NULL removes it.  The diagonal form is y = d .* x (e.g. d from
  * storm_hip_op_get_diagonal(..., invert = 1): Jacobi); the vector must outlive the solves. */
 int storm_hip_krylov_set_preconditioner_fn(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user, int side);

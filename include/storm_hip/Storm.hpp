@@ -692,6 +692,32 @@ private:
   real_t _alpha, _beta;
 };
 
+/// A = beta2 I + alpha2 M (beta1 I + alpha1 M) over one StencilMatrix as an Operator<DeviceVector>: the linear part of
+/// the playground's Cahn-Hilliard lambda (Playground.cpp:153-167, two stormDivGrad calls per apply; beta1 = sigma,
+/// alpha1 = -Gamma, beta2 = 1, alpha2 = -tau).  The solvers bind it natively -- no callback; CG on a small mesh is one
+/// cooperative kernel per solve (storm_hip_solve_cg2).  `intermediate` (optional; the caller keeps it alive) receives
+/// t = beta1 x + alpha1 M x of every `mul`: the lambda's w_hat minus its constant part.
+class HipTwoStageOperator final : public Operator<DeviceVector> {
+public:
+  HipTwoStageOperator(const StencilMatrix& matrix, real_t alpha1, real_t beta1, real_t alpha2, real_t beta2,
+                      DeviceVector* intermediate = nullptr)
+      : _matrix{&matrix}, _alpha1{alpha1}, _beta1{beta1}, _alpha2{alpha2}, _beta2{beta2}, _intermediate{intermediate} {}
+  void mul(DeviceVector& y_vec, const DeviceVector& x_vec) const override {
+    detail::check(storm_hip_op_apply2(_matrix->handle(), _alpha1, _beta1, _alpha2, _beta2, x_vec.handle(),
+                                      _intermediate != nullptr ? _intermediate->handle() : nullptr, y_vec.handle()));
+  }
+  const StencilMatrix& matrix() const noexcept { return *_matrix; }
+  real_t alpha1() const noexcept { return _alpha1; }
+  real_t beta1() const noexcept { return _beta1; }
+  real_t alpha2() const noexcept { return _alpha2; }
+  real_t beta2() const noexcept { return _beta2; }
+
+private:
+  const StencilMatrix* _matrix;
+  real_t _alpha1, _beta1, _alpha2, _beta2;
+  DeviceVector* _intermediate;
+};
+
 /// What one column of a block solve reports: the fields of IterativeSolver (Solver.hpp:66-72) after `solve`.
 struct BlockColumnResult {
   std::size_t iteration = 0;
@@ -753,6 +779,8 @@ class JacobiPreconditioner final : public Preconditioner<DeviceVector> {
 public:
   void build(const DeviceVector& x_vec, const DeviceVector& /*b_vec*/,
              const Operator<DeviceVector>& any_op) override {
+    if (dynamic_cast<const HipTwoStageOperator*>(&any_op) != nullptr)
+      throw std::runtime_error("JacobiPreconditioner cannot read the diagonal of a HipTwoStageOperator");
     const auto* hip_op = dynamic_cast<const HipStencilOperator*>(&any_op);
     if (hip_op == nullptr) throw std::runtime_error("JacobiPreconditioner needs a HipStencilOperator");
     _dinv.assign(x_vec, false);
@@ -790,7 +818,7 @@ inline void log_solve(std::size_t iteration, real_t absolute_error, real_t relat
 }
 
 /// One `storm_hip_krylov` object -- the library's device-resident solver loops (csrc/krylov.hip) -- with the
-/// caller's Operator / Preconditioner objects bound to it.  A HipStencilOperator binds natively; any other
+/// caller's Operator / Preconditioner objects bound to it.  A HipStencilOperator or HipTwoStageOperator binds natively; any other
 /// operator (a lambda through make_operator, Playground.cpp:151-167) and any preconditioner but the Jacobi
 /// one bind as callbacks, which only enqueue kernels.  An exception thrown inside a callback aborts the solve
 /// and is rethrown from the call that ran it.
@@ -814,6 +842,8 @@ public:
     _op = Bound{&any_op, &_thrown};
     if (const auto* hip_op = dynamic_cast<const HipStencilOperator*>(&any_op))
       check(storm_hip_krylov_set_operator(_h, hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta()));
+    else if (const auto* two = dynamic_cast<const HipTwoStageOperator*>(&any_op))
+      check(storm_hip_krylov_set_operator2(_h, two->matrix().handle(), two->alpha1(), two->beta1(), two->alpha2(), two->beta2()));
     else
       check(storm_hip_krylov_set_operator_fn(_h, &Engine::trampoline, &_op));
     const int c_side = side == PreconditionerSide::Left    ? STORM_HIP_LEFT

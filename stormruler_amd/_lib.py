@@ -147,6 +147,7 @@ SIGNATURES = {
     "storm_hip_op_apply": (C.c_int, [vp, C.c_double, C.c_double, vp, vp]),
     "storm_hip_op_apply_block": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, vp, vp]),
     "storm_hip_op_apply_add": (C.c_int, [vp, C.c_double, vp, vp]),
+    "storm_hip_op_apply2": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]),
     "storm_hip_op_get_diagonal": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, vp]),
     "storm_hip_op_get_stats": (C.c_int, [vp, C.POINTER(OpStats)]),
     "storm_hip_op_destroy": (C.c_int, [vp]),
@@ -157,11 +158,14 @@ SIGNATURES = {
                                            C.POINTER(SolverResult), f64p]),
     "storm_hip_solve_gmres": (C.c_int, [vp, C.c_double, C.c_double, vp, vp, C.POINTER(SolverParams),
                                         C.POINTER(SolverResult), f64p]),
+    "storm_hip_solve_cg2": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, C.POINTER(SolverParams),
+                                      C.POINTER(SolverResult), f64p]),
     "storm_hip_solve_cg_block": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, vp, vp, C.POINTER(SolverParams),
                                            C.POINTER(SolverResult), f64p]),
     "storm_hip_krylov_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
     "storm_hip_krylov_destroy": (C.c_int, [vp]),
     "storm_hip_krylov_set_operator": (C.c_int, [vp, vp, C.c_double, C.c_double]),
+    "storm_hip_krylov_set_operator2": (C.c_int, [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double]),
     "storm_hip_krylov_set_operator_fn": (C.c_int, [vp, APPLY_FN, vp]),
     "storm_hip_krylov_set_preconditioner_fn": (C.c_int, [vp, APPLY_FN, vp, C.c_int]),
     "storm_hip_krylov_set_preconditioner_diag": (C.c_int, [vp, vp, C.c_int]),

@@ -747,6 +747,27 @@ class HipStencilOperator(Operator):
         check(lib.storm_hip_op_apply_block(self.matrix._h, self.alpha, self.beta, k, x_block._h, y_block._h))
 
 
+class HipTwoStageOperator(Operator):
+    """``A = beta2*I + alpha2*M (beta1*I + alpha1*M)`` over one :class:`StencilMatrix` as an ``Operator<DeviceVector>``:
+    the linear part of the playground's Cahn-Hilliard lambda (Playground.cpp:153-167, two ``stormDivGrad`` calls per
+    apply; ``beta1 = sigma, alpha1 = -Gamma, beta2 = 1, alpha2 = -tau``).  The solvers bind it natively (no callback); CG
+    on a small mesh is one cooperative kernel per solve (``storm_hip_solve_cg2``).  ``intermediate``: an optional vector
+    that receives ``t = beta1 x + alpha1 M x`` of every :meth:`mul` (the lambda's ``w_hat`` minus its constant part)."""
+
+    def __init__(self, matrix: StencilMatrix, alpha1: float, beta1: float, alpha2: float, beta2: float,
+                 intermediate: Optional[DeviceVector] = None):
+        self.matrix = matrix
+        self.alpha1, self.beta1, self.alpha2, self.beta2 = float(alpha1), float(beta1), float(alpha2), float(beta2)
+        self.intermediate = intermediate
+
+    def mul(self, y_vec: DeviceVector, x_vec: DeviceVector) -> None:
+        t = None if self.intermediate is None else self.intermediate._h
+        check(lib.storm_hip_op_apply2(self.matrix._h, self.alpha1, self.beta1, self.alpha2, self.beta2, x_vec._h, t, y_vec._h))
+
+    def conj_mul(self, x_vec, y_vec):
+        raise RuntimeError("`Operator::conj_mul` was not overriden")
+
+
 # ---------------------------------------------------------------------------------------------
 # Solvers (Solvers/Solver.hpp)
 
@@ -787,6 +808,9 @@ class JacobiPreconditioner(Preconditioner):
         self._dinv: Optional[DeviceVector] = None
 
     def build(self, x_vec, b_vec, any_op) -> None:
+        if isinstance(any_op, HipTwoStageOperator):
+            raise TypeError("JacobiPreconditioner cannot read the diagonal of a HipTwoStageOperator (the diagonal of "
+                            "beta2 I + alpha2 M (beta1 I + alpha1 M) is not stored); precondition with another operator")
         if not isinstance(any_op, HipStencilOperator):
             raise TypeError("JacobiPreconditioner needs a HipStencilOperator to read the diagonal from")
         self._dinv = _like(x_vec)
@@ -806,7 +830,7 @@ class Solver:  # Solver.hpp:43-57
 
 class _Engine:
     """One ``storm_hip_krylov`` object (the library's device-resident solver loops, csrc/krylov.hip) with the
-    reference-side objects bound to it: a :class:`HipStencilOperator` binds natively, any other ``Operator`` --
+    reference-side objects bound to it: a :class:`HipStencilOperator` or :class:`HipTwoStageOperator` binds natively, any other ``Operator`` --
     e.g. a lambda through ``make_operator``, the reference's only call site (Playground.cpp:151-167) -- as a
     callback that merely enqueues its kernels; likewise ``pre_op`` (a :class:`JacobiPreconditioner` binds as a
     device diagonal).  An exception raised inside a callback aborts the solve and is re-raised from it."""
@@ -846,6 +870,9 @@ class _Engine:
         self._keep, self._error = [], None
         if isinstance(any_op, HipStencilOperator):
             check(lib.storm_hip_krylov_set_operator(self._h, any_op.matrix._h, any_op.alpha, any_op.beta))
+        elif isinstance(any_op, HipTwoStageOperator):
+            check(lib.storm_hip_krylov_set_operator2(self._h, any_op.matrix._h, any_op.alpha1, any_op.beta1, any_op.alpha2,
+                                                     any_op.beta2))
         else:
             check(lib.storm_hip_krylov_set_operator_fn(self._h, self._callback(any_op.mul), None))
         if pre_op is None:

@@ -501,6 +501,13 @@ int cg_latency_solve(const storm_hip_op *op, double alpha, double beta, const do
                      double *r, SolverState *d_state, bool *taken);
 int bicgstab_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x,
                            double *const work[4], SolverState *d_state, bool *taken);
+// CG for A = beta2 I + alpha2 M (beta1 I + alpha1 M); work: p, r, t (zero-filled)
+int cg2_latency_solve(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const double *b,
+                      double *x, double *const work[3], SolverState *d_state, bool *taken);
+// solver_cg.hip: the two-stage CG solve on the one-kernel path, state and result included (*taken = false: it did not run)
+int cg2_latency_try(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const storm_hip_vec *b,
+                    storm_hip_vec *x, const storm_hip_solver_params *params, storm_hip_solver_result *result, double *history,
+                    bool *taken);
 
 // resident.hip
 bool res_eligible(const storm_hip_op *op, bool bicgstab);

@@ -581,6 +581,10 @@ struct KrylovEngine {
   // operator / preconditioner
   const storm_hip_op *op = nullptr;
   double op_alpha = 0.0, op_beta = 0.0;
+  // two_stage: A = op_beta2 I + op_alpha2 M (op_beta I + op_alpha M)   (storm_hip_krylov_set_operator2)
+  bool two_stage = false;
+  double op_alpha2 = 0.0, op_beta2 = 0.0;
+  storm_hip_vec *op_t = nullptr;  // ... the first stage's result: one work vector per solve (begin_solve)
   storm_hip_apply_fn op_fn = nullptr;
   void *op_user = nullptr;
   storm_hip_apply_fn pre_fn = nullptr;
@@ -993,7 +997,7 @@ struct KrylovEngine {
   // y = A(x)  AND  reg_wy = <w, y>, reg_yy = <y, y> (register < 0: not wanted): the stencil SpMV's fused epilogue
   // when the operator is native and has no CSR tail, separate reductions otherwise.
   void apply_dots(V yv, const storm_hip_vec *xv, int reg_wy, const storm_hip_vec *wv, int reg_yy = -1) {
-    const bool fusable = op_fn == nullptr && op != nullptr && op->tail_rows == 0 && n > 0 &&
+    const bool fusable = op_fn == nullptr && op != nullptr && !two_stage && op->tail_rows == 0 && n > 0 &&
                          reg_wy >= 0;
     if (!fusable) {
       apply(yv, xv);
@@ -1043,6 +1047,9 @@ struct KrylovEngine {
         if (st > 0 || storm_hip_last_error()[0] == 0) set_error("krylov: the operator callback returned %d", st);
         st = st < 0 ? st : STORM_HIP_E_INVALID;
       }
+    } else if (two_stage) {  // both stages as library launches, predicated like a callback's
+      ApiDone guard(c, dp);
+      st = storm_hip_op_apply2(op, op_alpha, op_beta, op_alpha2, op_beta2, xv, op_t, yv);
     } else {
       c->spmv_reverse = flip();
       st = spmv_launch(op, host_scal(op_alpha), host_scal(op_beta), xv->d, yv->d, nullptr, dp);
@@ -1663,6 +1670,7 @@ int check_ready(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
 void release_work(K *k) {
   for (auto *w : k->work) storm_hip_vec_destroy(w);
   k->work.clear();
+  k->op_t = nullptr;
   k->qs.clear(), k->zs.clear(), k->rs.clear(), k->us.clear(), k->ps.clear(), k->gs.clear();
   if (k->d_history) (void)hipFree(k->d_history), k->d_history = nullptr;
   k->active = false;
@@ -1696,6 +1704,7 @@ int begin_solve(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
   k->it_enqueued = 0;
   k->active = true;
   k->setup();
+  if (k->two_stage) k->op_t = k->vec();
   if (!k->ok()) return k->status;
   // register file
   if (k->S_top > k->S_cap) {
@@ -1784,13 +1793,29 @@ int storm_hip_krylov_destroy(storm_hip_krylov *k) {
 
 int storm_hip_krylov_set_operator(storm_hip_krylov *k, const storm_hip_op *op, double alpha, double beta) {
   STORM_REQUIRE(k && op, "krylov_set_operator: null argument");
-  k->op = op, k->op_alpha = alpha, k->op_beta = beta, k->op_fn = nullptr, k->op_user = nullptr;
+  k->op = op, k->op_alpha = alpha, k->op_beta = beta, k->op_fn = nullptr, k->op_user = nullptr, k->two_stage = false;
+  return STORM_HIP_OK;
+}
+
+static int two_stage_supported(const storm_hip_op *op, const char *what) {
+  if (op->halo.n_nbrs > 0 || op->n_halo > 0 || op->ctx->comm != nullptr)
+    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "%s: the two-stage operator is single-rank (the operator has a halo plan or halo "
+                                        "columns, or the context a communicator)", what);
+  return STORM_HIP_OK;
+}
+
+int storm_hip_krylov_set_operator2(storm_hip_krylov *k, const storm_hip_op *op, double alpha1, double beta1, double alpha2,
+                                   double beta2) {
+  STORM_REQUIRE(k && op, "krylov_set_operator2: null argument");
+  STORM_TRY(two_stage_supported(op, "krylov_set_operator2"));
+  k->op = op, k->op_alpha = alpha1, k->op_beta = beta1, k->op_alpha2 = alpha2, k->op_beta2 = beta2, k->two_stage = true;
+  k->op_fn = nullptr, k->op_user = nullptr;
   return STORM_HIP_OK;
 }
 
 int storm_hip_krylov_set_operator_fn(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user) {
   STORM_REQUIRE(k && apply, "krylov_set_operator_fn: null argument");
-  k->op = nullptr, k->op_fn = apply, k->op_user = user;
+  k->op = nullptr, k->op_fn = apply, k->op_user = user, k->two_stage = false;
   return STORM_HIP_OK;
 }
 
@@ -1819,6 +1844,8 @@ int storm_hip_krylov_set_real(storm_hip_krylov *k, const char *key, double value
 static int krylov_solve_engine(storm_hip_krylov *k, const storm_hip_vec *b, storm_hip_vec *x,
                                const storm_hip_solver_params *params, storm_hip_solver_result *result, double *history,
                                int64_t *pre_applies);
+static int solve_cg2_on(storm_hip_krylov *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_solver_params *params,
+                        storm_hip_solver_result *result, double *history);
 namespace {
 struct EngineSolveArgs {
   storm_hip_krylov *k;
@@ -1847,7 +1874,12 @@ int storm_hip_krylov_solve(storm_hip_krylov *k, const storm_hip_vec *b, storm_hi
   //  restored and the solve re-run without them -- latency.hip, coop_solve_with_fallback)
   EngineSolveArgs a{k, b, x, params, result, history, pre_applies};
   int fb = 0;
-  const bool fused_path = k->op != nullptr && !k->has_pre() && c->opt_generic_solvers == 0 &&
+  // CG on a two-stage operator: the one-kernel path where it fits (storm_hip_solve_cg2), as single-stage CG below
+  if (k->two_stage && k->method == STORM_HIP_CG && !k->has_pre() && c->opt_generic_solvers == 0) {
+    if (pre_applies) *pre_applies = 0;
+    return solve_cg2_on(k, b, x, params, result, history);
+  }
+  const bool fused_path = k->op != nullptr && !k->two_stage && !k->has_pre() && c->opt_generic_solvers == 0 &&
                           (k->method == STORM_HIP_CG || k->method == STORM_HIP_BICGSTAB ||
                            (k->method == STORM_HIP_GMRES && params->num_inner_iterations < kMaxMulti));
   if (fused_path) return krylov_solve_engine(k, b, x, params, result, history, pre_applies);  // (has its own fallback)
@@ -1862,7 +1894,7 @@ static int krylov_solve_engine(storm_hip_krylov *k, const storm_hip_vec *b, stor
                                int64_t *pre_applies) {
   storm_hip_ctx *c = k->c;
   // A stencil operator without preconditioner: CG / BiCGStab / GMRES have fused kernels (solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip).
-  if (k->op != nullptr && !k->has_pre() && c->opt_generic_solvers == 0) {
+  if (k->op != nullptr && !k->two_stage && !k->has_pre() && c->opt_generic_solvers == 0) {
     fused_entry fused = k->method == STORM_HIP_CG         ? &storm_hip_solve_cg
                         : k->method == STORM_HIP_BICGSTAB ? &storm_hip_solve_bicgstab
                         : k->method == STORM_HIP_GMRES && params->num_inner_iterations < kMaxMulti
@@ -1949,6 +1981,89 @@ int storm_hip_krylov_finalize(storm_hip_krylov *k) {
   const int st = k->status;
   (void)hipStreamSynchronize(k->c->stream);
   release_work(k);
+  return st;
+}
+
+}  // extern "C"
+
+// ---- the two-stage operator A = beta2 I + alpha2 M (beta1 I + alpha1 M) ------------------------------------------------
+// The linear part of the playground's Cahn-Hilliard lambda (Playground.cpp:153-167: two stormDivGrad calls per apply).
+namespace {
+struct Cg2Args {
+  storm_hip_krylov *k;  // two_stage operator set
+  const storm_hip_vec *b;
+  storm_hip_vec *x;
+  const storm_hip_solver_params *params;
+  storm_hip_solver_result *result;
+  double *history;
+};
+// One attempt: the one-kernel path (latency.hip, cg2_latency_kernel) where the operator is eligible and a register variant
+// holds its rows, else -- and after a refused launch -- the engine's CG loop with the two stages as library launches.
+int run_cg2_body(void *p) {
+  const Cg2Args &a = *static_cast<const Cg2Args *>(p);
+  storm_hip_krylov *k = a.k;
+  storm_hip_ctx *c = k->c;
+  bool taken = false;
+  STORM_TRY(cg2_latency_try(k->op, k->op_alpha, k->op_beta, k->op_alpha2, k->op_beta2, a.b, a.x, a.params, a.result, a.history, &taken));
+  if (taken) return STORM_HIP_OK;
+  // (not eligible, no register variant holds the rows, or the launch was refused -- noted in result->path_fallback)
+  ++c->n_engine_solves;
+  return krylov_solve_engine(k, a.b, a.x, a.params, a.result, a.history, nullptr);
+}
+}  // namespace
+
+static int solve_cg2_on(storm_hip_krylov *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_solver_params *params,
+                        storm_hip_solver_result *result, double *history) {
+  storm_hip_ctx *c = k->c;
+  HIP_TRY(hipSetDevice(c->device));
+  Cg2Args a{k, b, x, params, result, history};
+  int fb = 0;
+  int st = coop_solve_with_fallback(c, x, run_cg2_body, &a, &fb);
+  if (st == STORM_HIP_OK) result->path_fallback = fb;
+  if (st == STORM_HIP_OK) st = comm_check_error(c);
+  return st;
+}
+
+extern "C" {
+
+int storm_hip_op_apply2(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const storm_hip_vec *x,
+                        storm_hip_vec *t, storm_hip_vec *y) {
+  STORM_REQUIRE(op && x && y, "op_apply2: null argument");
+  STORM_REQUIRE(x->ctx == op->ctx && y->ctx == op->ctx && (t == nullptr || t->ctx == op->ctx), "op_apply2: context mismatch");
+  STORM_REQUIRE(x != y && x->d != y->d && x != t && y != t && (t == nullptr || (t->d != x->d && t->d != y->d)),
+                "op_apply2: x, t and y must be pairwise distinct");
+  STORM_REQUIRE(x->n_owned == op->n_rows && y->n_owned == op->n_rows && (t == nullptr || t->n_owned == op->n_rows),
+                "op_apply2: operator has %lld rows, x %lld, t %lld, y %lld", (long long)op->n_rows, (long long)x->n_owned,
+                (long long)(t ? t->n_owned : op->n_rows), (long long)y->n_owned);
+  STORM_TRY(two_stage_supported(op, "op_apply2"));
+  storm_hip_vec *work = nullptr;
+  if (t == nullptr) {  // a pooled work vector (stream-ordered: released below, reused by the next call)
+    STORM_TRY(vec_create_work_batch(x, 1, &work));
+    t = work;
+  }
+  // t = beta1 x + alpha1 M x;  y = beta2 x;  y += alpha2 M t  (the lambda's statements, Playground.cpp:153-167)
+  int st = storm_hip_op_apply(op, alpha1, beta1, x, t);
+  if (st == STORM_HIP_OK) st = storm_hip_copy(y, x);
+  if (st == STORM_HIP_OK) st = storm_hip_scale(y, beta2);
+  if (st == STORM_HIP_OK) st = storm_hip_op_apply_add(op, alpha2, t, y);
+  if (work != nullptr) {
+    if (st == STORM_HIP_OK) st = lazy_sync(op->ctx);  // (nothing that reads the work vector may still be waiting)
+    (void)storm_hip_vec_destroy(work);
+  }
+  return st;
+}
+
+int storm_hip_solve_cg2(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const storm_hip_vec *b,
+                        storm_hip_vec *x, const storm_hip_solver_params *params, storm_hip_solver_result *result, double *history) {
+  STORM_REQUIRE(op && b && x && params && result, "solve_cg2: null argument");
+  STORM_TRY(two_stage_supported(op, "solve_cg2"));
+  STORM_TRY(lazy_sync(op->ctx));
+  storm_hip_krylov *k = nullptr;  // (its state comes from the context's free list after the first solve)
+  STORM_TRY(storm_hip_krylov_create(op->ctx, STORM_HIP_CG, &k));
+  int st = storm_hip_krylov_set_operator2(k, op, alpha1, beta1, alpha2, beta2);
+  if (st == STORM_HIP_OK) st = check_ready(k, b, x, params);
+  if (st == STORM_HIP_OK) st = solve_cg2_on(k, b, x, params, result, history);
+  (void)storm_hip_krylov_destroy(k);
   return st;
 }
 

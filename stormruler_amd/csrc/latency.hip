@@ -23,7 +23,7 @@
 //   * rows are summed slot by slot exactly as the throughput kernels do (same expression, same contraction): the
 //     SpMV values are bit-identical; dot products group their terms differently (rounding-level differences).
 //
-// Taken by storm_hip_solve_cg / storm_hip_solve_bicgstab when the operator has a latency copy (n_rows <= option `latency_rows`, no halo, no
+// Taken by storm_hip_solve_cg / storm_hip_solve_bicgstab / storm_hip_solve_cg2 (the two-stage operator: cg2_latency_kernel) when the operator has a latency copy (n_rows <= option `latency_rows`, no halo, no
 // CSR tail), the context has no communicator, and option `latency_path` != 0.
 #include <algorithm>
 #include <cmath>
@@ -61,11 +61,13 @@ struct LatArgs {
   const char *pack;          // compact records
   const int64_t *rec_off;    // [n_slices + 1] byte offsets
   int64_t n_rows, n_slices;
-  double alpha, beta;        // A = beta I + alpha M
+  double alpha, beta;        // A = beta I + alpha M (the two-stage kernel: the FIRST stage, beta1 I + alpha1 M)
+  double alpha2, beta2;      // cg2_latency_kernel: A = beta2 I + alpha2 M (beta I + alpha M)
   const double *b;
   double *x;
   double *p, *r;             // published rows of the current direction and the new residual (see the header)
   double *v0, *v1;           // BiCGStab: published rows of v = A p of even / odd iterations
+  double *t;                 // cg2_latency_kernel: published rows of the first stage's result
   char *slots;               // all-reduce slots, kLatSlotStride bytes per block, zeroed before the launch
   SolverState *st;
   int publish_xchg;          // rows are published with atomic exchanges whose return is awaited (option latency_publish)
@@ -205,6 +207,10 @@ struct LatPlain {
   const double *v;
   __device__ __forceinline__ double operator()(int c) const { return v[c]; }
 };
+struct LatPublished {  // a vector other blocks have published in this launch (coherent loads)
+  const double *v;
+  __device__ __forceinline__ double operator()(int c) const { return co_load(v + c); }
+};
 struct LatDirection {
   const double *r, *p;
   double beta;
@@ -219,9 +225,11 @@ struct LatRecords {  // the records of a wave's slices: W slots per row in regis
   double ext[W ? S : 1];
 };
 
-// (M v)_row for one row of slice s: sum_k w_k (v[col_k] - v_i) + ext v_i, slots in order.
+// (M t)_row for one row of slice s: sum_k w_k (t[col_k] - t_i) + ext t_i, slots in order; the row of
+// beta v + alpha M t is beta * v_i + alpha * that.  One stage (every kernel but cg2_latency_kernel) has t = v.
 template <class Get>
-__device__ __forceinline__ double lat_row(const LatArgs &a, int64_t s, int lane, const Get &get, double vi) {
+__device__ __forceinline__ double lat_row2(const LatArgs &a, int64_t s, int lane, const Get &get, double ti, double vi, double alpha,
+                                           double beta) {
   const int64_t o0 = a.rec_off[s];
   const int width = (int)((a.rec_off[s + 1] - o0 - kWave * 8) / (kWave * 12));
   const char *rec = a.pack + o0;
@@ -234,20 +242,24 @@ __device__ __forceinline__ double lat_row(const LatArgs &a, int64_t s, int lane,
     const int c0 = col[k * kWave], c1 = col[(k + 1) * kWave], c2 = col[(k + 2) * kWave], c3 = col[(k + 3) * kWave];
     const double w0 = val[k * kWave], w1 = val[(k + 1) * kWave], w2 = val[(k + 2) * kWave], w3 = val[(k + 3) * kWave];
     const double g0 = get(c0), g1 = get(c1), g2 = get(c2), g3 = get(c3);
-    acc += w0 * (g0 - vi);
-    acc += w1 * (g1 - vi);
-    acc += w2 * (g2 - vi);
-    acc += w3 * (g3 - vi);
+    acc += w0 * (g0 - ti);
+    acc += w1 * (g1 - ti);
+    acc += w2 * (g2 - ti);
+    acc += w3 * (g3 - ti);
   }
-  for (; k < width; ++k) acc += val[k * kWave] * (get(col[k * kWave]) - vi);
-  return a.beta * vi + a.alpha * (acc + ext * vi);
+  for (; k < width; ++k) acc += val[k * kWave] * (get(col[k * kWave]) - ti);
+  return beta * vi + alpha * (acc + ext * ti);
+}
+template <class Get>
+__device__ __forceinline__ double lat_row(const LatArgs &a, int64_t s, int lane, const Get &get, double vi) {
+  return lat_row2(a, s, lane, get, vi, vi, a.alpha, a.beta);
 }
 // The same from registers: W slots (4: triangle / quadrilateral meshes; 8), the ones past the row's width carry weight 0 and the row's own
-// column (a term 0 * (v_i - v_i) leaves the sum as it is).
+// column (a term 0 * (t_i - t_i) leaves the sum as it is).
 // (CHUNK neighbours in flight at a time: a neighbour costs one load with LatPlain, up to three with BiCGStab's.)
 template <int S, int W, int CHUNK = W, class Get>
-__device__ __forceinline__ double lat_row_cached(const LatArgs &a, const LatRecords<S, W> &rec, int q, const Get &get,
-                                                 double vi) {
+__device__ __forceinline__ double lat_row_cached2(const LatRecords<S, W> &rec, int q, const Get &get, double ti, double vi,
+                                                  double alpha, double beta) {
   double acc = 0.0;
 #pragma unroll
   for (int k0 = 0; k0 < W; k0 += CHUNK) {
@@ -255,9 +267,14 @@ __device__ __forceinline__ double lat_row_cached(const LatArgs &a, const LatReco
 #pragma unroll
     for (int k = 0; k < CHUNK; ++k) g[k] = get(rec.col[q][k0 + k]);
 #pragma unroll
-    for (int k = 0; k < CHUNK; ++k) acc += rec.val[q][k0 + k] * (g[k] - vi);
+    for (int k = 0; k < CHUNK; ++k) acc += rec.val[q][k0 + k] * (g[k] - ti);
   }
-  return a.beta * vi + a.alpha * (acc + rec.ext[q] * vi);
+  return beta * vi + alpha * (acc + rec.ext[q] * ti);
+}
+template <int S, int W, int CHUNK = W, class Get>
+__device__ __forceinline__ double lat_row_cached(const LatArgs &a, const LatRecords<S, W> &rec, int q, const Get &get,
+                                                 double vi) {
+  return lat_row_cached2<S, W, CHUNK>(rec, q, get, vi, vi, a.alpha, a.beta);
 }
 
 // The records of a wave's slices into registers (W > 0 variants).
@@ -356,6 +373,141 @@ __global__ __launch_bounds__(kLatBlock) void cg_latency_kernel(LatArgs a) {
         co_publish(a.r + row, r[q], a.publish_xchg, seen), co_publish(a.p + row, p[q], a.publish_xchg, seen);
     }
     // the new r and the current p are out (at the point of coherence before a block's tag is stored) with the <r, r> partials
+    const double gamma_bar = gamma;
+    gamma = lat_allreduce(acc, a.slots, ++seq, lds, true, seen);
+    beta = safe_divide(gamma, gamma_bar);
+    abs_err = sqrt(gamma);
+    rel_err = abs_err / initial_error;
+    converged = (abs_tol > 0.0 && abs_err < abs_tol) || (rel_tol > 0.0 && rel_err < rel_tol);  // Solver.hpp:132-140
+    ++it;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && history) history[it] = abs_err;
+#pragma unroll
+    for (int q = 0; q < S; ++q) p[q] = r[q] + beta * p[q];
+  }
+#pragma unroll
+  for (int q = 0; q < S; ++q) {
+    const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+    if (s < a.n_slices && row < a.n_rows) a.x[row] = x[q];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    st->initial_error = initial_error;
+    st->absolute_error = abs_err;
+    st->relative_error = rel_err;
+    st->iteration = it;
+    st->converged = converged ? 1 : 0;
+    st->done = 1;
+  }
+}
+
+// ---- CG for the TWO-STAGE operator on the latency path --------------------------------------------------------------
+// A = beta2 I + alpha2 M (beta1 I + alpha1 M): the linear part of the playground's Cahn-Hilliard lambda, which applies
+// stormDivGrad twice (Playground.cpp:153-167).  cg_latency_kernel with the apply in two halves and THREE synchronisation
+// points per iteration:
+//   1. t_i = beta1 p_i + alpha1 (M p')_i, neighbours formed as r[c] + beta p_prev[c] from the published rows as above;
+//      the wave keeps t_i and publishes its row; a synchronisation point that carries no sum of the recurrence;
+//   2. z_i = beta2 p_i + alpha2 (M t)_i, the neighbours' t from the published rows, the own one from the register;
+//      the <p, z> all-reduce;
+//   3. x += alpha p, r -= alpha z, r and p published, the <r, r> all-reduce: cg_latency_kernel's, unchanged.
+// The init has the same extra point (t of x before r = b - A x).  Rounding per stage as lat_row's:
+// beta * v_i + alpha * (acc + ext * t_i).
+//   ONE buffer t is enough.  A block publishes the next t (point 1 of iteration k + 1, or of iteration 0 behind the
+// init) only after it has passed the <p, z> and the <r, r> all-reduce that follow the current one, and every block
+// enters the <p, z> all-reduce (the init: the <r, r> one) only after its gathers of the current t: when the first
+// block is past it, nobody reads the current t any more.  The same argument covers r and p as in cg_latency_kernel:
+// they are gathered in stage 1, in front of points 1 and 2, and overwritten behind point 2.
+template <int S, int W>
+__global__ __launch_bounds__(kLatBlock) void cg2_latency_kernel(LatArgs a) {
+  __shared__ double lds[kLatWaves];
+  SolverState *st = a.st;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave_id = (int64_t)blockIdx.x * kLatWaves + (threadIdx.x >> 6);
+  const int64_t n_waves = (int64_t)gridDim.x * kLatWaves;
+  unsigned long long seq = 0, seen = 0;  // seen: what the publishing exchanges returned (consumed at the all-reduces)
+  double x[S], r[S], p[S], z[S], t[S];
+  LatRecords<S, W> rec;
+  lat_load_records<S, W>(a, wave_id, n_waves, lane, rec);
+  // row of beta v + alpha M t, the neighbours' t through `get`, the own one ti
+  auto stage_row = [&](int q, int64_t s, const auto &get, double ti, double vi, double alpha, double beta) -> double {
+    if constexpr (W > 0) return lat_row_cached2<S, W>(rec, q, get, ti, vi, alpha, beta);
+    else return lat_row2(a, s, lane, get, ti, vi, alpha, beta);
+  };
+  const LatPublished of_t{a.t};
+
+  // ---- init: r = b - A x; p = r; gamma = <r, r>                                   SolverCg.hpp:54-84
+  // (a.p arrives zero-filled, so the first direction r + 0 * p is r; a.t too: a padded slot reads a finite value)
+#pragma unroll
+  for (int q = 0; q < S; ++q) {
+    const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+    const bool valid = s < a.n_slices && row < a.n_rows;
+    x[q] = valid ? a.x[row] : 0.0;
+    r[q] = p[q] = z[q] = t[q] = 0.0;
+    if (s < a.n_slices) {
+      t[q] = stage_row(q, s, LatPlain{a.x}, x[q], x[q], a.alpha, a.beta);  // x is not written before the kernel's end
+      t[q] = valid ? t[q] : 0.0;
+      if (valid) co_publish(a.t + row, t[q], a.publish_xchg, seen);
+    }
+  }
+  (void)lat_allreduce(0.0, a.slots, ++seq, lds, true, seen);  // t of x is out
+  double acc = 0.0;
+#pragma unroll
+  for (int q = 0; q < S; ++q) {
+    const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+    const bool valid = s < a.n_slices && row < a.n_rows;
+    if (s < a.n_slices) {
+      const double ax = stage_row(q, s, of_t, t[q], x[q], a.alpha2, a.beta2);
+      r[q] = valid ? a.b[row] - ax : 0.0;
+      p[q] = r[q];
+      if (valid) co_publish(a.r + row, r[q], a.publish_xchg, seen);
+      acc += r[q] * r[q];
+    }
+  }
+  double gamma = lat_allreduce(acc, a.slots, ++seq, lds, true, seen);
+  const double initial_error = sqrt(gamma);
+  const double abs_tol = st->abs_tol, rel_tol = st->rel_tol;
+  const long long num_iterations = st->num_iterations;
+  double *history = st->history;
+  bool converged = abs_tol > 0.0 && initial_error < abs_tol;  // Solver.hpp:124-128
+  double abs_err = initial_error, rel_err = 0.0, beta = 0.0;
+  long long it = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && history) history[0] = initial_error;
+
+  // ---- iterations                                                                 SolverCg.hpp:86-126
+  // entering: registers hold x, r and the direction p of the own rows; memory holds r and the PREVIOUS direction,
+  // from which a neighbour's current direction is r[c] + beta p_prev[c]
+  while (!converged && it < num_iterations) {
+    const LatDirection dir{a.r, a.p, beta};
+#pragma unroll
+    for (int q = 0; q < S; ++q) {
+      const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+      if (s < a.n_slices) {
+        t[q] = stage_row(q, s, dir, p[q], p[q], a.alpha, a.beta);
+        t[q] = (row < a.n_rows) ? t[q] : 0.0;
+        if (row < a.n_rows) co_publish(a.t + row, t[q], a.publish_xchg, seen);
+      }
+    }
+    (void)lat_allreduce(0.0, a.slots, ++seq, lds, true, seen);  // t of the direction is out
+    acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < S; ++q) {
+      const int64_t s = wave_id + q * n_waves;
+      if (s < a.n_slices) {
+        z[q] = stage_row(q, s, of_t, t[q], p[q], a.alpha2, a.beta2);
+        z[q] = (s * kWave + lane < a.n_rows) ? z[q] : 0.0;
+        acc += p[q] * z[q];
+      }
+    }
+    // every gather of this iteration's t is done once all blocks have published their <p, z> partial
+    const double alpha = safe_divide(gamma, lat_allreduce(acc, a.slots, ++seq, lds, false));
+    acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < S; ++q) {
+      const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+      x[q] += alpha * p[q];
+      r[q] -= alpha * z[q];
+      acc += r[q] * r[q];
+      if (s < a.n_slices && row < a.n_rows)
+        co_publish(a.r + row, r[q], a.publish_xchg, seen), co_publish(a.p + row, p[q], a.publish_xchg, seen);
+    }
     const double gamma_bar = gamma;
     gamma = lat_allreduce(acc, a.slots, ++seq, lds, true, seen);
     beta = safe_divide(gamma, gamma_bar);
@@ -1477,9 +1629,10 @@ bool cg_latency_eligible(const storm_hip_op *op) {
          c->opt_profile_spmv == 0;
 }
 
-// The whole solve; fills the SolverState on the device (the caller reads it back).  `bicgstab`: which of the two
-// kernels; work vectors p, r (CG) and p, r, v0, v1 (BiCGStab) arrive zero-filled.
-static int latency_solve(bool bicgstab, const storm_hip_op *op, LatArgs a, bool *taken) {
+// The whole solve; fills the SolverState on the device (the caller reads it back).  `family`: which of the three
+// kernels; work vectors p, r (CG), p, r, v0, v1 (BiCGStab) and p, r, t (two-stage CG) arrive zero-filled.
+enum LatFamily { LAT_CG, LAT_BICGSTAB, LAT_CG2 };
+static int latency_solve(LatFamily family, const storm_hip_op *op, LatArgs a, bool *taken) {
   storm_hip_ctx *c = op->ctx;
   *taken = false;
   const int64_t n_slices = (op->n_rows + kWave - 1) / kWave;
@@ -1496,7 +1649,11 @@ static int latency_solve(bool bicgstab, const storm_hip_op *op, LatArgs a, bool 
       pick((const void *)bicgstab_latency_kernel<1, 0>, (const void *)bicgstab_latency_kernel<1, 4>,
            (const void *)bicgstab_latency_kernel<1, 8>),
       (const void *)bicgstab_latency_kernel<2, 0>, (const void *)bicgstab_latency_kernel<4, 0>, (const void *)bicgstab_latency_kernel<8, 0>};
-  const void *const *variants = bicgstab ? bi : cg;
+  const void *cg2[4] = {
+      pick((const void *)cg2_latency_kernel<1, 0>, (const void *)cg2_latency_kernel<1, 4>, (const void *)cg2_latency_kernel<1, 8>),
+      pick((const void *)cg2_latency_kernel<2, 0>, (const void *)cg2_latency_kernel<2, 4>, (const void *)cg2_latency_kernel<2, 8>),
+      (const void *)cg2_latency_kernel<4, 0>, (const void *)cg2_latency_kernel<8, 0>};
+  const void *const *variants = family == LAT_BICGSTAB ? bi : family == LAT_CG2 ? cg2 : cg;
   const int capacity[4] = {1, 2, 4, 8};
   const void *fn = nullptr;
   int64_t blocks = 0;
@@ -1522,14 +1679,22 @@ int cg_latency_solve(const storm_hip_op *op, double alpha, double beta, const do
                      double *r, SolverState *d_state, bool *taken) {
   LatArgs a{};
   a.alpha = alpha, a.beta = beta, a.b = b, a.x = x, a.p = p, a.r = r, a.st = d_state;
-  return latency_solve(false, op, a, taken);
+  return latency_solve(LAT_CG, op, a, taken);
 }
 
 int bicgstab_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x,
                            double *const work[4], SolverState *d_state, bool *taken) {
   LatArgs a{};
   a.alpha = alpha, a.beta = beta, a.b = b, a.x = x, a.p = work[0], a.r = work[1], a.v0 = work[2], a.v1 = work[3], a.st = d_state;
-  return latency_solve(true, op, a, taken);
+  return latency_solve(LAT_BICGSTAB, op, a, taken);
+}
+
+int cg2_latency_solve(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const double *b,
+                      double *x, double *const work[3], SolverState *d_state, bool *taken) {
+  LatArgs a{};
+  a.alpha = alpha1, a.beta = beta1, a.alpha2 = alpha2, a.beta2 = beta2, a.b = b, a.x = x;
+  a.p = work[0], a.r = work[1], a.t = work[2], a.st = d_state;
+  return latency_solve(LAT_CG2, op, a, taken);
 }
 
 }  // namespace storm

@@ -659,6 +659,28 @@ static int solve_cg_body(const FusedSolveArgs &args) {
   return collect(d, args, 1);
 }
 
+// CG for the two-stage operator A = beta2 I + alpha2 M (beta1 I + alpha1 M) as one cooperative kernel (latency.hip,
+// cg2_latency_kernel), under the rules of the single-stage solve above.  *taken = false: the caller runs its own loop.
+int cg2_latency_try(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const storm_hip_vec *b,
+                    storm_hip_vec *x, const storm_hip_solver_params *params, storm_hip_solver_result *result, double *history,
+                    bool *taken) {
+  *taken = false;
+  if (!cg_latency_eligible(op)) return STORM_HIP_OK;
+  storm_hip_ctx *c = op->ctx;
+  const FusedSolveArgs args{op, alpha1, beta1, b, x, params, result, history, nullptr};
+  Driver d;
+  STORM_TRY(prepare_state(args, &d));
+  VecPool pool;
+  int st = pool.make(x, 3);  // p, r, t; zero-filled: the kernel relies on that for the first direction
+  if (st == STORM_HIP_OK) {
+    double *const work[3] = {pool.v[0]->d, pool.v[1]->d, pool.v[2]->d};
+    st = cg2_latency_solve(op, alpha1, beta1, alpha2, beta2, b->d, x->d, work, c->d_state, taken);
+  }
+  if (st == STORM_HIP_OK && *taken) return ++c->n_latency_solves, collect(d, args, 1);  // (one apply is both stages)
+  if (d.d_history) (void)hipFree(d.d_history), d.d_history = nullptr;
+  return st;
+}
+
 }  // namespace storm
 
 extern "C" int storm_hip_solve_cg(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *b, storm_hip_vec *x,
