@@ -185,6 +185,9 @@ int storm_hip_block_axpy(storm_hip_vec *Y, const double *a, const storm_hip_vec 
  *     vmul_add(y, s, a, b)                                   fma(s, fl(a b), y)
  *     multi_axpy(y, coefs, xs, k)                            y = fma(coefs[j], xs[j], y) for j = 0 .. k - 1 in turn
  *     map                                                    every operation rounded on its own (see below)
+ *   and the two statements around the callback of a finite-difference operator (storm_hip_krylov_set_operator_fd):
+ *     s = x + delta y                                        fl(x + fl(delta y)) = fma(1, x, fl(delta y)): NOT fma(delta, y, x)
+ *     z = delta_inverse (z - w)                              fl(delta_inverse fl(z - w))
  * So BiCGStab's p through storm_hip_lin3(p, r, beta, 1, p, -omega, v) -- fma(beta, fl(p + fl(-omega v)), r) -- and through
  * storm_hip_bicgstab_p differ in the last place on about one row in eleven: a caller who wants the bits of one must
  * call that one. */
@@ -387,7 +390,10 @@ int storm_hip_ctx_set_option(storm_hip_ctx *ctx, const char *key, int64_t value)
 /* Which path the solves of this context took so far (no reference counterpart: a diagnostic of this library; the
  * reference logs one line per solve, Solver.hpp:144-145).  Keys: "resident_solves" (csrc/resident.hip),
  * "latency_solves" (csrc/latency.hip: one cooperative kernel per solve), "throughput_solves" (a kernel per statement,
- * fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip), "engine_solves" (csrc/krylov.hip), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "cg_fused_steps" (solves whose CG step rode in
+ * fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip), "engine_solves" (csrc/krylov.hip), "jfnk_inner_solves" (inner BiCGStab solves of
+ * STORM_HIP_JFNK), "fd_fused_dots" (products of a finite-difference operator whose difference statement took the method's
+ * reductions of z along in its pass), "host_reductions" (calls of storm_hip_dot / _norm2 / _multi_dot / _multi_dot_end / _block_dot: the reduction
+ * entry points that make the host wait for their sums -- a device-resident loop leaves it where it was), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "cg_fused_steps" (solves whose CG step rode in
  * the SpMV launch), "lazy_fused_dots" / "lazy_fused_pairs" / "lazy_apply_dots" / "lazy_cg_steps" / "lazy_waiting" (option
  * lazy_statements: reductions that rode in a statement's kernel, pairs of statements that left as one pass, applies that
  * left with a fused dot, fused CG steps, statements waiting now).  On the peer-window transport, where the time of the exchanges went (ticks of 10 ns of the device's
@@ -647,7 +653,17 @@ enum storm_hip_method {
   STORM_HIP_TFQMR1 = 6,      /* SolverTfqmr.hpp:252-265 */
   STORM_HIP_BICGSTAB_L = 7,  /* SolverBiCgStab.hpp:184-383; num_inner_iterations = l (default 2) */
   STORM_HIP_IDRS = 8,        /* SolverIdrs.hpp:52-291;      num_inner_iterations = s (default 4) */
-  STORM_HIP_RICHARDSON = 9   /* SolverRichardson.hpp:41-98 */
+  STORM_HIP_RICHARDSON = 9,  /* SolverRichardson.hpp:41-98 */
+  /* JfnkSolver, SolverNewton.hpp:101-173: Newton steps on A(x) = b for a NONLINEAR callback A (any operator kind is taken; a
+   * native one is linear and one step lands on the answer).  init: w = A(x), r = b - w, |r| (:106-122).  iterate (:124-161):
+   * mu = sqrt(eps) sqrt(1 + |x|) formed on the device; t = r; J(x) t = r by a nested BiCGStab object (tolerances 1e-8, 2000
+   * iterations, no preconditioner, :133-135) on the finite-difference operator of storm_hip_krylov_set_operator_fd at (x, w,
+   * mu); x += t; w = A(x); r = b - w; |r|.  No scalar visits the host: the inner solve's own polling is the only host
+   * involvement inside a step.  iterations counts Newton steps, num_applies every application of A (outer and inner);
+   * storm_hip_krylov_get_int "inner_iterations" the inner iterations.  A preconditioner that is set is IGNORED, as in the
+   * reference (:107-109, :126-128 take pre_op and never read it).  A finite-difference operator as A is refused
+   * (STORM_HIP_E_UNSUPPORTED). */
+  STORM_HIP_JFNK = 10
 };
 enum storm_hip_side { STORM_HIP_LEFT = 0, STORM_HIP_RIGHT = 1, STORM_HIP_SYMMETRIC = 2 }; /* Preconditioner.hpp:39-60 */
 
@@ -657,6 +673,19 @@ int storm_hip_krylov_destroy(storm_hip_krylov *k);
  * kernels of storm_hip_solve_*), or a callback. */
 int storm_hip_krylov_set_operator(storm_hip_krylov *k, const storm_hip_op *op, double alpha, double beta);
 int storm_hip_krylov_set_operator_fn(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user);
+/* z = (A(x + delta y) - w) / delta, delta = safe_divide(mu, |y|) (MathUtils.hpp:49-52: 0 when |y| == 0, and then z = 0):
+ * the Jacobian-vector product of SolverNewton.hpp:143-156 as an operator any method can take (GMRES on a Jacobian, say).
+ * Per product: <y, y> with delta and 1 / delta formed behind it on the device, s = x + delta y, the callback, and
+ * z = (z - w) / delta with the reductions the method takes of z next in the same pass -- four launches, no host wait.
+ * x and w = A(x) must stay alive and unchanged during a solve.  mu not finite or <= 0, x / w of different sizes or
+ * contexts: STORM_HIP_E_INVALID. */
+int storm_hip_krylov_set_operator_fd(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user,
+                                     const storm_hip_vec *x, const storm_hip_vec *w, double mu);
+/* z = A(y) with the object's operator (any kind; Operator::mul, Operator.hpp:74), enqueued; no host wait.  z must not alias
+ * y; not while a stepping solve is open on the object. */
+int storm_hip_krylov_apply(storm_hip_krylov *k, const storm_hip_vec *y, storm_hip_vec *z);
+/* "inner_iterations" (JFNK: total inner BiCGStab iterations of the last solve, SolverNewton.hpp:133-155). */
+int storm_hip_krylov_get_int(const storm_hip_krylov *k, const char *key, int64_t *value);
 /* The two-stage operator A = beta2 I + alpha2 M (beta1 I + alpha1 M) of storm_hip_op_apply2 (the playground's lambda,
  * Playground.cpp:153-167, without a callback): an apply is both stages as library launches, so every method and every
  * preconditioner side works on it; CG without preconditioner runs storm_hip_solve_cg2.  Halo plan / communicator:

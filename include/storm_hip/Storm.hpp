@@ -718,6 +718,65 @@ private:
   DeviceVector* _intermediate;
 };
 
+/// The finite-difference Jacobian of `any_op` at `x_vec` (SolverNewton.hpp:143-156) as an Operator<DeviceVector>:
+/// z = (A(x + delta y) - w) / delta with w_vec = A(x_vec) (the caller forms it) and delta = safe_divide(mu, |y|).  The
+/// solvers bind it natively (storm_hip_krylov_set_operator_fd): |y|, delta and 1 / delta stay on the device, the two
+/// statements around `any_op.mul` are one kernel each and the reductions the method takes of z ride in the second, so
+/// `solve<GmresSolver>(t, r, HipFdJacobianOperator{op, x, w, mu})` solves J(x) t = r without a host wait per product.
+/// The three objects must outlive the operator; x_vec and w_vec stay unchanged during a solve.
+class HipFdJacobianOperator final : public Operator<DeviceVector> {
+public:
+  HipFdJacobianOperator(const Operator<DeviceVector>& any_op, const DeviceVector& x_vec, const DeviceVector& w_vec, real_t mu)
+      : _op{&any_op}, _x{&x_vec}, _w{&w_vec}, _mu{mu} {}
+  HipFdJacobianOperator(const HipFdJacobianOperator&) = delete;
+  HipFdJacobianOperator& operator=(const HipFdJacobianOperator&) = delete;
+  ~HipFdJacobianOperator() override { storm_hip_krylov_destroy(_k); }  // (waits for the stream, once)
+  /// z = J(y) outside a solve: storm_hip_krylov_apply on an object of its own, created by the first call and kept --
+  /// every later call only enqueues (the callback runs on the host inside the call, so `bound` may live on its stack).
+  void mul(DeviceVector& z_vec, const DeviceVector& y_vec) const override {
+    storm_hip_ctx* ctx = nullptr;
+    detail::check(storm_hip_vec_context(z_vec.handle(), &ctx));
+    if (_k == nullptr || ctx != _ctx) {
+      storm_hip_krylov_destroy(_k);
+      _k = nullptr;
+      detail::check(storm_hip_krylov_create(ctx, STORM_HIP_BICGSTAB, &_k));
+      _ctx = ctx;
+    }
+    Bound bound{_op, nullptr};
+    int st = storm_hip_krylov_set_operator_fd(_k, &HipFdJacobianOperator::trampoline, &bound, _x->handle(), _w->handle(), _mu);
+    if (st == STORM_HIP_OK) st = storm_hip_krylov_apply(_k, y_vec.handle(), z_vec.handle());
+    if (bound.thrown) std::rethrow_exception(bound.thrown);
+    detail::check(st);
+  }
+  const Operator<DeviceVector>& op() const noexcept { return *_op; }
+  const DeviceVector& x() const noexcept { return *_x; }
+  const DeviceVector& w() const noexcept { return *_w; }
+  real_t mu() const noexcept { return _mu; }
+
+private:
+  struct Bound {
+    const Operator<DeviceVector>* op;
+    std::exception_ptr thrown;
+  };
+  static int trampoline(void* user, storm_hip_vec* y, const storm_hip_vec* x) noexcept {
+    auto* bound = static_cast<Bound*>(user);
+    try {
+      DeviceVector y_view = DeviceVector::view_of(y);
+      const DeviceVector x_view = DeviceVector::view_of(const_cast<storm_hip_vec*>(x));
+      bound->op->mul(y_view, x_view);
+      return 0;
+    } catch (...) {
+      bound->thrown = std::current_exception();
+      return 1;
+    }
+  }
+  const Operator<DeviceVector>* _op;
+  const DeviceVector *_x, *_w;
+  real_t _mu;
+  mutable storm_hip_krylov* _k = nullptr;
+  mutable storm_hip_ctx* _ctx = nullptr;
+};
+
 /// What one column of a block solve reports: the fields of IterativeSolver (Solver.hpp:66-72) after `solve`.
 struct BlockColumnResult {
   std::size_t iteration = 0;
@@ -818,7 +877,8 @@ inline void log_solve(std::size_t iteration, real_t absolute_error, real_t relat
 }
 
 /// One `storm_hip_krylov` object -- the library's device-resident solver loops (csrc/krylov.hip) -- with the
-/// caller's Operator / Preconditioner objects bound to it.  A HipStencilOperator or HipTwoStageOperator binds natively; any other
+/// caller's Operator / Preconditioner objects bound to it.  A HipStencilOperator, HipTwoStageOperator or HipFdJacobianOperator
+/// (its inner operator as the callback) binds natively; any other
 /// operator (a lambda through make_operator, Playground.cpp:151-167) and any preconditioner but the Jacobi
 /// one bind as callbacks, which only enqueue kernels.  An exception thrown inside a callback aborts the solve
 /// and is rethrown from the call that ran it.
@@ -844,7 +904,10 @@ public:
       check(storm_hip_krylov_set_operator(_h, hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta()));
     else if (const auto* two = dynamic_cast<const HipTwoStageOperator*>(&any_op))
       check(storm_hip_krylov_set_operator2(_h, two->matrix().handle(), two->alpha1(), two->beta1(), two->alpha2(), two->beta2()));
-    else
+    else if (const auto* fd = dynamic_cast<const HipFdJacobianOperator*>(&any_op)) {
+      _op = Bound{&fd->op(), &_thrown};
+      check(storm_hip_krylov_set_operator_fd(_h, &Engine::trampoline, &_op, fd->x().handle(), fd->w().handle(), fd->mu()));
+    } else
       check(storm_hip_krylov_set_operator_fn(_h, &Engine::trampoline, &_op));
     const int c_side = side == PreconditionerSide::Left    ? STORM_HIP_LEFT
                        : side == PreconditionerSide::Right ? STORM_HIP_RIGHT
@@ -965,6 +1028,8 @@ protected:
   virtual int device_method() const noexcept { return -1; }
   virtual void fill_params(storm_hip_solver_params& /*p*/) const {}
   virtual void configure(storm_hip_krylov* /*k*/) const {}
+  /// After a device-loop solve or a stepping iterate: what a shipped solver reads back from its object.
+  virtual void collect(storm_hip_krylov* /*k*/) {}
 
   storm_hip_solver_params params() const {
     storm_hip_solver_params p;
@@ -993,6 +1058,7 @@ public:
         absolute_error = r.absolute_error, relative_error = r.relative_error;
         num_applies = (std::size_t)r.num_applies, num_pre_applies = (std::size_t)n_pre;
         path_fallback = r.path_fallback;
+        collect(_engine.handle());
         detail::log_solve(iteration, absolute_error, relative_error);
         return r.converged != 0;
       }
@@ -1107,6 +1173,7 @@ protected:
   real_t iterate(Vector&, const Vector&, const Operator<Vector>&, const Preconditioner<Vector>*) final {
     real_t residual_norm = 0.0;
     this->_engine.finish(storm_hip_krylov_iterate(this->_engine.handle(), &residual_norm));
+    this->collect(this->_engine.handle());
     return residual_norm;
   }
   void finalize(Vector&, const Vector&, const Operator<Vector>&, const Preconditioner<Vector>*) final {
@@ -1243,6 +1310,23 @@ private:
     inner_iterations += inner.iteration;
     x_vec += _step;
     return residual_of(x_vec, b_vec, any_op);
+  }
+};
+
+/// SolverNewton.hpp:101-173 inside the library (STORM_HIP_JFNK): the Newton loop is an engine method and every
+/// Jacobian-vector product of the inner BiCGStab (1e-8, :133-135) the native finite-difference operator of
+/// HipFdJacobianOperator -- no scalar visits the host inside a Newton step, where JfnkSolver waits for |y| at every
+/// product.  `any_op` may be nonlinear (a lambda) or native; `pre_op` is ignored, as the reference ignores it (:107-109).
+template<class Vector>
+class HipJfnkSolver final : public detail::DeviceIterativeSolver<Vector, STORM_HIP_JFNK> {
+public:
+  std::size_t inner_iterations{0};  ///< inner BiCGStab iterations of the last solve
+
+private:
+  void collect(storm_hip_krylov* k) override {
+    int64_t value = 0;
+    detail::check(storm_hip_krylov_get_int(k, "inner_iterations", &value));
+    inner_iterations = (std::size_t)value;
   }
 };
 

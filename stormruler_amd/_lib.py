@@ -167,6 +167,9 @@ SIGNATURES = {
     "storm_hip_krylov_set_operator": (C.c_int, [vp, vp, C.c_double, C.c_double]),
     "storm_hip_krylov_set_operator2": (C.c_int, [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double]),
     "storm_hip_krylov_set_operator_fn": (C.c_int, [vp, APPLY_FN, vp]),
+    "storm_hip_krylov_set_operator_fd": (C.c_int, [vp, APPLY_FN, vp, vp, vp, C.c_double]),
+    "storm_hip_krylov_apply": (C.c_int, [vp, vp, vp]),
+    "storm_hip_krylov_get_int": (C.c_int, [vp, C.c_char_p, i64p]),
     "storm_hip_krylov_set_preconditioner_fn": (C.c_int, [vp, APPLY_FN, vp, C.c_int]),
     "storm_hip_krylov_set_preconditioner_diag": (C.c_int, [vp, vp, C.c_int]),
     "storm_hip_krylov_set_real": (C.c_int, [vp, C.c_char_p, C.c_double]),

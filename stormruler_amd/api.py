@@ -768,6 +768,28 @@ class HipTwoStageOperator(Operator):
         raise RuntimeError("`Operator::conj_mul` was not overriden")
 
 
+class FdJacobianOperator(Operator):
+    """The finite-difference Jacobian of ``any_op`` at ``x_vec`` (SolverNewton.hpp:143-156) as an ``Operator<DeviceVector>``:
+    ``z = (A(x + delta y) - w) / delta`` with ``w_vec = A(x_vec)`` (the caller forms it) and ``delta = safe_divide(mu, |y|)``.
+    The solvers bind it natively (``storm_hip_krylov_set_operator_fd``): ``|y|``, ``delta`` and ``1 / delta`` stay on the
+    device, the two statements around ``any_op.mul`` are one kernel each, and the reductions the method takes of ``z`` ride
+    in the second -- ``solve(GmresSolver, t, r, FdJacobianOperator(op, x, w, mu))`` solves ``J(x) t = r`` without a host
+    wait per product.  ``x_vec`` and ``w_vec`` must stay alive and unchanged during a solve."""
+
+    def __init__(self, any_op: Operator, x_vec: DeviceVector, w_vec: DeviceVector, mu: float):
+        self.op, self.x, self.w, self.mu = any_op, x_vec, w_vec, float(mu)
+        self._krylov: Optional["Krylov"] = None
+
+    def mul(self, z_vec: DeviceVector, y_vec: DeviceVector) -> None:
+        if self._krylov is None or self._krylov.ctx is not z_vec.ctx or self._krylov._h is None:
+            self._krylov = Krylov(z_vec.ctx)
+        self._krylov.set_operator(self)
+        self._krylov.apply(z_vec, y_vec)
+
+    def conj_mul(self, x_vec, y_vec):
+        raise RuntimeError("`Operator::conj_mul` was not overriden")
+
+
 # ---------------------------------------------------------------------------------------------
 # Solvers (Solvers/Solver.hpp)
 
@@ -873,6 +895,9 @@ class _Engine:
         elif isinstance(any_op, HipTwoStageOperator):
             check(lib.storm_hip_krylov_set_operator2(self._h, any_op.matrix._h, any_op.alpha1, any_op.beta1, any_op.alpha2,
                                                      any_op.beta2))
+        elif isinstance(any_op, FdJacobianOperator):
+            check(lib.storm_hip_krylov_set_operator_fd(self._h, self._callback(any_op.op.mul), None, any_op.x._h, any_op.w._h,
+                                                       any_op.mu))
         else:
             check(lib.storm_hip_krylov_set_operator_fn(self._h, self._callback(any_op.mul), None))
         if pre_op is None:
@@ -887,6 +912,26 @@ class _Engine:
         if err is not None:
             raise err
         check(status)
+
+
+class Krylov(_Engine):
+    """A ``storm_hip_krylov`` object used directly: bind an operator of any kind and apply it (``storm_hip_krylov_apply``:
+    enqueued, no host wait).  ``method`` is the object's method id (BiCGStab by default; irrelevant to :meth:`apply`)."""
+
+    def __init__(self, ctx: Context, method: int = 1):
+        super().__init__(ctx, method)
+
+    def set_operator(self, any_op: Operator) -> None:
+        self.bind(any_op, None, PreconditionerSide.Right)
+
+    def apply(self, z_vec: DeviceVector, y_vec: DeviceVector) -> None:
+        """``z = A(y)`` (output first, like ``Operator.mul``)."""
+        self.call(lib.storm_hip_krylov_apply(self._h, y_vec._h, z_vec._h))
+
+    def get_int(self, key: str) -> int:
+        v = C.c_int64()
+        check(lib.storm_hip_krylov_get_int(self._h, key.encode(), C.byref(v)))
+        return v.value
 
 
 class IterativeSolver(Solver):
@@ -1208,6 +1253,39 @@ class JfnkSolver(IterativeSolver):
         self.inner_iterations += inner.iteration
         x_vec += step
         return self._residual(x_vec, b_vec, any_op)
+
+
+class DeviceJfnkSolver(IterativeSolver):
+    """SolverNewton.hpp:101-173 inside the library (``STORM_HIP_JFNK``): the Newton loop is an engine method, every
+    Jacobian-vector product of the inner BiCGStab (1e-8, :133-135) a native finite-difference operator
+    (:class:`FdJacobianOperator`'s kernels) -- no scalar visits the host inside a Newton step, where :class:`JfnkSolver`
+    waits for ``|y|`` at every product.  ``any_op`` may be nonlinear (a callback) or native; ``pre_op`` is ignored, as the
+    reference ignores it (:107-109).  ``inner_iterations``: the inner iterations of the last solve, as on
+    :class:`JfnkSolver`."""
+
+    _method = 10  # STORM_HIP_JFNK
+
+    def __init__(self):
+        super().__init__()
+        self.inner_iterations = 0
+
+    def _read_inner(self) -> None:
+        if self._engine is not None and self._engine._h is not None:
+            v = C.c_int64()
+            check(lib.storm_hip_krylov_get_int(self._engine._h, b"inner_iterations", C.byref(v)))
+            self.inner_iterations = v.value
+
+    def solve(self, x_vec, b_vec, any_op) -> bool:
+        try:
+            return super().solve(x_vec, b_vec, any_op)
+        finally:
+            self._read_inner()
+
+    def iterate(self, x_vec, b_vec, any_op, pre_op) -> float:
+        try:
+            return super().iterate(x_vec, b_vec, any_op, pre_op)
+        finally:
+            self._read_inner()
 
 
 def _like(v: DeviceVector) -> DeviceVector:

@@ -858,6 +858,7 @@ int storm_hip_multi_dot_end(storm_hip_ctx *c, int request, double *out) {
   const unsigned tag = slot.tag;
   const int k = slot.k;
   slot.tag = 0;
+  ++c->n_host_reductions;  // (storm_hip_dot, _norm2 and _multi_dot all end here: one count per call)
   if (slot.ready) {
     for (int j = 0; j < k; ++j) out[j] = slot.value[j];
     return STORM_HIP_OK;
@@ -889,7 +890,10 @@ int storm_hip_multi_dot(const storm_hip_vec *a, const storm_hip_vec *const *bs, 
   if (a && bs && k == 1 && bs[0] && a->ctx == bs[0]->ctx && a->n_owned == bs[0]->n_owned && !a->ctx->lazy_q.empty()) {
     // statements wait (option lazy_statements): the reduction rides in the kernel of the one that writes its operand
     int st = STORM_HIP_OK;
-    if (lazy_try_dot(a->ctx, a->d, bs[0]->d, a->n_owned, out, &st)) return st;
+    if (lazy_try_dot(a->ctx, a->d, bs[0]->d, a->n_owned, out, &st)) {
+      ++a->ctx->n_host_reductions;
+      return st;
+    }
     STORM_TRY(st);
   }
   int request = 0;

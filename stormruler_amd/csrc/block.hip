@@ -361,6 +361,7 @@ int storm_hip_block_dot(const storm_hip_vec *A, const storm_hip_vec *B, int k, d
   storm_hip_ctx *c = A->ctx;
   HIP_TRY(hipSetDevice(c->device));
   STORM_TRY(lazy_sync(c));
+  ++c->n_host_reductions;
   const int64_t n = A->n_owned / k;
   if (n == 0) {
     for (int j = 0; j < k; ++j) out[j] = 0.0;
@@ -466,7 +467,7 @@ int storm_hip_solve_cg_block(const storm_hip_op *op, double alpha, double beta, 
 #undef GO
     HIP_TRY(hipGetLastError());
     bool stop = false;
-    if (it >= lag) STORM_TRY(ring_wait(c, c->h_done_ring, it - lag, &stop));
+    if (it >= lag) STORM_TRY(ring_wait(c, c->h_done_ring, it - lag, &stop, c->ring_gen));
     if (stop) break;
   }
 

@@ -258,6 +258,9 @@ struct storm_hip_ctx {
   const int *api_done = nullptr;
   // diagnostics: which path the solves took (storm_hip_ctx_get_counter)
   int64_t n_resident_solves = 0, n_latency_solves = 0, n_throughput_solves = 0, n_engine_solves = 0, n_cg_fused_steps = 0;
+  int64_t n_host_reductions = 0;    // reduction entry points that made the host wait for their sums (storm_hip_dot ...)
+  int64_t n_jfnk_inner_solves = 0;  // krylov.hip: inner solves of STORM_HIP_JFNK
+  int64_t n_fd_fused_dots = 0;      // krylov.hip: finite-difference products whose difference statement took the reductions of z along
   int64_t n_block_solves = 0;  // storm_hip_solve_cg_block (block.hip)
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
@@ -428,7 +431,8 @@ int state_init(storm_hip_ctx *c, SolverState *d_state, double abs_tol, double re
 // `lag` iterations ahead, polls the word -- no marker in the stream: an event recorded behind every iteration is a
 // barrier with a system-scope release between two kernels, 5.9 us per CG iteration at 256^3
 // (profiles/r03t_event_gap.txt).
-int ring_wait(storm_hip_ctx *c, volatile unsigned long long *ring, int64_t it, bool *stop);  // (words of c->ring_gen only)
+// (words of `generation` only: the one state_init drew for the solve that waits -- a nested solve has drawn another since)
+int ring_wait(storm_hip_ctx *c, volatile unsigned long long *ring, int64_t it, bool *stop, unsigned long long generation);
 
 // spmv.hip
 // y = beta*x + alpha*M x over slices [s0, s1); when dot_w != null also writes

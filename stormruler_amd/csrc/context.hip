@@ -248,6 +248,9 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "throughput_solves")) *value = c->n_throughput_solves;
   else if (!strcmp(key, "engine_solves")) *value = c->n_engine_solves;
   else if (!strcmp(key, "block_solves")) *value = c->n_block_solves;
+  else if (!strcmp(key, "host_reductions")) *value = c->n_host_reductions;
+  else if (!strcmp(key, "jfnk_inner_solves")) *value = c->n_jfnk_inner_solves;
+  else if (!strcmp(key, "fd_fused_dots")) *value = c->n_fd_fused_dots;
   else if (!strcmp(key, "cg_fused_steps")) *value = c->n_cg_fused_steps;
   else if (!strcmp(key, "cg_residual_marches")) *value = c->n_cg_residual_marches;
   else if (!strcmp(key, "cg_residual_plane_marches")) *value = c->n_cg_residual_plane_marches;
@@ -366,10 +369,10 @@ extern "C" int storm_hip_vec_create(storm_hip_ctx *c, int64_t n_owned, int64_t n
 }
 namespace storm {
 // The verdict of iteration index `it` (0-based; the device counts from 1).
-int ring_wait(storm_hip_ctx *c, volatile unsigned long long *ring, int64_t it, bool *stop) {
+int ring_wait(storm_hip_ctx *c, volatile unsigned long long *ring, int64_t it, bool *stop, unsigned long long generation) {
   volatile unsigned long long *w = ring + it % kStateRing;
   const unsigned long long want = (unsigned long long)(it + 1);
-  const unsigned long long gen = c->ring_gen & 0xfffffull;
+  const unsigned long long gen = generation & 0xfffffull;
   auto posted = [&](bool *s) {  // (a word of another generation -- a late post of an aborted solve -- is not this solve's)
     const unsigned long long v = *w;
     if ((v >> 44) != gen) return false;

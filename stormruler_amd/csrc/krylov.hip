@@ -548,6 +548,121 @@ __global__ __launch_bounds__(kBlock) void lin2_dot_prog_kernel(int64_t n, LinArg
   publish_and_finish<2>(partials, mine, f, bx);
 }
 
+// ---- the finite-difference Jacobian: J(y) = (A(x + delta y) - A(x)) / delta, SolverNewton.hpp:143-156 ---------------
+// Two vector statements around the callback, with the REFERENCE's roundings (two per element each), which none of
+// lin_kernel's forms gives: it would contract x + delta y into one fma, and its NESTED form has no c (v1 - v2) without a
+// leading operand.  delta and delta_inverse are registers: the scalar program behind <y, y> leaves them there.
+//
+// s = fl(x + fl(delta y)): the axpbz form fma(1, x, fl(b z)) of the header's table.  The product is a statement of its
+// own, so -ffp-contract=on (contraction within ONE expression) cannot fuse it into the sum.  lin_kernel's streaming shape:
+// one trip per thread, kUnroll independent 16-byte accesses per stream in flight; NT: non-temporal accesses.
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void fd_shift_kernel(int64_t n, double *s, const double *x, const double *y,
+                                                          const double *delta_reg, const int *done, int flags) {
+  if (done && *done) return;
+  const unsigned bx = sweep_block(flags);
+  const double delta = *delta_reg;
+  const std::integral_constant<bool, NT> nt{};
+  const int64_t n2 = n >> 1;
+  double2v *s2 = reinterpret_cast<double2v *>(s);
+  const double2v *x2 = reinterpret_cast<const double2v *>(x), *y2 = reinterpret_cast<const double2v *>(y);
+  for (int64_t base = (int64_t)bx * (kBlock * kUnroll) + threadIdx.x; base < n2;
+       base += (int64_t)gridDim.x * (kBlock * kUnroll)) {
+    double2v vx[kUnroll], vy[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int64_t i = base + u * kBlock;
+      if (i < n2) vx[u] = ldv(x2 + i, nt), vy[u] = ldv(y2 + i, nt);
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int64_t i = base + u * kBlock;
+      if (i < n2) {
+        const double2v prod = delta * vy[u];  // (rounded here ...)
+        const double2v sum = vx[u] + prod;    // (... and here)
+        stv(s2 + i, sum, nt);
+      }
+    }
+  }
+  if ((n & 1) && bx == 0 && threadIdx.x == 0) {
+    const double prod = delta * y[n - 1];
+    const double sum = x[n - 1] + prod;
+    s[n - 1] = sum;
+  }
+}
+
+// z = fl(delta_inverse * fl(z - w)) in place, and per-thread terms of <z, z> / <z, u> of the new z: lin_dot_body's shape
+// and unroll rule with w and u counted as streams.
+template <bool HASW>
+__device__ __forceinline__ void fd_diff_body(int64_t n, double *z, const double *w, const double *u, double dinv, int nt,
+                                             double &acc_zz, double &acc_zu) {
+  const unsigned bx = sweep_block(nt);
+  nt &= 1;
+  const int64_t n2 = n >> 1;
+  double2v *z2 = reinterpret_cast<double2v *>(z);
+  const double2v *w2 = reinterpret_cast<const double2v *>(w), *u2 = reinterpret_cast<const double2v *>(u);
+  constexpr int U = lin_unroll(2 + (HASW ? 1 : 0));
+  nt_dispatch(nt, [&](auto nt) {
+  for (int64_t base = (int64_t)bx * (kBlock * U) + threadIdx.x; base < n2; base += (int64_t)gridDim.x * (kBlock * U)) {
+    double2v vz[U], vw[U], vu[U];
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const int64_t i = base + q * kBlock;
+      if (i < n2) {
+        vz[q] = ldv(z2 + i, nt), vw[q] = ldv(w2 + i, nt);
+        if (HASW) vu[q] = ldv(u2 + i, nt);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const int64_t i = base + q * kBlock;
+      if (i < n2) {
+        const double2v diff = vz[q] - vw[q];
+        const double2v o = dinv * diff;
+        stv(z2 + i, o, nt);
+        acc_zz += o.x * o.x;
+        acc_zz += o.y * o.y;
+        if (HASW) acc_zu += o.x * vu[q].x, acc_zu += o.y * vu[q].y;
+      }
+    }
+  }
+  });
+  if ((n & 1) && bx == 0 && threadIdx.x == 0) {
+    const int64_t i = n - 1;
+    const double diff = z[i] - w[i];
+    const double o = dinv * diff;
+    z[i] = o;
+    acc_zz += o * o;
+    if (HASW) acc_zu += o * u[i];
+  }
+}
+
+// The statement alone: what follows the product is no reduction of z (GMRES's Gram-Schmidt chain, a plain apply).
+__global__ __launch_bounds__(kBlock) void fd_diff_kernel(int64_t n, double *z, const double *w, const double *dinv_reg,
+                                                         const int *done, int nt) {
+  if (done && *done) return;
+  double acc_zz = 0.0, acc_zu = 0.0;
+  fd_diff_body<false>(n, z, w, nullptr, *dinv_reg, nt, acc_zz, acc_zu);
+}
+
+// ... and with the reductions the solver takes of z next in the same pass, finished in the last block with the scalar
+// program behind them (lin_dot_prog_kernel's dot_yy / w pair): BiCGStab's <rt, v> behind its first product, <t, s> and
+// <t, t> behind its second (SolverBiCgStab.hpp:93-165).
+template <bool HASW>
+__global__ __launch_bounds__(kBlock) void fd_diff_dots_prog_kernel(int64_t n, double *z, const double *w, const double *u,
+                                                                   const double *dinv_reg, int dot_zz, double *partials,
+                                                                   const int *done, int nt, FinalPass f) {
+  if (done && *done) return;
+  __shared__ double lds4[4];
+  double acc_zz = 0.0, acc_zu = 0.0;
+  fd_diff_body<HASW>(n, z, w, u, *dinv_reg, nt, acc_zz, acc_zu);
+  double mine[2] = {0.0, 0.0};
+  int j = 0;
+  if (dot_zz) mine[j++] = block_sum256(acc_zz, lds4);
+  if (HASW) mine[j] = block_sum256(acc_zu, lds4);
+  publish_and_finish<2>(partials, mine, f, sweep_block(nt));
+}
+
 }  // namespace kry
 }  // namespace storm
 
@@ -587,6 +702,23 @@ struct KrylovEngine {
   storm_hip_vec *op_t = nullptr;  // ... the first stage's result: one work vector per solve (begin_solve)
   storm_hip_apply_fn op_fn = nullptr;
   void *op_user = nullptr;
+  // fd: A = the finite-difference Jacobian of the callback op_fn at fd_x, with fd_w = op_fn(fd_x) (storm_hip_krylov_set_operator_fd):
+  // z = (op_fn(fd_x + delta y) - fd_w) / delta, delta = safe_divide(mu, |y|).  mu: the host number fd_mu, or the device word fd_mu_dev.
+  bool fd = false;
+  const storm_hip_vec *fd_x = nullptr, *fd_w = nullptr;
+  double fd_mu = 0.0;
+  const double *fd_mu_dev = nullptr;
+  storm_hip_vec *fd_s = nullptr;  // ... the shifted point: one work vector per solve (begin_solve)
+  int r_fd = 0;                   // registers <y, y> -> |y|, delta, delta_inverse, mu
+  // The difference statement z = delta_inverse (z - fd_w) of the last product, held back: when the next thing the method
+  // asks for is a reduction of z it rides in the statement's pass (dots_v), anything else makes it leave alone (flush).
+  bool fd_held = false;
+  double *fd_z = nullptr;
+  const double *pend_fd_u = nullptr;
+  // JFNK (STORM_HIP_JFNK): the inner BiCGStab engine, created with the object and reused by every Newton step
+  storm_hip_krylov *jf_inner = nullptr;
+  int64_t jf_inner_iterations = 0;
+  unsigned long long my_ring_gen = 0;  // the generation state_init drew for THIS solve (a nested solve draws its own)
   storm_hip_apply_fn pre_fn = nullptr;
   void *pre_user = nullptr;
   const storm_hip_vec *pre_diag = nullptr;
@@ -616,7 +748,7 @@ struct KrylovEngine {
   int red_nb = 0, red_k = 0;
   RedOut red_out{};
   // a reduction whose partials kernel is launched at flush(), with the final pass and the scalar program inside
-  enum { PEND_NONE, PEND_DOTS, PEND_LIN_DOT, PEND_LIN2_DOT, PEND_VMUL_DOTS } pend = PEND_NONE;
+  enum { PEND_NONE, PEND_DOTS, PEND_LIN_DOT, PEND_LIN2_DOT, PEND_VMUL_DOTS, PEND_FD_DIFF } pend = PEND_NONE;
   double *pend_z = nullptr;
   const double *pend_d = nullptr, *pend_r = nullptr;
   const double *pend_a = nullptr, *pend_w = nullptr;
@@ -713,14 +845,23 @@ struct KrylovEngine {
         if (ptr == q_lin.v[t]) return true;
     return false;
   }
+  void settle_fd() {  // the held-back difference statement of the finite-difference product goes out alone
+    if (!fd_held) return;
+    fd_held = false;
+    if (!ok() || n <= 0) return;
+    const int64_t per_block = (int64_t)kBlock * lin_unroll(2) * 2;
+    const int64_t nb = std::min<int64_t>(65536, std::max<int64_t>(1, (n + per_block - 1) / per_block));
+    hipLaunchKernelGGL(fd_diff_kernel, dim3((int)nb), dim3(kBlock), 0, c->stream, n, fd_z, fd_w->d, S + r_fd + 2, dp, stream_flags());
+  }
   void flush(bool keep_queued = false) {
+    settle_fd();  // (older than everything else that waits: apply() flushed before it ran the callback)
     if (q_has) {
       const int wait = (keep_queued && ok()) ? prog_lets_queued_wait() : 0;
       if (wait == 0) settle();
       else if (wait == 2) q_gate = (long long)cur_it + 1;
     }
     if (!ok()) {
-      reset_prog(), red_pending = false, q_has = false;
+      reset_prog(), red_pending = false, q_has = false, fd_held = false;
       return;
     }
     if (red_pending && pend != PEND_NONE) {
@@ -742,6 +883,11 @@ struct KrylovEngine {
 #undef DOTS_GO
       } else if (pend == PEND_VMUL_DOTS) {
         hipLaunchKernelGGL(vmul_dots_prog_kernel, g, b, 0, c->stream, n, pend_z, pend_d, pend_r, c->d_partials, dp, nti, f);
+      } else if (pend == PEND_FD_DIFF) {
+        if (pend_fd_u != nullptr)
+          hipLaunchKernelGGL(fd_diff_dots_prog_kernel<true>, g, b, 0, c->stream, n, pend_z, pend_r, pend_fd_u, S + r_fd + 2, pend_yy, c->d_partials, dp, nti, f);
+        else
+          hipLaunchKernelGGL(fd_diff_dots_prog_kernel<false>, g, b, 0, c->stream, n, pend_z, pend_r, pend_fd_u, S + r_fd + 2, pend_yy, c->d_partials, dp, nti, f);
       } else if (pend == PEND_LIN_DOT) {
 #define LIN_GO(NT_)                                                                                                                   \
   if (pend_w != nullptr)                                                                                                              \
@@ -800,7 +946,38 @@ struct KrylovEngine {
     dots_v(a, o);
   }
   bool one_launch(int k) const { return c->comm == nullptr && c->opt_fused_reduce != 0 && n > 0 && k <= kDotChunk; }
+  // The reductions of z behind a finite-difference product -- <z, z> and / or <z, u> for ONE other vector u -- ride in
+  // the pass of its held-back difference statement (fd_diff_dots_prog_kernel).  Same rule as a held-back lin: option
+  // lin_fuse, the one-launch reductions, and a request of exactly that shape; otherwise the statement leaves alone.
+  bool fd_dots(const storm_hip_vec *a, const std::vector<std::pair<int, const storm_hip_vec *>> &outs) {
+    if (!fd_held || !ok() || a->d != fd_z || c->opt_lin_fuse == 0 || !one_launch(2) || n <= 0) return false;
+    if (prog.n > 0 || red_pending || q_has) return false;  // (scalar statements issued since the product come first)
+    int reg_zz = -1, reg_zu = -1;
+    const double *u = nullptr;
+    for (const auto &o : outs) {
+      if (o.second->d == fd_z) {
+        if (reg_zz >= 0) return false;
+        reg_zz = o.first;
+      } else {
+        if (reg_zu >= 0) return false;
+        reg_zu = o.first, u = o.second->d;
+      }
+    }
+    if (outs.empty() || outs.size() > 2) return false;
+    fd_held = false;  // (nothing else waits: apply() flushed before the callback, and nothing was issued since)
+    ++c->n_fd_fused_dots;
+    const int64_t per_block = (int64_t)kBlock * lin_unroll(2 + (u != nullptr ? 1 : 0)) * 2;  // (the kernel's U)
+    int64_t nb = std::max<int64_t>(1, (n + per_block - 1) / per_block);
+    nb = std::min<int64_t>(nb, std::min<int64_t>(32768, c->partials_capacity / 2));
+    pend = PEND_FD_DIFF, pend_z = fd_z, pend_r = fd_w->d, pend_fd_u = u, pend_yy = (int)(reg_zz >= 0), pend_flags = stream_flags();
+    red_k = 0;
+    if (reg_zz >= 0) red_out.idx[red_k++] = reg_zz;
+    if (u != nullptr) red_out.idx[red_k++] = reg_zu;
+    red_nb = (int)nb, red_pending = true;
+    return true;
+  }
   void dots_v(const storm_hip_vec *a, const std::vector<std::pair<int, const storm_hip_vec *>> &outs) {
+    if (fd_dots(a, outs)) return;
     bool overtake = !queued_touches(a->d, false);  // a pure read: conflicts only with the held-back statement's target
     for (const auto &o : outs) overtake = overtake && !queued_touches(o.second->d, false);
     flush(overtake);
@@ -1036,6 +1213,7 @@ struct KrylovEngine {
     ~ApiDone() { c->api_done = saved, --c->callback_depth; }
   };
   void apply(V yv, const storm_hip_vec *xv) {  // y = A(x)          Operator::mul, Operator.hpp:74
+    if (fd) return apply_fd(yv, xv);
     flush();
     if (!ok()) return;
     ++applies;
@@ -1056,6 +1234,33 @@ struct KrylovEngine {
       c->spmv_reverse = 0;
     }
     if (st != STORM_HIP_OK) fail(st);
+  }
+  // z = J(y): four launches -- <y, y> with the scalar program that leaves delta and delta_inverse in their registers, the
+  // shift, the callback, the difference (held back: see fd_held) -- and no scalar on the host.
+  void apply_fd(V zv, const storm_hip_vec *yv) {
+    dot(r_fd, yv, yv);
+    sc(SC_SQRT, r_fd, r_fd);
+    sc(SC_SDIV, r_fd + 1, r_fd + 3, r_fd);   // delta = safe_divide(mu, |y|)                  SolverNewton.hpp:144
+    sc(SC_SDIV, r_fd + 2, R_ONE, r_fd + 1);  // delta_inverse = safe_divide(1, delta)         :147
+    flush();
+    if (!ok()) return;
+    if (n > 0) {
+      const int fl = stream_flags();
+      const dim3 g(stream_blocks(n)), b(kBlock);
+      if (fl & 1) hipLaunchKernelGGL(fd_shift_kernel<true>, g, b, 0, c->stream, n, fd_s->d, fd_x->d, yv->d, S + r_fd + 1, dp, fl);
+      else hipLaunchKernelGGL(fd_shift_kernel<false>, g, b, 0, c->stream, n, fd_s->d, fd_x->d, yv->d, S + r_fd + 1, dp, fl);
+    }
+    ++applies;
+    int st;
+    {
+      ApiDone guard(c, dp);
+      st = op_fn(op_user, zv, fd_s);
+    }
+    if (st != 0) {
+      if (st > 0 || storm_hip_last_error()[0] == 0) set_error("krylov: the operator callback returned %d", st);
+      return fail(st < 0 ? st : STORM_HIP_E_INVALID);
+    }
+    fd_held = true, fd_z = zv->d;
   }
   void pre(V yv, const storm_hip_vec *xv) {  // y = P(x)          Preconditioner::mul
     flush();
@@ -1131,6 +1336,7 @@ struct storm_hip_krylov : KrylovEngine {};  // the opaque handle of the C ABI
 
 namespace {
 typedef KrylovEngine K;
+int jfnk_inner_solve(K *outer);  // (behind krylov_solve_engine, below)
 }
 
 // Registers and work vectors of a method (the reference allocates in init(): e.g. SolverCg.hpp:57-59).
@@ -1201,10 +1407,15 @@ void K::setup() {
       r_a0 = alloc(2 * kMaxMulti);  // classical Gram-Schmidt x2: the two passes' coefficients
       H0 = alloc((m + 1) * m);
     } break;
+    case STORM_HIP_JFNK:  // SolverNewton.hpp:108-111 (s lives in the inner engine: the work vector of its operator)
+      t = vec(), r = vec(), v = vec();  // v: w = A(x)
+      r_a0 = alloc(1);                  // mu
+      break;
     default:
       set_error("krylov: unknown method %d", method);
       fail(STORM_HIP_E_INVALID);
   }
+  if (fd) r_fd = alloc(4);
 }
 
 // ---- GMRES / FGMRES pieces ----------------------------------------------------------------------------------
@@ -1311,6 +1522,11 @@ void K::init() {
     case STORM_HIP_GMRES:
     case STORM_HIP_FGMRES:  // SolverGmres.hpp:51-91
       gmres_start(true);
+      break;
+    case STORM_HIP_JFNK:  // SolverNewton.hpp:106-122: w = A(x); r = b - w (pre_op is taken and never read, :107-109)
+      apply(v, x);
+      lin(r, {{num(1.0), b}, {num(-1.0), v}});
+      norm_to_err_and(SC_BEGIN, r);
       break;
   }
   flush();
@@ -1625,6 +1841,24 @@ void K::iterate(int64_t it) {
         gmres_update_x(k);
       }
     } break;
+
+    case STORM_HIP_JFNK: {  // SolverNewton.hpp:124-161
+      dot(R_T0, x, x);  // mu = sqrt(eps) sqrt(1 + |x|), :128-130, into a register: the inner operator reads it there
+      sc(SC_SQRT, R_T1, R_T0);
+      sc(SC_ADD, R_T1, R_ONE, R_T1);
+      sc(SC_SQRT, R_T1, R_T1);
+      sc(SC_MUL, r_a0, imm(std::sqrt(2.220446049250313e-16)), R_T1);
+      copy(t, r);  // the warm start, :131
+      flush();
+      if (ok()) {
+        const int st = jfnk_inner_solve(this);  // J(x) t = r, :133-155 (the step's only host involvement: its polling)
+        if (st != STORM_HIP_OK) fail(st);
+      }
+      axpy(x, num(1.0), t);  // :156
+      apply(v, x);           // :157
+      lin(r, {{num(1.0), b}, {num(-1.0), v}});
+      norm_to_err_and(SC_ADVANCE, r);
+    } break;
   }
   flush();
 }
@@ -1663,14 +1897,33 @@ int check_ready(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
                   (long long)x->n_halo, (long long)k->op->n_halo);
   }
   if (k->pre_diag) STORM_REQUIRE(k->pre_diag->n_owned == x->n_owned, "krylov: diagonal preconditioner size mismatch");
+  if (k->fd) {
+    STORM_REQUIRE(k->fd_x->ctx == k->c, "krylov: the finite-difference operator's vectors belong to another context");
+    STORM_REQUIRE(k->fd_x->n_owned == x->n_owned, "krylov: the finite-difference operator has %lld rows, x %lld",
+                  (long long)k->fd_x->n_owned, (long long)x->n_owned);
+    STORM_REQUIRE(x != k->fd_x && x != k->fd_w && x->d != k->fd_x->d && x->d != k->fd_w->d,
+                  "krylov: x must not alias the finite-difference operator's linearisation point or w");
+    if (k->method == STORM_HIP_JFNK)
+      STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "krylov: JFNK differentiates the operator itself; it takes no finite-difference operator");
+  }
   STORM_REQUIRE(p->num_iterations >= 0, "krylov: num_iterations < 0");
+  return STORM_HIP_OK;
+}
+
+// mu of a finite-difference operator into its register (stream-ordered: a device word is read when the copy runs)
+int fd_load_mu(K *k) {
+  if (!k->fd) return STORM_HIP_OK;
+  if (k->fd_mu_dev != nullptr)
+    HIP_TRY(hipMemcpyAsync(k->S + k->r_fd + 3, k->fd_mu_dev, sizeof(double), hipMemcpyDeviceToDevice, k->c->stream));
+  else
+    HIP_TRY(hipMemcpyAsync(k->S + k->r_fd + 3, &k->fd_mu, sizeof(double), hipMemcpyHostToDevice, k->c->stream));
   return STORM_HIP_OK;
 }
 
 void release_work(K *k) {
   for (auto *w : k->work) storm_hip_vec_destroy(w);
   k->work.clear();
-  k->op_t = nullptr;
+  k->op_t = nullptr, k->fd_s = nullptr, k->fd_held = false;
   k->qs.clear(), k->zs.clear(), k->rs.clear(), k->us.clear(), k->ps.clear(), k->gs.clear();
   if (k->d_history) (void)hipFree(k->d_history), k->d_history = nullptr;
   k->active = false;
@@ -1705,6 +1958,8 @@ int begin_solve(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
   k->active = true;
   k->setup();
   if (k->two_stage) k->op_t = k->vec();
+  if (k->fd) k->fd_s = k->vec();
+  k->jf_inner_iterations = 0;
   if (!k->ok()) return k->status;
   // register file
   if (k->S_top > k->S_cap) {
@@ -1718,6 +1973,7 @@ int begin_solve(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
     static const double one = 1.0;
     HIP_TRY(hipMemcpyAsync(k->S + R_ONE, &one, sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
+  STORM_TRY(fd_load_mu(k));
   // solver state
   for (int i = 0; i < kStateRing; ++i) k->h_ring[i] = 0;
   if (history && !stepping) {
@@ -1727,6 +1983,7 @@ int begin_solve(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
   // (stepping: the caller owns the convergence decision)
   STORM_TRY(state_init(c, k->d_st, stepping ? 0.0 : p->absolute_error_tolerance, stepping ? 0.0 : p->relative_error_tolerance,
                        stepping ? (1LL << 62) : p->num_iterations, (history && !stepping) ? k->d_history : nullptr, k->d_ring));
+  k->my_ring_gen = c->ring_gen;
   k->init();
   k->applies_after.assign(1, k->applies);
   k->pre_after.assign(1, k->pre_applies);
@@ -1747,7 +2004,7 @@ extern "C" {
 
 int storm_hip_krylov_create(storm_hip_ctx *ctx, int method, storm_hip_krylov **out) {
   STORM_REQUIRE(ctx && out, "krylov_create: null argument");
-  STORM_REQUIRE(method >= STORM_HIP_CG && method <= STORM_HIP_RICHARDSON, "krylov_create: unknown method %d", method);
+  STORM_REQUIRE(method >= STORM_HIP_CG && method <= STORM_HIP_JFNK, "krylov_create: unknown method %d", method);
   *out = nullptr;
   HIP_TRY(hipSetDevice(ctx->device));
   auto *k = new storm_hip_krylov();
@@ -1770,12 +2027,20 @@ int storm_hip_krylov_create(storm_hip_ctx *ctx, int method, storm_hip_krylov **o
       HIP_TRY(e);
     }
   }
+  if (method == STORM_HIP_JFNK) {  // the inner solver of SolverNewton.hpp:133: one object for every Newton step
+    const int st = storm_hip_krylov_create(ctx, STORM_HIP_BICGSTAB, &k->jf_inner);
+    if (st != STORM_HIP_OK) {
+      (void)storm_hip_krylov_destroy(k);
+      return st;
+    }
+  }
   *out = k;
   return STORM_HIP_OK;
 }
 
 int storm_hip_krylov_destroy(storm_hip_krylov *k) {
   if (!k) return STORM_HIP_OK;
+  if (k->jf_inner) (void)storm_hip_krylov_destroy(k->jf_inner), k->jf_inner = nullptr;
   (void)hipSetDevice(k->c->device);
   (void)hipStreamSynchronize(k->c->stream);
   release_work(k);
@@ -1794,6 +2059,7 @@ int storm_hip_krylov_destroy(storm_hip_krylov *k) {
 int storm_hip_krylov_set_operator(storm_hip_krylov *k, const storm_hip_op *op, double alpha, double beta) {
   STORM_REQUIRE(k && op, "krylov_set_operator: null argument");
   k->op = op, k->op_alpha = alpha, k->op_beta = beta, k->op_fn = nullptr, k->op_user = nullptr, k->two_stage = false;
+  k->fd = false;
   return STORM_HIP_OK;
 }
 
@@ -1809,14 +2075,87 @@ int storm_hip_krylov_set_operator2(storm_hip_krylov *k, const storm_hip_op *op, 
   STORM_REQUIRE(k && op, "krylov_set_operator2: null argument");
   STORM_TRY(two_stage_supported(op, "krylov_set_operator2"));
   k->op = op, k->op_alpha = alpha1, k->op_beta = beta1, k->op_alpha2 = alpha2, k->op_beta2 = beta2, k->two_stage = true;
-  k->op_fn = nullptr, k->op_user = nullptr;
+  k->op_fn = nullptr, k->op_user = nullptr, k->fd = false;
   return STORM_HIP_OK;
 }
 
 int storm_hip_krylov_set_operator_fn(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user) {
   STORM_REQUIRE(k && apply, "krylov_set_operator_fn: null argument");
-  k->op = nullptr, k->op_fn = apply, k->op_user = user, k->two_stage = false;
+  k->op = nullptr, k->op_fn = apply, k->op_user = user, k->two_stage = false, k->fd = false;
   return STORM_HIP_OK;
+}
+
+int storm_hip_krylov_set_operator_fd(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user, const storm_hip_vec *x,
+                                     const storm_hip_vec *w, double mu) {
+  STORM_REQUIRE(std::isfinite(mu) && mu > 0.0, "krylov_set_operator_fd: mu = %g must be finite and > 0", mu);
+  STORM_REQUIRE(k && apply && x && w, "krylov_set_operator_fd: null argument");
+  STORM_REQUIRE(x->ctx == k->c && w->ctx == k->c, "krylov_set_operator_fd: x / w belong to another context");
+  STORM_REQUIRE(x->n_owned == w->n_owned, "krylov_set_operator_fd: x has %lld rows, w %lld", (long long)x->n_owned,
+                (long long)w->n_owned);
+  k->op = nullptr, k->op_fn = apply, k->op_user = user, k->two_stage = false;
+  k->fd = true, k->fd_x = x, k->fd_w = w, k->fd_mu = mu, k->fd_mu_dev = nullptr;
+  return STORM_HIP_OK;
+}
+
+int storm_hip_krylov_get_int(const storm_hip_krylov *k, const char *key, int64_t *value) {
+  STORM_REQUIRE(k && key && value, "krylov_get_int: null argument");
+  if (!strcmp(key, "inner_iterations")) *value = k->jf_inner_iterations;
+  else STORM_FAIL(STORM_HIP_E_INVALID, "krylov_get_int: unknown key '%s'", key);
+  return STORM_HIP_OK;
+}
+
+// z = A(y) with the object's operator, outside a solve: enqueued on the context's stream, predicated like any library
+// call when a callback makes it.
+int storm_hip_krylov_apply(storm_hip_krylov *k, const storm_hip_vec *y, storm_hip_vec *z) {
+  STORM_REQUIRE(k && y && z, "krylov_apply: null argument");
+  STORM_REQUIRE(k->op != nullptr || k->op_fn != nullptr, "krylov_apply: no operator set");
+  STORM_REQUIRE(z != y && z->d != y->d, "krylov_apply: z must not alias y");
+  STORM_REQUIRE(y->ctx == k->c && z->ctx == k->c, "krylov_apply: context mismatch");
+  STORM_REQUIRE(y->n_owned == z->n_owned, "krylov_apply: y has %lld rows, z %lld", (long long)y->n_owned, (long long)z->n_owned);
+  STORM_REQUIRE(!k->active, "krylov_apply: a solve is in progress on this object");
+  storm_hip_ctx *c = k->c;
+  if (k->fd) {
+    STORM_REQUIRE(k->fd_x->n_owned == y->n_owned, "krylov_apply: the finite-difference operator has %lld rows, y %lld",
+                  (long long)k->fd_x->n_owned, (long long)y->n_owned);
+    STORM_REQUIRE(z->d != k->fd_x->d && z->d != k->fd_w->d, "krylov_apply: z must not alias the operator's x or w");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  STORM_TRY(lazy_sync(c));
+  if (!k->fd) {
+    if (k->op_fn != nullptr) {
+      const int st = k->op_fn(k->op_user, z, y);
+      if (st == 0) return STORM_HIP_OK;
+      if (st > 0 || storm_hip_last_error()[0] == 0) set_error("krylov_apply: the operator callback returned %d", st);
+      return st < 0 ? st : STORM_HIP_E_INVALID;
+    }
+    if (k->two_stage) return storm_hip_op_apply2(k->op, k->op_alpha, k->op_beta, k->op_alpha2, k->op_beta2, y, nullptr, z);
+    return storm_hip_op_apply(k->op, k->op_alpha, k->op_beta, y, z);
+  }
+  // the engine's statements on a register file of the common registers and the operator's four
+  k->status = STORM_HIP_OK, k->n = y->n_owned, k->dp = c->api_done;
+  k->reset_prog(), k->red_pending = false, k->q_has = false, k->fd_held = false;
+  k->S_top = R_USER;
+  k->r_fd = k->alloc(4);
+  if (k->S_top > k->S_cap) {
+    if (k->S) (void)hipFree(k->S);
+    k->S = nullptr, k->S_cap = 0;
+    HIP_TRY(hipMalloc((void **)&k->S, sizeof(double) * (size_t)k->S_top));
+    k->S_cap = k->S_top;
+  }
+  HIP_TRY(hipMemsetAsync(k->S, 0, sizeof(double) * (size_t)k->S_top, c->stream));
+  {
+    static const double one = 1.0;
+    HIP_TRY(hipMemcpyAsync(k->S + R_ONE, &one, sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  STORM_TRY(fd_load_mu(k));
+  storm_hip_vec *s = nullptr;  // a pooled work vector (stream-ordered: released below, reused by the next call)
+  STORM_TRY(vec_create_work_batch(y, 1, &s));
+  k->fd_s = s;
+  k->apply(z, y);
+  k->flush();
+  k->fd_s = nullptr, k->dp = nullptr;
+  (void)storm_hip_vec_destroy(s);
+  return k->status;
 }
 
 int storm_hip_krylov_set_preconditioner_fn(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user, int side) {
@@ -1859,6 +2198,32 @@ struct EngineSolveArgs {
 int run_engine_body(void *p) {
   const EngineSolveArgs &a = *static_cast<const EngineSolveArgs *>(p);
   return krylov_solve_engine(a.k, a.b, a.x, a.params, a.result, a.history, a.pre_applies);
+}
+
+// A(s) for the inner engine of a JFNK object: the outer object's operator, whatever its kind, as library launches
+// (predicated on the inner solve's flag like any callback's).
+int jfnk_outer_apply(void *user, storm_hip_vec *y, const storm_hip_vec *x) {
+  const K *o = static_cast<const K *>(user);
+  if (o->op_fn != nullptr) return o->op_fn(o->op_user, y, x);
+  if (o->two_stage) return storm_hip_op_apply2(o->op, o->op_alpha, o->op_beta, o->op_alpha2, o->op_beta2, x, o->op_t, y);
+  return storm_hip_op_apply(o->op, o->op_alpha, o->op_beta, x, y);
+}
+// J(x) t = r: the reference's inner BiCGStab (tolerances 1e-8, 2000 iterations, no preconditioner, SolverNewton.hpp:133-135)
+// on the finite-difference operator at (x, w, mu), mu a register of the outer engine.
+int jfnk_inner_solve(K *o) {
+  storm_hip_krylov *in = o->jf_inner;
+  in->op = nullptr, in->two_stage = false, in->op_fn = &jfnk_outer_apply, in->op_user = o;
+  in->fd = true, in->fd_x = o->x, in->fd_w = o->v, in->fd_mu = 0.0, in->fd_mu_dev = o->S + o->r_a0;
+  in->pre_fn = nullptr, in->pre_user = nullptr, in->pre_diag = nullptr;
+  storm_hip_solver_params ip;
+  storm_hip_solver_params_default(&ip);
+  ip.num_iterations = 2000, ip.absolute_error_tolerance = ip.relative_error_tolerance = 1.0e-8;
+  storm_hip_solver_result ir{};
+  ++o->c->n_jfnk_inner_solves;
+  STORM_TRY(krylov_solve_engine(in, o->r, o->t, &ip, &ir, nullptr, nullptr));
+  o->jf_inner_iterations += ir.iterations;
+  o->applies += ir.num_applies;
+  return STORM_HIP_OK;
 }
 }  // namespace
 
@@ -1913,10 +2278,12 @@ static int krylov_solve_engine(storm_hip_krylov *k, const storm_hip_vec *b, stor
     k->it_enqueued = it + 1;
     k->applies_after.push_back(k->applies);
     k->pre_after.push_back(k->pre_applies);
-    // look at the verdict of iteration it - lag
-    if (it >= k->lag) {
+    // look at the verdict of iteration it - lag (JFNK: of this one -- a Newton step past convergence would run a
+    // whole inner solve for nothing, and the inner solve has waited for the device anyway)
+    const int64_t lag = k->method == STORM_HIP_JFNK ? 0 : k->lag;
+    if (it >= lag) {
       bool stop = false;
-      st = ring_wait(c, k->h_ring, it - k->lag, &stop);
+      st = ring_wait(c, k->h_ring, it - lag, &stop, k->my_ring_gen);  // (a nested solve drew a generation of its own since)
       if (stop) break;
     }
   }

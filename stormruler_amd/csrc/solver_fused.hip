@@ -247,7 +247,7 @@ int prepare_state(const FusedSolveArgs &args, Driver *dp) {
 
 int post_and_poll(Driver &d, int64_t it, bool *stop) {
   *stop = false;
-  if (it >= d.lag) STORM_TRY(ring_wait(d.c, d.c->h_done_ring, it - d.lag, stop));
+  if (it >= d.lag) STORM_TRY(ring_wait(d.c, d.c->h_done_ring, it - d.lag, stop, d.c->ring_gen));
   return STORM_HIP_OK;
 }
 
