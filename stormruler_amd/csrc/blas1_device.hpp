@@ -1,4 +1,4 @@
-// Shared by blas1.hip and krylov.hip: the accumulation loop of the multi-dot kernels (ONE definition, so that the
+// Shared by blas1.hip and krylov_engine.hip: the accumulation loop of the multi-dot kernels (ONE definition, so that the
 // partial sums -- and with them every reduction's bits -- do not depend on which kernel ran the loop).
 #pragma once
 #include <type_traits>

@@ -146,7 +146,7 @@ struct storm_hip_ctx {
   storm::SolverState *h_state = nullptr;  // pinned staging copy of the state
   unsigned long long *h_done_ring = nullptr;  // pinned, written by the device's step kernels (solver_device.hpp advance())
   unsigned long long *d_done_ring = nullptr;  // device pointer to the same memory
-  std::vector<storm::KrylovRes> krylov_free;   // krylov.hip: resources of destroyed engines, reused by the next create
+  std::vector<storm::KrylovRes> krylov_free;   // krylov_abi.hip: resources of destroyed engines, reused by the next create
   unsigned long long ring_gen = 0;            // generation of the current solve's ring words (state_init draws the next one)
   // options
   int64_t opt_ell_cap = 0;
@@ -259,8 +259,8 @@ struct storm_hip_ctx {
   // diagnostics: which path the solves took (storm_hip_ctx_get_counter)
   int64_t n_resident_solves = 0, n_latency_solves = 0, n_throughput_solves = 0, n_engine_solves = 0, n_cg_fused_steps = 0;
   int64_t n_host_reductions = 0;    // reduction entry points that made the host wait for their sums (storm_hip_dot ...)
-  int64_t n_jfnk_inner_solves = 0;  // krylov.hip: inner solves of STORM_HIP_JFNK
-  int64_t n_fd_fused_dots = 0;      // krylov.hip: finite-difference products whose difference statement took the reductions of z along
+  int64_t n_jfnk_inner_solves = 0;  // krylov_abi.hip: inner solves of STORM_HIP_JFNK
+  int64_t n_fd_fused_dots = 0;      // krylov_engine.hip: finite-difference products whose difference statement took the reductions of z along
   int64_t n_block_solves = 0;  // storm_hip_solve_cg_block (block.hip)
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
@@ -495,7 +495,7 @@ struct ChainApply {
 int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w, const double *const *q, int k, int m,
                          double *H, double *norm2_out, bool normalise, bool *taken, const MgsGivens *givens,
                          const ChainApply *apply = nullptr, bool *applied = nullptr);
-// solver_gmres.hip: the Gram-Schmidt step of storm_hip_solve_gmres, shared with the general engine (krylov.hip)
+// solver_gmres.hip: the Gram-Schmidt step of storm_hip_solve_gmres, shared with the general engine (krylov_methods.hip)
 int gmres_orthogonalize(storm_hip_ctx *c, int64_t n, const SolverState *st, const int *done, double *qn,
                         const double *const *q, int k, int m, double *H, double *norm2_out, double *scratch,
                         int gram_schmidt, bool *normalised, const MgsGivens *givens = nullptr,

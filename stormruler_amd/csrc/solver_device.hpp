@@ -1,5 +1,5 @@
 // Device-side pieces shared by the solver translation units (solver_fused.hip and the unit of each loop: the fused CG /
-// BiCGStab / GMRES loops of a stencil operator; krylov.hip: the general Krylov engine): the reference's scalar helpers and the
+// BiCGStab / GMRES loops of a stencil operator; krylov_engine.hip: the general Krylov engine): the reference's scalar helpers and the
 // body of IterativeSolver::solve's loop, evaluated on the device against a SolverState -- and the fold and final
 // pass every reduction of the library ends with (blas1.hip's too).
 #pragma once
@@ -148,7 +148,7 @@ struct OutPtrs {
 
 // Final pass of k simultaneous reductions + the scalar epilogue behind them: one block folds partials[j * nblocks ..],
 // on the peer-window transport (use_ipc) exchanges its sums with the other ranks itself (ipc_device.hpp), stores sum j
-// into *out.p[j] and runs epi() -- a scalar step (solver_fused.hpp) or a scalar program (krylov.hip) -- in thread 0.
+// into *out.p[j] and runs epi() -- a scalar step (solver_fused.hpp) or a scalar program (krylov_engine.hip) -- in thread 0.
 template <class Epi, int K>
 __global__ __launch_bounds__(kBlock) void reduce_finish_kernel(const double *__restrict__ partials, int nblocks, int k,
                                                                OutPtrs<K> out, const int *done, IpcDev w, int use_ipc, Epi epi) {

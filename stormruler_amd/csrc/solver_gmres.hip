@@ -1,5 +1,5 @@
 // The fused GMRES(m) loop of a stencil operator (SolverGmres.hpp:51-249), its kernels, and the Gram-Schmidt ladder it
-// shares with the general engine (krylov.hip); see solver_fused.hip.
+// shares with the general engine (krylov_methods.hip); see solver_fused.hip.
 #include <algorithm>
 #include "solver_fused.hpp"
 #include "blas1_device.hpp"
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(kWave) void gmres_backsolve_kernel(SolverState *st,
 //     step applies  w -= H(i,k) q_i  and already accumulates the next reduction (<w,q_{i+1}>, or <w,w>);
 //   gram_schmidt == 1: classical Gram-Schmidt applied twice (2 multi-dots + 2 multi-axpys, batched reductions);
 //     `scratch` = 2 * kMaxMulti doubles for the two passes' coefficients.
-// Shared by storm_hip_solve_gmres below and by the general engine (krylov.hip).
+// Shared by storm_hip_solve_gmres below and by the general engine (krylov_methods.hip).
 // *normalised (nullable) = true when qn has already been divided by its norm (the cooperative chain does that).
 int gmres_orthogonalize(storm_hip_ctx *c, int64_t n, const SolverState *st, const int *done, double *qn,
                         const double *const *q, int k, int m, double *H, double *norm2_out, double *scratch,

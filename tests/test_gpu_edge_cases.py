@@ -370,7 +370,7 @@ def test_solve_non_uniform_shifts_an_affine_operator(env):
 @pytest.mark.parametrize("kind", ["cg", "bicgstab", "cgs", "tfqmr", "idrs", "bicgstabl"])
 @pytest.mark.parametrize("shape", [(9, 7, 5), (40, 40, 40), (64, 64, 64)])
 def test_one_launch_reductions_give_the_same_bits(kind, shape):
-    """Engine reductions finish in the partials kernel itself (option `fused_reduce`, csrc/krylov.hip
+    """Engine reductions finish in the partials kernel itself (option `fused_reduce`, csrc/krylov_engine.hip
     publish_and_finish over csrc/ticket_device.hpp): run to run the residual history and x must be IDENTICAL; against
     the two-launch final pass (another folding order) they agree to rounding.  With a lambda operator and with a
     diagonal preconditioner."""
@@ -457,7 +457,7 @@ def test_ticket_groups_at_their_edges(n_rows):
 @pytest.mark.parametrize("kind", ["cg", "bicgstab", "cgs", "tfqmr", "tfqmr1", "idrs", "bicgstabl", "gmres", "fgmres"])
 def test_paired_vector_statements_give_the_same_bits(kind):
     """The engine holds one vector statement back and sends two consecutive ones out as ONE pass (`lin_fuse`,
-    csrc/krylov.hip lin2_kernel), or lets an independent reduction overtake it.  Elementwise statements executed per
+    csrc/krylov_device.hpp lin2_kernel), or lets an independent reduction overtake it.  Elementwise statements executed per
     element in program order are the same arithmetic: histories and x IDENTICAL with the option off; lambda operator,
     Jacobi preconditioner on either side."""
     from stormruler_amd import api, mesh

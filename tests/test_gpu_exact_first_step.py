@@ -134,7 +134,7 @@ CG_SMALL = [
     # CSR tail: no fused dot in the SpMV (nb == 0), <p,z> by a separate k_multi_dot
     ("tail", {"latency_path": 0}, "throughput_solves", 0),
     ("tail", {"latency_path": 0, "ticket_reduce": 0}, "throughput_solves", 0),
-    # the engine (krylov.hip): the reference's statements as kernels, scalar programs behind reduce_finish_kernel
+    # the engine (krylov_*.hip): the reference's statements as kernels, scalar programs behind reduce_finish_kernel
     ("lattice", {"generic_solvers": 1}, "engine_solves", 0),
     ("tail", {"generic_solvers": 1}, "engine_solves", 0),
     ("lattice", {"generic_solvers": 1, "ticket_reduce": 0}, "engine_solves", 0),
@@ -289,7 +289,7 @@ def test_gmres_first_step(env, fmt, m, chain):
 
 # ---- the engine's other methods -------------------------------------------------------------------------------------------
 #
-# CGS, TFQMR, TFQMR1, Richardson, BiCGStab(l), IDR(s) (krylov.hip) and the preconditioned engine solves against the
+# CGS, TFQMR, TFQMR1, Richardson, BiCGStab(l), IDR(s) (krylov_methods.hip) and the preconditioned engine solves against the
 # coefficient-form restatement of the reference's headers (tests/exact_ref.py, ``Pins``): history[0] bitwise wherever
 # r0 is b, Richardson (omega = 2^-5) bitwise in x_k and history[1], history[1] of the rest by the floor rule or the
 # closed forms, every later or preconditioned entry within max(floor, 16 e_k) of the exact value, e_k the oracle's own

@@ -6,7 +6,7 @@
     configs[3]  GMRES(30), convection-diffusion 128^3       376 iterations
 
 Every case runs twice on the device: through the fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip (what a stencil operator gets)
-and through the general engine of csrc/krylov.hip (`generic_solvers = 1`: what a callback operator gets).
+and through the general engine of csrc/krylov_*.hip (`generic_solvers = 1`: what a callback operator gets).
 
 CG and GMRES reproduce the fixtures: same iteration count and operator applications, every entry of the residual
 history to 1e-7 relative (measured: 1.7e-8 / 2.1e-8 -- tree sums against sequential ones over 1.7e7 / 2.1e6 terms), the

@@ -18,7 +18,7 @@ for kv in sys.argv[2:]:
 g = mesh.structured_box(n)
 mat = api.StencilMatrix.from_face_graph(ctx, g)
 op = api.HipStencilOperator(mat, -1.0, 0.0)
-if os.environ.get("FIXED_COST_LAMBDA"):  # the operator as a lambda (the general engine, csrc/krylov.hip)
+if os.environ.get("FIXED_COST_LAMBDA"):  # the operator as a lambda (the general engine, csrc/krylov_*.hip)
     op = api.make_operator(lambda y, x: mat.apply(-1.0, 0.0, x, y))
 b = api.DeviceVector(ctx, g.n_cells)
 api.fill_with(b, 1.0)

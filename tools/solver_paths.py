@@ -2,7 +2,7 @@
 """Iteration rates of the solver PATHS of this library on one MI355X (one JSON line per case, for profiles/):
 
     fused          stencil operator, the fused kernels of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip (CG / BiCGStab / GMRES only)
-    engine         stencil operator through the general engine of csrc/krylov.hip (`generic_solvers = 1`)
+    engine         stencil operator through the general engine of csrc/krylov_*.hip (`generic_solvers = 1`)
     engine-lambda  the operator handed over as a lambda through make_operator -- what the reference's only call
                    site does (Playground.cpp:151-167) -- device-resident loop, the callback only enqueues
     engine-jacobi  stencil operator + the diagonal preconditioner behind pre_op
