@@ -335,6 +335,8 @@ int storm_hip_op_create_csr(storm_hip_ctx *ctx, int64_t n_rows, int64_t n_halo,
  *              its LDS-ring and four-steps-per-synchronisation forms (2 = forced, for tests; 0 = off);
  *   mgs_steps (4): modified-Gram-Schmidt steps per pass over w on the kernel-per-statement path (2, 3, 4);
  *   generic_solvers (0): 1 sends storm_hip_krylov_solve through the engine even where a fused loop exists;
+ *   cheb_fused (1): storm_hip_cheb_apply runs its fused step kernel where it applies (fp64 records, no CSR tail); 0: the
+ *              statement path everywhere (the same bits);
  *   cg_fuse (1), cg_march (8), cg_march_fill (2048): the SpMV launch of a tiled format-4 operator ends the previous CG
  *              iteration (x += alpha p, p = r + beta p) itself, as blocks marching through this many planes (0: tiles), fewer
  *              planes per block on small lattices so that the grid holds about cg_march_fill blocks (0: as given);
@@ -393,7 +395,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *ctx, const char *key, int64_t value)
  * fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip), "engine_solves" (csrc/krylov_abi.hip), "jfnk_inner_solves" (inner BiCGStab solves of
  * STORM_HIP_JFNK), "fd_fused_dots" (products of a finite-difference operator whose difference statement took the method's
  * reductions of z along in its pass), "host_reductions" (calls of storm_hip_dot / _norm2 / _multi_dot / _multi_dot_end / _block_dot: the reduction
- * entry points that make the host wait for their sums -- a device-resident loop leaves it where it was), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "cg_fused_steps" (solves whose CG step rode in
+ * entry points that make the host wait for their sums -- a device-resident loop leaves it where it was), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "cheb_fused_applies" / "cheb_statement_applies" (storm_hip_cheb_apply by path), "cg_fused_steps" (solves whose CG step rode in
  * the SpMV launch), "lazy_fused_dots" / "lazy_fused_pairs" / "lazy_apply_dots" / "lazy_cg_steps" / "lazy_waiting" (option
  * lazy_statements: reductions that rode in a statement's kernel, pairs of statements that left as one pass, applies that
  * left with a fused dot, fused CG steps, statements waiting now).  On the peer-window transport, where the time of the exchanges went (ticks of 10 ns of the device's
@@ -711,6 +713,53 @@ int storm_hip_krylov_init(storm_hip_krylov *k, const storm_hip_vec *b, storm_hip
                           const storm_hip_solver_params *params, double *initial_error);
 int storm_hip_krylov_iterate(storm_hip_krylov *k, double *error);
 int storm_hip_krylov_finalize(storm_hip_krylov *k);
+
+/* ---- Chebyshev polynomial preconditioner -------------------------------------------------------------------------
+ * z = p_m(diag(s) A) diag(s) r for A = beta I + alpha M and an optional scale s (e.g. the inverse diagonal; s = 1
+ * without): Saad, Iterative Methods for Sparse Linear Systems, Alg. 12.1 started from zero, for an eigenvalue interval
+ * [lmin, lmax] of diag(s) A.  With theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta,
+ * rho_0 = 1 / sigma:
+ *     d_0 = (s .* r) / theta,  z = d_0,  res = r;
+ *     for k = 0 .. m-1:  res -= A d_k;  rho_{k+1} = 1 / (2 sigma - rho_k);
+ *                        d_{k+1} = (rho_{k+1} rho_k) d_k + (2 rho_{k+1} / delta) (s .* res);  z += d_{k+1}
+ * The residual polynomial is T_{m+1}((theta - lambda) / delta) / T_{m+1}(sigma).  Only operator applies and streaming
+ * statements: no reduction, no host wait; a fixed linear operator (SPD where diag(s) A is and the interval holds its
+ * spectrum), so every method and side may use it.  degree = m = operator products per apply, 1 .. 16.
+ *
+ * Two paths give the same bits (tests/test_gpu_cheb.py).  The STATEMENT path, for every record format, is this sequence
+ * of library calls (d, e: the object's two direction buffers, swapped after every step; it = 1 / theta, a host double):
+ *     d_0:      s given:  storm_hip_vmul(d, s, r);  storm_hip_axpbz(d, it, d, 0, d)      else  storm_hip_axpbz(d, it, r, 0, r)
+ *     step k:   storm_hip_op_apply(op, alpha, beta, d, e)
+ *               storm_hip_axpbz(res, 1, k == 0 ? r : res, -1, e)
+ *               s given:  storm_hip_vmul(e, s, res);  storm_hip_axpbz(e, c1_k, d, c2_k, e)   else  storm_hip_axpbz(e, c1_k, d, c2_k, res)
+ *               k == 0:   storm_hip_axpbz(z, 1, d, 1, e)                                       else  storm_hip_axpy(z, 1, e)
+ * The FUSED path (option cheb_fused, default 1; operators on fp64 records -- built with option spmv_dict = 0 -- without
+ * a CSR tail) is one streaming kernel for d_0 and one kernel per step that forms the row's product and updates res, the
+ * direction and z on the row it holds: m + 1 launches instead of about 4 m + 1.  Counters "cheb_fused_applies" and
+ * "cheb_statement_applies" (storm_hip_ctx_get_counter) say which path an apply took. */
+typedef struct storm_hip_cheb storm_hip_cheb;
+/* theta and the m pairs c1[k] = rho_{k+1} rho_k, c2[k] = 2 rho_{k+1} / delta.  Host code, needs no device.
+ * STORM_HIP_E_INVALID unless 0 < lmin < lmax, both finite, 1 <= degree <= 16. */
+int storm_hip_cheb_coefficients(double lmin, double lmax, int degree, double *theta, double *c1, double *c2);
+/* Gershgorin's bound of diag(s) A, A = beta I + alpha M:  max_i |s_i| (|a_ii| + sum_k |alpha w_ik|); scale may be NULL
+ * (s = 1).  Every record format, ELL records and CSR tail.  One host wait (build time).  Halo plan / communicator:
+ * STORM_HIP_E_UNSUPPORTED. */
+int storm_hip_op_gershgorin(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *scale,
+                            double *lambda_max);
+/* lmax <= 0: Gershgorin's bound is taken; lmin <= 0: lmax / 30 (the ratio hypre and Ifpack2 default to -- a default, not
+ * a claim).  The object owns three work vectors; `op` and `dinv` (nullable) must outlive it -- applying an object
+ * whose operator was destroyed is the caller's error.  Halo plan / communicator: STORM_HIP_E_UNSUPPORTED. */
+int storm_hip_cheb_create(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *dinv, int degree,
+                          double lmin, double lmax, storm_hip_cheb **out);
+/* z = P(r); z must not alias r, r is not written.  Enqueues and never waits; inside a solver callback the kernels are
+ * predicated on the solve's `done` flag like those of storm_hip_vmul and storm_hip_op_apply. */
+int storm_hip_cheb_apply(const storm_hip_cheb *h, const storm_hip_vec *r, storm_hip_vec *z);
+/* "lambda_min", "lambda_max" (the bounds in use, defaults resolved), "degree". */
+int storm_hip_cheb_get(const storm_hip_cheb *h, const char *key, double *value);
+int storm_hip_cheb_destroy(storm_hip_cheb *h);
+/* pre_op as the library's Chebyshev preconditioner (h == NULL removes it): bound natively, no callback.  Its operator
+ * need not be the solve's.  A size that differs from the solve's vectors: STORM_HIP_E_INVALID from the solve. */
+int storm_hip_krylov_set_preconditioner_cheb(storm_hip_krylov *k, const storm_hip_cheb *h, int side);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -854,6 +854,56 @@ private:
   DeviceVector _dinv;
 };
 
+/// Chebyshev polynomial preconditioner z = p_m(diag(s) A) diag(s) r of a HipStencilOperator (storm_hip_cheb_*,
+/// storm_hip.h): `degree` operator products per apply, no reduction, no host wait.  lambda_max <= 0 takes Gershgorin's
+/// bound, lambda_min <= 0 a thirtieth of lambda_max; `jacobi` scales with the inverse diagonal.  The knob-holder solvers
+/// bind it natively; `mul` is storm_hip_cheb_apply.  The operator it was built from must outlive it.
+class ChebyshevPreconditioner final : public Preconditioner<DeviceVector> {
+public:
+  int degree = 4;
+  real_t lambda_min = 0.0, lambda_max = 0.0;
+  bool jacobi = false;
+
+  ChebyshevPreconditioner() = default;
+  explicit ChebyshevPreconditioner(int degree_, real_t lambda_min_ = 0.0, real_t lambda_max_ = 0.0, bool jacobi_ = false)
+      : degree(degree_), lambda_min(lambda_min_), lambda_max(lambda_max_), jacobi(jacobi_) {}
+  ChebyshevPreconditioner(const ChebyshevPreconditioner&) = delete;
+  ChebyshevPreconditioner& operator=(const ChebyshevPreconditioner&) = delete;
+  ~ChebyshevPreconditioner() override { storm_hip_cheb_destroy(_h); }
+
+  void build(const DeviceVector& x_vec, const DeviceVector& /*b_vec*/, const Operator<DeviceVector>& any_op) override {
+    if (dynamic_cast<const HipTwoStageOperator*>(&any_op) != nullptr)
+      throw std::runtime_error("ChebyshevPreconditioner cannot take a HipTwoStageOperator");
+    const auto* hip_op = dynamic_cast<const HipStencilOperator*>(&any_op);
+    if (hip_op == nullptr) throw std::runtime_error("ChebyshevPreconditioner needs a HipStencilOperator");
+    storm_hip_cheb_destroy(_h);
+    _h = nullptr;
+    if (jacobi) {
+      _dinv.assign(x_vec, false);
+      detail::check(storm_hip_op_get_diagonal(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), 1, _dinv.handle()));
+    }
+    detail::check(storm_hip_cheb_create(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(),
+                                        jacobi ? _dinv.handle() : nullptr, degree, lambda_min, lambda_max, &_h));
+  }
+  void mul(DeviceVector& y_vec, const DeviceVector& x_vec) const override {
+    detail::check(storm_hip_cheb_apply(_h, x_vec.handle(), y_vec.handle()));
+  }
+  void conj_mul(DeviceVector& x_vec, const DeviceVector& y_vec) const override {
+    detail::check(storm_hip_cheb_apply(_h, y_vec.handle(), x_vec.handle()));
+  }
+  /// "lambda_min" / "lambda_max" (the bounds in use) or "degree".
+  real_t get(const char* key) const {
+    double v = 0.0;
+    detail::check(storm_hip_cheb_get(_h, key, &v));
+    return v;
+  }
+  const storm_hip_cheb* handle() const noexcept { return _h; }
+
+private:
+  DeviceVector _dinv;
+  storm_hip_cheb* _h = nullptr;
+};
+
 #ifndef STORM_HIP_NO_SOLVERS
 // ---------------------------------------------------------------------------------------------
 template<class InVector, class OutVector = InVector>
@@ -880,7 +930,7 @@ inline void log_solve(std::size_t iteration, real_t absolute_error, real_t relat
 /// caller's Operator / Preconditioner objects bound to it.  A HipStencilOperator, HipTwoStageOperator or HipFdJacobianOperator
 /// (its inner operator as the callback) binds natively; any other
 /// operator (a lambda through make_operator, Playground.cpp:151-167) and any preconditioner but the Jacobi
-/// one bind as callbacks, which only enqueue kernels.  An exception thrown inside a callback aborts the solve
+/// and the Chebyshev one bind as callbacks, which only enqueue kernels.  An exception thrown inside a callback aborts the solve
 /// and is rethrown from the call that ran it.
 class Engine {
 public:
@@ -917,6 +967,8 @@ public:
       check(storm_hip_krylov_set_preconditioner_diag(_h, nullptr, c_side));
     else if (const auto* jacobi = dynamic_cast<const JacobiPreconditioner*>(pre_op))
       check(storm_hip_krylov_set_preconditioner_diag(_h, jacobi->inverse_diagonal().handle(), c_side));
+    else if (const auto* cheb = dynamic_cast<const ChebyshevPreconditioner*>(pre_op))
+      check(storm_hip_krylov_set_preconditioner_cheb(_h, cheb->handle(), c_side));
     else
       check(storm_hip_krylov_set_preconditioner_fn(_h, &Engine::trampoline, &_pre, c_side));
   }

@@ -177,6 +177,13 @@ SIGNATURES = {
     "storm_hip_krylov_init": (C.c_int, [vp, vp, vp, C.POINTER(SolverParams), f64p]),
     "storm_hip_krylov_iterate": (C.c_int, [vp, f64p]),
     "storm_hip_krylov_finalize": (C.c_int, [vp]),
+    "storm_hip_cheb_coefficients": (C.c_int, [C.c_double, C.c_double, C.c_int, f64p, f64p, f64p]),
+    "storm_hip_op_gershgorin": (C.c_int, [vp, C.c_double, C.c_double, vp, f64p]),
+    "storm_hip_cheb_create": (C.c_int, [vp, C.c_double, C.c_double, vp, C.c_int, C.c_double, C.c_double, C.POINTER(vp)]),
+    "storm_hip_cheb_apply": (C.c_int, [vp, vp, vp]),
+    "storm_hip_cheb_get": (C.c_int, [vp, C.c_char_p, f64p]),
+    "storm_hip_cheb_destroy": (C.c_int, [vp]),
+    "storm_hip_krylov_set_preconditioner_cheb": (C.c_int, [vp, vp, C.c_int]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -714,6 +714,13 @@ class StencilMatrix:
         """``d`` <- the diagonal of ``beta*I + alpha*M`` (its safe inverse with ``invert``)."""
         check(lib.storm_hip_op_get_diagonal(self._h, float(alpha), float(beta), int(invert), d._h))
 
+    def gershgorin(self, alpha: float, beta: float, scale: Optional[DeviceVector] = None) -> float:
+        """Gershgorin's bound ``max_i |s_i| (|a_ii| + sum_k |a_ik|)`` of ``diag(s) (beta*I + alpha*M)`` (``s = 1`` without
+        ``scale``): an upper bound of the largest eigenvalue.  One host wait."""
+        v = C.c_double()
+        check(lib.storm_hip_op_gershgorin(self._h, float(alpha), float(beta), None if scale is None else scale._h, C.byref(v)))
+        return v.value
+
     def close(self):
         if getattr(self, "_h", None):
             if getattr(self.ctx, "_h", None):  # never touch a dead context (see DeviceVector._free)
@@ -845,6 +852,78 @@ class JacobiPreconditioner(Preconditioner):
         vmul(x_vec, self._dinv, y_vec)
 
 
+def cheb_coefficients(lambda_min: float, lambda_max: float, degree: int):
+    """``(theta, c1, c2)`` of the Chebyshev recurrence on ``[lambda_min, lambda_max]`` (``storm_hip_cheb_coefficients``):
+    ``d_0 = (s .* r) / theta`` and ``d_{k+1} = c1[k] d_k + c2[k] (s .* res)``.  Host code."""
+    degree = int(degree)
+    theta = C.c_double()
+    c1 = np.zeros(max(degree, 1))
+    c2 = np.zeros(max(degree, 1))
+    check(lib.storm_hip_cheb_coefficients(float(lambda_min), float(lambda_max), degree, C.byref(theta),
+                                          c1.ctypes.data_as(_lib.f64p), c2.ctypes.data_as(_lib.f64p)))
+    return theta.value, c1[:degree], c2[:degree]
+
+
+class ChebyshevPreconditioner(Preconditioner):
+    """Chebyshev polynomial preconditioner ``z = p_m(diag(s) A) diag(s) r`` for a :class:`HipStencilOperator`
+    (``storm_hip_cheb_*``, include/storm_hip.h): ``degree`` operator products per apply, no reduction and no host wait.
+    ``lambda_max=None`` takes Gershgorin's bound, ``lambda_min=None`` a thirtieth of ``lambda_max``; ``jacobi`` scales with
+    the inverse diagonal.  The solvers bind it natively; :meth:`mul` is ``storm_hip_cheb_apply``, so it is an operator on
+    its own as well.  The operator it was built from must outlive it."""
+
+    def __init__(self, degree: int = 4, lambda_min: Optional[float] = None, lambda_max: Optional[float] = None,
+                 jacobi: bool = False):
+        self.degree, self.lambda_min, self.lambda_max, self.jacobi = int(degree), lambda_min, lambda_max, bool(jacobi)
+        self._h, self._dinv, self._op, self.ctx = None, None, None, None
+
+    def build(self, x_vec, b_vec, any_op) -> None:
+        if isinstance(any_op, HipTwoStageOperator):
+            raise TypeError("ChebyshevPreconditioner cannot take a HipTwoStageOperator (its applies are those of one "
+                            "stage); precondition with another operator")
+        if not isinstance(any_op, HipStencilOperator):
+            raise TypeError("ChebyshevPreconditioner needs a HipStencilOperator to apply")
+        self._free()
+        self.ctx, self._op = x_vec.ctx, any_op
+        if self.jacobi:
+            self._dinv = _like(x_vec)
+            any_op.matrix.diagonal(any_op.alpha, any_op.beta, self._dinv, invert=True)
+        h = C.c_void_p()
+        check(lib.storm_hip_cheb_create(any_op.matrix._h, any_op.alpha, any_op.beta,
+                                        None if self._dinv is None else self._dinv._h, self.degree,
+                                        0.0 if self.lambda_min is None else float(self.lambda_min),
+                                        0.0 if self.lambda_max is None else float(self.lambda_max), C.byref(h)))
+        self._h = h
+        self.ctx._children.add(self)
+
+    def get(self, key: str) -> float:
+        """``lambda_min`` / ``lambda_max`` (the bounds in use) or ``degree``."""
+        v = C.c_double()
+        check(lib.storm_hip_cheb_get(self._h, key.encode(), C.byref(v)))
+        return v.value
+
+    def mul(self, y_vec, x_vec):
+        check(lib.storm_hip_cheb_apply(self._h, x_vec._h, y_vec._h))
+
+    def conj_mul(self, x_vec, y_vec):  # (a polynomial of a symmetric operator is symmetric)
+        check(lib.storm_hip_cheb_apply(self._h, y_vec._h, x_vec._h))
+
+    def _free(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):
+                lib.storm_hip_cheb_destroy(self._h)
+            self._h = None
+        self._dinv = None
+
+    def close(self):
+        self._free()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self._free()
+        except Exception:
+            pass
+
+
 class Solver:  # Solver.hpp:43-57
     def solve(self, x_vec: DeviceVector, b_vec: DeviceVector, any_op: Operator) -> bool:
         raise NotImplementedError
@@ -855,7 +934,7 @@ class _Engine:
     reference-side objects bound to it: a :class:`HipStencilOperator` or :class:`HipTwoStageOperator` binds natively, any other ``Operator`` --
     e.g. a lambda through ``make_operator``, the reference's only call site (Playground.cpp:151-167) -- as a
     callback that merely enqueues its kernels; likewise ``pre_op`` (a :class:`JacobiPreconditioner` binds as a
-    device diagonal).  An exception raised inside a callback aborts the solve and is re-raised from it."""
+    device diagonal, a :class:`ChebyshevPreconditioner` as the library's object).  An exception raised inside a callback aborts the solve and is re-raised from it."""
 
     def __init__(self, ctx: Context, method: int):
         h = C.c_void_p()
@@ -904,6 +983,8 @@ class _Engine:
             check(lib.storm_hip_krylov_set_preconditioner_diag(self._h, None, int(pre_side)))
         elif isinstance(pre_op, JacobiPreconditioner):
             check(lib.storm_hip_krylov_set_preconditioner_diag(self._h, pre_op._dinv._h, int(pre_side)))
+        elif isinstance(pre_op, ChebyshevPreconditioner):
+            check(lib.storm_hip_krylov_set_preconditioner_cheb(self._h, pre_op._h, int(pre_side)))
         else:
             check(lib.storm_hip_krylov_set_preconditioner_fn(self._h, self._callback(pre_op.mul), None, int(pre_side)))
 

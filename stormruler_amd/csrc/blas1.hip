@@ -97,7 +97,7 @@ struct AxpbzF {
   Scal a, b;
   double av, bv;
   __device__ void prepare() { av = ld_scal(a), bv = ld_scal(b); }
-  __device__ double operator()(double, double x0, double x1) const { return av * x0 + bv * x1; }
+  __device__ double operator()(double, double x0, double x1) const { return axpbz_value(av, x0, bv, x1); }
 };
 // y = a*x0: the one-term statement `y <<= a * x` (a x + 0 x is NaN for x = +-inf and +0 for a < 0, x = +0)
 struct ScaleXF {

@@ -32,6 +32,10 @@ __device__ __forceinline__ void nt_dispatch(int nt, Body &&body) {  // bit 0 of 
   else body(std::false_type{});
 }
 
+// y = a x0 + b x1 of storm_hip_axpbz, ONE statement (-ffp-contract=on contracts within a statement only): AxpbzF (blas1.hip) and
+// the fused Chebyshev step (precond_cheb.hip) both call it, so the statement and its fused form round alike.
+__device__ __forceinline__ double axpbz_value(double a, double x0, double b, double x1) { return a * x0 + b * x1; }
+
 // KB sums at once, ONE pair of barriers: the same wave trees and the same (w0 + w1) + (w2 + w3) as block_sum256, so the
 // same bits; sums[j] valid in every thread.
 template <int KB>

@@ -262,6 +262,8 @@ struct storm_hip_ctx {
   int64_t n_jfnk_inner_solves = 0;  // krylov_abi.hip: inner solves of STORM_HIP_JFNK
   int64_t n_fd_fused_dots = 0;      // krylov_engine.hip: finite-difference products whose difference statement took the reductions of z along
   int64_t n_block_solves = 0;  // storm_hip_solve_cg_block (block.hip)
+  int64_t opt_cheb_fused = 1;  // storm_hip_cheb_apply: the fused step kernel where it applies (fp64 records, no CSR tail); 0: library statements everywhere
+  int64_t n_cheb_fused_applies = 0, n_cheb_statement_applies = 0;  // precond_cheb.hip: which path an apply took
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_cg_pz_consumer_folds = 0;  // ... of those, the solves whose plane march folded <p,z> itself (option cg_pz_fold)
@@ -336,6 +338,19 @@ struct storm_hip_op {
   int64_t *d_lat_off = nullptr;
   int64_t lat_bytes = 0;
   storm::HaloPlan halo;
+};
+
+// The Chebyshev polynomial preconditioner (precond_cheb.hip): z = p_m(diag(s) A) diag(s) r for A = beta I + alpha M.
+constexpr int kChebMaxDegree = 16;
+struct storm_hip_cheb {
+  storm_hip_ctx *ctx = nullptr;
+  const storm_hip_op *op = nullptr;  // not owned
+  double alpha = 0.0, beta = 0.0;
+  const storm_hip_vec *dinv = nullptr;  // the scale s (not owned), or null: s = 1
+  int degree = 0;
+  double lmin = 0.0, lmax = 0.0, theta = 0.0, inv_theta = 0.0;
+  double c1[kChebMaxDegree] = {}, c2[kChebMaxDegree] = {};  // (rho_{k+1} rho_k, 2 rho_{k+1} / delta)
+  storm_hip_vec *d[2] = {nullptr, nullptr}, *res = nullptr;  // the two direction buffers and the residual
 };
 
 namespace storm {

@@ -237,6 +237,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *c, const char *key, int64_t value) {
   else if (!strcmp(key, "cg_pz_fold")) c->opt_cg_pz_fold = value;
   else if (!strcmp(key, "spmv_record_index")) c->opt_spmv_record_index = value;
   else if (!strcmp(key, "blas1_nt")) c->opt_blas1_nt = value;
+  else if (!strcmp(key, "cheb_fused")) c->opt_cheb_fused = value;
   else STORM_FAIL(STORM_HIP_E_INVALID, "ctx_set_option: unknown key '%s'", key);
   return STORM_HIP_OK;
 }
@@ -249,6 +250,8 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "engine_solves")) *value = c->n_engine_solves;
   else if (!strcmp(key, "block_solves")) *value = c->n_block_solves;
   else if (!strcmp(key, "host_reductions")) *value = c->n_host_reductions;
+  else if (!strcmp(key, "cheb_fused_applies")) *value = c->n_cheb_fused_applies;
+  else if (!strcmp(key, "cheb_statement_applies")) *value = c->n_cheb_statement_applies;
   else if (!strcmp(key, "jfnk_inner_solves")) *value = c->n_jfnk_inner_solves;
   else if (!strcmp(key, "fd_fused_dots")) *value = c->n_fd_fused_dots;
   else if (!strcmp(key, "cg_fused_steps")) *value = c->n_cg_fused_steps;

@@ -24,6 +24,11 @@ int check_ready(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
                   (long long)x->n_halo, (long long)op.stencil->n_halo);
   }
   if (k->pre_diag) STORM_REQUIRE(k->pre_diag->n_owned == x->n_owned, "krylov: diagonal preconditioner size mismatch");
+  if (k->pre_cheb) {
+    STORM_REQUIRE(k->pre_cheb->ctx == k->c, "krylov: the Chebyshev preconditioner belongs to another context");
+    STORM_REQUIRE(k->pre_cheb->op->n_rows == x->n_owned, "krylov: the Chebyshev preconditioner has %lld rows, x %lld",
+                  (long long)k->pre_cheb->op->n_rows, (long long)x->n_owned);
+  }
   if (op.is(Operator::FD)) {
     STORM_REQUIRE(op.x->ctx == k->c, "krylov: the finite-difference operator's vectors belong to another context");
     STORM_REQUIRE(op.x->n_owned == x->n_owned, "krylov: the finite-difference operator has %lld rows, x %lld",
@@ -229,7 +234,7 @@ int jfnk_outer_apply(void *user, storm_hip_vec *y, const storm_hip_vec *x) {
 int storm::kry::jfnk_inner_solve(K *o) {
   storm_hip_krylov *in = o->jf_inner;
   in->op = Operator::fd(&jfnk_outer_apply, o, o->x, o->v, 0.0, o->S + o->r_a0);
-  in->pre_fn = nullptr, in->pre_user = nullptr, in->pre_diag = nullptr;
+  in->pre_fn = nullptr, in->pre_user = nullptr, in->pre_diag = nullptr, in->pre_cheb = nullptr;
   storm_hip_solver_params ip;
   storm_hip_solver_params_default(&ip);
   ip.num_iterations = 2000, ip.absolute_error_tolerance = ip.relative_error_tolerance = 1.0e-8;
@@ -377,7 +382,7 @@ int storm_hip_krylov_apply(storm_hip_krylov *k, const storm_hip_vec *y, storm_hi
 int storm_hip_krylov_set_preconditioner_fn(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user, int side) {
   STORM_REQUIRE(k, "krylov_set_preconditioner_fn: null solver");
   STORM_REQUIRE(side >= STORM_HIP_LEFT && side <= STORM_HIP_SYMMETRIC, "krylov: unknown preconditioner side %d", side);
-  k->pre_fn = apply, k->pre_user = user, k->pre_diag = nullptr, k->side = side;
+  k->pre_fn = apply, k->pre_user = user, k->pre_diag = nullptr, k->pre_cheb = nullptr, k->side = side;
   return STORM_HIP_OK;
 }
 
@@ -385,7 +390,15 @@ int storm_hip_krylov_set_preconditioner_diag(storm_hip_krylov *k, const storm_hi
   STORM_REQUIRE(k, "krylov_set_preconditioner_diag: null solver");
   STORM_REQUIRE(side >= STORM_HIP_LEFT && side <= STORM_HIP_SYMMETRIC, "krylov: unknown preconditioner side %d", side);
   STORM_REQUIRE(d == nullptr || d->ctx == k->c, "krylov: preconditioner diagonal belongs to another context");
-  k->pre_fn = nullptr, k->pre_user = nullptr, k->pre_diag = d, k->side = side;
+  k->pre_fn = nullptr, k->pre_user = nullptr, k->pre_diag = d, k->pre_cheb = nullptr, k->side = side;
+  return STORM_HIP_OK;
+}
+
+int storm_hip_krylov_set_preconditioner_cheb(storm_hip_krylov *k, const storm_hip_cheb *h, int side) {
+  STORM_REQUIRE(k, "krylov_set_preconditioner_cheb: null solver");
+  STORM_REQUIRE(side >= STORM_HIP_LEFT && side <= STORM_HIP_SYMMETRIC, "krylov: unknown preconditioner side %d", side);
+  STORM_REQUIRE(h == nullptr || h->ctx == k->c, "krylov: the Chebyshev preconditioner belongs to another context");
+  k->pre_fn = nullptr, k->pre_user = nullptr, k->pre_diag = nullptr, k->pre_cheb = h, k->side = side;
   return STORM_HIP_OK;
 }
 

@@ -411,6 +411,8 @@ void K::pre(V yv, const storm_hip_vec *xv) {
   ApiDone guard(c, dp);
   if (pre_fn != nullptr) {
     st = callback_status(pre_fn(pre_user, yv, xv), "krylov: the preconditioner callback");
+  } else if (pre_cheb != nullptr) {  // (its launches are predicated on api_done like a callback's)
+    st = storm_hip_cheb_apply(pre_cheb, xv, yv);
   } else {
     c->stream_reverse = flip();
     st = storm_hip_vmul(yv, pre_diag, xv);

@@ -163,6 +163,7 @@ struct KrylovEngine {
   storm_hip_apply_fn pre_fn = nullptr;
   void *pre_user = nullptr;
   const storm_hip_vec *pre_diag = nullptr;
+  const storm_hip_cheb *pre_cheb = nullptr;  // the library's Chebyshev preconditioner (precond_cheb.hip): storm_hip_cheb_apply, no callback
   int side = STORM_HIP_RIGHT;
   double relaxation = 1.0e-4;  // SolverRichardson.hpp:45
   // JFNK (STORM_HIP_JFNK): the inner BiCGStab engine, created with the object and reused by every Newton step
@@ -219,7 +220,7 @@ struct KrylovEngine {
       r_a4 = 0;
   int H0 = 0, B0 = 0, CS0 = 0, SN0 = 0, r_hn = 0;
 
-  bool has_pre() const { return pre_fn != nullptr || pre_diag != nullptr; }
+  bool has_pre() const { return pre_fn != nullptr || pre_diag != nullptr || pre_cheb != nullptr; }
   bool left() const { return has_pre() && side == STORM_HIP_LEFT; }
   bool right() const { return has_pre() && side == STORM_HIP_RIGHT; }
   bool ok() const { return status == STORM_HIP_OK; }
@@ -266,7 +267,8 @@ struct KrylovEngine {
   // when the operator is native and has no CSR tail, separate reductions otherwise.
   void apply_dots(V yv, const storm_hip_vec *xv, int reg_wy, const storm_hip_vec *wv, int reg_yy = -1);
   void pre(V yv, const storm_hip_vec *xv);  // y = P(x)          Preconditioner::mul
-  // z = P(r) AND reg_rz = <r, z>, reg_rr = <r, r>: one pass when the preconditioner is the library's diagonal one.
+  // z = P(r) AND reg_rz = <r, z>, reg_rr = <r, r>: one pass when the preconditioner is the library's diagonal one (any other
+  // kind, the Chebyshev one included: pre, then dots).
   void pre_dots(V zv, const storm_hip_vec *rv, int reg_rz, int reg_rr);
   // The dispatch every preconditioned body repeats (chained mul, Operator.hpp:82-88):
   //   left: z = P(y = A x);  right: z = A(y = P x);  none: z = A x.

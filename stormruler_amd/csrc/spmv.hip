@@ -51,6 +51,7 @@
 // launchers that take a RangeLaunch; spmv_build.hip -- the host-side build and the create entry points; this file --
 // the dispatch (which launches make up an apply, which format takes each), the diagonal and the apply entry points.
 #include <algorithm>
+#include <cstring>
 
 #include "spmv_device.hpp"
 
@@ -303,6 +304,71 @@ __global__ void diag_tail_kernel(int64_t n_tail, const int *__restrict__ tail_ro
   d[tail_row[t]] -= alpha * sum;  // each overflowing row appears once in the tail
 }
 
+// ---- Gershgorin's bound of diag(s) (beta I + alpha M) (storm_hip_op_gershgorin) -------------------------------------
+// Row sums straight from the device records, with diag_sell_kernel's slot addressing in every format (the compact formats
+// need no kernel of their own here: a weight is a dictionary look-up).  Three small kernels: md_i = ext_i - sum_k w_ik (the
+// diagonal of M) and ab_i = sum_k |w_ik| from the ELL records; the CSR tail's share added; then
+// max_i |s_i| (|beta + alpha md_i| + |alpha| ab_i), folded by wave and one vector atomic max per wave on the bit pattern
+// (the values are non-negative doubles, whose order is that of their bit patterns as unsigned integers).
+__global__ __launch_bounds__(kBlock) void rowsum_sell_kernel(const char *__restrict__ pack, const int64_t *__restrict__ slice_off,
+                                                             int64_t n_rows, const double *__restrict__ dict, int fmt2,
+                                                             double *__restrict__ md, double *__restrict__ ab) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t s = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+  const int64_t r = s * kWave + lane;
+  if (r >= n_rows) return;
+  double sum = 0.0, asum = 0.0, ext;
+  if (fmt2 >= 3) {
+    const uint64_t iw = reinterpret_cast<const uint64_t *>(pack + (r >> 7) * (fmt2 == 4 ? kCanonRecBytes : kPairRecBytes))[r & 127];
+    for (int k = 0; k < 7; ++k) {
+      const double w = dict[((unsigned)(iw >> (8 * (k + 1))) & 0xffu) >> 3];
+      sum += w, asum += fabs(w);
+    }
+    ext = dict[((unsigned)iw & 0xffu) >> 3];
+  } else if (dict) {
+    const char *rec = pack + slice_off[s];
+    const int w = fmt2 ? 7 : (int)((slice_off[s + 1] - slice_off[s] - kExtBytes) / kColSlotBytes);
+    const uint64_t iw = reinterpret_cast<const uint64_t *>(rec)[fmt2 ? 2 * lane : lane];
+    for (int k = 0; k < w; ++k) {
+      const double v = dict[(unsigned)(iw >> (8 * (k + 1))) & 0xffu];
+      sum += v, asum += fabs(v);
+    }
+    ext = dict[(unsigned)iw & 0xffu];
+  } else {
+    const char *rec = pack + slice_off[s];
+    const int w = (int)((slice_off[s + 1] - slice_off[s] - kExtBytes) / kSlotBytes);
+    const double *val = reinterpret_cast<const double *>(rec + kExtBytes + (int64_t)w * (kWave * 4));
+    const int np2 = w >> 1;
+    for (int k = 0; k < w; ++k) {
+      const int at = (k < 2 * np2) ? ((k >> 1) * kWave + lane) * 2 + (k & 1) : np2 * 2 * kWave + lane;
+      sum += val[at], asum += fabs(val[at]);
+    }
+    ext = reinterpret_cast<const double *>(rec)[lane];
+  }
+  md[r] = ext - sum, ab[r] = asum;
+}
+
+__global__ void rowsum_tail_kernel(int64_t n_tail, const int *__restrict__ tail_row, const int64_t *__restrict__ tail_ptr,
+                                   const double *__restrict__ tail_val, double *__restrict__ md, double *__restrict__ ab) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_tail) return;
+  double sum = 0.0, asum = 0.0;
+  for (int64_t k = tail_ptr[t]; k < tail_ptr[t + 1]; ++k) sum += tail_val[k], asum += fabs(tail_val[k]);
+  md[tail_row[t]] -= sum, ab[tail_row[t]] += asum;  // each overflowing row appears once in the tail
+}
+
+__global__ __launch_bounds__(kBlock) void gershgorin_fold_kernel(int64_t n, const double *__restrict__ md, const double *__restrict__ ab,
+                                                                 const double *__restrict__ scale, double alpha, double beta,
+                                                                 unsigned long long *out) {
+  double v = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const double row = fabs(beta + alpha * md[i]) + fabs(alpha) * ab[i];
+    v = fmax(v, scale ? fabs(scale[i]) * row : row);
+  }
+  for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
+  if ((threadIdx.x & (kWave - 1)) == 0) atomicMax(out, (unsigned long long)__double_as_longlong(v));
+}
+
 __global__ void safe_invert_kernel(int64_t n, double *__restrict__ d) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) d[i] = d[i] == 0.0 ? 0.0 : 1.0 / d[i];  // safe_inverse, Crow/MathUtils.hpp:54-58
@@ -372,6 +438,43 @@ int storm_hip_op_get_diagonal(const storm_hip_op *op, double alpha, double beta,
     hipLaunchKernelGGL(safe_invert_kernel, dim3((int)((op->n_rows + 255) / 256)), dim3(256), 0, c->stream, op->n_rows,
                        d->d);
   HIP_TRY(hipGetLastError());
+  return STORM_HIP_OK;
+}
+
+int storm_hip_op_gershgorin(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *scale, double *lambda_max) {
+  STORM_REQUIRE(op && lambda_max, "op_gershgorin: null argument");
+  STORM_REQUIRE(scale == nullptr || (scale->ctx == op->ctx && scale->n_owned == op->n_rows),
+                "op_gershgorin: the scale must be a vector of the operator's context and size");
+  if (op->halo.n_nbrs > 0 || op->n_halo > 0 || op->ctx->comm != nullptr)
+    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "op_gershgorin: single-rank operators only (the operator has a halo plan or halo "
+                                        "columns, or the context a communicator)");
+  *lambda_max = 0.0;
+  if (op->n_rows == 0) return STORM_HIP_OK;
+  storm_hip_ctx *c = op->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  STORM_TRY(lazy_sync(c));
+  const int64_t n = op->n_rows;
+  double *work = nullptr;  // md | ab | the maximum's word  (build time: an allocation and one host wait)
+  HIP_TRY(hipMalloc((void **)&work, sizeof(double) * (size_t)(2 * n + 1)));
+  double *md = work, *ab = work + n;
+  unsigned long long *word = reinterpret_cast<unsigned long long *>(work + 2 * n);
+  hipError_t e = hipMemsetAsync(word, 0, sizeof(*word), c->stream);
+  const int64_t n64 = (n + kWave - 1) / kWave;
+  const int nb = (int)((n64 + (kBlock / kWave) - 1) / (kBlock / kWave));
+  hipLaunchKernelGGL(rowsum_sell_kernel, dim3(nb), dim3(kBlock), 0, c->stream, op->d_pack, op->d_slice_off, n, op->d_dict,
+                     op->pair >= 2 ? op->pair + 2 : op->pair ? 3 : (int)(op->offs_size > 0), md, ab);
+  if (op->tail_rows > 0)
+    hipLaunchKernelGGL(rowsum_tail_kernel, dim3((int)((op->tail_rows + 255) / 256)), dim3(256), 0, c->stream, op->tail_rows,
+                       op->d_tail_row, op->d_tail_ptr, op->d_tail_val, md, ab);
+  hipLaunchKernelGGL(gershgorin_fold_kernel, dim3((int)std::min<int64_t>((n + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0,
+                     c->stream, n, md, ab, scale ? scale->d : nullptr, alpha, beta, word);
+  if (e == hipSuccess) e = hipGetLastError();
+  unsigned long long bits = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&bits, word, sizeof(bits), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(work);
+  HIP_TRY(e);
+  memcpy(lambda_max, &bits, sizeof(bits));
   return STORM_HIP_OK;
 }
 
