@@ -185,7 +185,7 @@ struct storm_hip_ctx {
   int64_t opt_spmv_mixed = 1;        // partitioned operators: format 4 for the groups that read no halo column, format 3 for the rest
   int64_t opt_profile_spmv = 0;
   std::vector<storm::LazyStmt> lazy_q;  // held-back statements (lazy.hip), in program order
-  std::unordered_map<const void *, int> occupancy;  // latency.hip: blocks per CU of a cooperative kernel on THIS context's device
+  std::unordered_map<const void *, int> occupancy;  // coop_host.hip: blocks per CU of a cooperative kernel on THIS context's device
   int64_t opt_test_disable = 0;         // option test_disable (context.hip): a bit mask that switches single refinements OFF so that tests can compare a kernel with its plainer form, bit for bit
   int64_t opt_lazy = 0;                 // option lazy_statements
   int callback_depth = 0;               // > 0 while a solver is inside an operator / preconditioner callback (nothing waits there)
@@ -193,9 +193,9 @@ struct storm_hip_ctx {
   storm_hip_vec *lazy_spare = nullptr;  // where a fused CG step writes the new direction (lazy.hip: try_cg_step)
   int64_t opt_profile_comm = 0;       // RCCL transport: stamp kernels around the halo exchange and the all-reduces (comm.hip comm_profile_*)
   int64_t opt_blas1_nt = 1;  // non-temporal loads/stores in the streaming kernels: 0 never, 1 for vectors of at least kBlas1NtRows rows, 2 always
-  int64_t opt_coop_mgs = 1;             // GMRES: the Gram-Schmidt chain of an Arnoldi step as one cooperative kernel (latency.hip)
+  int64_t opt_coop_mgs = 1;             // GMRES: the Gram-Schmidt chain of an Arnoldi step as one cooperative kernel (mgs_chain.hip)
   int64_t opt_latency_publish = 1;      // ... its rows published with awaited atomic exchanges (0: write-through stores, ordered by their acknowledgement)
-  int64_t opt_coop_plain = 1;           // the cooperative kernels by ordinary launches (latency.hip coop_launch; 0: hipLaunchCooperativeKernel)
+  int64_t opt_coop_plain = 1;           // the cooperative kernels by ordinary launches (coop_host.hip coop_launch; 0: hipLaunchCooperativeKernel)
   int64_t opt_coop_force_fail = 0;      // test hook: 1 = cooperative launches "fail", 2 = cooperative kernels "gave up" (once per solve)
   int coop_ran = 0;                     // a cooperative kernel of the current solve has run
   int coop_disabled = 0;                // set while a solve is re-run without cooperative kernels
@@ -267,7 +267,7 @@ struct storm_hip_ctx {
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_cg_pz_consumer_folds = 0;  // ... of those, the solves whose plane march folded <p,z> itself (option cg_pz_fold)
-  int64_t n_mgs_chain_steps = 0, n_mgs_quad_steps = 0;  // Gram-Schmidt steps run as a chain kernel (latency.hip); ... as mgs_chain_quad_kernel
+  int64_t n_mgs_chain_steps = 0, n_mgs_quad_steps = 0;  // Gram-Schmidt steps run as a chain kernel (mgs_chain.hip); ... as mgs_chain_quad_kernel
   // communicator
   storm::Comm *comm = nullptr;
   int n_ranks = 1, rank = 0;
@@ -487,14 +487,31 @@ int spmv_block_launch(const storm_hip_op *op, double alpha, double beta, int k, 
                       double *pz_partials, int *n_partials, const int *done);
 int spmv_block_check(const storm_hip_op *op, int k, const storm_hip_vec *X, const storm_hip_vec *Y, const char *what);
 
-// latency.hip
-int op_make_latency_copy(storm_hip_op *op, int64_t n, int64_t n_halo, const std::vector<int64_t> &row_ptr,
-                         const std::vector<int> &col, const std::vector<double> &val, const std::vector<double> &ext);
-bool cg_latency_eligible(const storm_hip_op *op);
+// coop_host.hip: the host side every cooperative (co-resident, grid-synchronising) path uses
+constexpr int kLatBlock = 1024;  // threads of a latency / chain block -- one block per CU: a synchronisation point costs per participating BLOCK
+// Blocks of `fn` that fit a CU (0: it cannot run with this much dynamic LDS); asked once per context and FUNCTION
+int occupancy_cached(storm_hip_ctx *c, const void *fn, int threads, size_t dyn_lds);
+// A launch that may be refused: false = not launched, nothing ran, the error is cleared (a fallback, not an error)
+bool coop_launch(storm_hip_ctx *c, const void *fn, unsigned blocks, void **args, size_t dyn_lds = 0, unsigned threads = kLatBlock);
 constexpr int kStatusCoopGaveUp = 1000;  // internal status of lat_check_gave_up: the caller re-runs the solve (below)
 int lat_check_gave_up(storm_hip_ctx *c);
 // Run a solve that may use cooperative kernels; when one of them gave up, restore x and run it again without them.
 int coop_solve_with_fallback(storm_hip_ctx *c, storm_hip_vec *x, int (*run)(void *), void *arg, int *fallback_out);
+
+// latency.hip
+int op_make_latency_copy(storm_hip_op *op, int64_t n, int64_t n_halo, const std::vector<int64_t> &row_ptr,
+                         const std::vector<int> &col, const std::vector<double> &val, const std::vector<double> &ext);
+bool cg_latency_eligible(const storm_hip_op *op);
+// *taken = false: no cooperative kernel ran (none fits, or the launch was refused) -- take the throughput path
+int cg_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x, double *p,
+                     double *r, SolverState *d_state, bool *taken);
+int bicgstab_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x,
+                           double *const work[4], SolverState *d_state, bool *taken);
+// CG for A = beta2 I + alpha2 M (beta1 I + alpha1 M); work: p, r, t (zero-filled)
+int cg2_latency_solve(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const double *b,
+                      double *x, double *const work[3], SolverState *d_state, bool *taken);
+
+// mgs_chain.hip
 // What the cooperative chain needs to finish an Arnoldi step itself (fused GMRES loop): the state, the Hessenberg and
 // rotation arrays, and where sqrt(<w,w>) goes.
 struct MgsGivens {
@@ -510,19 +527,12 @@ struct ChainApply {
 int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w, const double *const *q, int k, int m,
                          double *H, double *norm2_out, bool normalise, bool *taken, const MgsGivens *givens,
                          const ChainApply *apply = nullptr, bool *applied = nullptr);
+
 // solver_gmres.hip: the Gram-Schmidt step of storm_hip_solve_gmres, shared with the general engine (krylov_methods.hip)
 int gmres_orthogonalize(storm_hip_ctx *c, int64_t n, const SolverState *st, const int *done, double *qn,
                         const double *const *q, int k, int m, double *H, double *norm2_out, double *scratch,
                         int gram_schmidt, bool *normalised, const MgsGivens *givens = nullptr,
                         bool *givens_done = nullptr, const ChainApply *apply = nullptr);
-// *taken = false: no cooperative kernel ran (none fits, or the launch was refused) -- take the throughput path
-int cg_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x, double *p,
-                     double *r, SolverState *d_state, bool *taken);
-int bicgstab_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x,
-                           double *const work[4], SolverState *d_state, bool *taken);
-// CG for A = beta2 I + alpha2 M (beta1 I + alpha1 M); work: p, r, t (zero-filled)
-int cg2_latency_solve(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const double *b,
-                      double *x, double *const work[3], SolverState *d_state, bool *taken);
 // solver_cg.hip: the two-stage CG solve on the one-kernel path, state and result included (*taken = false: it did not run)
 int cg2_latency_try(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const storm_hip_vec *b,
                     storm_hip_vec *x, const storm_hip_solver_params *params, storm_hip_solver_result *result, double *history,

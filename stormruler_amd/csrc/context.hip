@@ -68,7 +68,7 @@ int storm_hip_ctx_create(int device_id, storm_hip_ctx **out) {
   HIP_TRY(hipHostMalloc((void **)&c->h_result_words, sizeof(unsigned long long) * 16 * 8, hipHostMallocMapped));
   memset(c->h_result_words, 0, sizeof(unsigned long long) * 16 * 8);
   HIP_TRY(hipHostGetDevicePointer((void **)&c->d_result_words, c->h_result_words, 0));
-  HIP_TRY(hipMalloc((void **)&c->d_lat_slots, 2 * 256 * 256 + 256));  // latency.hip: all-reduce slots (two per block) + the gave-up flag
+  HIP_TRY(hipMalloc((void **)&c->d_lat_slots, 2 * 256 * 256 + 256));  // coop_device.hpp: all-reduce slots (two per block) + the gave-up flag
   HIP_TRY(hipMemset(c->d_lat_slots, 0, 2 * 256 * 256 + 256));
   HIP_TRY(hipMalloc((void **)&c->d_ticket_sums, sizeof(double) * 8 * 2048));  // [k <= 8][kTicketMaxGroups] group sums
   HIP_TRY(hipMalloc((void **)&c->d_tickets, sizeof(int) * (1 + 2048) * 16));  // ticket_device.hpp: kTicketMaxGroups, kTicketStride

@@ -1,6 +1,6 @@
 // Device helpers shared by the persistent, grid-synchronising kernels (latency.hip: one kernel per solve for small
-// operators, the Gram-Schmidt chain; resident.hip: block-resident lattice solves): coherent accesses, the tagged
-// all-reduce slots, the wave sum.
+// operators; mgs_chain.hip: the Gram-Schmidt chain; resident.hip: block-resident lattice solves): coherent accesses, the
+// bounded wait, the tagged all-reduce slots in their three layouts, the wave sum.
 #pragma once
 
 #include "common.hpp"
@@ -52,56 +52,20 @@ __device__ __forceinline__ size_t lat_slot_offset(unsigned block, unsigned long 
   return ((size_t)(seq & 1) * 256 + block) * kLatSlotStride;
 }
 constexpr long long kLatTimeoutTicks = 1000000000LL;  // 10 s of the 100 MHz real-time counter
-__device__ __forceinline__ bool co_load_slot(const char *slot, unsigned tag, double *value) {
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  u32x4 w;
-  asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(w) : "v"(slot) : "memory");
-  *value = __hiloint2double((int)w.z, (int)w.x);
-  return w.y == tag && w.w == tag;
-}
 __device__ __forceinline__ void co_store_slot(char *slot, unsigned tag, double value) {
   const unsigned long long lo = ((unsigned long long)tag << 32) | (unsigned)__double2loint(value);
   const unsigned long long hi = ((unsigned long long)tag << 32) | (unsigned)__double2hiint(value);
   __hip_atomic_store(reinterpret_cast<unsigned long long *>(slot), lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(reinterpret_cast<unsigned long long *>(slot) + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// Two sums in one slot: four words.
-__device__ __forceinline__ bool co_load_slot2(const char *slot, unsigned tag, double *v0, double *v1) {
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  u32x4 w0, w1;
-  asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %2, off offset:16 sc1\n\ts_waitcnt vmcnt(0)"
-               : "=&v"(w0), "=&v"(w1)
-               : "v"(slot)
-               : "memory");
-  *v0 = __hiloint2double((int)w0.z, (int)w0.x);
-  *v1 = __hiloint2double((int)w1.z, (int)w1.x);
-  return w0.y == tag && w0.w == tag && w1.y == tag && w1.w == tag;
-}
-// Three sums in one slot: six words, ONE round trip (round 3 polled them with two dependent loads -- the paired
-// Gram-Schmidt chain's synchronisation point cost two memory round trips per poll instead of one).
-__device__ __forceinline__ bool co_load_slot3(const char *slot, unsigned tag, double *v0, double *v1, double *v2) {
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  u32x4 w0, w1, w2;
-  asm volatile(
-      "global_load_dwordx4 %0, %3, off sc1\n\tglobal_load_dwordx4 %1, %3, off offset:16 sc1\n\t"
-      "global_load_dwordx4 %2, %3, off offset:32 sc1\n\ts_waitcnt vmcnt(0)"
-      : "=&v"(w0), "=&v"(w1), "=&v"(w2)
-      : "v"(slot)
-      : "memory");
-  *v0 = __hiloint2double((int)w0.z, (int)w0.x);
-  *v1 = __hiloint2double((int)w1.z, (int)w1.x);
-  *v2 = __hiloint2double((int)w2.z, (int)w2.x);
-  return w0.y == tag && w0.w == tag && w1.y == tag && w1.w == tag && w2.y == tag && w2.w == tag;
-}
 __device__ __forceinline__ double lat_wave_sum(double v) {
   return wave_sum_all(v);  // (= the xor butterfly's value in every lane, bit for bit: wave_device.hpp)
 }
 
 
-// N sums (N <= 10) over a co-resident grid of blocks of WAVES wavefronts, in slots `stride` bytes apart (parity-major:
-// slot of block b at ((seq & 1) * 256 + b) * stride); every value travels as two self-validating words like the
-// one- to three-value forms above, all of a slot's words are polled in ONE round trip.  Identical bits in every thread of
-// every block (fixed folding order); bounded wait -> *gave_up.
+// The polling load of a slot of NV values (1, 2, 3, 6 or 10): every value travels as two self-validating words, all of
+// a slot's words are requested in ONE round trip (two dependent loads cost the paired Gram-Schmidt chain's
+// synchronisation point two memory round trips per poll instead of one).
 template <int NV>
 __device__ __forceinline__ bool co_load_slot_n(const char *slot, unsigned tag, double (&v)[NV]) {
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -149,54 +113,152 @@ __device__ __forceinline__ bool co_load_slot_n(const char *slot, unsigned tag, d
   }
   return ok;
 }
-template <int NV, int WAVES>
-__device__ __forceinline__ void co_allreduce_n(double (&s)[NV], char *slots, int stride, int *gave_up, unsigned long long seq,
-                                               double *lds /* [NV * WAVES] */) {
-  static_assert(NV == 1 || NV == 6 || NV == 10, "co_allreduce_n: the wait statement lists its registers");
+// The one- and the two-value poll as resident.hip's all-reduce wait has them (res_allreduce_wait: see there).
+__device__ __forceinline__ bool co_load_slot(const char *slot, unsigned tag, double *value) {
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 w;
+  asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(w) : "v"(slot) : "memory");
+  *value = __hiloint2double((int)w.z, (int)w.x);
+  return w.y == tag && w.w == tag;
+}
+__device__ __forceinline__ bool co_load_slot2(const char *slot, unsigned tag, double *v0, double *v1) {
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  u32x4 w0, w1;
+  asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %2, off offset:16 sc1\n\ts_waitcnt vmcnt(0)"
+               : "=&v"(w0), "=&v"(w1)
+               : "v"(slot)
+               : "memory");
+  *v0 = __hiloint2double((int)w0.z, (int)w0.x);
+  *v1 = __hiloint2double((int)w1.z, (int)w1.x);
+  return w0.y == tag && w0.w == tag && w1.y == tag && w1.w == tag;
+}
+// THE bounded wait of every grid-synchronising kernel: `arrived()` polls once and says whether what was waited for is
+// there.  The grids are launched co-resident, but should a block never arrive -- the device shared with another
+// process's cooperative kernel, say -- the others give up after kLatTimeoutTicks instead of spinning forever, raise
+// *gave_up and fall through every later wait at once (the flag is looked at every 1 024 spins); the host turns the flag
+// into a re-run of the solve (lat_check_gave_up, coop_host.hip).  Returns true when the wait was ABANDONED: what the
+// poll left behind is then not to be used.
+// (resident.hip keeps this loop WRITTEN OUT three times -- res_allreduce_wait, res_fetch2, res_fetch4: a change to the
+//  timeout policy goes there too.)
+template <class Poll>
+__device__ __forceinline__ bool co_bounded_wait(int *gave_up, Poll &&arrived) {
+  const long long t0 = wall_clock64();
+  for (int spins = 0;; ++spins) {
+    if (arrived()) return false;
+    __builtin_amdgcn_s_sleep(1);
+    if ((spins & 1023) == 1023 &&
+        (wall_clock64() - t0 > kLatTimeoutTicks || __hip_atomic_load(gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+      __hip_atomic_store(gave_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return true;
+    }
+  }
+}
+
+// The block barrier of the all-reduces.  RAW, for a kernel with LDS-DMA in flight: __syncthreads() carries a fence that
+// waits for every outstanding vector-memory operation of the wave -- the DMAs included -- so the barrier is a bare
+// `s_barrier` behind `s_waitcnt lgkmcnt(0)` (the LDS writes it orders), and only the POLLING waves, which the caller
+// keeps free of DMAs until they are through, wait on the vector-memory counter.
+__device__ __forceinline__ void raw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+template <bool RAW>
+__device__ __forceinline__ void co_block_barrier() {
+  if constexpr (RAW) raw_barrier();
+  else __syncthreads();
+}
+
+// THE slot all-reduce: NV sums (1, 2 or 3) over a co-resident grid of at most 256 blocks of WAVES wavefronts, through
+// the 64-byte slots of lat_slot_offset, 16 bytes per value; identical bits in every thread of every block (a fixed
+// folding order: the block's waves in index order by thread j for sum j, then lanes over the blocks' slots, then the four
+// polling waves).  In two halves: ARRIVE (the block's sums folded and stored to its slot) and WAIT (every block's slot
+// polled) -- a caller may put stores or loads of its own between them (resident.hip's early publish: behind the block's
+// slot in the memory pipeline, not in front of it, or every block's arrival is late by the time those stores take to
+// drain).  lds: NV x WAVES doubles.
+//   SEEN: the block's waves have published rows that other blocks read once they are past this point -- `seen`, what
+// the publishing exchanges returned (co_publish), is consumed here, and with `publishes` every wave drains its own
+// store counter before the block's words go out (the store variant: acknowledged).  Without SEEN there is no fence.
+template <int NV, int WAVES, bool RAW = false, bool SEEN = false>
+__device__ __forceinline__ void co_allreduce_slots_arrive(const double (&s)[NV], char *slots, unsigned long long seq, double *lds,
+                                                          bool publishes = false, unsigned long long seen = 0ull) {
   const unsigned tag = (unsigned)seq;
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   double v[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) v[j] = lat_wave_sum(s[j]);
-  __syncthreads();  // (lds may still be read by the previous call)
+  if constexpr (SEEN) {
+    asm volatile("" : : "v"(seen) : "memory");  // the exchanges that published this wave's rows have returned
+    if (publishes) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  }
+  co_block_barrier<RAW>();  // (lds may still be read by the previous call)
   if (lane == 0) {
 #pragma unroll
     for (int j = 0; j < NV; ++j) lds[j * WAVES + wave] = v[j];
   }
-  __syncthreads();
+  co_block_barrier<RAW>();
   if ((int)threadIdx.x < NV) {  // thread j folds and stores sum j
     double t = 0.0;
 #pragma unroll
     for (int w = 0; w < WAVES; ++w) t += lds[threadIdx.x * WAVES + w];
-    co_store_slot(slots + ((size_t)(seq & 1) * 256 + blockIdx.x) * stride + 16 * threadIdx.x, tag, t);
+    co_store_slot(slots + lat_slot_offset(blockIdx.x, seq) + 16 * threadIdx.x, tag, t);
   }
+}
+template <int NV, int WAVES, bool RAW = false>
+__device__ __forceinline__ void co_allreduce_slots_wait(double (&s)[NV], char *slots, int *gave_up, unsigned long long seq,
+                                                        double *lds) {
+  const unsigned tag = (unsigned)seq;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  double v[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) v[j] = 0.0;
   if (threadIdx.x < gridDim.x) {  // gridDim.x <= 256: thread t (waves 0 .. 3) watches block t
-    const char *slot = slots + ((size_t)(seq & 1) * 256 + threadIdx.x) * stride;
-    const long long t0 = wall_clock64();
-    for (int spins = 0;; ++spins) {
-      if (co_load_slot_n<NV>(slot, tag, v)) break;
-      __builtin_amdgcn_s_sleep(1);
-      if ((spins & 1023) == 1023 &&
-          (wall_clock64() - t0 > kLatTimeoutTicks || __hip_atomic_load(gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-        __hip_atomic_store(gave_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const char *slot = slots + lat_slot_offset(threadIdx.x, seq);
+    if (co_bounded_wait(gave_up, [&]() { return co_load_slot_n<NV>(slot, tag, v); })) {
 #pragma unroll
-        for (int j = 0; j < NV; ++j) v[j] = 0.0;
-        break;
-      }
+      for (int j = 0; j < NV; ++j) v[j] = 0.0;
     }
   }
+  // slot order: lanes, then the (up to four) polling waves -- the same tree in every block
 #pragma unroll
   for (int j = 0; j < NV; ++j) v[j] = lat_wave_sum(v[j]);
-  __syncthreads();
+  co_block_barrier<RAW>();
   if (lane == 0 && wave < 4) {
 #pragma unroll
     for (int j = 0; j < NV; ++j) lds[j * WAVES + wave] = v[j];
   }
-  __syncthreads();
+  co_block_barrier<RAW>();
 #pragma unroll
   for (int j = 0; j < NV; ++j) s[j] = (lds[j * WAVES] + lds[j * WAVES + 1]) + (lds[j * WAVES + 2] + lds[j * WAVES + 3]);
+}
+template <int NV, int WAVES, bool RAW = false, bool SEEN = false>
+__device__ __forceinline__ void co_allreduce_slots(double (&s)[NV], char *slots, int *gave_up, unsigned long long seq, double *lds,
+                                                   bool publishes = false, unsigned long long seen = 0ull) {
+  co_allreduce_slots_arrive<NV, WAVES, RAW, SEEN>(s, slots, seq, lds, publishes, seen);
+  co_allreduce_slots_wait<NV, WAVES, RAW>(s, slots, gave_up, seq, lds);
+}
+
+// The latency solvers' and the register / LDS-ring chains' use of it: blocks of kLatBlock threads, the give-up flag
+// behind the slots.  Sum over all blocks of per-thread partials; `publishes` / `seen` as above.
+constexpr int kLatWaves = kLatBlock / kWave;
+__device__ __forceinline__ int *lat_gave_up(char *slots) { return reinterpret_cast<int *>(slots + (size_t)2 * 256 * kLatSlotStride); }
+__device__ __forceinline__ double lat_allreduce(double mine, char *slots, unsigned long long seq, double *lds /* [kLatWaves] */,
+                                                bool publishes = true, unsigned long long seen = 0ull) {
+  double s[1] = {mine};
+  co_allreduce_slots<1, kLatWaves, false, true>(s, slots, lat_gave_up(slots), seq, lds, publishes, seen);
+  return s[0];
+}
+// ... TWO sums at once (BiCGStab's <t, s>, <t, t> and <r, r>, <rt, r>): the slot carries four words
+__device__ __forceinline__ void lat_allreduce2(double &s0, double &s1, char *slots, unsigned long long seq,
+                                               double *lds /* [2 * kLatWaves] */, bool publishes = true, unsigned long long seen = 0ull) {
+  double s[2] = {s0, s1};
+  co_allreduce_slots<2, kLatWaves, false, true>(s, slots, lat_gave_up(slots), seq, lds, publishes, seen);
+  s0 = s[0], s1 = s[1];
+}
+// ... and THREE (the paired Gram-Schmidt step: <w, q_i>, <w, q_i+1>, <q_i, q_i+1>): six words, 48 bytes of the slot;
+// nothing is published in front of it.  RAW: the LDS-ring chain's, see co_block_barrier.
+template <bool RAW = false>
+__device__ __forceinline__ void lat_allreduce3(double &s0, double &s1, double &s2, char *slots, unsigned long long seq,
+                                               double *lds /* [3 * kLatWaves] */) {
+  double s[3] = {s0, s1, s2};
+  co_allreduce_slots<3, kLatWaves, RAW>(s, slots, lat_gave_up(slots), seq, lds);
+  s0 = s[0], s1 = s[1], s2 = s[2];
 }
 
 
@@ -236,17 +298,9 @@ __device__ __forceinline__ void co_allreduce2_n(double (&s)[NV], char *slots, in
 #pragma unroll
       for (int j = 0; j < NV; ++j) v[j] = 0.0;
       if (active) {
-        const long long t0 = wall_clock64();
-        for (int spins = 0;; ++spins) {
-          if (co_load_slot_n<NV>(slot, tag, v)) break;
-          __builtin_amdgcn_s_sleep(1);
-          if ((spins & 1023) == 1023 &&
-              (wall_clock64() - t0 > kLatTimeoutTicks || __hip_atomic_load(gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-            __hip_atomic_store(gave_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (co_bounded_wait(gave_up, [&]() { return co_load_slot_n<NV>(slot, tag, v); })) {
 #pragma unroll
-            for (int j = 0; j < NV; ++j) v[j] = 0.0;
-            break;
-          }
+          for (int j = 0; j < NV; ++j) v[j] = 0.0;
         }
       }
 #pragma unroll
@@ -278,7 +332,7 @@ __device__ __forceinline__ void co_allreduce2_n(double (&s)[NV], char *slots, in
 // go through LDS; value j is folded by lanes over the blocks in a fixed order (the same bits in every block, run to
 // run).  lds: NV x 256 + NV doubles.  slots: 2 x 16 x 256 x 16 bytes.  T = WAVES x 64 threads, all of them poll.
 constexpr int kDenseMaxValues = 16;
-// (in two halves, like res_allreduce: a caller may request loads of its own between the block's arrival and its wait for
+// (in two halves, like co_allreduce_slots: a caller may request loads of its own between the block's arrival and its wait for
 //  the others -- the Gram-Schmidt chain asks for the next group's vectors there)
 template <int NV, int WAVES>
 __device__ __forceinline__ void co_allreduce_dense_arrive(const double (&s)[NV], char *slots, unsigned long long seq, double *lds) {
@@ -325,8 +379,7 @@ __device__ __forceinline__ void co_allreduce_dense_wait(double (&s)[NV], char *s
     p[i] = base + (size_t)(need[i] ? g : 0) * 16;
   }
   u32x4 w[MAXG];
-  const long long t0 = wall_clock64();
-  for (int spins = 0;; ++spins) {
+  (void)co_bounded_wait(gave_up, [&]() {  // (abandoned: whatever the last poll read goes into the sums)
     if constexpr (MAXG == 1)
       asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(w[0]) : "v"(p[0]) : "memory");
     else if constexpr (MAXG == 2)
@@ -348,14 +401,8 @@ __device__ __forceinline__ void co_allreduce_dense_wait(double (&s)[NV], char *s
     bool ok = true;
 #pragma unroll
     for (int i = 0; i < MAXG; ++i) ok = ok && (!need[i] || (w[i].y == tag && w[i].w == tag));
-    if (ok) break;
-    __builtin_amdgcn_s_sleep(1);
-    if ((spins & 1023) == 1023 &&
-        (wall_clock64() - t0 > kLatTimeoutTicks || __hip_atomic_load(gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-      __hip_atomic_store(gave_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
-    }
-  }
+    return ok;
+  });
   double *vals = lds;  // [NV][256]
 #pragma unroll
   for (int i = 0; i < MAXG; ++i) {
@@ -417,8 +464,7 @@ __device__ __forceinline__ void co_allreduce_dense(double (&s)[NV], char *slots,
     p[i] = base + (size_t)(need[i] ? g : 0) * 16;
   }
   u32x4 w[MAXG];
-  const long long t0 = wall_clock64();
-  for (int spins = 0;; ++spins) {
+  (void)co_bounded_wait(gave_up, [&]() {  // (abandoned: whatever the last poll read goes into the sums)
     if constexpr (MAXG == 1)
       asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(w[0]) : "v"(p[0]) : "memory");
     else if constexpr (MAXG == 2)
@@ -440,14 +486,8 @@ __device__ __forceinline__ void co_allreduce_dense(double (&s)[NV], char *slots,
     bool ok = true;
 #pragma unroll
     for (int i = 0; i < MAXG; ++i) ok = ok && (!need[i] || (w[i].y == tag && w[i].w == tag));
-    if (ok) break;
-    __builtin_amdgcn_s_sleep(1);
-    if ((spins & 1023) == 1023 &&
-        (wall_clock64() - t0 > kLatTimeoutTicks || __hip_atomic_load(gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-      __hip_atomic_store(gave_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
-    }
-  }
+    return ok;
+  });
   double *vals = lds;  // [NV][256]
 #pragma unroll
   for (int i = 0; i < MAXG; ++i) {

@@ -192,7 +192,7 @@ int stages2_supported(const storm_hip_op *op, const char *what) {
   return STORM_HIP_OK;
 }
 
-// A solve under coop_solve_with_fallback (latency.hip: should a cooperative kernel give up -- the engine's GMRES runs its
+// A solve under coop_solve_with_fallback (coop_host.hip: should a cooperative kernel give up -- the engine's GMRES runs its
 // Gram-Schmidt chains as such where they fit -- x is restored and `attempt` repeated without them).
 template <class F>
 int solve_with_fallback(storm_hip_ctx *c, storm_hip_vec *x, storm_hip_solver_result *result, F attempt) {

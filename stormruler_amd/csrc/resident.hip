@@ -20,7 +20,7 @@
 //     self-validating 16-byte granules { low half | tag }, { high half | tag } (tag = the exchange's sequence number)
 //     with one write-through store each, and polls its neighbours' granules until both tags of each are current: no
 //     flag follows the data, no ordering between stores is relied on, a row that was never published never validates
-//     (bounded wait -> the fallback of latency.hip).  128^3: 4 096 of a block's 8 192 rows, 64 KB out and in per
+//     (bounded wait -> the fallback of coop_host.hip).  128^3: 4 096 of a block's 8 192 rows, 64 KB out and in per
 //     block and exchange, 16 MB chip-wide -- against the 168 MB a throughput iteration streams;
 //   * a buffer row is overwritten only behind an all-reduce that every block enters after its last read of it;
 //   * the reductions are the tagged-slot all-reduces of the latency path (each is its own grid barrier): two per CG
@@ -78,29 +78,15 @@ struct ResArgs {
   int early_publish;  // CG: the residual's surface before the second all-reduce (res_halo MODE 2); BiCGStab: res_bicgstab_early_kernel
 };
 
-// ---- all-reduce over the co-resident grid (latency.hip's scheme for 8 waves per block) --------------------------
-// Two halves: ARRIVE (the block's sums folded and stored to its slot) and WAIT (every block's slot polled, the same tree in
-// every block) -- a caller may put stores of its own between them (CG's early publish: behind the block's slot in the
-// memory pipeline, not in front of it, or every block's arrival is late by the time those stores take to drain).
+// ---- all-reduce over the co-resident grid, 8 waves per block, in two halves: a caller may put stores of its own between
+// them (CG's early publish).  The arrive half is co_allreduce_slots_arrive (coop_device.hpp).  The wait half is the same
+// tree as co_allreduce_slots_wait, WRITTEN OUT with its own polls (co_load_slot / co_load_slot2) and its own bounded
+// wait: through the shared one the registers of every res_bicgstab kernel are allocated differently, and with the text
+// below the device code of this unit is what it was before the all-reduce moved to coop_device.hpp, instruction for
+// instruction (NOTES.md, "The cooperative unit split").  A change to either wait half goes to both. -------------------
 template <int NV>
 __device__ __forceinline__ void res_allreduce_arrive(const double (&s)[NV], const ResArgs &A, unsigned long long seq, double *lds) {
-  const unsigned tag = (unsigned)seq;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  double v[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) v[j] = lat_wave_sum(s[j]);
-  __syncthreads();  // (lds may still be read by the previous call)
-  if (lane == 0) {
-#pragma unroll
-    for (int j = 0; j < NV; ++j) lds[j * kResWaves + wave] = v[j];
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < NV) {  // thread j folds and stores sum j
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kResWaves; ++w) t += lds[threadIdx.x * kResWaves + w];
-    co_store_slot(A.slots + lat_slot_offset(blockIdx.x, seq) + 16 * threadIdx.x, tag, t);
-  }
+  co_allreduce_slots_arrive<NV, kResWaves>(s, A.slots, seq, lds);
 }
 template <int NV>
 __device__ __forceinline__ void res_allreduce_wait(double (&s)[NV], const ResArgs &A, unsigned long long seq, double *lds) {
@@ -163,6 +149,8 @@ __device__ __forceinline__ double res_value(u32x4r w) { return __hiloint2double(
 
 // The pairs at rows ra and rb (even; a pair outside [0, n) reads as zeros) as published with `tag`: four coherent
 // 16-byte loads in flight, repeated until every needed granule carries the tag.  Bounded like the all-reduce.
+// (its wait is co_bounded_wait's loop written out, here and in res_fetch4: through the helper the allocator spills 3 to
+//  35 more SGPRs in every kernel of this unit and 128^3 is 1 % slower, CG 13.78 against 13.64 us -- NOTES.md)
 __device__ __forceinline__ void res_fetch2(const ResArgs &A, int64_t ra, int64_t rb, unsigned tag, double2r *va, double2r *vb) {
   const int64_t n = A.n_rows;
   const bool a0 = ra >= 0 && ra < n, a1 = ra >= 0 && ra + 1 < n, b0 = rb >= 0 && rb < n, b1 = rb >= 0 && rb + 1 < n;
@@ -1194,10 +1182,6 @@ int res_solve(bool bicgstab, const storm_hip_op *op, double alpha, double beta, 
   *taken = false;
   ResGeometry G;
   if (!res_geometry(op, &G, bicgstab)) return STORM_HIP_OK;
-  if (c->opt_coop_force_fail == 1) {
-    c->coop_fallback = 1;
-    return STORM_HIP_OK;
-  }
   const void *fn = nullptr;
   switch (G.tz) {
     case 1: fn = res_kernel<1>(bicgstab, G.x_lds, G.early); break;
@@ -1209,17 +1193,11 @@ int res_solve(bool bicgstab, const storm_hip_op *op, double alpha, double beta, 
     case 12: fn = res_kernel<12>(bicgstab, G.x_lds); break;
     default: return STORM_HIP_OK;
   }
-  // every block must be resident: one per CU with this much LDS, as the occupancy query sees it
-  if (G.lds_bytes > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.lds_bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      c->coop_fallback = 1;
-      return STORM_HIP_OK;
-    }
-  }
+  // every block must be resident: one per CU with this much LDS, as the occupancy query sees it (asked every time:
+  // the LDS depends on the lattice, occupancy_cached's answer on the function alone)
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kResThreads, G.lds_bytes) != hipSuccess || per_cu < 1) {
+  if ((G.lds_bytes > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.lds_bytes) != hipSuccess) ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kResThreads, G.lds_bytes) != hipSuccess || per_cu < 1) {
     (void)hipGetLastError();
     c->coop_fallback = 1;
     return STORM_HIP_OK;
@@ -1261,18 +1239,7 @@ int res_solve(bool bicgstab, const storm_hip_op *op, double alpha, double beta, 
     c->res_prof_blocks = G.blocks;
   }
   void *args[] = {&A};
-  // (launched like any kernel: the grid is one block per CU at most and the occupancy query accepts it -- see
-  //  latency.hip coop_launch; option coop_plain = 0: through the runtime's cooperative queue)
-  const hipError_t e = c->opt_coop_plain != 0
-                           ? hipLaunchKernel(fn, dim3((unsigned)G.blocks), dim3(kResThreads), args, G.lds_bytes, c->stream)
-                           : hipLaunchCooperativeKernel(fn, dim3((unsigned)G.blocks), dim3(kResThreads), args, (unsigned)G.lds_bytes, c->stream);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    c->coop_fallback = 1;
-    return STORM_HIP_OK;
-  }
-  c->coop_ran = 1;
-  *taken = true;
+  *taken = coop_launch(c, fn, (unsigned)G.blocks, args, G.lds_bytes, kResThreads);
   return STORM_HIP_OK;
 }
 

@@ -179,7 +179,7 @@ int post_and_poll(Driver &d, int64_t it, bool *stop);
 // The end of a solve: the slab into args.result and args.history; num_applies = 1 + per_it * iterations (+ with m > 0 one
 // per restart cycle of m iterations).
 int collect(Driver &d, const FusedSolveArgs &args, int per_it, int64_t m = 0);
-// A fused solve that may take a cooperative kernel, re-run without them should one give up (latency.hip)
+// A fused solve that may take a cooperative kernel, re-run without them should one give up (coop_host.hip)
 int fused_solve(FusedSolveArgs a);
 
 }  // namespace storm

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(kWave) void gmres_givens_kernel(SolverState *st, Gm
 //   w -= ha qa;  w -= hb qb;                       (ha, hb from the Hessenberg; qa == nullptr: nothing to subtract,
 //                                                   qb == nullptr: one vector)
 //   then, of the updated w:  a = <w, qc>, b = <w, qd>, c = <qc, qd>   ->   *out_c = a,  *out_d = b - a c
-//   (the reference's h = <w - a qc, qd>, by bilinearity -- see mgs_chain_kernel, latency.hip);
+//   (the reference's h = <w - a qc, qd>, by bilinearity -- see mgs_chain_kernel, mgs_chain.hip);
 //   qd == nullptr: *out_c = <w, qc>;  qc == nullptr: *out_c = <w, w> (SolverGmres.hpp:161).
 // 24 B/row/step and half a launch per step instead of 32 B/row/step and two launches (mgs_step_kernel + final pass).
 __global__ __launch_bounds__(kBlock) void mgs_pair_kernel(int64_t n, const int *done, double *__restrict__ w,
@@ -323,7 +323,7 @@ int gmres_orthogonalize(storm_hip_ctx *c, int64_t n, const SolverState *st, cons
                         int gram_schmidt, bool *normalised, const MgsGivens *givens, bool *givens_done,
                         const ChainApply *apply) {
   // apply (nullable): qn = beta q[k] + alpha M(q[k]) has NOT been formed yet -- the cooperative chain does it itself where
-  // it can (latency.hip: mgs_chain_quad_kernel<S, T, true>), otherwise it is formed here, before anything reads qn
+  // it can (mgs_chain.hip: mgs_chain_quad_kernel<S, T, true>), otherwise it is formed here, before anything reads qn
   if (normalised) *normalised = false;
   if (givens_done) *givens_done = false;
   bool applied = false;

@@ -16,7 +16,7 @@ never tighter than what the ORACLE ITSELF can be held to: the same C source buil
 oracle against oracle 4e-8 (64^3), 9e-8 (128^3), 2.8e-6 (convection-diffusion); device against oracle 3.9e-8, 1.8e-7,
 6.1e-6: the device sits inside the oracle's own rounding sensitivity, which is the strongest statement a comparison of
 two roundings of this recurrence admits.  GMRES: oracle against oracle ~1e-12, device 1e-10 ... 3e-10 (its Gram-Schmidt
-steps are grouped by bilinearity, csrc/latency.hip: the same algebra, dot products rounded in another grouping)."""
+steps are grouped by bilinearity, csrc/mgs_chain.hip: the same algebra, dot products rounded in another grouping)."""
 import numpy as np
 import pytest
 

@@ -285,7 +285,7 @@ def test_latency_path_is_bitwise_reproducible(env, kind, shape):
 @pytest.mark.parametrize("shape", [(48, 40, 36), (64, 64, 33), (20, 18, 16)])
 def test_chain_kernel_applies_the_operator_itself_with_the_same_bits(shape):
     """GMRES's Arnoldi step w = A q_k (SolverGmres.hpp:155) inside the Gram-Schmidt chain kernel (test hook test_disable bit 1 switches it off;
-    latency.hip: mgs_chain_quad_kernel<S, T, true>) -- spmv_canon_kernel's arithmetic on the thread's own row pairs: the
+    mgs_chain.hip: mgs_chain_quad_kernel<S, T, true>) -- spmv_canon_kernel's arithmetic on the thread's own row pairs: the
     residual histories and the solutions are BITWISE those of the launch-then-chain form, for the symmetric and the
     convection-diffusion operator; a chain variant that cannot apply gets the launch in front of it."""
     from stormruler_amd import api, mesh
