@@ -498,9 +498,49 @@ int lat_check_gave_up(storm_hip_ctx *c);
 // Run a solve that may use cooperative kernels; when one of them gave up, restore x and run it again without them.
 int coop_solve_with_fallback(storm_hip_ctx *c, storm_hip_vec *x, int (*run)(void *), void *arg, int *fallback_out);
 
+// op_pack.hip -- the host-only half of the operator build: everything the build decides and every byte the apply kernels
+// read, as host data (no context, no device; spmv_build.hip uploads it)
+struct PackOptions {  // plain values of the context's options of the same names
+  int64_t ell_cap = 0, spmv_dict = 4, spmv_mixed = 1, spmv_spw = 0, latency_path = 1, latency_rows = 1 << 19;
+};
+struct OpImage {  // the fields of storm_hip_op of the same names; an array stands for its d_ / h_ one
+  int64_t n_rows = 0, n_halo = 0, nnz = 0, n_slices = 0, max_row_len = 0, ell_slots = 0;
+  int uniform_width = 0, pair = 0, bnd_width = 0, canon_k = 0, canon_m1 = -1;
+  int canon_off[7] = {0, 0, 0, 0, 0, 0, 0};
+  int dict_size = 0, offs_size = 0;
+  int64_t spw = 1, tail_rows = 0, tail_nnz = 0, pack_bytes = 0;
+  std::vector<int64_t> slice_off;
+  std::vector<char> pack;
+  std::vector<double> dict;  // kDictSize values, or empty
+  std::vector<int> offs;     // kDictSize offsets, or empty
+  std::vector<uint8_t> rec_idx;
+  std::vector<uint64_t> rec_words;
+  std::vector<char> bnd_pack;
+  std::vector<int> tail_row;
+  std::vector<int64_t> tail_ptr;
+  std::vector<int> tail_col;
+  std::vector<double> tail_val;
+  std::vector<int> interior, boundary;
+  std::vector<int64_t> lat_off;  // the latency path's compact fp64 copy; both empty when the operator does not qualify
+  std::vector<char> lat_pack;
+};
+// from off-diagonal CSR rows (entries already in the order they must be summed) and the diagonal term ext
+int op_pack(const PackOptions &o, int64_t n, int64_t n_halo, const std::vector<int64_t> &row_ptr, const std::vector<int> &col,
+            const std::vector<double> &val, const std::vector<double> &ext, OpImage *img);
+// the host halves of the storm_hip_op_create_* entry points: their arguments behind the context and the null check of it
+int op_pack_from_face_weights(const PackOptions &o, int64_t n_owned, int64_t n_halo, int64_t n_faces, const int64_t *inner,
+                              const int64_t *outer, const double *w_inner, const double *w_outer, const double *diag_extra,
+                              OpImage *img);
+int op_pack_from_faces(const PackOptions &o, int64_t n_owned, int64_t n_halo, int64_t n_faces, const int64_t *inner,
+                       const int64_t *outer, const double *coef, int64_t n_bfaces, const int64_t *b_cell, const double *b_coef,
+                       const double *volume, OpImage *img);
+int op_pack_from_mesh(const PackOptions &o, int64_t n_owned, int64_t n_halo, int32_t dim, int64_t n_faces, const int64_t *inner,
+                      const int64_t *outer, const double *area, const double *center, int64_t n_bfaces, const int64_t *b_cell,
+                      const double *b_area, const double *b_center, const double *volume, OpImage *img);
+int op_pack_csr(const PackOptions &o, int64_t n_rows, int64_t n_halo, const int64_t *row_ptr, const int64_t *col,
+                const double *val, OpImage *img);
+
 // latency.hip
-int op_make_latency_copy(storm_hip_op *op, int64_t n, int64_t n_halo, const std::vector<int64_t> &row_ptr,
-                         const std::vector<int> &col, const std::vector<double> &val, const std::vector<double> &ext);
 bool cg_latency_eligible(const storm_hip_op *op);
 // *taken = false: no cooperative kernel ran (none fits, or the launch was refused) -- take the throughput path
 int cg_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x, double *p,

@@ -10,7 +10,7 @@
 //     p'[c] = r[c] + beta p[c], with the same expression (hence the same bits) as the owner does in registers.
 //     That removes the third synchronisation point of a CG iteration ("p complete"): TWO grid barriers per
 //     iteration remain, one behind each reduction;
-//   * the operator is read from a compact fp64 sliced-ELL copy made when the operator was built
+//   * the operator is read from a compact fp64 sliced-ELL copy made when the operator was built (op_pack.hip)
 //     ([ext 64 f64][col W x 64 i32][val W x 64 f64] per slice, slot-major; small: it stays in L2 / Infinity Cache);
 //   * a reduction IS the barrier: every block publishes its partial in its own slot as two self-validating 8-byte
 //     words { half of the value, sequence number } (fire and forget: no ordering to rely on), and every block polls
@@ -524,46 +524,6 @@ __global__ __launch_bounds__(kLatBlock) void bicgstab_latency_kernel(LatArgs a) 
     if (s < a.n_slices && row < a.n_rows) a.x[row] = x[q];
   }
   lat_finish(a.st, g);
-}
-
-// Compact fp64 copy of an operator for the latency path (called by build_op); absent when the operator is too
-// large, partitioned, or has rows longer than its ELL cap.
-int op_make_latency_copy(storm_hip_op *op, int64_t n, int64_t n_halo, const std::vector<int64_t> &row_ptr,
-                         const std::vector<int> &col, const std::vector<double> &val, const std::vector<double> &ext) {
-  storm_hip_ctx *c = op->ctx;
-  if (c->opt_latency_path == 0 || n_halo != 0 || n <= 0 || n > c->opt_latency_rows) return STORM_HIP_OK;
-  const int64_t n_slices = (n + kWave - 1) / kWave;
-  std::vector<int64_t> off((size_t)n_slices + 1, 0);
-  for (int64_t s = 0; s < n_slices; ++s) {
-    int64_t w = 0;
-    for (int64_t r = s * kWave; r < std::min(n, (s + 1) * kWave); ++r) w = std::max(w, row_ptr[r + 1] - row_ptr[r]);
-    if (w > 64) return STORM_HIP_OK;  // a very long row: the throughput path's CSR tail handles those
-    off[(size_t)s + 1] = off[(size_t)s] + kWave * 8 + w * (kWave * 12);
-  }
-  std::vector<char> pack((size_t)off[(size_t)n_slices], 0);
-  for (int64_t s = 0; s < n_slices; ++s) {
-    const int width = (int)((off[(size_t)s + 1] - off[(size_t)s] - kWave * 8) / (kWave * 12));
-    char *rec = pack.data() + off[(size_t)s];
-    double *e_ = reinterpret_cast<double *>(rec);
-    int *c_ = reinterpret_cast<int *>(rec + kWave * 8);
-    double *v_ = reinterpret_cast<double *>(rec + kWave * 8 + (int64_t)width * (kWave * 4));
-    for (int l = 0; l < kWave; ++l) {
-      const int64_t r = s * kWave + l;
-      e_[l] = r < n ? ext[(size_t)r] : 0.0;
-      const int64_t b0 = r < n ? row_ptr[r] : 0, e0 = r < n ? row_ptr[r + 1] : 0;
-      for (int k = 0; k < width; ++k) {
-        const bool real = b0 + k < e0;
-        c_[k * kWave + l] = real ? col[(size_t)(b0 + k)] : (int)(r < n ? r : n - 1);
-        v_[k * kWave + l] = real ? val[(size_t)(b0 + k)] : 0.0;
-      }
-    }
-  }
-  HIP_TRY(hipMalloc((void **)&op->d_lat_pack, pack.size() ? pack.size() : 1));
-  HIP_TRY(hipMalloc((void **)&op->d_lat_off, sizeof(int64_t) * off.size()));
-  HIP_TRY(hipMemcpy(op->d_lat_pack, pack.data(), pack.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(op->d_lat_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice));
-  op->lat_bytes = (int64_t)pack.size();
-  return STORM_HIP_OK;
 }
 
 bool cg_latency_eligible(const storm_hip_op *op) {

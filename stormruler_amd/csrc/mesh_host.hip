@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "host_threads.hpp"
 
 namespace storm {
 // std::vector without the zero-fill of resize(): the big arrays are first touched by the threads that fill them
@@ -92,12 +93,6 @@ struct PhaseTimer {  // STORM_HIP_MESH_TIMING=1: seconds per phase on stderr
   }
 };
 
-int host_threads() {
-  const char *e = getenv("STORM_HIP_BUILD_THREADS");
-  int t = e ? atoi(e) : 0;
-  if (t <= 0) t = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  return t;
-}
 template <class F>
 void par_for(int64_t n, F &&fn, int64_t min_chunk = 32768) {  // fn(thread, begin, end)
   const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (n + min_chunk - 1) / min_chunk));

@@ -22,16 +22,11 @@
 #include <vector>
 
 #include "common.hpp"
+#include "host_threads.hpp"
 
 namespace storm {
 namespace {
 
-int order_threads() {
-  const char *e = getenv("STORM_HIP_BUILD_THREADS");
-  int t = e ? atoi(e) : 0;
-  if (t <= 0) t = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  return t;
-}
 template <class F>
 void par_for(int64_t n, int nt, F &&fn) {  // fn(thread, begin, end)
   nt = (int)std::max<int64_t>(1, std::min<int64_t>(nt, (n + 65535) / 65536));
@@ -194,7 +189,7 @@ static int order_cells_impl(int32_t dim, int64_t n_cells, const double *centers,
   STORM_REQUIRE(mode >= 0 && mode <= 3, "order_cells: mode 0 (lattice, else Morton), 1 (Morton), 2 (lattice or fail), 3 (Hilbert)");
   if (kind) *kind = 0;
   if (n_cells == 0) return STORM_HIP_OK;
-  const int nt = order_threads();
+  const int nt = host_threads();
   double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
   for (int d = 0; d < dim; ++d) lo[d] = hi[d] = centers[d];
   {

@@ -48,7 +48,7 @@
 //
 // Translation units (NOTES.md, "Source layout and dispatch of the apply", has the table): spmv_device.hpp -- argument structs, helpers, the launch
 // interface; spmv_sell.hip, spmv_dict.hip, spmv_pair.hip, spmv_lattice.hip -- one per kernel family, each exporting
-// launchers that take a RangeLaunch; spmv_build.hip -- the host-side build and the create entry points; this file --
+// launchers that take a RangeLaunch; op_pack.hip -- the host-side build; spmv_build.hip -- its upload and the create entry points; this file --
 // the dispatch (which launches make up an apply, which format takes each), the diagonal and the apply entry points.
 #include <algorithm>
 #include <cstring>
@@ -257,8 +257,8 @@ int spmv_launch(const storm_hip_op *op, Scal alpha, Scal beta, const double *x, 
 
 // ---- diagonal of beta*I + alpha*M (for a Jacobi preconditioner) -----------------------------------
 // In the difference form  (Mx)_i = sum_k w_ik (x_col - x_i) + ext_i x_i  the coefficient of x_i is
-// ext_i - sum_k w_ik (no slot has col == i: build_op receives off-diagonal entries only, and padding
-// slots carry w = 0).  One lane per row, same slot addressing as build_op; not a hot kernel.
+// ext_i - sum_k w_ik (no slot has col == i: op_pack receives off-diagonal entries only, and padding
+// slots carry w = 0).  One lane per row, same slot addressing as op_pack.hip; not a hot kernel.
 __global__ __launch_bounds__(kBlock) void diag_sell_kernel(const char *__restrict__ pack,
                                                            const int64_t *__restrict__ slice_off, int64_t n_rows,
                                                            const double *__restrict__ dict, int fmt2, double alpha,

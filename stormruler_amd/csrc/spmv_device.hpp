@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "op_layout.hpp"
 #include "ticket_device.hpp"
 #include "ipc_device.hpp"
 #include "wave_device.hpp"
@@ -18,9 +19,6 @@ __device__ __forceinline__ double ld_scal2(const Scal &s) { return s.p ? (*s.p) 
 typedef int int2v __attribute__((ext_vector_type(2)));
 typedef double double2v __attribute__((ext_vector_type(2)));
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kExtBytes = kWave * 8;      // 512
-constexpr int kSlotBytes = kWave * 12;    // 768: one ELL slot of a slice (64 cols + 64 vals)
 
 struct SellArgs {
   const char *__restrict__ pack;          // slice records
@@ -39,10 +37,6 @@ struct SellArgs {
   const unsigned long long *__restrict__ rec_words = nullptr;
   int rec_words_n = 0;
 };
-
-constexpr int kDictSize = 256;
-constexpr int kPairRecBytes = 2 * kWave * 8 + kWave * 8;  // format 3: 64 x (u64, u64) weights + 64 x u64 offsets per 128 rows
-constexpr int kColSlotBytes = kWave * 4;  // 256: one slot of a value-dictionary record (columns only)
 
 struct DotArgs {
   const double *w;   // partial of <w, y>, may be null
@@ -117,7 +111,6 @@ __device__ __forceinline__ double ld_d(const double *p) {
 // 8 + 8 + 8 = 24 B/row and 8 vector-memory instructions per row pair (format 3: 28 B/row and 10).  The sums run
 // over the slots in the common order = every row's own face order, with exactly the bit patterns of the other
 // formats: results are bit-identical (tests/test_gpu_formats.py).
-constexpr int kCanonRecBytes = 2 * kWave * 8;
 struct CanonArgs {
   int off[7];
   int max_gather;  // largest guard-relative index a 16-byte gather may start at
