@@ -41,6 +41,9 @@ extern "C" {
  * (storm_hip_op_apply2, storm_hip_solve_cg2, storm_hip_krylov_set_operator2; HipTwoStageOperator in storm_hip/Storm.hpp),
  * which was added within ABI 6.  A caller that must also build against an older header tests it with #ifdef. */
 #define STORM_HIP_HAS_TWO_STAGE 1
+/* ... and by every header that declares the updatable face-weight operator (storm_hip_op_create_from_face_weights_updatable,
+ * storm_hip_op_set_face_weights, storm_hip_op_cells_to_faces, storm_hip_op_face_count), added within ABI 6 as well. */
+#define STORM_HIP_HAS_FACE_UPDATE 1
 
 enum {
   STORM_HIP_OK = 0,
@@ -303,6 +306,42 @@ int storm_hip_op_create_from_face_weights(storm_hip_ctx *ctx, int64_t n_owned, i
                                           const double *w_outer, const double *diag_extra,
                                           storm_hip_op **out);
 
+/* The same operator, UPDATABLE: its face weights can be rewritten on the device (storm_hip_op_set_face_weights) from
+ * vectors of per-face values, with no host rebuild -- for coefficients that change every step and are known only on
+ * the device: an upwind convection term whose velocity moves (Feathers/ConvectionScheme.hpp:80-107; the playground's
+ * commented-out CONV, Playground.cpp:155-166), a mobility M(c), a variable density.  Same arguments, same rows, same
+ * face-order summation.  The operator keeps the fp64 records (as under option spmv_dict = 0) whatever it would qualify
+ * for, keeps no compact copy for the one-kernel paths, and carries a source map: 4 bytes per record slot and CSR-tail
+ * entry plus 8 bytes per face of device memory.  n_faces >= 2^30: STORM_HIP_E_INVALID.
+ *
+ * A FACE VECTOR is an ordinary storm_hip_vec of the operator's context with n_owned == n_faces and n_halo == 0, element f
+ * belonging to face f of the arrays the operator was created from; every vector statement (storm_hip_map, _vmul, ...)
+ * works on it.
+ *
+ * storm_hip_op_face_count: n_faces of an updatable operator, 0 for any other.
+ * storm_hip_op_set_face_weights: the weights become w_inner / w_outer and the diagonal term diag_extra (n_owned rows of
+ *   the operator; NULL: zeros).  Enqueued on the context's stream; never waits for the device.  Contract: afterwards the
+ *   operator is in every respect -- apply, block apply, diagonal, Gershgorin bound, every solver -- the one a fresh create
+ *   with those weights gives, bit for bit.  Objects that cached something derived from the OLD values are the caller's to
+ *   rebuild: a storm_hip_cheb (its eigenvalue bounds) and a diagonal obtained earlier.  An update between
+ *   storm_hip_krylov_init and storm_hip_krylov_finalize of a solve on this operator is the caller's error.
+ *   Counted by "op_face_updates" (storm_hip_ctx_get_counter).
+ * storm_hip_op_cells_to_faces: at_inner[f] = cell[inner[f]], at_outer[f] = cell[outer[f]] for a cell vector of the
+ *   operator's size (its halo tail is read as it stands: no exchange); either output may be NULL.
+ * Refusals, all before a device is touched, with a message that names the sizes: an operator that was not created
+ * updatable STORM_HIP_E_UNSUPPORTED; a null argument, a vector of the wrong length or of another context
+ * STORM_HIP_E_INVALID. */
+int storm_hip_op_create_from_face_weights_updatable(storm_hip_ctx *ctx, int64_t n_owned, int64_t n_halo,
+                                                    int64_t n_faces, const int64_t *inner,
+                                                    const int64_t *outer, const double *w_inner,
+                                                    const double *w_outer, const double *diag_extra,
+                                                    storm_hip_op **out);
+int storm_hip_op_face_count(const storm_hip_op *op, int64_t *n_faces);
+int storm_hip_op_set_face_weights(storm_hip_op *op, const storm_hip_vec *w_inner, const storm_hip_vec *w_outer,
+                                  const storm_hip_vec *diag_extra);
+int storm_hip_op_cells_to_faces(const storm_hip_op *op, const storm_hip_vec *cell, storm_hip_vec *at_inner,
+                                storm_hip_vec *at_outer);
+
 /* Assembled CSR rows (n_rows owned rows, columns in [0, n_rows + n_halo)). */
 int storm_hip_op_create_csr(storm_hip_ctx *ctx, int64_t n_rows, int64_t n_halo,
                             const int64_t *row_ptr, const int64_t *col, const double *val,
@@ -395,7 +434,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *ctx, const char *key, int64_t value)
  * fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip), "engine_solves" (csrc/krylov_abi.hip), "jfnk_inner_solves" (inner BiCGStab solves of
  * STORM_HIP_JFNK), "fd_fused_dots" (products of a finite-difference operator whose difference statement took the method's
  * reductions of z along in its pass), "host_reductions" (calls of storm_hip_dot / _norm2 / _multi_dot / _multi_dot_end / _block_dot: the reduction
- * entry points that make the host wait for their sums -- a device-resident loop leaves it where it was), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "cheb_fused_applies" / "cheb_statement_applies" (storm_hip_cheb_apply by path), "cg_fused_steps" (solves whose CG step rode in
+ * entry points that make the host wait for their sums -- a device-resident loop leaves it where it was), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "op_face_updates" (storm_hip_op_set_face_weights, csrc/op_update.hip), "cheb_fused_applies" / "cheb_statement_applies" (storm_hip_cheb_apply by path), "cg_fused_steps" (solves whose CG step rode in
  * the SpMV launch), "lazy_fused_dots" / "lazy_fused_pairs" / "lazy_apply_dots" / "lazy_cg_steps" / "lazy_waiting" (option
  * lazy_statements: reductions that rode in a statement's kernel, pairs of statements that left as one pass, applies that
  * left with a fused dot, fused CG steps, statements waiting now).  On the peer-window transport, where the time of the exchanges went (ticks of 10 ns of the device's

@@ -518,6 +518,17 @@ public:
                                                         w_inner.data(), w_outer.data(), diag_extra, &m._h));
     return m;
   }
+  /// The same operator with weights that set_face_weights rewrites on the device (storm_hip.h: "UPDATABLE").
+  static StencilMatrix from_face_weights_updatable(const Context& ctx, std::size_t n_owned, std::size_t n_halo,
+                                                   const std::vector<int64_t>& inner, const std::vector<int64_t>& outer,
+                                                   const std::vector<real_t>& w_inner, const std::vector<real_t>& w_outer,
+                                                   const real_t* diag_extra = nullptr) {
+    StencilMatrix m;
+    detail::check(storm_hip_op_create_from_face_weights_updatable(ctx.handle(), (int64_t)n_owned, (int64_t)n_halo,
+                                                                  (int64_t)inner.size(), inner.data(), outer.data(),
+                                                                  w_inner.data(), w_outer.data(), diag_extra, &m._h));
+    return m;
+  }
   /// Takes ownership of an operator handle made through the C ABI.
   static StencilMatrix adopt(storm_hip_op* handle) noexcept {
     StencilMatrix m;
@@ -543,6 +554,22 @@ public:
   /// y += alpha M(x)
   void apply_add(real_t alpha, const DeviceVector& x, DeviceVector& y) const {
     detail::check(storm_hip_op_apply_add(_h, alpha, x.handle(), y.handle()));
+  }
+  /// Faces of an updatable operator (the length of its face vectors); 0 for any other.
+  std::size_t face_count() const {
+    int64_t n = 0;
+    detail::check(storm_hip_op_face_count(_h, &n));
+    return (std::size_t)n;
+  }
+  /// The weights of an updatable operator from face vectors (face_count() elements), the diagonal term from a cell vector
+  /// (null: zeros), on the device; the operator is then the one a fresh from_face_weights with those values gives.
+  void set_face_weights(const DeviceVector& w_inner, const DeviceVector& w_outer, const DeviceVector* diag_extra = nullptr) {
+    detail::check(storm_hip_op_set_face_weights(_h, w_inner.handle(), w_outer.handle(), diag_extra ? diag_extra->handle() : nullptr));
+  }
+  /// at_inner[f] = cell[inner[f]], at_outer[f] = cell[outer[f]] over the faces of an updatable operator (either may be null).
+  void cells_to_faces(const DeviceVector& cell, DeviceVector* at_inner, DeviceVector* at_outer) const {
+    detail::check(storm_hip_op_cells_to_faces(_h, cell.handle(), at_inner ? at_inner->handle() : nullptr,
+                                              at_outer ? at_outer->handle() : nullptr));
   }
   storm_hip_op* handle() const noexcept { return _h; }
 

@@ -129,6 +129,11 @@ SIGNATURES = {
                                                 C.c_int64, i64p, f64p, f64p, f64p, C.POINTER(vp)]),
     "storm_hip_op_create_from_face_weights": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, i64p, i64p,
                                                         f64p, f64p, f64p, C.POINTER(vp)]),
+    "storm_hip_op_create_from_face_weights_updatable": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, i64p, i64p,
+                                                                  f64p, f64p, f64p, C.POINTER(vp)]),
+    "storm_hip_op_face_count": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+    "storm_hip_op_set_face_weights": (C.c_int, [vp, vp, vp, vp]),
+    "storm_hip_op_cells_to_faces": (C.c_int, [vp, vp, vp, vp]),
     "storm_hip_op_create_csr": (C.c_int, [vp, C.c_int64, C.c_int64, i64p, i64p, f64p, C.POINTER(vp)]),
     "storm_hip_op_set_halo": (C.c_int, [vp, C.c_int, i32p, i64p, i64p, i64p]),
     "storm_hip_mesh_read_tetgen": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(vp)]),

@@ -680,6 +680,44 @@ class StencilMatrix:
         return cls(ctx, h)
 
     @classmethod
+    def from_face_weights_updatable(cls, ctx: Context, n_owned: int, n_halo: int, inner, outer, w_inner, w_outer,
+                                    diag_extra=None) -> "StencilMatrix":
+        """:meth:`from_face_weights` whose weights :meth:`set_face_weights` can rewrite on the device
+        (``storm_hip_op_create_from_face_weights_updatable``): fp64 records and a source map, the same bits."""
+        h = C.c_void_p()
+        i64, f64 = _lib.i64p, _lib.f64p
+        inner = np.ascontiguousarray(inner, np.int64)
+        outer = np.ascontiguousarray(outer, np.int64)
+        w_inner = np.ascontiguousarray(w_inner, np.float64)
+        w_outer = np.ascontiguousarray(w_outer, np.float64)
+        de = None if diag_extra is None else np.ascontiguousarray(diag_extra, np.float64)
+        check(lib.storm_hip_op_create_from_face_weights_updatable(
+            ctx._h, n_owned, n_halo, inner.size, inner.ctypes.data_as(i64), outer.ctypes.data_as(i64),
+            w_inner.ctypes.data_as(f64), w_outer.ctypes.data_as(f64),
+            None if de is None else de.ctypes.data_as(f64), C.byref(h)))
+        return cls(ctx, h)
+
+    @property
+    def face_count(self) -> int:
+        """Faces of an updatable operator (the length of its face vectors); 0 for any other."""
+        n = C.c_int64()
+        check(lib.storm_hip_op_face_count(self._h, C.byref(n)))
+        return n.value
+
+    def set_face_weights(self, w_inner: DeviceVector, w_outer: DeviceVector, diag_extra: Optional[DeviceVector] = None) -> None:
+        """Rewrite the weights of an updatable operator from face vectors (``face_count`` elements, no halo) and the
+        diagonal term from a cell vector (``None``: zeros), on the device: afterwards the operator is the one a fresh
+        :meth:`from_face_weights` with those values gives.  A :class:`ChebyshevPreconditioner` or a diagonal derived
+        from the old values is the caller's to rebuild."""
+        check(lib.storm_hip_op_set_face_weights(self._h, w_inner._h, w_outer._h, None if diag_extra is None else diag_extra._h))
+
+    def cells_to_faces(self, cell: DeviceVector, at_inner: Optional[DeviceVector], at_outer: Optional[DeviceVector]) -> None:
+        """``at_inner[f] = cell[inner[f]]``, ``at_outer[f] = cell[outer[f]]`` over the faces of an updatable operator
+        (either output may be ``None``; the halo tail of ``cell`` is read as it stands)."""
+        check(lib.storm_hip_op_cells_to_faces(self._h, cell._h, None if at_inner is None else at_inner._h,
+                                              None if at_outer is None else at_outer._h))
+
+    @classmethod
     def from_csr(cls, ctx: Context, a, n_halo: int = 0) -> "StencilMatrix":
         a = a.tocsr()
         rp = np.ascontiguousarray(a.indptr, np.int64)

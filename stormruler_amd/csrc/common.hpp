@@ -262,6 +262,7 @@ struct storm_hip_ctx {
   int64_t n_jfnk_inner_solves = 0;  // krylov_abi.hip: inner solves of STORM_HIP_JFNK
   int64_t n_fd_fused_dots = 0;      // krylov_engine.hip: finite-difference products whose difference statement took the reductions of z along
   int64_t n_block_solves = 0;  // storm_hip_solve_cg_block (block.hip)
+  int64_t n_op_face_updates = 0;  // storm_hip_op_set_face_weights (op_update.hip)
   int64_t opt_cheb_fused = 1;  // storm_hip_cheb_apply: the fused step kernel where it applies (fp64 records, no CSR tail); 0: library statements everywhere
   int64_t n_cheb_fused_applies = 0, n_cheb_statement_applies = 0;  // precond_cheb.hip: which path an apply took
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
@@ -338,6 +339,11 @@ struct storm_hip_op {
   int64_t *d_lat_off = nullptr;
   int64_t lat_bytes = 0;
   storm::HaloPlan halo;
+  // an updatable face-weight operator (op_update.hip): the source map of its records and tail, the faces' cells
+  int updatable = 0;
+  int64_t n_faces = 0;
+  int *d_src = nullptr, *d_tail_src = nullptr;        // OpImage::src, tail_src
+  int *d_face_inner = nullptr, *d_face_outer = nullptr;  // [n_faces]
 };
 
 // The Chebyshev polynomial preconditioner (precond_cheb.hip): z = p_m(diag(s) A) diag(s) r for A = beta I + alpha M.
@@ -502,6 +508,7 @@ int coop_solve_with_fallback(storm_hip_ctx *c, storm_hip_vec *x, int (*run)(void
 // read, as host data (no context, no device; spmv_build.hip uploads it)
 struct PackOptions {  // plain values of the context's options of the same names
   int64_t ell_cap = 0, spmv_dict = 4, spmv_mixed = 1, spmv_spw = 0, latency_path = 1, latency_rows = 1 << 19;
+  int64_t updatable = 0;  // (no option: set by storm_hip_op_create_from_face_weights_updatable) fp64 records + a source map, no latency copy
 };
 struct OpImage {  // the fields of storm_hip_op of the same names; an array stands for its d_ / h_ one
   int64_t n_rows = 0, n_halo = 0, nnz = 0, n_slices = 0, max_row_len = 0, ell_slots = 0;
@@ -523,10 +530,17 @@ struct OpImage {  // the fields of storm_hip_op of the same names; an array stan
   std::vector<int> interior, boundary;
   std::vector<int64_t> lat_off;  // the latency path's compact fp64 copy; both empty when the operator does not qualify
   std::vector<char> lat_pack;
+  // An updatable operator (PackOptions::updatable; all empty / 0 otherwise): where every weight came from, as source ids
+  // 2 f + side -- side 0: the entry of row inner[f] that carries w_inner[f], side 1: that of row outer[f] with w_outer[f].
+  int updatable = 0;
+  int64_t n_faces = 0;
+  std::vector<int> src;       // the val regions of all slices one behind the other, a slot at its index inside its region; padding -1
+  std::vector<int> tail_src;  // parallel to tail_val
+  std::vector<int> face_inner, face_outer;  // the faces' cells
 };
 // from off-diagonal CSR rows (entries already in the order they must be summed) and the diagonal term ext
 int op_pack(const PackOptions &o, int64_t n, int64_t n_halo, const std::vector<int64_t> &row_ptr, const std::vector<int> &col,
-            const std::vector<double> &val, const std::vector<double> &ext, OpImage *img);
+            const std::vector<double> &val, const std::vector<double> &ext, OpImage *img, const std::vector<int> *src = nullptr);
 // the host halves of the storm_hip_op_create_* entry points: their arguments behind the context and the null check of it
 int op_pack_from_face_weights(const PackOptions &o, int64_t n_owned, int64_t n_halo, int64_t n_faces, const int64_t *inner,
                               const int64_t *outer, const double *w_inner, const double *w_outer, const double *diag_extra,

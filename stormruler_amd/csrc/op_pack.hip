@@ -125,6 +125,7 @@ struct Rows {  // what op_pack receives
   const std::vector<int64_t> &row_ptr;
   const std::vector<int> &col;
   const std::vector<double> &val, &ext;
+  const std::vector<int> *src;  // updatable operators: the source id 2 f + side of every entry, parallel to val (else null)
   int64_t len(int64_t r) const { return row_ptr[r + 1] - row_ptr[r]; }
   int64_t groups() const { return (n + 2 * kWave - 1) / (2 * kWave); }  // 128-row groups of paired rows (formats 3, 4)
 };
@@ -423,9 +424,13 @@ void sell_records(const Rows &A, const std::vector<int> &width, ValueDict *vd, V
   const int64_t n = A.n;
   const bool cv = vd != nullptr, co = od != nullptr;
   img->pack.assign((size_t)img->slice_off[(size_t)img->n_slices], 0);
+  // the source map of an updatable operator (fp64 records only): one id per slot of every slice's val region, at the
+  // slot's own index `at` behind the slots of the slices before it; padding slots -1
+  if (A.src) img->src.assign((size_t)((img->slice_off[(size_t)img->n_slices] - img->n_slices * kExtBytes) / (kSlotBytes / kWave)), -1);
   for (int64_t s = 0; s < img->n_slices; ++s) {
     const int W = width[(size_t)s];
     char *rec = img->pack.data() + img->slice_off[(size_t)s];
+    int *s_ = A.src ? img->src.data() + (img->slice_off[(size_t)s] - s * kExtBytes) / (kSlotBytes / kWave) : nullptr;
     double *e_ = reinterpret_cast<double *>(rec);
     uint64_t *i_ = reinterpret_cast<uint64_t *>(rec);  // cv: the index words take the place of ext
     int *c_ = reinterpret_cast<int *>(rec + kExtBytes);
@@ -457,6 +462,7 @@ void sell_records(const Rows &A, const std::vector<int> &width, ValueDict *vd, V
         const double w_k = real ? A.val[(size_t)(b + k)] : 0.0;
         if (cv) iw |= (uint64_t)vd->index(w_k) << (8 * (k + 1));
         else v_[at] = w_k;
+        if (s_ && real) s_[at] = (*A.src)[(size_t)(b + k)];
         touches_halo |= real && c_[at] >= n;
       }
       if (cv && !co) i_[l] = iw;
@@ -465,6 +471,7 @@ void sell_records(const Rows &A, const std::vector<int> &width, ValueDict *vd, V
         for (int64_t k = b + W; k < e; ++k) {
           img->tail_col.push_back(A.col[(size_t)k]);
           img->tail_val.push_back(A.val[(size_t)k]);
+          if (A.src) img->tail_src.push_back((*A.src)[(size_t)k]);
           touches_halo |= A.col[(size_t)k] >= n;
         }
         img->tail_ptr.push_back((int64_t)img->tail_col.size());
@@ -492,9 +499,13 @@ void dictionary_tables(const ValueDict *vd, const ValueDict *od, OpImage *img) {
 
 // The most compact lossless format the operator qualifies for, capped by option spmv_dict: 4 (common offset order),
 // 3 (paired rows), 2 (value + offset dictionary), 1 (value dictionary), 0 (fp64 sliced ELL).
-int op_pack(const PackOptions &o, int64_t n, int64_t n_halo, const std::vector<int64_t> &row_ptr, const std::vector<int> &col,
-            const std::vector<double> &val, const std::vector<double> &ext, OpImage *img) {
-  const Rows A{n, n_halo, row_ptr, col, val, ext};
+// `src` (updatable operators, PackOptions::updatable): the source id of every entry; the operator then keeps its fp64
+// records whatever it would qualify for, carries the source map (OpImage::src, tail_src) and forms no latency copy.
+int op_pack(const PackOptions &options, int64_t n, int64_t n_halo, const std::vector<int64_t> &row_ptr, const std::vector<int> &col,
+            const std::vector<double> &val, const std::vector<double> &ext, OpImage *img, const std::vector<int> *src) {
+  PackOptions o = options;
+  if (src) o.spmv_dict = 0, o.latency_path = 0;
+  const Rows A{n, n_halo, row_ptr, col, val, ext, src};
   *img = OpImage();
   img->n_rows = n, img->n_halo = n_halo, img->nnz = row_ptr[n];
   BuildTimer timer;
@@ -570,8 +581,13 @@ namespace {
 // (A row that takes > 255 entries from one chunk: every thread scans all faces for its own range of rows instead.)
 template <class W>
 void rows_from_faces(int64_t n_owned, int64_t n_faces, const int64_t *inner, const int64_t *outer, W &&weight,
-                     std::vector<int64_t> &row_ptr, std::vector<int> &col, std::vector<double> &val) {
+                     std::vector<int64_t> &row_ptr, std::vector<int> &col, std::vector<double> &val, std::vector<int> *src = nullptr) {
   row_ptr.assign((size_t)n_owned + 1, 0);
+  // one entry: its column, its weight and -- where asked for -- its source id 2 f + side (side 1: the entry of row outer[f])
+  auto put = [&](size_t at, int64_t c, int64_t f, bool outer_side) {
+    col[at] = (int)c, val[at] = weight(f, outer_side);
+    if (src) (*src)[at] = (int)(2 * f + (outer_side ? 1 : 0));
+  };
   const int64_t face_chunk = forced_min_chunk() > 0 ? forced_min_chunk() : (1 << 16);
   const int T = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), n_faces / face_chunk));
   const int64_t per = (n_faces + T - 1) / T;
@@ -598,17 +614,18 @@ void rows_from_faces(int64_t n_owned, int64_t n_faces, const int64_t *inner, con
     });
     for (int64_t i = 0; i < n_owned; ++i) row_ptr[(size_t)i + 1] += row_ptr[(size_t)i];
     col.resize((size_t)row_ptr[(size_t)n_owned]), val.resize(col.size());
+    if (src) src->resize(col.size());
     std::vector<int64_t> fill(row_ptr.begin(), row_ptr.end() - 1);
     parallel_chunks(n_owned, 1 << 15, [&](int, int64_t r0, int64_t r1) {
       for (int64_t f = 0; f < n_faces; ++f) {
         const int64_t a = inner[f], b = outer[f];
         if (a >= r0 && a < r1) {
           const size_t at = (size_t)fill[(size_t)a]++;
-          col[at] = (int)b, val[at] = weight(f, false);
+          put(at, b, f, false);
         }
         if (b >= r0 && b < r1) {
           const size_t at = (size_t)fill[(size_t)b]++;
-          col[at] = (int)a, val[at] = weight(f, true);
+          put(at, a, f, true);
         }
       }
     });
@@ -632,17 +649,18 @@ void rows_from_faces(int64_t n_owned, int64_t n_faces, const int64_t *inner, con
     row_ptr[(size_t)i + 1] += row_ptr[(size_t)i];
   }
   col.resize((size_t)row_ptr[(size_t)n_owned]), val.resize(col.size());
+  if (src) src->resize(col.size());
   if (long_rows) {  // (offsets no longer fit a byte: one thread, plain fill)
     std::vector<int64_t> fill(row_ptr.begin(), row_ptr.end() - 1);
     for (int64_t f = 0; f < n_faces; ++f) {
       const int64_t a = inner[f], b = outer[f];
       if (a < n_owned) {
         const size_t at = (size_t)fill[(size_t)a]++;
-        col[at] = (int)b, val[at] = weight(f, false);
+        put(at, b, f, false);
       }
       if (b < n_owned) {
         const size_t at = (size_t)fill[(size_t)b]++;
-        col[at] = (int)a, val[at] = weight(f, true);
+        put(at, a, f, true);
       }
     }
     return;
@@ -654,11 +672,11 @@ void rows_from_faces(int64_t n_owned, int64_t n_faces, const int64_t *inner, con
         const int64_t a = inner[f], b = outer[f];
         if (a < n_owned) {
           const size_t at = (size_t)(row_ptr[(size_t)a] + o_[(size_t)a]++);
-          col[at] = (int)b, val[at] = weight(f, false);
+          put(at, b, f, false);
         }
         if (b < n_owned) {
           const size_t at = (size_t)(row_ptr[(size_t)b] + o_[(size_t)b]++);
-          col[at] = (int)a, val[at] = weight(f, true);
+          put(at, a, f, true);
         }
       }
     }
@@ -745,17 +763,24 @@ int op_pack_from_face_weights(const PackOptions &o, int64_t n_owned, int64_t n_h
   STORM_REQUIRE(n_faces == 0 || (inner && outer && w_inner && w_outer), "op_create: null face array");
   const int64_t nt = n_owned + n_halo;
   STORM_REQUIRE(nt < (int64_t)INT32_MAX, "op_create: %lld cells exceed int32 indexing", (long long)nt);
+  STORM_REQUIRE(o.updatable == 0 || n_faces < ((int64_t)1 << 30), "op_create: %lld faces exceed the 2^30 an updatable operator's int32 source ids hold",
+                (long long)n_faces);
   BuildTimer timer;
   STORM_TRY(require_valid_faces("op_create", n_faces, inner, outer, nt));
   std::vector<int64_t> row_ptr;
-  std::vector<int> col;
+  std::vector<int> col, src;
   std::vector<double> val;
   rows_from_faces(n_owned, n_faces, inner, outer, [&](int64_t f, bool outer_side) { return outer_side ? w_outer[f] : w_inner[f]; },
-                  row_ptr, col, val);
+                  row_ptr, col, val, o.updatable != 0 ? &src : nullptr);
   timer.lap("rows from faces");
   std::vector<double> ext((size_t)n_owned, 0.0);
   if (diag_extra) std::copy(diag_extra, diag_extra + n_owned, ext.begin());
-  return op_pack(o, n_owned, n_halo, row_ptr, col, val, ext, img);
+  STORM_TRY(op_pack(o, n_owned, n_halo, row_ptr, col, val, ext, img, o.updatable != 0 ? &src : nullptr));
+  if (o.updatable != 0) {  // the faces' cells, for cells_to_faces (int32: nt < 2^31 was checked above)
+    img->updatable = 1, img->n_faces = n_faces;
+    img->face_inner.assign(inner, inner + n_faces), img->face_outer.assign(outer, outer + n_faces);
+  }
+  return STORM_HIP_OK;
 }
 
 int op_pack_from_faces(const PackOptions &o, int64_t n_owned, int64_t n_halo, int64_t n_faces, const int64_t *inner,

@@ -523,6 +523,10 @@ int storm_hip_op_destroy(storm_hip_op *op) {
   (void)hipFree(op->d_tail_val);
   (void)hipFree(op->d_lat_pack);
   (void)hipFree(op->d_lat_off);
+  (void)hipFree(op->d_src);
+  (void)hipFree(op->d_tail_src);
+  (void)hipFree(op->d_face_inner);
+  (void)hipFree(op->d_face_outer);
   (void)hipFree(op->halo.d_send_idx);
   (void)hipFree(op->halo.d_sendbuf);
   delete op;

@@ -73,6 +73,12 @@ static int op_upload_arrays(storm_hip_ctx *c, const OpImage &img, storm_hip_op *
     STORM_TRY(upload(&op->d_bnd_pack, img.bnd_pack, &bytes));
     STORM_TRY(op_upload_slice_lists(op));
   }
+  if (img.updatable) {  // the source map (4 B per ELL slot and tail entry) and the faces' cells (8 B per face)
+    STORM_TRY(upload(&op->d_src, img.src, &bytes));
+    STORM_TRY(upload(&op->d_tail_src, img.tail_src, &bytes));
+    STORM_TRY(upload(&op->d_face_inner, img.face_inner, &bytes));
+    STORM_TRY(upload(&op->d_face_outer, img.face_outer, &bytes));
+  }
   timer.lap("upload");
   op->device_bytes += bytes;
   // fused-dot partials: two per SpMV block
@@ -90,6 +96,7 @@ static int op_upload(storm_hip_ctx *c, OpImage &&img, storm_hip_op **out) {
   op->dict_size = img.dict_size, op->offs_size = img.offs_size, op->rec_words = (int)img.rec_words.size();
   op->spw = img.spw, op->tail_rows = img.tail_rows, op->tail_nnz = img.tail_nnz, op->pack_bytes = img.pack_bytes;
   op->xcd_group_sell = (int)c->opt_spmv_xcd_remap_sell;
+  op->updatable = img.updatable, op->n_faces = img.n_faces;
   op->h_interior = std::move(img.interior), op->h_boundary = std::move(img.boundary);
   op->n_interior_slices = (int64_t)op->h_interior.size();
   const int st = op_upload_arrays(c, img, op);
@@ -122,6 +129,18 @@ int storm_hip_op_create_from_face_weights(storm_hip_ctx *c, int64_t n_owned, int
   *out = nullptr;
   OpImage img;
   STORM_TRY(op_pack_from_face_weights(pack_options(c), n_owned, n_halo, n_faces, inner, outer, w_inner, w_outer, diag_extra, &img));
+  return op_upload(c, std::move(img), out);
+}
+
+int storm_hip_op_create_from_face_weights_updatable(storm_hip_ctx *c, int64_t n_owned, int64_t n_halo, int64_t n_faces,
+                                                    const int64_t *inner, const int64_t *outer, const double *w_inner,
+                                                    const double *w_outer, const double *diag_extra, storm_hip_op **out) {
+  STORM_REQUIRE(c && out, "op_create: null argument");
+  *out = nullptr;
+  OpImage img;
+  PackOptions o = pack_options(c);
+  o.updatable = 1;
+  STORM_TRY(op_pack_from_face_weights(o, n_owned, n_halo, n_faces, inner, outer, w_inner, w_outer, diag_extra, &img));
   return op_upload(c, std::move(img), out);
 }
 
