@@ -44,6 +44,9 @@ extern "C" {
 /* ... and by every header that declares the updatable face-weight operator (storm_hip_op_create_from_face_weights_updatable,
  * storm_hip_op_set_face_weights, storm_hip_op_cells_to_faces, storm_hip_op_face_count), added within ABI 6 as well. */
 #define STORM_HIP_HAS_FACE_UPDATE 1
+/* ... and by every header that declares the fp32-weight companion records (storm_hip_op_build_reduced and the *_reduced
+ * entry points, storm_hip_cheb_create_reduced), added within ABI 6 as well. */
+#define STORM_HIP_HAS_REDUCED_RECORDS 1
 
 enum {
   STORM_HIP_OK = 0,
@@ -434,7 +437,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *ctx, const char *key, int64_t value)
  * fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip), "engine_solves" (csrc/krylov_abi.hip), "jfnk_inner_solves" (inner BiCGStab solves of
  * STORM_HIP_JFNK), "fd_fused_dots" (products of a finite-difference operator whose difference statement took the method's
  * reductions of z along in its pass), "host_reductions" (calls of storm_hip_dot / _norm2 / _multi_dot / _multi_dot_end / _block_dot: the reduction
- * entry points that make the host wait for their sums -- a device-resident loop leaves it where it was), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "op_face_updates" (storm_hip_op_set_face_weights, csrc/op_update.hip), "cheb_fused_applies" / "cheb_statement_applies" (storm_hip_cheb_apply by path), "cg_fused_steps" (solves whose CG step rode in
+ * entry points that make the host wait for their sums -- a device-resident loop leaves it where it was), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "op_face_updates" (storm_hip_op_set_face_weights, csrc/op_update.hip), "cheb_fused_applies" / "cheb_statement_applies" (storm_hip_cheb_apply by path), "cheb_reduced_applies" (... of reduced objects, counted in addition), "op_reduced_builds" / "op_reduced_refreshes" (csrc/op_reduced.hip: companions built; converted again behind storm_hip_op_set_face_weights), "cg_fused_steps" (solves whose CG step rode in
  * the SpMV launch), "lazy_fused_dots" / "lazy_fused_pairs" / "lazy_apply_dots" / "lazy_cg_steps" / "lazy_waiting" (option
  * lazy_statements: reductions that rode in a statement's kernel, pairs of statements that left as one pass, applies that
  * left with a fused dot, fused CG steps, statements waiting now).  On the peer-window transport, where the time of the exchanges went (ticks of 10 ns of the device's
@@ -793,12 +796,58 @@ int storm_hip_cheb_create(const storm_hip_op *op, double alpha, double beta, con
 /* z = P(r); z must not alias r, r is not written.  Enqueues and never waits; inside a solver callback the kernels are
  * predicated on the solve's `done` flag like those of storm_hip_vmul and storm_hip_op_apply. */
 int storm_hip_cheb_apply(const storm_hip_cheb *h, const storm_hip_vec *r, storm_hip_vec *z);
-/* "lambda_min", "lambda_max" (the bounds in use, defaults resolved), "degree". */
+/* "lambda_min", "lambda_max" (the bounds in use, defaults resolved), "degree", "reduced" (1 for an object made by
+ * storm_hip_cheb_create_reduced, 0 otherwise). */
 int storm_hip_cheb_get(const storm_hip_cheb *h, const char *key, double *value);
 int storm_hip_cheb_destroy(storm_hip_cheb *h);
 /* pre_op as the library's Chebyshev preconditioner (h == NULL removes it): bound natively, no callback.  Its operator
  * need not be the solve's.  A size that differs from the solve's vectors: STORM_HIP_E_INVALID from the solve. */
 int storm_hip_krylov_set_preconditioner_cheb(storm_hip_krylov *k, const storm_hip_cheb *h, int side);
+
+/* ---- fp32-weight companion records ("reduced records") --------------------------------------------------------------
+ * An operator on fp64 records (format 0: what any mesh gets; a box built with option spmv_dict = 0) can carry a second copy
+ * of its ELL records and CSR tail values whose weights and diagonal terms are rounded to fp32: 256 + 512 W bytes per slice
+ * of width W instead of 512 + 768 W.  It is a companion, not a format: only the entry points below read it, and every
+ * other call on the operator -- apply, solves, block and fused paths -- keeps reading the fp64 records.  Its purpose is the
+ * Chebyshev preconditioner, whose every step is an operator product: a preconditioner only has to be a fixed linear operator
+ * close to the inverse, and the polynomial of the rounded operator is as good a one as the polynomial of A.
+ *
+ * THE CONTRACT.  w32 = (float)w is IEEE round-to-nearest-even; a weight is widened back to double, exactly, where a kernel
+ * loads it.  Vectors, sums and every other operand stay fp64, every operation is the fp64 kernel's in the same order with the
+ * same contraction.  So storm_hip_op_apply_reduced, storm_hip_op_gershgorin_reduced, storm_hip_cheb_apply of a reduced
+ * object (either path) and a solve preconditioned by it give, BIT FOR BIT, what storm_hip_op_apply, storm_hip_op_gershgorin
+ * and an ordinary Chebyshev object give on a fresh fp64-record operator built from double(float(w)), double(float(ext))
+ * (tests/test_gpu_reduced.py).
+ *
+ * RANGE.  storm_hip_op_build_reduced converts on the device and makes one host wait: if a nonzero weight or diagonal term is
+ * not finite or has a magnitude outside fp32's normal range [2^-126, FLT_MAX], it frees the companion and returns
+ * STORM_HIP_E_UNSUPPORTED (the operator itself is untouched).  storm_hip_op_set_face_weights on an updatable operator that
+ * has a companion enqueues the same conversion behind its refresh, so the companion is always the rounding of the current
+ * fp64 records -- but it makes no host wait and reports no range check: there the range is the CALLER'S PRECONDITION.
+ * A storm_hip_cheb made before a refresh keeps its bounds; rebuilding it is the caller's, as for an ordinary object.
+ *
+ * Refused with STORM_HIP_E_UNSUPPORTED: an operator that is not on fp64 records (a value / offset dictionary, paired rows,
+ * a mixed operator); a halo plan, halo columns or a communicator; apply / gershgorin / cheb_create_reduced on an operator
+ * without a companion (nothing is built behind the caller's back).  Counters (storm_hip_ctx_get_counter):
+ * "op_reduced_builds", "op_reduced_refreshes", "cheb_reduced_applies" (beside "cheb_fused_applies" / "cheb_statement_applies").
+ * storm_hip_op_destroy frees the companion; device_bytes of storm_hip_op_get_stats includes it. */
+int storm_hip_op_build_reduced(storm_hip_op *op); /* idempotent */
+int storm_hip_op_drop_reduced(storm_hip_op *op);  /* waits for the context's stream; no companion: a no-op */
+/* bytes of the companion's records; 0: no companion */
+int storm_hip_op_reduced_bytes(const storm_hip_op *op, int64_t *record_bytes);
+/* y = beta x + alpha M~ x.  Enqueue-only (held-back lazy statements are launched first); inside a solver callback predicated
+ * on the solve's `done` flag like storm_hip_op_apply.  y must not alias x and is not read. */
+int storm_hip_op_apply_reduced(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *x, storm_hip_vec *y);
+/* storm_hip_op_gershgorin from the companion records.  One host wait. */
+int storm_hip_op_gershgorin_reduced(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *scale,
+                                    double *lambda_max);
+/* storm_hip_cheb_create whose object takes its operator products (and, with lmax <= 0, its Gershgorin default) from the
+ * companion records.  storm_hip_cheb_apply runs the fused step on them where the fp64 fused step would run (option
+ * cheb_fused on, no CSR tail), otherwise the statement sequence with storm_hip_op_apply_reduced in place of
+ * storm_hip_op_apply: the same bits.  The solvers bind the object like any other.  Applying it after
+ * storm_hip_op_drop_reduced: STORM_HIP_E_UNSUPPORTED. */
+int storm_hip_cheb_create_reduced(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *dinv, int degree,
+                                  double lmin, double lmax, storm_hip_cheb **out);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

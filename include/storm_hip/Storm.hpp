@@ -710,6 +710,9 @@ public:
     detail::check(storm_hip_op_apply_block(_matrix->handle(), _alpha, _beta, (int)x_block.num_vars(), x_block.handle(),
                                            y_block.handle()));
   }
+  /// Give the matrix (fp64 records: option spmv_dict = 0) its fp32-weight companion records (storm_hip_op_build_reduced;
+  /// idempotent): what a ChebyshevPreconditioner with `reduced_records` reads.  A weight outside fp32's normal range throws.
+  void build_reduced() const { detail::check(storm_hip_op_build_reduced(_matrix->handle())); }
   const StencilMatrix& matrix() const noexcept { return *_matrix; }
   real_t alpha() const noexcept { return _alpha; }
   real_t beta() const noexcept { return _beta; }
@@ -884,12 +887,15 @@ private:
 /// Chebyshev polynomial preconditioner z = p_m(diag(s) A) diag(s) r of a HipStencilOperator (storm_hip_cheb_*,
 /// storm_hip.h): `degree` operator products per apply, no reduction, no host wait.  lambda_max <= 0 takes Gershgorin's
 /// bound, lambda_min <= 0 a thirtieth of lambda_max; `jacobi` scales with the inverse diagonal.  The knob-holder solvers
-/// bind it natively; `mul` is storm_hip_cheb_apply.  The operator it was built from must outlive it.
+/// bind it natively; `mul` is storm_hip_cheb_apply.  The operator it was built from must outlive it.  `reduced_records`:
+/// the operator products read the matrix's fp32-weight companion records (built here if missing) -- the polynomial of the
+/// operator with weights rounded to fp32; every vector and sum stays fp64 (storm_hip.h, "fp32-weight companion records").
 class ChebyshevPreconditioner final : public Preconditioner<DeviceVector> {
 public:
   int degree = 4;
   real_t lambda_min = 0.0, lambda_max = 0.0;
   bool jacobi = false;
+  bool reduced_records = false;
 
   ChebyshevPreconditioner() = default;
   explicit ChebyshevPreconditioner(int degree_, real_t lambda_min_ = 0.0, real_t lambda_max_ = 0.0, bool jacobi_ = false)
@@ -909,8 +915,14 @@ public:
       _dinv.assign(x_vec, false);
       detail::check(storm_hip_op_get_diagonal(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), 1, _dinv.handle()));
     }
-    detail::check(storm_hip_cheb_create(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(),
-                                        jacobi ? _dinv.handle() : nullptr, degree, lambda_min, lambda_max, &_h));
+    if (reduced_records) {
+      hip_op->build_reduced();
+      detail::check(storm_hip_cheb_create_reduced(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(),
+                                                  jacobi ? _dinv.handle() : nullptr, degree, lambda_min, lambda_max, &_h));
+    } else {
+      detail::check(storm_hip_cheb_create(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(),
+                                          jacobi ? _dinv.handle() : nullptr, degree, lambda_min, lambda_max, &_h));
+    }
   }
   void mul(DeviceVector& y_vec, const DeviceVector& x_vec) const override {
     detail::check(storm_hip_cheb_apply(_h, x_vec.handle(), y_vec.handle()));
@@ -918,7 +930,7 @@ public:
   void conj_mul(DeviceVector& x_vec, const DeviceVector& y_vec) const override {
     detail::check(storm_hip_cheb_apply(_h, y_vec.handle(), x_vec.handle()));
   }
-  /// "lambda_min" / "lambda_max" (the bounds in use) or "degree".
+  /// "lambda_min" / "lambda_max" (the bounds in use), "degree" or "reduced".
   real_t get(const char* key) const {
     double v = 0.0;
     detail::check(storm_hip_cheb_get(_h, key, &v));

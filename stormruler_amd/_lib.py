@@ -185,6 +185,12 @@ SIGNATURES = {
     "storm_hip_cheb_coefficients": (C.c_int, [C.c_double, C.c_double, C.c_int, f64p, f64p, f64p]),
     "storm_hip_op_gershgorin": (C.c_int, [vp, C.c_double, C.c_double, vp, f64p]),
     "storm_hip_cheb_create": (C.c_int, [vp, C.c_double, C.c_double, vp, C.c_int, C.c_double, C.c_double, C.POINTER(vp)]),
+    "storm_hip_cheb_create_reduced": (C.c_int, [vp, C.c_double, C.c_double, vp, C.c_int, C.c_double, C.c_double, C.POINTER(vp)]),
+    "storm_hip_op_build_reduced": (C.c_int, [vp]),
+    "storm_hip_op_drop_reduced": (C.c_int, [vp]),
+    "storm_hip_op_reduced_bytes": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+    "storm_hip_op_apply_reduced": (C.c_int, [vp, C.c_double, C.c_double, vp, vp]),
+    "storm_hip_op_gershgorin_reduced": (C.c_int, [vp, C.c_double, C.c_double, vp, f64p]),
     "storm_hip_cheb_apply": (C.c_int, [vp, vp, vp]),
     "storm_hip_cheb_get": (C.c_int, [vp, C.c_char_p, f64p]),
     "storm_hip_cheb_destroy": (C.c_int, [vp]),

@@ -759,6 +759,34 @@ class StencilMatrix:
         check(lib.storm_hip_op_gershgorin(self._h, float(alpha), float(beta), None if scale is None else scale._h, C.byref(v)))
         return v.value
 
+    # -- the fp32-weight companion of fp64 records (``storm_hip_op_*_reduced``, include/storm_hip.h) --
+    def build_reduced(self) -> None:
+        """Give an operator on fp64 records (option ``spmv_dict = 0``) a second copy of its records whose weights are
+        rounded to fp32; idempotent.  A weight outside fp32's normal range: ``STORM_HIP_E_UNSUPPORTED``."""
+        check(lib.storm_hip_op_build_reduced(self._h))
+
+    def drop_reduced(self) -> None:
+        check(lib.storm_hip_op_drop_reduced(self._h))
+
+    @property
+    def reduced_bytes(self) -> int:
+        """Bytes of the companion's records (256 + 512 W per slice of width W); 0 without a companion."""
+        n = C.c_int64()
+        check(lib.storm_hip_op_reduced_bytes(self._h, C.byref(n)))
+        return n.value
+
+    def apply_reduced(self, alpha: float, beta: float, x: DeviceVector, y: DeviceVector) -> None:
+        """``y = beta x + alpha M~ x`` from the companion records: bit for bit :meth:`apply` of an operator built from the
+        weights rounded to fp32.  Needs :meth:`build_reduced`."""
+        check(lib.storm_hip_op_apply_reduced(self._h, float(alpha), float(beta), x._h, y._h))
+
+    def gershgorin_reduced(self, alpha: float, beta: float, scale: Optional[DeviceVector] = None) -> float:
+        """:meth:`gershgorin` of the companion records.  One host wait."""
+        v = C.c_double()
+        check(lib.storm_hip_op_gershgorin_reduced(self._h, float(alpha), float(beta), None if scale is None else scale._h,
+                                                  C.byref(v)))
+        return v.value
+
     def close(self):
         if getattr(self, "_h", None):
             if getattr(self.ctx, "_h", None):  # never touch a dead context (see DeviceVector._free)
@@ -907,11 +935,14 @@ class ChebyshevPreconditioner(Preconditioner):
     (``storm_hip_cheb_*``, include/storm_hip.h): ``degree`` operator products per apply, no reduction and no host wait.
     ``lambda_max=None`` takes Gershgorin's bound, ``lambda_min=None`` a thirtieth of ``lambda_max``; ``jacobi`` scales with
     the inverse diagonal.  The solvers bind it natively; :meth:`mul` is ``storm_hip_cheb_apply``, so it is an operator on
-    its own as well.  The operator it was built from must outlive it."""
+    its own as well.  The operator it was built from must outlive it.  ``reduced_records``: the operator products read
+    the matrix's fp32-weight companion records (:meth:`StencilMatrix.build_reduced`, built here if it is missing) -- the
+    polynomial of the operator with weights rounded to fp32, every vector and sum still fp64."""
 
     def __init__(self, degree: int = 4, lambda_min: Optional[float] = None, lambda_max: Optional[float] = None,
-                 jacobi: bool = False):
+                 jacobi: bool = False, reduced_records: bool = False):
         self.degree, self.lambda_min, self.lambda_max, self.jacobi = int(degree), lambda_min, lambda_max, bool(jacobi)
+        self.reduced_records = bool(reduced_records)
         self._h, self._dinv, self._op, self.ctx = None, None, None, None
 
     def build(self, x_vec, b_vec, any_op) -> None:
@@ -926,15 +957,18 @@ class ChebyshevPreconditioner(Preconditioner):
             self._dinv = _like(x_vec)
             any_op.matrix.diagonal(any_op.alpha, any_op.beta, self._dinv, invert=True)
         h = C.c_void_p()
-        check(lib.storm_hip_cheb_create(any_op.matrix._h, any_op.alpha, any_op.beta,
-                                        None if self._dinv is None else self._dinv._h, self.degree,
-                                        0.0 if self.lambda_min is None else float(self.lambda_min),
-                                        0.0 if self.lambda_max is None else float(self.lambda_max), C.byref(h)))
+        create = lib.storm_hip_cheb_create
+        if self.reduced_records:
+            any_op.matrix.build_reduced()
+            create = lib.storm_hip_cheb_create_reduced
+        check(create(any_op.matrix._h, any_op.alpha, any_op.beta, None if self._dinv is None else self._dinv._h, self.degree,
+                     0.0 if self.lambda_min is None else float(self.lambda_min),
+                     0.0 if self.lambda_max is None else float(self.lambda_max), C.byref(h)))
         self._h = h
         self.ctx._children.add(self)
 
     def get(self, key: str) -> float:
-        """``lambda_min`` / ``lambda_max`` (the bounds in use) or ``degree``."""
+        """``lambda_min`` / ``lambda_max`` (the bounds in use), ``degree`` or ``reduced`` (1 for a reduced object)."""
         v = C.c_double()
         check(lib.storm_hip_cheb_get(self._h, key.encode(), C.byref(v)))
         return v.value

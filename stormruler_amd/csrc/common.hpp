@@ -265,6 +265,8 @@ struct storm_hip_ctx {
   int64_t n_op_face_updates = 0;  // storm_hip_op_set_face_weights (op_update.hip)
   int64_t opt_cheb_fused = 1;  // storm_hip_cheb_apply: the fused step kernel where it applies (fp64 records, no CSR tail); 0: library statements everywhere
   int64_t n_cheb_fused_applies = 0, n_cheb_statement_applies = 0;  // precond_cheb.hip: which path an apply took
+  int64_t n_op_reduced_builds = 0, n_op_reduced_refreshes = 0;  // op_reduced.hip: companions built; converted again behind a refresh
+  int64_t n_cheb_reduced_applies = 0;  // precond_cheb.hip: applies of a reduced object (counted beside the two above)
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_cg_pz_consumer_folds = 0;  // ... of those, the solves whose plane march folded <p,z> itself (option cg_pz_fold)
@@ -344,6 +346,12 @@ struct storm_hip_op {
   int64_t n_faces = 0;
   int *d_src = nullptr, *d_tail_src = nullptr;        // OpImage::src, tail_src
   int *d_face_inner = nullptr, *d_face_outer = nullptr;  // [n_faces]
+  // the fp32-weight companion of fp64 records (op_reduced.hip; all null / 0 without one): records of the same widths
+  // [ext 64 f32][pairs {col0, col1, w0, w1}][odd last slot {col, w}], their offsets (null with a uniform width), the tail's values
+  char *d_pack32 = nullptr;
+  int64_t *d_slice_off32 = nullptr;
+  float *d_tail_val32 = nullptr;
+  int64_t pack32_bytes = 0;
 };
 
 // The Chebyshev polynomial preconditioner (precond_cheb.hip): z = p_m(diag(s) A) diag(s) r for A = beta I + alpha M.
@@ -357,6 +365,7 @@ struct storm_hip_cheb {
   double lmin = 0.0, lmax = 0.0, theta = 0.0, inv_theta = 0.0;
   double c1[kChebMaxDegree] = {}, c2[kChebMaxDegree] = {};  // (rho_{k+1} rho_k, 2 rho_{k+1} / delta)
   storm_hip_vec *d[2] = {nullptr, nullptr}, *res = nullptr;  // the two direction buffers and the residual
+  int reduced = 0;  // 1: the operator products read the operator's fp32-weight companion (storm_hip_cheb_create_reduced)
 };
 
 namespace storm {
@@ -553,6 +562,14 @@ int op_pack_from_mesh(const PackOptions &o, int64_t n_owned, int64_t n_halo, int
                       const double *b_area, const double *b_center, const double *volume, OpImage *img);
 int op_pack_csr(const PackOptions &o, int64_t n_rows, int64_t n_halo, const int64_t *row_ptr, const int64_t *col,
                 const double *val, OpImage *img);
+
+// spmv.hip: Gershgorin's bound from the fp64 records, or (reduced) from the fp32-weight companion; checks are the caller's
+int gershgorin_run(const storm_hip_op *op, bool reduced, double alpha, double beta, const storm_hip_vec *scale, double *lambda_max);
+// op_reduced.hip
+int op_reduced_check(const storm_hip_op *op, const char *who);     // fp64 records, single rank: else STORM_HIP_E_UNSUPPORTED
+int op_reduced_require(const storm_hip_op *op, const char *who);   // ... and a companion: nothing is built behind the caller's back
+int op_reduced_convert(storm_hip_op *op, int *d_flag);             // enqueue the conversion kernels (d_flag: the range flag, or null)
+int op_reduced_apply(const storm_hip_op *op, double alpha, double beta, const double *x, double *y, const int *done);
 
 // latency.hip
 bool cg_latency_eligible(const storm_hip_op *op);

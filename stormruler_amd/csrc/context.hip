@@ -253,6 +253,9 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "host_reductions")) *value = c->n_host_reductions;
   else if (!strcmp(key, "cheb_fused_applies")) *value = c->n_cheb_fused_applies;
   else if (!strcmp(key, "cheb_statement_applies")) *value = c->n_cheb_statement_applies;
+  else if (!strcmp(key, "cheb_reduced_applies")) *value = c->n_cheb_reduced_applies;
+  else if (!strcmp(key, "op_reduced_builds")) *value = c->n_op_reduced_builds;
+  else if (!strcmp(key, "op_reduced_refreshes")) *value = c->n_op_reduced_refreshes;
   else if (!strcmp(key, "jfnk_inner_solves")) *value = c->n_jfnk_inner_solves;
   else if (!strcmp(key, "fd_fused_dots")) *value = c->n_fd_fused_dots;
   else if (!strcmp(key, "cg_fused_steps")) *value = c->n_cg_fused_steps;

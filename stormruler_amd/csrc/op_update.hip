@@ -142,6 +142,10 @@ int storm_hip_op_set_face_weights(storm_hip_op *op, const storm_hip_vec *w_inner
     hipLaunchKernelGGL(op_refresh_tail_kernel, dim3((int)((op->tail_nnz + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
                        op->tail_nnz, op->d_tail_src, w_inner->d, w_outer->d, op->d_tail_val);
   HIP_TRY(hipGetLastError());
+  if (op->d_pack32 != nullptr) {  // the fp32-weight companion (op_reduced.hip) stays the rounding of the records: no wait, no range check
+    STORM_TRY(op_reduced_convert(op, nullptr));
+    c->n_op_reduced_refreshes++;
+  }
   c->n_op_face_updates++;
   return STORM_HIP_OK;
 }

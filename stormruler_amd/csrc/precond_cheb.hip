@@ -11,6 +11,9 @@
 //               for axpbz(1, res, -1, t) and axpbz(1, d, 1, z).  The new direction goes to the OTHER buffer: neighbours still
 //               gather the old one.  Per row and step: records + 8 (res in) + 8 (res out) + 8 (direction out) + 8 + 8 (z) bytes,
 //               + 8 with the scale; FIRST reads the caller's r for res and does not read z, LAST stores z only.
+// A REDUCED object (storm_hip_cheb_create_reduced) takes its operator products from the operator's fp32-weight companion
+// records (op_reduced.hip): the fused step is the same kernel with the record policy Rec32 (sell_device.hpp), the statement
+// path calls storm_hip_op_apply_reduced in place of storm_hip_op_apply.
 #include <cmath>
 #include <cstring>
 #include <utility>
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(kBlock) void cheb_d0_kernel(int64_t n, double inv_t
 
 // One Chebyshev step on a slice per wavefront:
 //   t = A d;  res' = res - t;  d' = c1 d + c2 (s .* res');  z' = z + d'   (FIRST: z' = d + d').
-template <bool NT, bool XCD, bool JACOBI, bool FIRST, bool LAST>
+template <bool NT, bool XCD, bool JACOBI, bool FIRST, bool LAST, class R>
 __global__ __launch_bounds__(kBlock) void cheb_step_kernel(SellArgs A, double alpha, double beta, ChebStepArgs C,
                                                            int64_t n_slices, const int *done) {
   // (as in spmv_sell_kernel: the predicate is loaded first and tested before the first store)
@@ -99,16 +102,16 @@ __global__ __launch_bounds__(kBlock) void cheb_step_kernel(SellArgs A, double al
   int width;
   if (A.uniform_width > 0) {
     width = A.uniform_width;
-    base = slice * (int64_t)(kExtBytes + kSlotBytes * width);
+    base = slice * (int64_t)(R::kExt + R::kSlot * width);
   } else {
     base = A.slice_off[slice];
-    width = (int)((A.slice_off[slice + 1] - base - kExtBytes) / kSlotBytes);
+    width = (int)((A.slice_off[slice + 1] - base - R::kExt) / R::kSlot);
   }
   const char *rec = A.pack + base;
-  const double ext = ld_d<NT>(reinterpret_cast<const double *>(rec) + lane);
+  const double ext = R::template ext<NT>(rec, lane);
   const double xi1[1] = {xi};
   double acc1[1];
-  row_sum_any<NT, 1>(rec, width, lane, dv, xi1, acc1);
+  row_sum_any<NT, 1, R>(rec, width, lane, dv, xi1, acc1);
   const double t = sell_row_result(false, 0.0, beta, xi, alpha, acc1[0], ext);
   const double rn = ri - t;
   double w = rn;
@@ -137,7 +140,12 @@ static void launch_step(const storm_hip_cheb *h, const SellArgs &A, const ChebSt
   const dim3 grid(blocks_for(op, op->n_slices)), block(kBlock);
   hipStream_t st = h->ctx->stream;
 #define CHEB_GO(F_, L_) \
-  hipLaunchKernelGGL((cheb_step_kernel<NT, XCD, JACOBI, F_, L_>), grid, block, 0, st, A, h->alpha, h->beta, C, op->n_slices, done)
+  do {                                                                                                                             \
+    if (h->reduced)                                                                                                                \
+      hipLaunchKernelGGL((cheb_step_kernel<NT, XCD, JACOBI, F_, L_, Rec32>), grid, block, 0, st, A, h->alpha, h->beta, C, op->n_slices, done); \
+    else                                                                                                                           \
+      hipLaunchKernelGGL((cheb_step_kernel<NT, XCD, JACOBI, F_, L_, Rec64>), grid, block, 0, st, A, h->alpha, h->beta, C, op->n_slices, done); \
+  } while (0)
   if (first && last) CHEB_GO(true, true);
   else if (first) CHEB_GO(true, false);
   else if (last) CHEB_GO(false, true);
@@ -157,8 +165,9 @@ static int cheb_apply_fused(const storm_hip_cheb *h, const storm_hip_vec *r, sto
   else
     hipLaunchKernelGGL(cheb_d0_kernel<false>, dim3(stream_blocks(n)), dim3(kBlock), 0, c->stream, n, h->inv_theta, r->d,
                        (const double *)nullptr, h->d[0]->d, done, stream_nt(c, n));
-  const SellArgs A{op->d_pack, op->d_slice_off, op->n_rows, op->uniform_width, op->xcd_group_sell, op->d_dict, op->dict_size,
-                   op->d_offs, op->offs_size, 0};
+  SellArgs A{op->d_pack, op->d_slice_off, op->n_rows, op->uniform_width, op->xcd_group_sell, op->d_dict, op->dict_size,
+             op->d_offs, op->offs_size, 0};
+  if (h->reduced) A.pack = op->d_pack32, A.slice_off = op->d_slice_off32;
   const bool nt = c->opt_nt != 0, xcd = op->xcd_group_sell != 0;
   for (int k = 0; k < h->degree; ++k) {
     const bool first = k == 0, last = k == h->degree - 1;
@@ -196,7 +205,8 @@ static int cheb_apply_statements(const storm_hip_cheb *h, const storm_hip_vec *r
     STORM_TRY(storm_hip_axpbz(d, h->inv_theta, r, 0.0, r));
   }
   for (int k = 0; k < h->degree; ++k) {
-    STORM_TRY(storm_hip_op_apply(h->op, h->alpha, h->beta, d, e));
+    if (h->reduced) STORM_TRY(storm_hip_op_apply_reduced(h->op, h->alpha, h->beta, d, e));
+    else STORM_TRY(storm_hip_op_apply(h->op, h->alpha, h->beta, d, e));
     STORM_TRY(storm_hip_axpbz(res, 1.0, k == 0 ? r : res, -1.0, e));
     if (s != nullptr) {
       STORM_TRY(storm_hip_vmul(e, s, res));
@@ -215,6 +225,39 @@ static int cheb_single_rank(const storm_hip_op *op, const char *what) {
   if (op->halo.n_nbrs > 0 || op->n_halo > 0 || op->ctx->comm != nullptr)
     STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "%s: the Chebyshev preconditioner is single-rank (the operator has a halo plan or halo "
                                         "columns, or the context a communicator)", what);
+  return STORM_HIP_OK;
+}
+
+static int cheb_create(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *dinv, int degree, double lmin,
+                       double lmax, bool reduced, storm_hip_cheb **out) {
+  const char *who = reduced ? "cheb_create_reduced" : "cheb_create";
+  STORM_REQUIRE(op && out, "%s: null argument", who);
+  *out = nullptr;
+  STORM_REQUIRE(degree >= 1 && degree <= kChebMaxDegree, "%s: degree %d (1 .. %d)", who, degree, kChebMaxDegree);
+  STORM_REQUIRE(dinv == nullptr || dinv->ctx == op->ctx, "%s: the scale belongs to another context", who);
+  STORM_REQUIRE(dinv == nullptr || dinv->n_owned == op->n_rows, "%s: operator has %lld rows, the scale %lld", who,
+                (long long)op->n_rows, (long long)(dinv ? dinv->n_owned : 0));
+  STORM_REQUIRE(std::isfinite(lmin) && std::isfinite(lmax), "%s: the bounds must be finite", who);
+  STORM_TRY(cheb_single_rank(op, who));
+  if (reduced) STORM_TRY(op_reduced_require(op, who));
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  if (lmax <= 0.0) {
+    if (reduced) STORM_TRY(storm_hip_op_gershgorin_reduced(op, alpha, beta, dinv, &lmax));
+    else STORM_TRY(storm_hip_op_gershgorin(op, alpha, beta, dinv, &lmax));
+  }
+  if (lmin <= 0.0) lmin = lmax / 30.0;
+  storm_hip_cheb *h = new storm_hip_cheb();
+  h->ctx = op->ctx, h->op = op, h->alpha = alpha, h->beta = beta, h->dinv = dinv, h->degree = degree;
+  h->lmin = lmin, h->lmax = lmax, h->reduced = reduced ? 1 : 0;
+  int st = storm_hip_cheb_coefficients(lmin, lmax, degree, &h->theta, h->c1, h->c2);
+  h->inv_theta = 1.0 / h->theta;
+  storm_hip_vec **vs[3] = {&h->d[0], &h->d[1], &h->res};
+  for (int i = 0; i < 3 && st == STORM_HIP_OK; ++i) st = storm_hip_vec_create(op->ctx, op->n_rows, 0, vs[i]);
+  if (st != STORM_HIP_OK) {
+    (void)storm_hip_cheb_destroy(h);
+    return st;
+  }
+  *out = h;
   return STORM_HIP_OK;
 }
 
@@ -242,30 +285,12 @@ int storm_hip_cheb_coefficients(double lmin, double lmax, int degree, double *th
 
 int storm_hip_cheb_create(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *dinv, int degree, double lmin,
                           double lmax, storm_hip_cheb **out) {
-  STORM_REQUIRE(op && out, "cheb_create: null argument");
-  *out = nullptr;
-  STORM_REQUIRE(degree >= 1 && degree <= kChebMaxDegree, "cheb_create: degree %d (1 .. %d)", degree, kChebMaxDegree);
-  STORM_REQUIRE(dinv == nullptr || dinv->ctx == op->ctx, "cheb_create: the scale belongs to another context");
-  STORM_REQUIRE(dinv == nullptr || dinv->n_owned == op->n_rows, "cheb_create: operator has %lld rows, the scale %lld",
-                (long long)op->n_rows, (long long)(dinv ? dinv->n_owned : 0));
-  STORM_REQUIRE(std::isfinite(lmin) && std::isfinite(lmax), "cheb_create: the bounds must be finite");
-  STORM_TRY(cheb_single_rank(op, "cheb_create"));
-  HIP_TRY(hipSetDevice(op->ctx->device));
-  if (lmax <= 0.0) STORM_TRY(storm_hip_op_gershgorin(op, alpha, beta, dinv, &lmax));
-  if (lmin <= 0.0) lmin = lmax / 30.0;
-  storm_hip_cheb *h = new storm_hip_cheb();
-  h->ctx = op->ctx, h->op = op, h->alpha = alpha, h->beta = beta, h->dinv = dinv, h->degree = degree;
-  h->lmin = lmin, h->lmax = lmax;
-  int st = storm_hip_cheb_coefficients(lmin, lmax, degree, &h->theta, h->c1, h->c2);
-  h->inv_theta = 1.0 / h->theta;
-  storm_hip_vec **vs[3] = {&h->d[0], &h->d[1], &h->res};
-  for (int i = 0; i < 3 && st == STORM_HIP_OK; ++i) st = storm_hip_vec_create(op->ctx, op->n_rows, 0, vs[i]);
-  if (st != STORM_HIP_OK) {
-    (void)storm_hip_cheb_destroy(h);
-    return st;
-  }
-  *out = h;
-  return STORM_HIP_OK;
+  return cheb_create(op, alpha, beta, dinv, degree, lmin, lmax, false, out);
+}
+
+int storm_hip_cheb_create_reduced(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *dinv, int degree,
+                                  double lmin, double lmax, storm_hip_cheb **out) {
+  return cheb_create(op, alpha, beta, dinv, degree, lmin, lmax, true, out);
 }
 
 int storm_hip_cheb_destroy(storm_hip_cheb *h) {
@@ -282,6 +307,7 @@ int storm_hip_cheb_get(const storm_hip_cheb *h, const char *key, double *value) 
   if (!strcmp(key, "lambda_min")) *value = h->lmin;
   else if (!strcmp(key, "lambda_max")) *value = h->lmax;
   else if (!strcmp(key, "degree")) *value = (double)h->degree;
+  else if (!strcmp(key, "reduced")) *value = (double)h->reduced;
   else STORM_FAIL(STORM_HIP_E_INVALID, "cheb_get: unknown key '%s'", key);
   return STORM_HIP_OK;
 }
@@ -296,6 +322,10 @@ int storm_hip_cheb_apply(const storm_hip_cheb *h, const storm_hip_vec *r, storm_
   HIP_TRY(hipSetDevice(c->device));
   STORM_TRY(lazy_sync(c));
   if (h->op->n_rows == 0) return STORM_HIP_OK;
+  if (h->reduced) {  // (the companion may have been dropped since the object was created)
+    STORM_TRY(op_reduced_require(h->op, "cheb_apply"));
+    ++c->n_cheb_reduced_applies;
+  }
   if (cheb_fused_applies(h)) {
     ++c->n_cheb_fused_applies;
     return cheb_apply_fused(h, r, z);

@@ -1,5 +1,6 @@
-// The row arithmetic of the fp64 sliced-ELL records, shared by spmv_sell.hip (one column) and spmv_block.hip (a block of
-// K interleaved columns, element (i, j) at x[i K + j]): ONE definition of every statement that rounds, so that the two
+// The row arithmetic of the sliced-ELL records, shared by spmv_sell.hip (one column), spmv_block.hip (a block of
+// K interleaved columns, element (i, j) at x[i K + j]), precond_cheb.hip and op_reduced.hip (the fp32-weight companion
+// records, through the record policy below): ONE definition of every statement that rounds, so that the two
 // kernels contract the same products into the same additions and a block apply gives, column by column, the bits of
 // the single apply (tests/test_gpu_block.py).  Record layout: the header of spmv.hip.
 #pragma once
@@ -26,41 +27,91 @@ __device__ __forceinline__ void ld_cols(const double *__restrict__ x, int col, d
   }
 }
 
+// How the (col, w) of a row's slots are loaded -- the record policy of row_sum_block and everything above it.  The
+// accumulation below the loads is the same statement for every policy.
+//   Rec64  the fp64 records (header of spmv.hip): pairs read as int2 / double2, an odd last slot unpaired.
+//   Rec32  the fp32-weight companion (op_reduced.hip): [ext 64 x f32][pairs (W/2) x 64 x {int col0, col1, float w0, w1}]
+//          [odd last slot 64 x {int col, float w}] -- one 16-byte load per lane and slot pair; a weight is widened to double
+//          (exactly) where it is loaded.
+struct Rec64 {
+  static constexpr int kExt = kExtBytes, kSlot = kSlotBytes;
+  template <bool NT>
+  static __device__ __forceinline__ double ext(const char *rec, int lane) {
+    return ld_d<NT>(reinterpret_cast<const double *>(rec) + lane);
+  }
+  template <bool NT, int W>
+  static __device__ __forceinline__ void load(const char *rec, int width, int lane, int s0, int (&col)[W > 0 ? W : 1],
+                                              double (&w)[W > 0 ? W : 1]) {
+    constexpr int NP = W / 2;
+    const int npair_total = width >> 1;
+    const int2v *cp2 = reinterpret_cast<const int2v *>(rec + kExtBytes) + lane + (s0 >> 1) * kWave;
+    const char *vbase = rec + kExtBytes + (int64_t)width * (kWave * 4);
+    const double2v *vp2 = reinterpret_cast<const double2v *>(vbase) + lane + (s0 >> 1) * kWave;
+    int2v c[NP > 0 ? NP : 1];
+    double2v v[NP > 0 ? NP : 1];
+    int ct = 0;
+    double vt = 0.0;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+      c[q] = NT ? __builtin_nontemporal_load(cp2 + q * kWave) : cp2[q * kWave];
+      v[q] = NT ? __builtin_nontemporal_load(vp2 + q * kWave) : vp2[q * kWave];
+    }
+    if (W & 1) {  // the slice's unpaired last slot
+      ct = ld_i<NT>(reinterpret_cast<const int *>(rec + kExtBytes + (int64_t)npair_total * (kWave * 8)) + lane);
+      vt = ld_d<NT>(reinterpret_cast<const double *>(vbase + (int64_t)npair_total * (kWave * 16)) + lane);
+    }
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+      col[2 * q] = c[q].x, col[2 * q + 1] = c[q].y;
+      w[2 * q] = v[q].x, w[2 * q + 1] = v[q].y;
+    }
+    if (W & 1) col[W - 1] = ct, w[W - 1] = vt;
+  }
+};
+
+typedef int int4v __attribute__((ext_vector_type(4)));
+struct Rec32 {
+  static constexpr int kExt = kExt32Bytes, kSlot = kSlot32Bytes;
+  template <bool NT>
+  static __device__ __forceinline__ double ext(const char *rec, int lane) {
+    const float *p = reinterpret_cast<const float *>(rec) + lane;
+    return (double)(NT ? __builtin_nontemporal_load(p) : *p);
+  }
+  template <bool NT, int W>
+  static __device__ __forceinline__ void load(const char *rec, int width, int lane, int s0, int (&col)[W > 0 ? W : 1],
+                                              double (&w)[W > 0 ? W : 1]) {
+    constexpr int NP = W / 2;
+    const int npair_total = width >> 1;
+    const int4v *pp = reinterpret_cast<const int4v *>(rec + kExt32Bytes) + lane + (s0 >> 1) * kWave;
+    int4v c[NP > 0 ? NP : 1];
+    int2v ct = {0, 0};
+#pragma unroll
+    for (int q = 0; q < NP; ++q) c[q] = NT ? __builtin_nontemporal_load(pp + q * kWave) : pp[q * kWave];
+    if (W & 1) {  // the slice's unpaired last slot
+      const int2v *tp = reinterpret_cast<const int2v *>(rec + kExt32Bytes + (int64_t)npair_total * (kWave * 16)) + lane;
+      ct = NT ? __builtin_nontemporal_load(tp) : *tp;
+    }
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+      col[2 * q] = c[q].x, col[2 * q + 1] = c[q].y;
+      w[2 * q] = (double)__int_as_float(c[q].z), w[2 * q + 1] = (double)__int_as_float(c[q].w);
+    }
+    if (W & 1) col[W - 1] = ct.x, w[W - 1] = (double)__int_as_float(ct.y);
+  }
+};
+
 // acc[j] = sum_k w_k (x_j[col_k] - xi[j]) over slots [S0, S0 + W) of a record whose slice has `width` slots
-// (W compile-time, S0 even).  Pairs are read as int2 / double2, an odd last slot unpaired.  The (col, val) record is
-// loaded once for all columns; the neighbours' values are gathered kGather slots at a time (every slot at once up to
+// (W compile-time, S0 even).  The (col, val) record is loaded once for all columns (by the record policy R); the
+// neighbours' values are gathered kGather slots at a time (every slot at once up to
 // K = 4: at most 32 doubles in flight per lane), the sums run over the slots in order whatever the chunking.
-template <bool NT, int W, int K>
+template <bool NT, int W, int K, class R = Rec64>
 __device__ __forceinline__ void row_sum_block(const char *rec, int width, int lane, const double *__restrict__ x,
                                               const double (&xi)[K], double (&acc)[K], int s0 = 0) {
-  constexpr int NP = W / 2;
   constexpr int W1 = W > 0 ? W : 1;
   constexpr int kGather = K <= 4 ? W1 : 4;
-  const int npair_total = width >> 1;
-  const int2v *cp2 = reinterpret_cast<const int2v *>(rec + kExtBytes) + lane + (s0 >> 1) * kWave;
-  const char *vbase = rec + kExtBytes + (int64_t)width * (kWave * 4);
-  const double2v *vp2 = reinterpret_cast<const double2v *>(vbase) + lane + (s0 >> 1) * kWave;
-  int2v c[NP > 0 ? NP : 1];
-  double2v v[NP > 0 ? NP : 1];
-  int ct = 0;
-  double vt = 0.0;
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    c[q] = NT ? __builtin_nontemporal_load(cp2 + q * kWave) : cp2[q * kWave];
-    v[q] = NT ? __builtin_nontemporal_load(vp2 + q * kWave) : vp2[q * kWave];
-  }
-  if (W & 1) {  // the slice's unpaired last slot
-    ct = ld_i<NT>(reinterpret_cast<const int *>(rec + kExtBytes + (int64_t)npair_total * (kWave * 8)) + lane);
-    vt = ld_d<NT>(reinterpret_cast<const double *>(vbase + (int64_t)npair_total * (kWave * 16)) + lane);
-  }
   int col[W1];
   double w[W1];
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    col[2 * q] = c[q].x, col[2 * q + 1] = c[q].y;
-    w[2 * q] = v[q].x, w[2 * q + 1] = v[q].y;
-  }
-  if (W & 1) col[W - 1] = ct, w[W - 1] = vt;
+  R::template load<NT, W>(rec, width, lane, s0, col, w);
 #pragma unroll
   for (int j = 0; j < K; ++j) acc[j] = 0.0;
 #pragma unroll
@@ -80,7 +131,7 @@ __device__ __forceinline__ void row_sum_block(const char *rec, int width, int la
 }
 
 // Rows wider than 8 slots: chunk sums of 8, then the remainder.
-template <bool NT, int K>
+template <bool NT, int K, class R = Rec64>
 __device__ __forceinline__ void row_sum_wide_block(const char *rec, int width, int lane, const double *__restrict__ x,
                                                    const double (&xi)[K], double (&acc)[K]) {
   double part[K];
@@ -88,18 +139,18 @@ __device__ __forceinline__ void row_sum_wide_block(const char *rec, int width, i
   for (int j = 0; j < K; ++j) acc[j] = 0.0, part[j] = 0.0;
   int s0 = 0;
   for (; s0 + 8 <= width; s0 += 8) {
-    row_sum_block<NT, 8, K>(rec, width, lane, x, xi, part, s0);
+    row_sum_block<NT, 8, K, R>(rec, width, lane, x, xi, part, s0);
 #pragma unroll
     for (int j = 0; j < K; ++j) acc[j] += part[j];
   }
   switch (width - s0) {
-    case 1: row_sum_block<NT, 1, K>(rec, width, lane, x, xi, part, s0); break;
-    case 2: row_sum_block<NT, 2, K>(rec, width, lane, x, xi, part, s0); break;
-    case 3: row_sum_block<NT, 3, K>(rec, width, lane, x, xi, part, s0); break;
-    case 4: row_sum_block<NT, 4, K>(rec, width, lane, x, xi, part, s0); break;
-    case 5: row_sum_block<NT, 5, K>(rec, width, lane, x, xi, part, s0); break;
-    case 6: row_sum_block<NT, 6, K>(rec, width, lane, x, xi, part, s0); break;
-    case 7: row_sum_block<NT, 7, K>(rec, width, lane, x, xi, part, s0); break;
+    case 1: row_sum_block<NT, 1, K, R>(rec, width, lane, x, xi, part, s0); break;
+    case 2: row_sum_block<NT, 2, K, R>(rec, width, lane, x, xi, part, s0); break;
+    case 3: row_sum_block<NT, 3, K, R>(rec, width, lane, x, xi, part, s0); break;
+    case 4: row_sum_block<NT, 4, K, R>(rec, width, lane, x, xi, part, s0); break;
+    case 5: row_sum_block<NT, 5, K, R>(rec, width, lane, x, xi, part, s0); break;
+    case 6: row_sum_block<NT, 6, K, R>(rec, width, lane, x, xi, part, s0); break;
+    case 7: row_sum_block<NT, 7, K, R>(rec, width, lane, x, xi, part, s0); break;
     default: return;
   }
 #pragma unroll
@@ -109,7 +160,7 @@ __device__ __forceinline__ void row_sum_wide_block(const char *rec, int width, i
 // The row's sum for a slice of `width` slots.  The width is wave-uniform: dispatch to a body with the width as a
 // compile-time constant, so all (col, val) loads of the row are issued back to back, then the gathers, then the FMAs --
 // no branch (and no s_waitcnt) between the gathers of one row.
-template <bool NT, int K>
+template <bool NT, int K, class R = Rec64>
 __device__ __forceinline__ void row_sum_any(const char *rec, int width, int lane, const double *__restrict__ x,
                                             const double (&xi)[K], double (&acc)[K]) {
   switch (width) {
@@ -117,15 +168,15 @@ __device__ __forceinline__ void row_sum_any(const char *rec, int width, int lane
 #pragma unroll
       for (int j = 0; j < K; ++j) acc[j] = 0.0;
       break;
-    case 1: row_sum_block<NT, 1, K>(rec, 1, lane, x, xi, acc); break;
-    case 2: row_sum_block<NT, 2, K>(rec, 2, lane, x, xi, acc); break;
-    case 3: row_sum_block<NT, 3, K>(rec, 3, lane, x, xi, acc); break;
-    case 4: row_sum_block<NT, 4, K>(rec, 4, lane, x, xi, acc); break;
-    case 5: row_sum_block<NT, 5, K>(rec, 5, lane, x, xi, acc); break;
-    case 6: row_sum_block<NT, 6, K>(rec, 6, lane, x, xi, acc); break;
-    case 7: row_sum_block<NT, 7, K>(rec, 7, lane, x, xi, acc); break;
-    case 8: row_sum_block<NT, 8, K>(rec, 8, lane, x, xi, acc); break;
-    default: row_sum_wide_block<NT, K>(rec, width, lane, x, xi, acc); break;
+    case 1: row_sum_block<NT, 1, K, R>(rec, 1, lane, x, xi, acc); break;
+    case 2: row_sum_block<NT, 2, K, R>(rec, 2, lane, x, xi, acc); break;
+    case 3: row_sum_block<NT, 3, K, R>(rec, 3, lane, x, xi, acc); break;
+    case 4: row_sum_block<NT, 4, K, R>(rec, 4, lane, x, xi, acc); break;
+    case 5: row_sum_block<NT, 5, K, R>(rec, 5, lane, x, xi, acc); break;
+    case 6: row_sum_block<NT, 6, K, R>(rec, 6, lane, x, xi, acc); break;
+    case 7: row_sum_block<NT, 7, K, R>(rec, 7, lane, x, xi, acc); break;
+    case 8: row_sum_block<NT, 8, K, R>(rec, 8, lane, x, xi, acc); break;
+    default: row_sum_wide_block<NT, K, R>(rec, width, lane, x, xi, acc); break;
   }
 }
 
@@ -138,14 +189,15 @@ __device__ __forceinline__ double sell_row_result(bool accumulate, double y_old,
 
 // CSR tail, one wavefront per overflowing row t (row r): the lanes' partial products are folded with the __shfl_down
 // tree and lane 0 adds the row's remainder to y.  `stride`, j: column j of a block of `stride` columns (1, 0: a vector).
+template <class V>  // the tail's value type: double, or float of the fp32-weight companion (widened exactly)
 __device__ __forceinline__ void tail_row_add(int64_t t, int r, int lane, const int64_t *__restrict__ tail_ptr,
-                                             const int *__restrict__ tail_col, const double *__restrict__ tail_val,
+                                             const int *__restrict__ tail_col, const V *__restrict__ tail_val,
                                              double alpha, const double *__restrict__ x, double *__restrict__ y,
                                              int64_t stride, int j) {
   const double xi = x[r * stride + j];
   double acc = 0.0;
   for (int64_t k = tail_ptr[t] + lane; k < tail_ptr[t + 1]; k += kWave)
-    acc += tail_val[k] * (x[tail_col[k] * stride + j] - xi);
+    acc += (double)tail_val[k] * (x[tail_col[k] * stride + j] - xi);
   acc = wave_sum_down(acc);
   if (lane == 0) y[r * stride + j] += alpha * acc;
 }

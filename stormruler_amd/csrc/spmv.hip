@@ -310,9 +310,12 @@ __global__ void diag_tail_kernel(int64_t n_tail, const int *__restrict__ tail_ro
 // diagonal of M) and ab_i = sum_k |w_ik| from the ELL records; the CSR tail's share added; then
 // max_i |s_i| (|beta + alpha md_i| + |alpha| ab_i), folded by wave and one vector atomic max per wave on the bit pattern
 // (the values are non-negative doubles, whose order is that of their bit patterns as unsigned integers).
+// R32: `pack` / `slice_off` are the fp32-weight companion of fp64 records (op_reduced.hip; uniform32 > 0: every slice has
+// that width and slice_off is not read) -- the same sums over the same slots, each weight widened exactly.
+template <bool R32>
 __global__ __launch_bounds__(kBlock) void rowsum_sell_kernel(const char *__restrict__ pack, const int64_t *__restrict__ slice_off,
                                                              int64_t n_rows, const double *__restrict__ dict, int fmt2,
-                                                             double *__restrict__ md, double *__restrict__ ab) {
+                                                             double *__restrict__ md, double *__restrict__ ab, int uniform32) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t s = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
   const int64_t r = s * kWave + lane;
@@ -325,6 +328,17 @@ __global__ __launch_bounds__(kBlock) void rowsum_sell_kernel(const char *__restr
       sum += w, asum += fabs(w);
     }
     ext = dict[((unsigned)iw & 0xffu) >> 3];
+  } else if (R32) {
+    const int w = uniform32 > 0 ? uniform32 : (int)((slice_off[s + 1] - slice_off[s] - kExt32Bytes) / kSlot32Bytes);
+    const char *rec = pack + (uniform32 > 0 ? s * (int64_t)(kExt32Bytes + kSlot32Bytes * w) : slice_off[s]);
+    const float *slot = reinterpret_cast<const float *>(rec + kExt32Bytes);  // pairs {col0, col1, w0, w1}, an odd last {col, w}
+    const int np2 = w >> 1;
+    for (int k = 0; k < w; ++k) {
+      const int at = (k < 2 * np2) ? ((k >> 1) * kWave + lane) * 4 + 2 + (k & 1) : np2 * 4 * kWave + lane * 2 + 1;
+      const double v = (double)slot[at];
+      sum += v, asum += fabs(v);
+    }
+    ext = (double)reinterpret_cast<const float *>(rec)[lane];
   } else if (dict) {
     const char *rec = pack + slice_off[s];
     const int w = fmt2 ? 7 : (int)((slice_off[s + 1] - slice_off[s] - kExtBytes) / kColSlotBytes);
@@ -348,12 +362,13 @@ __global__ __launch_bounds__(kBlock) void rowsum_sell_kernel(const char *__restr
   md[r] = ext - sum, ab[r] = asum;
 }
 
+template <class V>
 __global__ void rowsum_tail_kernel(int64_t n_tail, const int *__restrict__ tail_row, const int64_t *__restrict__ tail_ptr,
-                                   const double *__restrict__ tail_val, double *__restrict__ md, double *__restrict__ ab) {
+                                   const V *__restrict__ tail_val, double *__restrict__ md, double *__restrict__ ab) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_tail) return;
   double sum = 0.0, asum = 0.0;
-  for (int64_t k = tail_ptr[t]; k < tail_ptr[t + 1]; ++k) sum += tail_val[k], asum += fabs(tail_val[k]);
+  for (int64_t k = tail_ptr[t]; k < tail_ptr[t + 1]; ++k) sum += (double)tail_val[k], asum += fabs((double)tail_val[k]);
   md[tail_row[t]] -= sum, ab[tail_row[t]] += asum;  // each overflowing row appears once in the tail
 }
 
@@ -448,6 +463,13 @@ int storm_hip_op_gershgorin(const storm_hip_op *op, double alpha, double beta, c
   if (op->halo.n_nbrs > 0 || op->n_halo > 0 || op->ctx->comm != nullptr)
     STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "op_gershgorin: single-rank operators only (the operator has a halo plan or halo "
                                         "columns, or the context a communicator)");
+  return gershgorin_run(op, false, alpha, beta, scale, lambda_max);
+}
+
+}  // extern "C"
+
+int storm::gershgorin_run(const storm_hip_op *op, bool reduced, double alpha, double beta, const storm_hip_vec *scale,
+                          double *lambda_max) {
   *lambda_max = 0.0;
   if (op->n_rows == 0) return STORM_HIP_OK;
   storm_hip_ctx *c = op->ctx;
@@ -461,10 +483,17 @@ int storm_hip_op_gershgorin(const storm_hip_op *op, double alpha, double beta, c
   hipError_t e = hipMemsetAsync(word, 0, sizeof(*word), c->stream);
   const int64_t n64 = (n + kWave - 1) / kWave;
   const int nb = (int)((n64 + (kBlock / kWave) - 1) / (kBlock / kWave));
-  hipLaunchKernelGGL(rowsum_sell_kernel, dim3(nb), dim3(kBlock), 0, c->stream, op->d_pack, op->d_slice_off, n, op->d_dict,
-                     op->pair >= 2 ? op->pair + 2 : op->pair ? 3 : (int)(op->offs_size > 0), md, ab);
-  if (op->tail_rows > 0)
-    hipLaunchKernelGGL(rowsum_tail_kernel, dim3((int)((op->tail_rows + 255) / 256)), dim3(256), 0, c->stream, op->tail_rows,
+  if (reduced)
+    hipLaunchKernelGGL(rowsum_sell_kernel<true>, dim3(nb), dim3(kBlock), 0, c->stream, op->d_pack32, op->d_slice_off32, n,
+                       (const double *)nullptr, 0, md, ab, op->uniform_width);
+  else
+    hipLaunchKernelGGL(rowsum_sell_kernel<false>, dim3(nb), dim3(kBlock), 0, c->stream, op->d_pack, op->d_slice_off, n, op->d_dict,
+                       op->pair >= 2 ? op->pair + 2 : op->pair ? 3 : (int)(op->offs_size > 0), md, ab, 0);
+  if (op->tail_rows > 0 && reduced)
+    hipLaunchKernelGGL(rowsum_tail_kernel<float>, dim3((int)((op->tail_rows + 255) / 256)), dim3(256), 0, c->stream, op->tail_rows,
+                       op->d_tail_row, op->d_tail_ptr, op->d_tail_val32, md, ab);
+  else if (op->tail_rows > 0)
+    hipLaunchKernelGGL(rowsum_tail_kernel<double>, dim3((int)((op->tail_rows + 255) / 256)), dim3(256), 0, c->stream, op->tail_rows,
                        op->d_tail_row, op->d_tail_ptr, op->d_tail_val, md, ab);
   hipLaunchKernelGGL(gershgorin_fold_kernel, dim3((int)std::min<int64_t>((n + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0,
                      c->stream, n, md, ab, scale ? scale->d : nullptr, alpha, beta, word);
@@ -477,6 +506,8 @@ int storm_hip_op_gershgorin(const storm_hip_op *op, double alpha, double beta, c
   memcpy(lambda_max, &bits, sizeof(bits));
   return STORM_HIP_OK;
 }
+
+extern "C" {
 
 int storm_hip_op_get_stats(const storm_hip_op *op, storm_hip_op_stats *s) {
   STORM_REQUIRE(op && s, "op_get_stats: null argument");
@@ -527,6 +558,9 @@ int storm_hip_op_destroy(storm_hip_op *op) {
   (void)hipFree(op->d_tail_src);
   (void)hipFree(op->d_face_inner);
   (void)hipFree(op->d_face_outer);
+  (void)hipFree(op->d_pack32);
+  (void)hipFree(op->d_slice_off32);
+  (void)hipFree(op->d_tail_val32);
   (void)hipFree(op->halo.d_send_idx);
   (void)hipFree(op->halo.d_sendbuf);
   delete op;
