@@ -326,7 +326,8 @@ int storm_hip_op_create_from_face_weights(storm_hip_ctx *ctx, int64_t n_owned, i
  *   the operator; NULL: zeros).  Enqueued on the context's stream; never waits for the device.  Contract: afterwards the
  *   operator is in every respect -- apply, block apply, diagonal, Gershgorin bound, every solver -- the one a fresh create
  *   with those weights gives, bit for bit.  Objects that cached something derived from the OLD values are the caller's to
- *   rebuild: a storm_hip_cheb (its eigenvalue bounds) and a diagonal obtained earlier.  An update between
+ *   rebuild: a storm_hip_cheb (its eigenvalue bounds), a storm_hip_amg (its whole hierarchy: coarse operators, transfers,
+ *   smoothers' scales and bounds are those of the old weights) and a diagonal obtained earlier.  An update between
  *   storm_hip_krylov_init and storm_hip_krylov_finalize of a solve on this operator is the caller's error.
  *   Counted by "op_face_updates" (storm_hip_ctx_get_counter).
  * storm_hip_op_cells_to_faces: at_inner[f] = cell[inner[f]], at_outer[f] = cell[outer[f]] for a cell vector of the
@@ -848,6 +849,110 @@ int storm_hip_op_gershgorin_reduced(const storm_hip_op *op, double alpha, double
  * storm_hip_op_drop_reduced: STORM_HIP_E_UNSUPPORTED. */
 int storm_hip_cheb_create_reduced(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *dinv, int degree,
                                   double lmin, double lmax, storm_hip_cheb **out);
+
+/* ---- Smoothed-aggregation multigrid preconditioner ------------------------------------------------------------------
+ * z = B r: one symmetric V-cycle of smoothed-aggregation multigrid (Vanek, Mandel, Brezina 1996) for A = beta I + alpha M,
+ * the one preconditioner of this library that removes operator products instead of making them cheaper.  Usable as pre_op
+ * of every method and side like storm_hip_cheb: it enqueues and never waits, has no reduction and no host wait inside an
+ * apply.  Single rank.  For symmetric (or diagonally symmetrisable) operators: a strongly non-symmetric operator, upwind
+ * convection-diffusion for instance, is outside what it claims.  Added within ABI 6 (STORM_HIP_HAS_AMG).
+ *
+ * THE RECIPE (normative; tests/amg_ref.py restates it).  A level operator A_l is CSR with sorted columns, duplicates
+ * merged, exact zeros dropped and an explicit diagonal.
+ *   1. Strength.  m_i = max_{j != i} |a_ij|.  The pair (i, j), j != i, is strong if a_ij != 0 and |a_ij| >= theta m_i, or the
+ *      same holds for (j, i): the union of both directions.  Its weight is max(|a_ij|, |a_ji|), a missing entry counting 0.
+ *   2. Aggregation, three sequential passes in row order.  Pass 1: a row that has a strong neighbour and is unaggregated
+ *      together with all of them founds an aggregate with them.  Pass 2: every row still free joins the aggregate -- as it
+ *      stood after pass 1 -- of its strong neighbour of largest weight that pass 1 aggregated; ties go to the lowest
+ *      column.  Pass 3: every row still free founds an aggregate with its still-free strong neighbours.  Aggregates are
+ *      numbered in order of creation.
+ *   3. Filtered matrix A^F: strong off-diagonal entries are kept, weak ones are added to the diagonal,
+ *      a^F_ii = a_ii + sum_weak a_ij.  A zero a^F_ii: STORM_HIP_E_INVALID.
+ *   4. Prolongator P = T - (omega / lambda_F) D_F^-1 A^F T with T_iI = 1 for row i in aggregate I and
+ *      lambda_F = max_i sum_j |a^F_ij| / |a^F_ii|; rows sorted by column, exact zeros dropped.  omega = 0: P = T.  R = P^T is
+ *      stored explicitly.  (Smoothing with the FILTERED matrix keeps the coarse operators sparse on anisotropic weights.)
+ *   5. Coarse operator A_{l+1} = P^T A_l P.
+ *   6. Stop when n_l <= coarse_rows; also when the next level would keep more than 90 % of the rows, or when max_levels
+ *      is reached -- in these two cases a level of at most 1024 rows becomes the coarsest, otherwise the result is
+ *      STORM_HIP_E_UNSUPPORTED with the level sizes in the message.
+ *   7. The coarsest level's dense inverse is formed on the host by Gauss-Jordan with partial pivoting.  A zero pivot or a
+ *      non-finite entry (a pure-Neumann operator, for instance): STORM_HIP_E_INVALID, and the message says so.
+ *
+ * THE CYCLE for level l with right-hand side r and output z (S_l: the level's Chebyshev smoother with the Jacobi scale,
+ * degree smoother_degree, on [lmax / smoother_ratio, lmax] with Gershgorin's lmax; t, e: the level's work vectors):
+ *     z  = S_l(r)                 storm_hip_cheb_apply
+ *     t  = r - A_l z              storm_hip_op_apply(op_l, alpha_l, beta_l, z, t); storm_hip_axpbz(t, 1, r, -1, t)
+ *     rc = R_l t                  acc = 0; acc = fma(w_k, t[c_k], acc) over the row's entries in column order
+ *     zc = cycle(l + 1, rc)       coarsest level: zc = Ainv rc, row i: lane j of a wavefront sums columns j, j + 64, ... by fma,
+ *                                 then the wavefront's tree sum
+ *     z  = z + P_l zc             the same sum, then z_i + acc
+ *     t  = r - A_l z
+ *     e  = S_l(t);  z = z + e     storm_hip_cheb_apply; storm_hip_axpy(z, 1, e)
+ * With option amg_fused (default 1) the residual on a level with fp64 records and no CSR tail is ONE kernel that gives the
+ * bits of the two statements; amg_fused = 0 takes the statements everywhere, and with cheb_fused = 0 as well the cycle holds
+ * no fused kernel but the transfers.  All settings give the same bits (tests/test_gpu_amg.py).  Counters
+ * (storm_hip_ctx_get_counter): "amg_applies", "amg_fused_residuals", "amg_statement_residuals".  About 11 launches per level:
+ * small meshes are launch-bound. */
+#define STORM_HIP_HAS_AMG 1
+typedef struct storm_hip_amg_params {
+  double strength_theta;    /* 0.25 */
+  double prolongator_omega; /* 4/3; 0: the unsmoothed, piecewise-constant prolongator */
+  int32_t smoother_degree;  /* 2 (1 .. 16) */
+  double smoother_ratio;    /* 30: lmin = lmax / ratio, the Chebyshev object's default */
+  int32_t max_levels;       /* 10 */
+  int32_t coarse_rows;      /* 512 (1 .. 1024) */
+  int32_t reduced_records;  /* 0; 1: every level's smoother reads fp32-weight companion records of its operator */
+} storm_hip_amg_params;
+typedef struct storm_hip_amg_hierarchy storm_hip_amg_hierarchy;
+typedef struct storm_hip_amg storm_hip_amg;
+void storm_hip_amg_params_default(storm_hip_amg_params *params);
+/* The hierarchy of assembled CSR (any column order, duplicates are summed).  HOST CODE: needs no context and no device.
+ * params == NULL: the defaults. */
+int storm_hip_amg_setup_csr(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
+                            const storm_hip_amg_params *params, storm_hip_amg_hierarchy **out);
+int storm_hip_amg_hierarchy_destroy(storm_hip_amg_hierarchy *h);
+int storm_hip_amg_hierarchy_levels(const storm_hip_amg_hierarchy *h, int *levels);
+/* rows and entries of A_l; aggregates and entries of P_l (both 0 on the coarsest level) */
+int storm_hip_amg_hierarchy_level_sizes(const storm_hip_amg_hierarchy *h, int level, int64_t *n_rows, int64_t *nnz_a,
+                                        int64_t *n_aggregates, int64_t *nnz_p);
+/* A_l as CSR into the caller's arrays ([n_rows + 1], [nnz_a], [nnz_a]) */
+int storm_hip_amg_hierarchy_get_operator(const storm_hip_amg_hierarchy *h, int level, int64_t *row_ptr, int64_t *col,
+                                         double *val);
+/* the aggregate of every row of level l ([n_rows]); not on the coarsest level */
+int storm_hip_amg_hierarchy_get_aggregates(const storm_hip_amg_hierarchy *h, int level, int64_t *aggregate);
+/* P_l (n_rows x n_aggregates) as CSR ([n_rows + 1], [nnz_p], [nnz_p]); not on the coarsest level */
+int storm_hip_amg_hierarchy_get_prolongator(const storm_hip_amg_hierarchy *h, int level, int64_t *row_ptr, int64_t *col,
+                                            double *val);
+/* the coarsest level's inverse, row-major [n x n] */
+int storm_hip_amg_hierarchy_get_coarse_inverse(const storm_hip_amg_hierarchy *h, double *inverse);
+/* "levels", "operator_complexity" (sum of nnz(A_l) / nnz(A_0)), "grid_complexity" (sum of n_l / n_0), "setup_seconds" */
+int storm_hip_amg_hierarchy_get(const storm_hip_amg_hierarchy *h, const char *key, double *value);
+/* The device object for an operator on fp64 records (format 0: what any mesh gets; a box built with option spmv_dict = 0;
+ * a CSR tail is allowed).  The records are downloaded once and decoded to CSR: a_ii = beta + alpha (ext_i - sum_k w_ik),
+ * a_ij = alpha sum w over the slots of column j, padding dropped; the setup above runs on the host; the coarse operators go
+ * through the CSR packer, forced to fp64 records; level 0 uses `op` itself.  With reduced_records every level's operator
+ * gets a companion (storm_hip_op_build_reduced: `op` too, if it has none).  Host waits (build time).
+ * STORM_HIP_E_UNSUPPORTED: compact record formats; a halo plan, halo columns or a communicator.
+ * `op` must outlive the object.  An object built before storm_hip_op_set_face_weights is STALE (its hierarchy and bounds are
+ * those of the old weights); rebuilding it is the caller's, as for a storm_hip_cheb. */
+int storm_hip_amg_create(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params, storm_hip_amg **out);
+/* z = B r; z must not alias r, r is not written.  Enqueues and never waits; inside a solver callback predicated on the
+ * solve's `done` flag. */
+int storm_hip_amg_apply(const storm_hip_amg *h, const storm_hip_vec *r, storm_hip_vec *z);
+/* The cycle's grid transfers and coarsest-level solve on their own (enqueued like an apply): coarse = R_l fine;
+ * fine += P_l coarse; z = Ainv r on the coarsest level.  Vectors of the levels' sizes; the two must not alias. */
+int storm_hip_amg_restrict(const storm_hip_amg *h, int level, const storm_hip_vec *fine, storm_hip_vec *coarse);
+int storm_hip_amg_prolong_add(const storm_hip_amg *h, int level, const storm_hip_vec *coarse, storm_hip_vec *fine);
+int storm_hip_amg_coarse_solve(const storm_hip_amg *h, const storm_hip_vec *r, storm_hip_vec *z);
+/* the keys of storm_hip_amg_hierarchy_get, and "device_bytes" (what the object allocated), "transfer_padding" (the share of
+ * the transfer records' slots that is padding), "upload_seconds", "smoother_degree", "reduced" */
+int storm_hip_amg_get(const storm_hip_amg *h, const char *key, double *value);
+/* the object's host hierarchy, for the export calls above (borrowed: it lives as long as the object) */
+int storm_hip_amg_get_hierarchy(const storm_hip_amg *h, const storm_hip_amg_hierarchy **out);
+int storm_hip_amg_destroy(storm_hip_amg *h);
+/* pre_op as the library's multigrid preconditioner (h == NULL removes it): bound natively, no callback.  A size that differs
+ * from the solve's vectors: STORM_HIP_E_INVALID from the solve. */
+int storm_hip_krylov_set_preconditioner_amg(storm_hip_krylov *k, const storm_hip_amg *h, int side);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -943,6 +943,83 @@ private:
   storm_hip_cheb* _h = nullptr;
 };
 
+/// Smoothed-aggregation multigrid preconditioner for a HipStencilOperator on fp64 records (storm_hip_amg_*, storm_hip.h,
+/// "Smoothed-aggregation multigrid preconditioner"): one symmetric V-cycle per apply with Jacobi-scaled Chebyshev smoothers,
+/// no reduction and no host wait inside an apply.  For symmetric operators, single rank.  `build` runs the setup on the host
+/// and uploads the hierarchy -- once: a solver calls it before every solve, and it returns at once while matrix, alpha, beta
+/// and `params` are those of the last build; the solvers bind the object natively; `mul` is storm_hip_amg_apply.  The
+/// operator it was built from must outlive it; after StencilMatrix::set_face_weights the object is stale: `reset()` it.
+/// `params.reduced_records`: every level's smoother reads fp32-weight companion records (the matrix gets one if missing).
+class AmgPreconditioner final : public Preconditioner<DeviceVector> {
+public:
+  storm_hip_amg_params params;
+
+  AmgPreconditioner() { storm_hip_amg_params_default(&params); }
+  explicit AmgPreconditioner(int smoother_degree, bool reduced_records = false) : AmgPreconditioner() {
+    params.smoother_degree = smoother_degree;
+    params.reduced_records = reduced_records ? 1 : 0;
+  }
+  AmgPreconditioner(const AmgPreconditioner&) = delete;
+  AmgPreconditioner& operator=(const AmgPreconditioner&) = delete;
+  ~AmgPreconditioner() override { storm_hip_amg_destroy(_h); }
+
+  void build(const DeviceVector& /*x_vec*/, const DeviceVector& /*b_vec*/, const Operator<DeviceVector>& any_op) override {
+    if (dynamic_cast<const HipTwoStageOperator*>(&any_op) != nullptr)
+      throw std::runtime_error("AmgPreconditioner cannot take a HipTwoStageOperator");
+    const auto* hip_op = dynamic_cast<const HipStencilOperator*>(&any_op);
+    if (hip_op == nullptr) throw std::runtime_error("AmgPreconditioner needs a HipStencilOperator");
+    // a solver calls build() before every solve: the hierarchy is kept while operator and parameters are the same
+    // (a matrix whose weights were refreshed is the same handle: reset() first -- staleness is the caller's)
+    if (_h != nullptr && _op == hip_op->matrix().handle() && _alpha == hip_op->alpha() && _beta == hip_op->beta() &&
+        _built.strength_theta == params.strength_theta && _built.prolongator_omega == params.prolongator_omega &&
+        _built.smoother_degree == params.smoother_degree && _built.smoother_ratio == params.smoother_ratio &&
+        _built.max_levels == params.max_levels && _built.coarse_rows == params.coarse_rows &&
+        _built.reduced_records == params.reduced_records)
+      return;
+    reset();
+    detail::check(storm_hip_amg_create(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params, &_h));
+    _op = hip_op->matrix().handle(), _alpha = hip_op->alpha(), _beta = hip_op->beta(), _built = params;
+  }
+  /// Drop the hierarchy: the next build() runs the setup again (after set_face_weights, for instance).
+  void reset() noexcept {
+    storm_hip_amg_destroy(_h);
+    _h = nullptr;
+  }
+  void mul(DeviceVector& y_vec, const DeviceVector& x_vec) const override {
+    detail::check(storm_hip_amg_apply(_h, x_vec.handle(), y_vec.handle()));
+  }
+  void conj_mul(DeviceVector& x_vec, const DeviceVector& y_vec) const override {
+    detail::check(storm_hip_amg_apply(_h, y_vec.handle(), x_vec.handle()));
+  }
+  /// "levels", "operator_complexity", "grid_complexity", "setup_seconds", "upload_seconds", "device_bytes",
+  /// "transfer_padding", "smoother_degree" or "reduced".
+  real_t get(const char* key) const {
+    double v = 0.0;
+    detail::check(storm_hip_amg_get(_h, key, &v));
+    return v;
+  }
+  /// Rows of every level, finest first.
+  std::vector<int64_t> level_rows() const {
+    const storm_hip_amg_hierarchy* hier = nullptr;
+    detail::check(storm_hip_amg_get_hierarchy(_h, &hier));
+    int levels = 0;
+    detail::check(storm_hip_amg_hierarchy_levels(hier, &levels));
+    std::vector<int64_t> rows((size_t)levels);
+    for (int l = 0; l < levels; ++l) {
+      int64_t nnz_a = 0, n_agg = 0, nnz_p = 0;
+      detail::check(storm_hip_amg_hierarchy_level_sizes(hier, l, &rows[(size_t)l], &nnz_a, &n_agg, &nnz_p));
+    }
+    return rows;
+  }
+  const storm_hip_amg* handle() const noexcept { return _h; }
+
+private:
+  storm_hip_amg* _h = nullptr;
+  const storm_hip_op* _op = nullptr;
+  real_t _alpha = 0.0, _beta = 0.0;
+  storm_hip_amg_params _built{};
+};
+
 #ifndef STORM_HIP_NO_SOLVERS
 // ---------------------------------------------------------------------------------------------
 template<class InVector, class OutVector = InVector>
@@ -1008,6 +1085,8 @@ public:
       check(storm_hip_krylov_set_preconditioner_diag(_h, jacobi->inverse_diagonal().handle(), c_side));
     else if (const auto* cheb = dynamic_cast<const ChebyshevPreconditioner*>(pre_op))
       check(storm_hip_krylov_set_preconditioner_cheb(_h, cheb->handle(), c_side));
+    else if (const auto* amg = dynamic_cast<const AmgPreconditioner*>(pre_op))
+      check(storm_hip_krylov_set_preconditioner_amg(_h, amg->handle(), c_side));
     else
       check(storm_hip_krylov_set_preconditioner_fn(_h, &Engine::trampoline, &_pre, c_side));
   }

@@ -59,6 +59,12 @@ class MeshView(C.Structure):
                 ("recv_ptr", i64p)]
 
 
+class AmgParams(C.Structure):
+    _fields_ = [("strength_theta", C.c_double), ("prolongator_omega", C.c_double), ("smoother_degree", C.c_int32),
+                ("smoother_ratio", C.c_double), ("max_levels", C.c_int32), ("coarse_rows", C.c_int32),
+                ("reduced_records", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                           C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -195,6 +201,25 @@ SIGNATURES = {
     "storm_hip_cheb_get": (C.c_int, [vp, C.c_char_p, f64p]),
     "storm_hip_cheb_destroy": (C.c_int, [vp]),
     "storm_hip_krylov_set_preconditioner_cheb": (C.c_int, [vp, vp, C.c_int]),
+    "storm_hip_amg_params_default": (None, [C.POINTER(AmgParams)]),
+    "storm_hip_amg_setup_csr": (C.c_int, [C.c_int64, i64p, i64p, f64p, C.POINTER(AmgParams), C.POINTER(vp)]),
+    "storm_hip_amg_hierarchy_destroy": (C.c_int, [vp]),
+    "storm_hip_amg_hierarchy_levels": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "storm_hip_amg_hierarchy_level_sizes": (C.c_int, [vp, C.c_int, i64p, i64p, i64p, i64p]),
+    "storm_hip_amg_hierarchy_get_operator": (C.c_int, [vp, C.c_int, i64p, i64p, f64p]),
+    "storm_hip_amg_hierarchy_get_aggregates": (C.c_int, [vp, C.c_int, i64p]),
+    "storm_hip_amg_hierarchy_get_prolongator": (C.c_int, [vp, C.c_int, i64p, i64p, f64p]),
+    "storm_hip_amg_hierarchy_get_coarse_inverse": (C.c_int, [vp, f64p]),
+    "storm_hip_amg_hierarchy_get": (C.c_int, [vp, C.c_char_p, f64p]),
+    "storm_hip_amg_create": (C.c_int, [vp, C.c_double, C.c_double, C.POINTER(AmgParams), C.POINTER(vp)]),
+    "storm_hip_amg_apply": (C.c_int, [vp, vp, vp]),
+    "storm_hip_amg_restrict": (C.c_int, [vp, C.c_int, vp, vp]),
+    "storm_hip_amg_prolong_add": (C.c_int, [vp, C.c_int, vp, vp]),
+    "storm_hip_amg_coarse_solve": (C.c_int, [vp, vp, vp]),
+    "storm_hip_amg_get": (C.c_int, [vp, C.c_char_p, f64p]),
+    "storm_hip_amg_get_hierarchy": (C.c_int, [vp, C.POINTER(vp)]),
+    "storm_hip_amg_destroy": (C.c_int, [vp]),
+    "storm_hip_krylov_set_preconditioner_amg": (C.c_int, [vp, vp, C.c_int]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

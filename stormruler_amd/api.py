@@ -996,6 +996,186 @@ class ChebyshevPreconditioner(Preconditioner):
             pass
 
 
+def _amg_params(**kw) -> "_lib.AmgParams":
+    p = _lib.AmgParams()
+    lib.storm_hip_amg_params_default(C.byref(p))
+    for k, v in kw.items():
+        if v is None:
+            continue
+        if not hasattr(p, k):
+            raise TypeError(f"unknown multigrid parameter {k!r}")
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+class AmgHierarchy:
+    """The host hierarchy of the smoothed-aggregation multigrid preconditioner (``storm_hip_amg_setup_csr`` and the
+    ``storm_hip_amg_hierarchy_*`` export calls, include/storm_hip.h): level operators, aggregates, prolongators and the
+    coarsest level's dense inverse, as scipy / numpy objects.  Host code: needs no :class:`Context` and no device."""
+
+    def __init__(self, handle, owned: bool = True, keep=None):
+        self._h, self._owned, self._keep = handle, owned, keep
+
+    @classmethod
+    def from_csr(cls, a, **params) -> "AmgHierarchy":
+        """Keywords: ``strength_theta``, ``prolongator_omega``, ``smoother_degree``, ``smoother_ratio``, ``max_levels``,
+        ``coarse_rows``, ``reduced_records`` (defaults: ``storm_hip_amg_params_default``)."""
+        a = a.tocsr()
+        rp = np.ascontiguousarray(a.indptr, np.int64)
+        col = np.ascontiguousarray(a.indices, np.int64)
+        val = np.ascontiguousarray(a.data, np.float64)
+        h = C.c_void_p()
+        p = _amg_params(**params)
+        check(lib.storm_hip_amg_setup_csr(a.shape[0], rp.ctypes.data_as(_lib.i64p), col.ctypes.data_as(_lib.i64p),
+                                          val.ctypes.data_as(_lib.f64p), C.byref(p), C.byref(h)))
+        return cls(h)
+
+    @property
+    def levels(self) -> int:
+        n = C.c_int()
+        check(lib.storm_hip_amg_hierarchy_levels(self._h, C.byref(n)))
+        return n.value
+
+    def sizes(self, level: int):
+        """``(rows, nnz of A_l, aggregates, nnz of P_l)``; the last two are 0 on the coarsest level."""
+        v = [C.c_int64() for _ in range(4)]
+        check(lib.storm_hip_amg_hierarchy_level_sizes(self._h, level, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def level_rows(self):
+        return [self.sizes(lv)[0] for lv in range(self.levels)]
+
+    def _csr(self, fn, level, n_rows, n_cols, nnz):
+        import scipy.sparse as sp
+
+        rp, col, val = np.zeros(n_rows + 1, np.int64), np.zeros(max(nnz, 1), np.int64), np.zeros(max(nnz, 1), np.float64)
+        check(fn(self._h, level, rp.ctypes.data_as(_lib.i64p), col.ctypes.data_as(_lib.i64p), val.ctypes.data_as(_lib.f64p)))
+        return sp.csr_matrix((val[:nnz], col[:nnz], rp), shape=(n_rows, n_cols))
+
+    def operator(self, level: int):
+        n, nnz, _, _ = self.sizes(level)
+        return self._csr(lib.storm_hip_amg_hierarchy_get_operator, level, n, n, nnz)
+
+    def prolongator(self, level: int):
+        n, _, n_agg, nnz = self.sizes(level)
+        return self._csr(lib.storm_hip_amg_hierarchy_get_prolongator, level, n, n_agg, nnz)
+
+    def aggregates(self, level: int) -> np.ndarray:
+        agg = np.zeros(self.sizes(level)[0], np.int64)
+        check(lib.storm_hip_amg_hierarchy_get_aggregates(self._h, level, agg.ctypes.data_as(_lib.i64p)))
+        return agg
+
+    def coarse_inverse(self) -> np.ndarray:
+        n = self.sizes(self.levels - 1)[0]
+        inv = np.zeros((n, n), np.float64)
+        check(lib.storm_hip_amg_hierarchy_get_coarse_inverse(self._h, inv.ctypes.data_as(_lib.f64p)))
+        return inv
+
+    def get(self, key: str) -> float:
+        """``levels``, ``operator_complexity``, ``grid_complexity`` or ``setup_seconds``."""
+        v = C.c_double()
+        check(lib.storm_hip_amg_hierarchy_get(self._h, key.encode(), C.byref(v)))
+        return v.value
+
+    def close(self):
+        if getattr(self, "_h", None) and self._owned:
+            lib.storm_hip_amg_hierarchy_destroy(self._h)
+        self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AmgPreconditioner(Preconditioner):
+    """Smoothed-aggregation multigrid preconditioner for a :class:`HipStencilOperator` on fp64 records (``storm_hip_amg_*``,
+    include/storm_hip.h): one symmetric V-cycle per apply, Jacobi-scaled Chebyshev smoothers of ``smoother_degree``, no
+    reduction and no host wait inside an apply.  For symmetric operators, single rank.  :meth:`build` runs the setup on the
+    host (seconds on a large mesh) and uploads the hierarchy -- once: a solver calls it before every solve, and it returns
+    at once while the matrix handle, alpha, beta and the parameters are those of the last build; the solvers bind the
+    object natively; :meth:`mul` is ``storm_hip_amg_apply``.  The operator it was built from must outlive it; after
+    :meth:`StencilMatrix.set_face_weights` the object is stale: :meth:`close` it, and the next build runs the setup again.  ``reduced_records``: every level's
+    smoother reads fp32-weight companion records (the matrix gets one if it has none)."""
+
+    def __init__(self, strength_theta: Optional[float] = None, prolongator_omega: Optional[float] = None,
+                 smoother_degree: Optional[int] = None, smoother_ratio: Optional[float] = None,
+                 max_levels: Optional[int] = None, coarse_rows: Optional[int] = None, reduced_records: bool = False):
+        self.params = dict(strength_theta=strength_theta, prolongator_omega=prolongator_omega, smoother_degree=smoother_degree,
+                           smoother_ratio=smoother_ratio, max_levels=max_levels, coarse_rows=coarse_rows,
+                           reduced_records=int(bool(reduced_records)))
+        self.reduced_records = bool(reduced_records)
+        self._h, self._op, self.ctx, self._key = None, None, None, None
+
+    def build(self, x_vec, b_vec, any_op) -> None:
+        if isinstance(any_op, HipTwoStageOperator):
+            raise TypeError("AmgPreconditioner cannot take a HipTwoStageOperator (the hierarchy is that of one stage); "
+                            "precondition with another operator")
+        if not isinstance(any_op, HipStencilOperator):
+            raise TypeError("AmgPreconditioner needs a HipStencilOperator to build its hierarchy from")
+        # a solver calls build() before every solve: the hierarchy is kept while operator and parameters are the same
+        # (a matrix whose weights were refreshed is the same handle: close() first -- staleness is the caller's)
+        key = (x_vec.ctx, any_op.matrix._h.value, float(any_op.alpha), float(any_op.beta), tuple(sorted(self.params.items())))
+        if self._h is not None and self._key == key:
+            return
+        self._free()
+        self.ctx, self._op = x_vec.ctx, any_op
+        h = C.c_void_p()
+        p = _amg_params(**self.params)
+        check(lib.storm_hip_amg_create(any_op.matrix._h, any_op.alpha, any_op.beta, C.byref(p), C.byref(h)))
+        self._h, self._key = h, key
+        self.ctx._children.add(self)
+
+    def get(self, key: str) -> float:
+        """``levels``, ``operator_complexity``, ``grid_complexity``, ``setup_seconds``, ``upload_seconds``, ``device_bytes``,
+        ``transfer_padding``, ``smoother_degree`` or ``reduced``."""
+        v = C.c_double()
+        check(lib.storm_hip_amg_get(self._h, key.encode(), C.byref(v)))
+        return v.value
+
+    @property
+    def hierarchy(self) -> AmgHierarchy:
+        """The object's host hierarchy (borrowed: valid while the preconditioner is)."""
+        h = C.c_void_p()
+        check(lib.storm_hip_amg_get_hierarchy(self._h, C.byref(h)))
+        return AmgHierarchy(h, owned=False, keep=self)
+
+    def mul(self, y_vec, x_vec):
+        check(lib.storm_hip_amg_apply(self._h, x_vec._h, y_vec._h))
+
+    def restrict(self, level: int, fine, coarse) -> None:
+        """``coarse = R_l fine`` (``storm_hip_amg_restrict``)."""
+        check(lib.storm_hip_amg_restrict(self._h, level, fine._h, coarse._h))
+
+    def prolong_add(self, level: int, coarse, fine) -> None:
+        """``fine += P_l coarse`` (``storm_hip_amg_prolong_add``)."""
+        check(lib.storm_hip_amg_prolong_add(self._h, level, coarse._h, fine._h))
+
+    def coarse_solve(self, r_vec, z_vec) -> None:
+        """``z = Ainv r`` on the coarsest level (``storm_hip_amg_coarse_solve``)."""
+        check(lib.storm_hip_amg_coarse_solve(self._h, r_vec._h, z_vec._h))
+
+    def conj_mul(self, x_vec, y_vec):  # (the V-cycle is symmetric)
+        check(lib.storm_hip_amg_apply(self._h, y_vec._h, x_vec._h))
+
+    def _free(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):
+                lib.storm_hip_amg_destroy(self._h)
+            self._h = None
+        self._key = None
+
+    def close(self):
+        self._free()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self._free()
+        except Exception:
+            pass
+
+
 class Solver:  # Solver.hpp:43-57
     def solve(self, x_vec: DeviceVector, b_vec: DeviceVector, any_op: Operator) -> bool:
         raise NotImplementedError
@@ -1006,7 +1186,7 @@ class _Engine:
     reference-side objects bound to it: a :class:`HipStencilOperator` or :class:`HipTwoStageOperator` binds natively, any other ``Operator`` --
     e.g. a lambda through ``make_operator``, the reference's only call site (Playground.cpp:151-167) -- as a
     callback that merely enqueues its kernels; likewise ``pre_op`` (a :class:`JacobiPreconditioner` binds as a
-    device diagonal, a :class:`ChebyshevPreconditioner` as the library's object).  An exception raised inside a callback aborts the solve and is re-raised from it."""
+    device diagonal, a :class:`ChebyshevPreconditioner` or :class:`AmgPreconditioner` as the library's object).  An exception raised inside a callback aborts the solve and is re-raised from it."""
 
     def __init__(self, ctx: Context, method: int):
         h = C.c_void_p()
@@ -1057,6 +1237,8 @@ class _Engine:
             check(lib.storm_hip_krylov_set_preconditioner_diag(self._h, pre_op._dinv._h, int(pre_side)))
         elif isinstance(pre_op, ChebyshevPreconditioner):
             check(lib.storm_hip_krylov_set_preconditioner_cheb(self._h, pre_op._h, int(pre_side)))
+        elif isinstance(pre_op, AmgPreconditioner):
+            check(lib.storm_hip_krylov_set_preconditioner_amg(self._h, pre_op._h, int(pre_side)))
         else:
             check(lib.storm_hip_krylov_set_preconditioner_fn(self._h, self._callback(pre_op.mul), None, int(pre_side)))
 

@@ -1,0 +1,444 @@
+// The device half of the smoothed-aggregation multigrid preconditioner (storm_hip_amg_*): z = B r, one symmetric V-cycle
+// for A = beta I + alpha M.  Recipe and cycle: include/storm_hip.h; the hierarchy comes from amg_setup.hip (host).
+//
+// Per level: a Jacobi-scaled Chebyshev smoother (precond_cheb.hip, the existing object), the level's operator (level 0: the
+// caller's; below: fp64 records from the CSR packer), the transfer records P and R = P^T, four work vectors.  The cycle
+// enqueues and never waits: no reduction, no host wait, no atomics, no cooperative launch.  Kernels of this unit:
+//   amg_residual_kernel     t = r - A z on fp64 records without a CSR tail: spmv_sell_kernel's / cheb_step_kernel's shape (one
+//                           wavefront per slice, one row per lane, the same XCD runs, records non-temporal, z gathered
+//                           plainly), the product from row_sum_any / sell_row_result, then fl(r_i - t_i): the bits of
+//                           storm_hip_op_apply(op, alpha, beta, z, t); storm_hip_axpbz(t, 1, r, -1, t), which any other
+//                           level (or option amg_fused = 0) takes.
+//   amg_transfer_kernel     y = T x (restriction) or y += T x (prolongation) on the transfer records: one wavefront per slice
+//                           of 64 rows, one row per lane, acc = fma(w_k, x[c_k], acc) in slot order.
+//   amg_coarse_kernel       z = Ainv r, dense: one wavefront per row, lane j takes columns j, j + 64, ... by fma, then the
+//                           wavefront's sum (wave_device.hpp).
+// Every kernel loads the context's api_done word first and tests it before its first store.
+#include <chrono>
+#include <cmath>
+#include <cstring>
+
+#include "amg.hpp"
+#include "sell_device.hpp"
+#include "wave_device.hpp"
+
+namespace storm {
+
+template <bool NT, bool XCD>
+__global__ __launch_bounds__(kBlock) void amg_residual_kernel(SellArgs A, double alpha, double beta, const double *__restrict__ r,
+                                                              const double *__restrict__ z, double *__restrict__ t,
+                                                              int64_t n_slices, const int *done) {
+  const int done_flag = done ? *done : 0;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bidx = (int)blockIdx.x;
+  const int lb = XCD ? (A.xcd_group > 1 ? xcd_remap_grouped(bidx, gridDim.x, A.xcd_group) : xcd_remap(bidx, gridDim.x))
+                     : bidx;
+  const int64_t slice = (int64_t)lb * (kBlock / kWave) + wave;
+  if (slice >= n_slices) return;  // wave-uniform; the kernel has no barrier
+  const int64_t row = slice * kWave + lane;
+  const bool valid = row < A.n_rows;
+  const double zi = valid ? z[row] : 0.0;
+  const double ri = valid ? ld_d<NT>(r + row) : 0.0;  // the row's own stream, early
+  int64_t base;
+  int width;
+  if (A.uniform_width > 0) {
+    width = A.uniform_width;
+    base = slice * (int64_t)(kExtBytes + kSlotBytes * width);
+  } else {
+    base = A.slice_off[slice];
+    width = (int)((A.slice_off[slice + 1] - base - kExtBytes) / kSlotBytes);
+  }
+  const char *rec = A.pack + base;
+  const double ext = Rec64::ext<NT>(rec, lane);
+  const double zi1[1] = {zi};
+  double acc1[1];
+  row_sum_any<NT, 1, Rec64>(rec, width, lane, z, zi1, acc1);
+  const double az = sell_row_result(false, 0.0, beta, zi, alpha, acc1[0], ext);
+  const double tn = ri - az;  // axpbz(t, 1, r, -1, t): the multiplications by +-1 are exact
+  if (valid && !done_flag) {
+    if (NT) __builtin_nontemporal_store(tn, t + row);
+    else t[row] = tn;
+  }
+}
+
+// y_i = [y_i +] sum_k w_k x[c_k] over the slots of the row's slice, in slot order.
+template <bool ADD>
+__global__ __launch_bounds__(kBlock) void amg_transfer_kernel(const char *__restrict__ pack, const int64_t *__restrict__ off,
+                                                              int64_t n_rows, int64_t n_slices, const double *__restrict__ x,
+                                                              double *__restrict__ y, const int *done) {
+  const int done_flag = done ? *done : 0;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t slice = (int64_t)blockIdx.x * (kBlock / kWave) + wave;
+  if (slice >= n_slices) return;  // wave-uniform
+  const int64_t row = slice * kWave + lane;
+  const bool valid = row < n_rows;
+  const int64_t base = off[slice];
+  const int width = (int)((off[slice + 1] - base) / (kWave * 12));
+  const int *__restrict__ cp = reinterpret_cast<const int *>(pack + base) + lane;
+  const double *__restrict__ vp = reinterpret_cast<const double *>(pack + base + (int64_t)width * (kWave * 4)) + lane;
+  double yi = 0.0;
+  if (ADD) yi = valid ? y[row] : 0.0;
+  double acc = 0.0;
+#pragma unroll 4  // (the loads of four slots in flight; the sum stays in slot order)
+  for (int k = 0; k < width; ++k) {  // (padding: column 0, weight 0 -- inside x for every lane of the slice)
+    const int c = __builtin_nontemporal_load(cp + k * kWave);
+    const double w = __builtin_nontemporal_load(vp + k * kWave);
+    acc = fma(w, x[c], acc);
+  }
+  if (valid && !done_flag) y[row] = ADD ? yi + acc : acc;
+}
+
+__global__ __launch_bounds__(kBlock) void amg_coarse_kernel(const double *__restrict__ ainv, int64_t n, const double *__restrict__ r,
+                                                            double *__restrict__ z, const int *done) {
+  const int done_flag = done ? *done : 0;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t row = (int64_t)blockIdx.x * (kBlock / kWave) + wave;
+  if (row >= n) return;  // wave-uniform: all 64 lanes take part in the sum
+  const double *__restrict__ a = ainv + row * n;
+  double acc = 0.0;
+  for (int64_t j = lane; j < n; j += kWave) acc = fma(a[j], r[j], acc);
+  acc = wave_sum_down(acc);  // the total in lane 0
+  if (lane == 0 && !done_flag) z[row] = acc;
+}
+
+int op_create_csr_fp64(storm_hip_ctx *c, int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
+                       storm_hip_op **out);  // spmv_build.hip
+
+static bool amg_residual_fused(const storm_hip_amg *h, const storm_hip_op *op) {
+  return h->ctx->opt_amg_fused != 0 && op->pair == 0 && op->dict_size == 0 && op->offs_size == 0 && op->tail_rows == 0 &&
+         op->d_bnd_pack == nullptr && op->n_rows > 0;
+}
+
+// t = r - A_l z
+static int amg_residual(const storm_hip_amg *h, const storm_hip_amg::Level &L, const storm_hip_vec *r, const storm_hip_vec *z,
+                        storm_hip_vec *t) {
+  storm_hip_ctx *c = h->ctx;
+  const storm_hip_op *op = L.op;
+  if (!amg_residual_fused(h, op)) {
+    ++c->n_amg_statement_residuals;
+    STORM_TRY(storm_hip_op_apply(op, L.alpha, L.beta, z, t));
+    return storm_hip_axpbz(t, 1.0, r, -1.0, t);
+  }
+  ++c->n_amg_fused_residuals;
+  const SellArgs A{op->d_pack, op->d_slice_off, op->n_rows, op->uniform_width, op->xcd_group_sell, op->d_dict, op->dict_size,
+                   op->d_offs, op->offs_size, 0};
+  const dim3 grid(blocks_for(op, op->n_slices)), block(kBlock);
+  const bool nt = c->opt_nt != 0, xcd = op->xcd_group_sell != 0;
+#define AMG_RES_GO(NT_, XCD_)                                                                                               \
+  hipLaunchKernelGGL((amg_residual_kernel<NT_, XCD_>), grid, block, 0, c->stream, A, L.alpha, L.beta, r->d, z->d, t->d, \
+                     op->n_slices, c->api_done)
+  if (nt && xcd) AMG_RES_GO(true, true);
+  else if (nt) AMG_RES_GO(true, false);
+  else if (xcd) AMG_RES_GO(false, true);
+  else AMG_RES_GO(false, false);
+#undef AMG_RES_GO
+  HIP_TRY(hipGetLastError());
+  return STORM_HIP_OK;
+}
+
+static int amg_transfer(const storm_hip_amg *h, const storm_hip_amg::Transfer &T, bool add, const storm_hip_vec *x, storm_hip_vec *y) {
+  storm_hip_ctx *c = h->ctx;
+  const dim3 grid((unsigned)((T.n_slices + 3) / 4)), block(kBlock);
+  if (add)
+    hipLaunchKernelGGL(amg_transfer_kernel<true>, grid, block, 0, c->stream, T.d_pack, T.d_off, T.n_rows, T.n_slices, x->d, y->d,
+                       c->api_done);
+  else
+    hipLaunchKernelGGL(amg_transfer_kernel<false>, grid, block, 0, c->stream, T.d_pack, T.d_off, T.n_rows, T.n_slices, x->d, y->d,
+                       c->api_done);
+  HIP_TRY(hipGetLastError());
+  return STORM_HIP_OK;
+}
+
+static int amg_cycle(const storm_hip_amg *h, size_t l, const storm_hip_vec *r, storm_hip_vec *z) {
+  storm_hip_ctx *c = h->ctx;
+  if (l + 1 == h->levels.size()) {
+    hipLaunchKernelGGL(amg_coarse_kernel, dim3((unsigned)((h->n_coarse + 3) / 4)), dim3(kBlock), 0, c->stream, h->d_ainv,
+                       h->n_coarse, r->d, z->d, c->api_done);
+    HIP_TRY(hipGetLastError());
+    return STORM_HIP_OK;
+  }
+  const storm_hip_amg::Level &L = h->levels[l];
+  const storm_hip_amg::Level &N = h->levels[l + 1];
+  STORM_TRY(storm_hip_cheb_apply(L.cheb, r, z));
+  STORM_TRY(amg_residual(h, L, r, z, L.t));
+  STORM_TRY(amg_transfer(h, L.R, false, L.t, N.r));
+  STORM_TRY(amg_cycle(h, l + 1, N.r, N.z));
+  STORM_TRY(amg_transfer(h, L.P, true, N.z, z));
+  STORM_TRY(amg_residual(h, L, r, z, L.t));
+  STORM_TRY(storm_hip_cheb_apply(L.cheb, L.t, L.e));
+  return storm_hip_axpy(z, 1.0, L.e);
+}
+
+// The operator's fp64 records (and CSR tail) as CSR of A = beta I + alpha M: a_ii = beta + alpha (ext_i - sum w_ik) over the
+// row's slots and tail entries in their order, a_ij = alpha sum w over the slots of column j; padding (weight 0) dropped.
+static int amg_decode(const storm_hip_op *op, double alpha, double beta, std::vector<int64_t> *ptr, std::vector<int64_t> *col,
+                      std::vector<double> *val) {
+  const int64_t n = op->n_rows, ns = op->n_slices;
+  std::vector<int64_t> off((size_t)ns + 1, 0);
+  HIP_TRY(hipStreamSynchronize(op->ctx->stream));
+  HIP_TRY(hipMemcpy(off.data(), op->d_slice_off, sizeof(int64_t) * (size_t)(ns + 1), hipMemcpyDeviceToHost));
+  std::vector<char> pack((size_t)std::max<int64_t>(off[(size_t)ns], 1));  // (the records end where the last offset says)
+  if (off[(size_t)ns] > 0) HIP_TRY(hipMemcpy(pack.data(), op->d_pack, (size_t)off[(size_t)ns], hipMemcpyDeviceToHost));
+  std::vector<int> trow((size_t)op->tail_rows), tcol((size_t)op->tail_nnz);
+  std::vector<int64_t> tptr((size_t)op->tail_rows + 1, 0);
+  std::vector<double> tval((size_t)op->tail_nnz);
+  if (op->tail_rows > 0) {
+    HIP_TRY(hipMemcpy(trow.data(), op->d_tail_row, sizeof(int) * trow.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tptr.data(), op->d_tail_ptr, sizeof(int64_t) * tptr.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tcol.data(), op->d_tail_col, sizeof(int) * tcol.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tval.data(), op->d_tail_val, sizeof(double) * tval.size(), hipMemcpyDeviceToHost));
+  }
+  std::vector<int64_t> tail_of((size_t)n, -1);
+  for (int64_t t = 0; t < op->tail_rows; ++t) {
+    STORM_REQUIRE(trow[(size_t)t] >= 0 && trow[(size_t)t] < n, "amg_create: a tail row outside the operator");
+    tail_of[(size_t)trow[(size_t)t]] = t;
+  }
+  ptr->assign((size_t)n + 1, 0);
+  col->clear(), val->clear();
+  std::vector<std::pair<int, double>> row;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t s = i / kWave;
+    const int l = (int)(i % kWave);
+    const char *rec = pack.data() + off[(size_t)s];
+    const int W = (int)((off[(size_t)s + 1] - off[(size_t)s] - kExtBytes) / kSlotBytes);
+    const int np2 = W >> 1;
+    const double ext = reinterpret_cast<const double *>(rec)[l];
+    const int *c_ = reinterpret_cast<const int *>(rec + kExtBytes);
+    const double *v_ = reinterpret_cast<const double *>(rec + kExtBytes + (int64_t)W * (kWave * 4));
+    row.clear();
+    double sum = 0.0;
+    for (int k = 0; k < W; ++k) {
+      const int at = (k < 2 * np2) ? ((k >> 1) * kWave + l) * 2 + (k & 1) : np2 * 2 * kWave + l;
+      if (v_[at] == 0.0) continue;
+      STORM_REQUIRE(c_[at] >= 0 && c_[at] < n, "amg_create: column %d of row %lld outside the operator", c_[at], (long long)i);
+      sum += v_[at];
+      row.emplace_back(c_[at], v_[at]);
+    }
+    if (tail_of[(size_t)i] >= 0)
+      for (int64_t k = tptr[(size_t)tail_of[(size_t)i]]; k < tptr[(size_t)tail_of[(size_t)i] + 1]; ++k) {
+        if (tval[(size_t)k] == 0.0) continue;
+        STORM_REQUIRE(tcol[(size_t)k] >= 0 && tcol[(size_t)k] < n, "amg_create: column %d of row %lld outside the operator",
+                      tcol[(size_t)k], (long long)i);
+        sum += tval[(size_t)k];
+        row.emplace_back(tcol[(size_t)k], tval[(size_t)k]);
+      }
+    std::stable_sort(row.begin(), row.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    double diag = beta + alpha * (ext - sum);
+    bool placed = false;
+    for (size_t k = 0; k < row.size();) {
+      double w = row[k].second;
+      size_t e = k + 1;
+      for (; e < row.size() && row[e].first == row[k].first; ++e) w += row[e].second;
+      if (row[k].first == i) {  // (a slot on the row's own column multiplies x_i - x_i: it adds nothing)
+        k = e;
+        continue;
+      }
+      if (!placed && row[k].first > i) col->push_back(i), val->push_back(diag), placed = true;
+      col->push_back(row[k].first), val->push_back(alpha * w);
+      k = e;
+    }
+    if (!placed) col->push_back(i), val->push_back(diag);
+    (*ptr)[(size_t)i + 1] = (int64_t)col->size();
+  }
+  return STORM_HIP_OK;
+}
+
+template <class T>
+static int amg_upload(T **dst, const T *src, size_t count, int64_t *bytes) {
+  const size_t nbytes = sizeof(T) * (count ? count : 1);
+  hipError_t e = hipMalloc((void **)dst, nbytes);
+  if (e != hipSuccess) STORM_FAIL(STORM_HIP_E_ALLOC, "amg_create: hipMalloc(%zu) failed: %s", nbytes, hipGetErrorString(e));
+  if (count) HIP_TRY(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
+  *bytes += (int64_t)nbytes;
+  return STORM_HIP_OK;
+}
+
+static int amg_upload_transfer(storm_hip_amg *h, const AmgCsr &M, storm_hip_amg::Transfer *T) {
+  AmgTransferImage img;
+  STORM_TRY(amg_pack_transfer(M, &img));
+  T->n_rows = img.n_rows, T->n_slices = img.n_slices;
+  STORM_TRY(amg_upload(&T->d_off, img.off.data(), img.off.size(), &h->device_bytes));
+  STORM_TRY(amg_upload(&T->d_pack, img.pack.data(), img.pack.size(), &h->device_bytes));
+  h->transfer_slots += img.slots, h->transfer_nnz += img.nnz;
+  return STORM_HIP_OK;
+}
+
+static int amg_build_device(storm_hip_amg *h, storm_hip_op *op0) {
+  storm_hip_ctx *c = h->ctx;
+  const storm_hip_amg_params &p = h->hier->params;
+  const size_t nl = h->hier->levels.size();
+  h->levels.resize(nl);
+  for (size_t l = 0; l < nl; ++l) {
+    const AmgHostLevel &H = h->hier->levels[l];
+    storm_hip_amg::Level &L = h->levels[l];
+    L.n = H.A.n_rows;
+    if (l > 0) {
+      STORM_TRY(storm_hip_vec_create(c, L.n, 0, &L.r));
+      STORM_TRY(storm_hip_vec_create(c, L.n, 0, &L.z));
+      h->device_bytes += 2 * (int64_t)L.r->bytes;
+    }
+    if (l + 1 == nl) break;  // the coarsest level is its dense inverse
+    if (l == 0) {
+      L.op = op0, L.alpha = h->alpha, L.beta = h->beta;
+    } else {
+      std::vector<int64_t> col(H.A.col.begin(), H.A.col.end());
+      STORM_TRY(op_create_csr_fp64(c, L.n, H.A.ptr.data(), col.data(), H.A.val.data(), &L.own_op));
+      L.op = L.own_op, L.alpha = 1.0, L.beta = 0.0;
+      h->device_bytes += L.own_op->device_bytes;
+    }
+    storm_hip_op *mine = l == 0 ? op0 : L.own_op;
+    STORM_TRY(storm_hip_vec_create(c, L.n, 0, &L.dinv));
+    STORM_TRY(storm_hip_vec_create(c, L.n, 0, &L.t));
+    STORM_TRY(storm_hip_vec_create(c, L.n, 0, &L.e));
+    h->device_bytes += 6 * (int64_t)L.t->bytes;  // ... and the smoother's three
+    STORM_TRY(storm_hip_op_get_diagonal(L.op, L.alpha, L.beta, 1, L.dinv));
+    double lmax = 0.0;
+    if (p.reduced_records) {
+      const int64_t before = mine->device_bytes;
+      STORM_TRY(storm_hip_op_build_reduced(mine));
+      if (l > 0) h->device_bytes += mine->device_bytes - before;
+      STORM_TRY(storm_hip_op_gershgorin_reduced(L.op, L.alpha, L.beta, L.dinv, &lmax));
+      STORM_TRY(storm_hip_cheb_create_reduced(L.op, L.alpha, L.beta, L.dinv, p.smoother_degree, lmax / p.smoother_ratio, lmax, &L.cheb));
+    } else {
+      STORM_TRY(storm_hip_op_gershgorin(L.op, L.alpha, L.beta, L.dinv, &lmax));
+      STORM_TRY(storm_hip_cheb_create(L.op, L.alpha, L.beta, L.dinv, p.smoother_degree, lmax / p.smoother_ratio, lmax, &L.cheb));
+    }
+    STORM_TRY(amg_upload_transfer(h, H.P, &L.P));
+    STORM_TRY(amg_upload_transfer(h, H.R, &L.R));
+  }
+  h->n_coarse = h->hier->levels.back().A.n_rows;
+  STORM_TRY(amg_upload(&h->d_ainv, h->hier->ainv.data(), h->hier->ainv.size(), &h->device_bytes));
+  return STORM_HIP_OK;
+}
+
+}  // namespace storm
+
+using namespace storm;
+
+extern "C" {
+
+int storm_hip_amg_create(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params, storm_hip_amg **out) {
+  STORM_REQUIRE(op && out, "amg_create: null argument");
+  *out = nullptr;
+  STORM_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "amg_create: alpha and beta must be finite");
+  if (op->pair != 0 || op->dict_size > 0 || op->offs_size > 0 || op->d_bnd_pack != nullptr)
+    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "amg_create: the operator is on compact records (a value / offset dictionary, paired rows "
+                                        "or a mixed operator); the multigrid preconditioner reads fp64 records (what any mesh "
+                                        "gets; a box built with option spmv_dict = 0)");
+  if (op->halo.n_nbrs > 0 || op->n_halo > 0 || op->ctx->comm != nullptr)
+    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "amg_create: the multigrid preconditioner is single-rank (the operator has a halo plan or "
+                                        "halo columns, or the context a communicator)");
+  STORM_REQUIRE(op->n_rows >= 1, "amg_create: the operator has no rows");
+  storm_hip_ctx *c = op->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  STORM_TRY(lazy_sync(c));
+  std::vector<int64_t> ptr, col;
+  std::vector<double> val;
+  STORM_TRY(amg_decode(op, alpha, beta, &ptr, &col, &val));
+  storm_hip_amg_hierarchy *hier = nullptr;
+  STORM_TRY(storm_hip_amg_setup_csr(op->n_rows, ptr.data(), col.data(), val.data(), params, &hier));
+  storm_hip_amg *h = new storm_hip_amg();
+  h->ctx = c, h->op = op, h->alpha = alpha, h->beta = beta, h->hier = hier;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int st = amg_build_device(h, op);
+  if (st != STORM_HIP_OK) {
+    (void)storm_hip_amg_destroy(h);
+    return st;
+  }
+  h->upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  *out = h;
+  return STORM_HIP_OK;
+}
+
+int storm_hip_amg_destroy(storm_hip_amg *h) {
+  if (!h) return STORM_HIP_OK;
+  for (auto &L : h->levels) {
+    (void)storm_hip_cheb_destroy(L.cheb);
+    storm_hip_vec *vs[5] = {L.dinv, L.r, L.z, L.t, L.e};
+    for (storm_hip_vec *v : vs) (void)storm_hip_vec_destroy(v);
+    (void)hipFree(L.P.d_off), (void)hipFree(L.P.d_pack), (void)hipFree(L.R.d_off), (void)hipFree(L.R.d_pack);
+    (void)storm_hip_op_destroy(L.own_op);
+  }
+  (void)hipFree(h->d_ainv);
+  (void)storm_hip_amg_hierarchy_destroy(h->hier);
+  delete h;
+  return STORM_HIP_OK;
+}
+
+int storm_hip_amg_apply(const storm_hip_amg *h, const storm_hip_vec *r, storm_hip_vec *z) {
+  STORM_REQUIRE(h && r && z, "amg_apply: null argument");
+  STORM_REQUIRE(r->ctx == h->ctx && z->ctx == h->ctx, "amg_apply: context mismatch");
+  STORM_REQUIRE(z != r && z->d != r->d, "amg_apply: z must not alias r");
+  STORM_REQUIRE(r->n_owned == h->op->n_rows && z->n_owned == h->op->n_rows, "amg_apply: operator has %lld rows, r %lld, z %lld",
+                (long long)h->op->n_rows, (long long)r->n_owned, (long long)z->n_owned);
+  storm_hip_ctx *c = h->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  STORM_TRY(lazy_sync(c));
+  // the library calls of the cycle go out as they are issued (no lazy_statements hold-back), predicated on api_done
+  struct Depth {
+    storm_hip_ctx *c;
+    explicit Depth(storm_hip_ctx *c_) : c(c_) { ++c->callback_depth; }
+    ~Depth() { --c->callback_depth; }
+  } depth(c);
+  ++c->n_amg_applies;
+  return amg_cycle(h, 0, r, z);
+}
+
+static int amg_level_check(const storm_hip_amg *h, int level, const storm_hip_vec *fine, const storm_hip_vec *coarse, const char *who) {
+  STORM_REQUIRE(level >= 0 && level + 1 < (int)h->levels.size(), "%s: level %d has no transfer (%d levels)", who, level,
+                (int)h->levels.size());
+  STORM_REQUIRE(fine->ctx == h->ctx && coarse->ctx == h->ctx, "%s: context mismatch", who);
+  STORM_REQUIRE(fine != coarse && fine->d != coarse->d, "%s: the vectors must not alias", who);
+  STORM_REQUIRE(fine->n_owned == h->levels[(size_t)level].n && coarse->n_owned == h->levels[(size_t)level + 1].n,
+                "%s: level %d has %lld rows and the next %lld; the vectors have %lld and %lld", who, level,
+                (long long)h->levels[(size_t)level].n, (long long)h->levels[(size_t)level + 1].n, (long long)fine->n_owned,
+                (long long)coarse->n_owned);
+  HIP_TRY(hipSetDevice(h->ctx->device));
+  return lazy_sync(h->ctx);
+}
+
+int storm_hip_amg_restrict(const storm_hip_amg *h, int level, const storm_hip_vec *fine, storm_hip_vec *coarse) {
+  STORM_REQUIRE(h && fine && coarse, "amg_restrict: null argument");
+  STORM_TRY(amg_level_check(h, level, fine, coarse, "amg_restrict"));
+  return amg_transfer(h, h->levels[(size_t)level].R, false, fine, coarse);
+}
+
+int storm_hip_amg_prolong_add(const storm_hip_amg *h, int level, const storm_hip_vec *coarse, storm_hip_vec *fine) {
+  STORM_REQUIRE(h && fine && coarse, "amg_prolong_add: null argument");
+  STORM_TRY(amg_level_check(h, level, fine, coarse, "amg_prolong_add"));
+  return amg_transfer(h, h->levels[(size_t)level].P, true, coarse, fine);
+}
+
+int storm_hip_amg_coarse_solve(const storm_hip_amg *h, const storm_hip_vec *r, storm_hip_vec *z) {
+  STORM_REQUIRE(h && r && z, "amg_coarse_solve: null argument");
+  STORM_REQUIRE(r->ctx == h->ctx && z->ctx == h->ctx, "amg_coarse_solve: context mismatch");
+  STORM_REQUIRE(z != r && z->d != r->d, "amg_coarse_solve: z must not alias r");
+  STORM_REQUIRE(r->n_owned == h->n_coarse && z->n_owned == h->n_coarse, "amg_coarse_solve: the coarsest level has %lld rows, r %lld, z %lld",
+                (long long)h->n_coarse, (long long)r->n_owned, (long long)z->n_owned);
+  HIP_TRY(hipSetDevice(h->ctx->device));
+  STORM_TRY(lazy_sync(h->ctx));
+  return amg_cycle(h, h->levels.size() - 1, r, z);
+}
+
+int storm_hip_amg_get(const storm_hip_amg *h, const char *key, double *value) {
+  STORM_REQUIRE(h && key && value, "amg_get: null argument");
+  if (!strcmp(key, "device_bytes")) *value = (double)h->device_bytes;
+  else if (!strcmp(key, "transfer_padding"))
+    *value = h->transfer_slots > 0 ? 1.0 - (double)h->transfer_nnz / (double)h->transfer_slots : 0.0;
+  else if (!strcmp(key, "upload_seconds")) *value = h->upload_seconds;
+  else if (!strcmp(key, "smoother_degree")) *value = (double)h->hier->params.smoother_degree;
+  else if (!strcmp(key, "reduced")) *value = (double)h->hier->params.reduced_records;
+  else return storm_hip_amg_hierarchy_get(h->hier, key, value);
+  return STORM_HIP_OK;
+}
+
+int storm_hip_amg_get_hierarchy(const storm_hip_amg *h, const storm_hip_amg_hierarchy **out) {
+  STORM_REQUIRE(h && out, "amg_get_hierarchy: null argument");
+  *out = h->hier;
+  return STORM_HIP_OK;
+}
+
+}  // extern "C"

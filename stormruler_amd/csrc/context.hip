@@ -238,6 +238,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *c, const char *key, int64_t value) {
   else if (!strcmp(key, "spmv_record_index")) c->opt_spmv_record_index = value;
   else if (!strcmp(key, "blas1_nt")) c->opt_blas1_nt = value;
   else if (!strcmp(key, "cheb_fused")) c->opt_cheb_fused = value;
+  else if (!strcmp(key, "amg_fused")) c->opt_amg_fused = value;
   else STORM_FAIL(STORM_HIP_E_INVALID, "ctx_set_option: unknown key '%s'", key);
   return STORM_HIP_OK;
 }
@@ -254,6 +255,9 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "cheb_fused_applies")) *value = c->n_cheb_fused_applies;
   else if (!strcmp(key, "cheb_statement_applies")) *value = c->n_cheb_statement_applies;
   else if (!strcmp(key, "cheb_reduced_applies")) *value = c->n_cheb_reduced_applies;
+  else if (!strcmp(key, "amg_applies")) *value = c->n_amg_applies;
+  else if (!strcmp(key, "amg_fused_residuals")) *value = c->n_amg_fused_residuals;
+  else if (!strcmp(key, "amg_statement_residuals")) *value = c->n_amg_statement_residuals;
   else if (!strcmp(key, "op_reduced_builds")) *value = c->n_op_reduced_builds;
   else if (!strcmp(key, "op_reduced_refreshes")) *value = c->n_op_reduced_refreshes;
   else if (!strcmp(key, "jfnk_inner_solves")) *value = c->n_jfnk_inner_solves;

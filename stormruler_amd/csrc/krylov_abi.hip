@@ -2,6 +2,7 @@
 // argument checks, the start and the end of a solve, the enqueue-ahead loop, the choice between the engine and a fused
 // kernel, JFNK's inner solve.  The statements are in krylov_engine.hip, the methods in krylov_methods.hip.
 #include "krylov_engine.hpp"
+#include "amg.hpp"
 
 using namespace storm;
 using namespace storm::kry;
@@ -28,6 +29,12 @@ int check_ready(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
     STORM_REQUIRE(k->pre_cheb->ctx == k->c, "krylov: the Chebyshev preconditioner belongs to another context");
     STORM_REQUIRE(k->pre_cheb->op->n_rows == x->n_owned, "krylov: the Chebyshev preconditioner has %lld rows, x %lld",
                   (long long)k->pre_cheb->op->n_rows, (long long)x->n_owned);
+  }
+  if (k->pre_amg) {
+    const int64_t rows = k->pre_amg->op->n_rows;
+    STORM_REQUIRE(k->pre_amg->ctx == k->c, "krylov: the multigrid preconditioner belongs to another context");
+    STORM_REQUIRE(rows == x->n_owned, "krylov: the multigrid preconditioner has %lld rows, x %lld", (long long)rows,
+                  (long long)x->n_owned);
   }
   if (op.is(Operator::FD)) {
     STORM_REQUIRE(op.x->ctx == k->c, "krylov: the finite-difference operator's vectors belong to another context");
@@ -234,7 +241,7 @@ int jfnk_outer_apply(void *user, storm_hip_vec *y, const storm_hip_vec *x) {
 int storm::kry::jfnk_inner_solve(K *o) {
   storm_hip_krylov *in = o->jf_inner;
   in->op = Operator::fd(&jfnk_outer_apply, o, o->x, o->v, 0.0, o->S + o->r_a0);
-  in->pre_fn = nullptr, in->pre_user = nullptr, in->pre_diag = nullptr, in->pre_cheb = nullptr;
+  in->pre_fn = nullptr, in->pre_user = nullptr, in->pre_diag = nullptr, in->pre_cheb = nullptr, in->pre_amg = nullptr;
   storm_hip_solver_params ip;
   storm_hip_solver_params_default(&ip);
   ip.num_iterations = 2000, ip.absolute_error_tolerance = ip.relative_error_tolerance = 1.0e-8;
@@ -382,7 +389,7 @@ int storm_hip_krylov_apply(storm_hip_krylov *k, const storm_hip_vec *y, storm_hi
 int storm_hip_krylov_set_preconditioner_fn(storm_hip_krylov *k, storm_hip_apply_fn apply, void *user, int side) {
   STORM_REQUIRE(k, "krylov_set_preconditioner_fn: null solver");
   STORM_REQUIRE(side >= STORM_HIP_LEFT && side <= STORM_HIP_SYMMETRIC, "krylov: unknown preconditioner side %d", side);
-  k->pre_fn = apply, k->pre_user = user, k->pre_diag = nullptr, k->pre_cheb = nullptr, k->side = side;
+  k->pre_fn = apply, k->pre_user = user, k->pre_diag = nullptr, k->pre_cheb = nullptr, k->pre_amg = nullptr, k->side = side;
   return STORM_HIP_OK;
 }
 
@@ -390,7 +397,7 @@ int storm_hip_krylov_set_preconditioner_diag(storm_hip_krylov *k, const storm_hi
   STORM_REQUIRE(k, "krylov_set_preconditioner_diag: null solver");
   STORM_REQUIRE(side >= STORM_HIP_LEFT && side <= STORM_HIP_SYMMETRIC, "krylov: unknown preconditioner side %d", side);
   STORM_REQUIRE(d == nullptr || d->ctx == k->c, "krylov: preconditioner diagonal belongs to another context");
-  k->pre_fn = nullptr, k->pre_user = nullptr, k->pre_diag = d, k->pre_cheb = nullptr, k->side = side;
+  k->pre_fn = nullptr, k->pre_user = nullptr, k->pre_diag = d, k->pre_cheb = nullptr, k->pre_amg = nullptr, k->side = side;
   return STORM_HIP_OK;
 }
 
@@ -398,7 +405,15 @@ int storm_hip_krylov_set_preconditioner_cheb(storm_hip_krylov *k, const storm_hi
   STORM_REQUIRE(k, "krylov_set_preconditioner_cheb: null solver");
   STORM_REQUIRE(side >= STORM_HIP_LEFT && side <= STORM_HIP_SYMMETRIC, "krylov: unknown preconditioner side %d", side);
   STORM_REQUIRE(h == nullptr || h->ctx == k->c, "krylov: the Chebyshev preconditioner belongs to another context");
-  k->pre_fn = nullptr, k->pre_user = nullptr, k->pre_diag = nullptr, k->pre_cheb = h, k->side = side;
+  k->pre_fn = nullptr, k->pre_user = nullptr, k->pre_diag = nullptr, k->pre_cheb = h, k->pre_amg = nullptr, k->side = side;
+  return STORM_HIP_OK;
+}
+
+int storm_hip_krylov_set_preconditioner_amg(storm_hip_krylov *k, const storm_hip_amg *h, int side) {
+  STORM_REQUIRE(k, "krylov_set_preconditioner_amg: null solver");
+  STORM_REQUIRE(side >= STORM_HIP_LEFT && side <= STORM_HIP_SYMMETRIC, "krylov: unknown preconditioner side %d", side);
+  STORM_REQUIRE(h == nullptr || h->ctx == k->c, "krylov: the multigrid preconditioner belongs to another context");
+  k->pre_fn = nullptr, k->pre_user = nullptr, k->pre_diag = nullptr, k->pre_cheb = nullptr, k->pre_amg = h, k->side = side;
   return STORM_HIP_OK;
 }
 

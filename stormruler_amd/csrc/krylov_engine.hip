@@ -413,6 +413,8 @@ void K::pre(V yv, const storm_hip_vec *xv) {
     st = callback_status(pre_fn(pre_user, yv, xv), "krylov: the preconditioner callback");
   } else if (pre_cheb != nullptr) {  // (its launches are predicated on api_done like a callback's)
     st = storm_hip_cheb_apply(pre_cheb, xv, yv);
+  } else if (pre_amg != nullptr) {
+    st = storm_hip_amg_apply(pre_amg, xv, yv);
   } else {
     c->stream_reverse = flip();
     st = storm_hip_vmul(yv, pre_diag, xv);

@@ -164,6 +164,7 @@ struct KrylovEngine {
   void *pre_user = nullptr;
   const storm_hip_vec *pre_diag = nullptr;
   const storm_hip_cheb *pre_cheb = nullptr;  // the library's Chebyshev preconditioner (precond_cheb.hip): storm_hip_cheb_apply, no callback
+  const storm_hip_amg *pre_amg = nullptr;    // the library's multigrid preconditioner (amg.hip): storm_hip_amg_apply, no callback
   int side = STORM_HIP_RIGHT;
   double relaxation = 1.0e-4;  // SolverRichardson.hpp:45
   // JFNK (STORM_HIP_JFNK): the inner BiCGStab engine, created with the object and reused by every Newton step
@@ -220,7 +221,7 @@ struct KrylovEngine {
       r_a4 = 0;
   int H0 = 0, B0 = 0, CS0 = 0, SN0 = 0, r_hn = 0;
 
-  bool has_pre() const { return pre_fn != nullptr || pre_diag != nullptr || pre_cheb != nullptr; }
+  bool has_pre() const { return pre_fn != nullptr || pre_diag != nullptr || pre_cheb != nullptr || pre_amg != nullptr; }
   bool left() const { return has_pre() && side == STORM_HIP_LEFT; }
   bool right() const { return has_pre() && side == STORM_HIP_RIGHT; }
   bool ok() const { return status == STORM_HIP_OK; }

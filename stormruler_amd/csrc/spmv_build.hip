@@ -115,6 +115,17 @@ static PackOptions pack_options(const storm_hip_ctx *c) {
   return o;
 }
 
+// amg.hip: a coarse-level operator from assembled CSR, forced to fp64 records (the context's ell_cap holds; no latency copy)
+int op_create_csr_fp64(storm_hip_ctx *c, int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
+                       storm_hip_op **out) {
+  *out = nullptr;
+  PackOptions o = pack_options(c);
+  o.spmv_dict = 0, o.latency_path = 0;
+  OpImage img;
+  STORM_TRY(op_pack_csr(o, n_rows, 0, row_ptr, col, val, &img));
+  return op_upload(c, std::move(img), out);
+}
+
 }  // namespace storm
 
 using namespace storm;
