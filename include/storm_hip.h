@@ -327,7 +327,8 @@ int storm_hip_op_create_from_face_weights(storm_hip_ctx *ctx, int64_t n_owned, i
  *   operator is in every respect -- apply, block apply, diagonal, Gershgorin bound, every solver -- the one a fresh create
  *   with those weights gives, bit for bit.  Objects that cached something derived from the OLD values are the caller's to
  *   rebuild: a storm_hip_cheb (its eigenvalue bounds), a storm_hip_amg (its whole hierarchy: coarse operators, transfers,
- *   smoothers' scales and bounds are those of the old weights) and a diagonal obtained earlier.  An update between
+ *   smoothers' scales and bounds are those of the old weights -- unless it was created refreshable: then
+ *   storm_hip_amg_refresh recomputes all of them on the device) and a diagonal obtained earlier.  An update between
  *   storm_hip_krylov_init and storm_hip_krylov_finalize of a solve on this operator is the caller's error.
  *   Counted by "op_face_updates" (storm_hip_ctx_get_counter).
  * storm_hip_op_cells_to_faces: at_inner[f] = cell[inner[f]], at_outer[f] = cell[outer[f]] for a cell vector of the
@@ -925,8 +926,65 @@ int storm_hip_amg_hierarchy_get_prolongator(const storm_hip_amg_hierarchy *h, in
                                             double *val);
 /* the coarsest level's inverse, row-major [n x n] */
 int storm_hip_amg_hierarchy_get_coarse_inverse(const storm_hip_amg_hierarchy *h, double *inverse);
-/* "levels", "operator_complexity" (sum of nnz(A_l) / nnz(A_0)), "grid_complexity" (sum of n_l / n_0), "setup_seconds" */
+/* "levels", "operator_complexity" (sum of nnz(A_l) / nnz(A_0)), "grid_complexity" (sum of n_l / n_0), "setup_seconds",
+ * "structural" */
 int storm_hip_amg_hierarchy_get(const storm_hip_amg_hierarchy *h, const char *key, double *value);
+/* ---- Refreshable hierarchies (STORM_HIP_HAS_AMG_REFRESH, added within ABI 6) ------------------------------------------------
+ * The split between symbolic and numeric setup: the graph work (strength, aggregation, pattern discovery) runs once on the
+ * host, the numbers are recomputed on the device whenever the operator's weights changed.
+ *
+ * STRUCTURAL SETUP.  storm_hip_amg_setup_csr_structural is THE RECIPE with one difference: no pattern depends on a value.
+ * Level 0 keeps every stored entry of the caller's CSR (duplicates merged, a zero stays); P_l lives on the pattern of
+ * T u A^F T; A_l P_l and R_l (A_l P_l) live on their structural patterns.  A zero entry is never strong, as in the recipe.
+ * Where the plain setup drops no zero the two hierarchies are equal bit for bit.  storm_hip_amg_hierarchy_get key
+ * "structural" is 1 for such a hierarchy.  storm_hip_amg_hierarchy_get_strong: the strong mask of level l, one byte per entry
+ * of A_l in the order of _get_operator (1: the pair is strong); available on plain hierarchies too, not on the coarsest level.
+ *
+ * THE FROZEN-STRUCTURE RECIPE (normative; tests/amg_refresh_ref.py restates it).  Frozen: the number of levels, the
+ * aggregates, the strong mask of every level, the patterns of A_l, P_l, R_l and of the intermediate A_l P_l.  For level l:
+ *   1. Level 0: a_ii = beta + alpha (ext_i - sum_k w_ik) and a_ij = alpha times the sum of w over the slots of column j: the
+ *      decode of storm_hip_amg_create, except that every REAL slot counts whatever its value.  A slot is real when its
+ *      source-map id is >= 0; padding (id -1) is left out.  (Hence the updatable operator: its source map says which.)
+ *   2. a^F_ii = a_ii + the sum of the entries the mask calls weak; the strong entries are kept.
+ *   3. lambda_F = max_i sum_j |a^F_ij| / |a^F_ii|.  A zero or non-finite a^F_ii: the refresh fails.
+ *   4. P_iJ = [J = agg(i)] - (omega / lambda_F) / a^F_ii sum_{j in J} a^F_ij on P's frozen pattern; omega = 0: P is not
+ *      touched.  R gets the same values, transposed.
+ *   5. A_{l+1} = R_l (A_l P_l) on the frozen patterns.  The coarse operator's records get ext_i = the row sum in column order
+ *      (as the CSR packer forms it), slots and CSR-tail entries the off-diagonal values.
+ *   6. The coarsest level's values go to the host, are inverted as in step 7 of THE RECIPE, and the inverse is uploaded.  A
+ *      singular level: the refresh fails.
+ *   7. Every level's smoother is rebuilt from the refreshed level operator: the Jacobi scale (storm_hip_op_get_diagonal),
+ *      Gershgorin's bound, the polynomial on [lmax / smoother_ratio, lmax].  With reduced_records the coarse operators'
+ *      companions are converted again first.
+ * Order of summation: inside a row of steps 2 to 4 and of A_l P_l the entries of A_l in column order; inside a row of
+ * R_l (A_l P_l) the entries of R_l in column order (fine rows ascending), each contribution A P's entries in column order;
+ * level 0 sums a column's slots in slot order, then its tail entries.  Every product is rounded before it is added.  A
+ * refresh is deterministic (the same records give the same bits) and uses no floating-point atomics.
+ *
+ * storm_hip_amg_create_refreshable: storm_hip_amg_create with the structural setup, for an operator from
+ *   storm_hip_op_create_from_face_weights_updatable (anything else: STORM_HIP_E_UNSUPPORTED).  The coarse operators carry a
+ *   source map (the id of a slot is its entry's index in A_l).  Uploaded once beside the plain object: per level A_l as CSR
+ *   (LEVEL 0 INCLUDED: the products read this copy, not the records), strong mask, aggregates, P_l as CSR, R_l's pattern,
+ *   A_l P_l as CSR, the slot -> entry maps of the transfer records and of level 0's records.  storm_hip_amg_get key
+ *   "refresh_bytes" reports this memory (it is part of "device_bytes"); "refreshable" is 1.
+ * storm_hip_amg_refresh: the recipe above on the operator's records as they stand on the context's stream.  Waits on the
+ *   host like a create: two max reductions per level (lambda_F, Gershgorin) and the coarsest level's round trip.  Not to be
+ *   called between storm_hip_krylov_init and _finalize.  A zero or non-finite filtered diagonal (found by a device-side check
+ *   that sets a flag word read at the level's wait) or a singular coarsest level: STORM_HIP_E_INVALID with level and row in
+ *   the message; the object is then INVALID -- storm_hip_amg_apply and a solve bound to it return STORM_HIP_E_INVALID -- until
+ *   a refresh succeeds.  On an object from storm_hip_amg_create: STORM_HIP_E_UNSUPPORTED.  Counter "amg_refreshes".
+ * storm_hip_amg_download: brings the object's host hierarchy (storm_hip_amg_get_hierarchy, the export calls) up to date with
+ *   what the cycle's kernels read: the level operators' records decoded as in step 1, the transfer records, the dense
+ *   inverse; the coarsest level, which has no records, from its value array.  Waits on the host.  On a plain object it changes
+ *   nothing. */
+#define STORM_HIP_HAS_AMG_REFRESH 1
+int storm_hip_amg_setup_csr_structural(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
+                                       const storm_hip_amg_params *params, storm_hip_amg_hierarchy **out);
+int storm_hip_amg_hierarchy_get_strong(const storm_hip_amg_hierarchy *h, int level, uint8_t *mask);
+int storm_hip_amg_create_refreshable(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params,
+                                     storm_hip_amg **out);
+int storm_hip_amg_refresh(storm_hip_amg *h);
+int storm_hip_amg_download(storm_hip_amg *h);
 /* The device object for an operator on fp64 records (format 0: what any mesh gets; a box built with option spmv_dict = 0;
  * a CSR tail is allowed).  The records are downloaded once and decoded to CSR: a_ii = beta + alpha (ext_i - sum_k w_ik),
  * a_ij = alpha sum w over the slots of column j, padding dropped; the setup above runs on the host; the coarse operators go
@@ -934,7 +992,8 @@ int storm_hip_amg_hierarchy_get(const storm_hip_amg_hierarchy *h, const char *ke
  * gets a companion (storm_hip_op_build_reduced: `op` too, if it has none).  Host waits (build time).
  * STORM_HIP_E_UNSUPPORTED: compact record formats; a halo plan, halo columns or a communicator.
  * `op` must outlive the object.  An object built before storm_hip_op_set_face_weights is STALE (its hierarchy and bounds are
- * those of the old weights); rebuilding it is the caller's, as for a storm_hip_cheb. */
+ * those of the old weights); rebuilding it is the caller's, as for a storm_hip_cheb -- or the object is created by
+ * storm_hip_amg_create_refreshable below and brought up to date by storm_hip_amg_refresh. */
 int storm_hip_amg_create(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params, storm_hip_amg **out);
 /* z = B r; z must not alias r, r is not written.  Enqueues and never waits; inside a solver callback predicated on the
  * solve's `done` flag. */
@@ -945,7 +1004,8 @@ int storm_hip_amg_restrict(const storm_hip_amg *h, int level, const storm_hip_ve
 int storm_hip_amg_prolong_add(const storm_hip_amg *h, int level, const storm_hip_vec *coarse, storm_hip_vec *fine);
 int storm_hip_amg_coarse_solve(const storm_hip_amg *h, const storm_hip_vec *r, storm_hip_vec *z);
 /* the keys of storm_hip_amg_hierarchy_get, and "device_bytes" (what the object allocated), "transfer_padding" (the share of
- * the transfer records' slots that is padding), "upload_seconds", "smoother_degree", "reduced" */
+ * the transfer records' slots that is padding), "upload_seconds", "smoother_degree", "reduced", "refresh_bytes",
+ * "refreshable" */
 int storm_hip_amg_get(const storm_hip_amg *h, const char *key, double *value);
 /* the object's host hierarchy, for the export calls above (borrowed: it lives as long as the object) */
 int storm_hip_amg_get_hierarchy(const storm_hip_amg *h, const storm_hip_amg_hierarchy **out);

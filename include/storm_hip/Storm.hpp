@@ -948,11 +948,14 @@ private:
 /// no reduction and no host wait inside an apply.  For symmetric operators, single rank.  `build` runs the setup on the host
 /// and uploads the hierarchy -- once: a solver calls it before every solve, and it returns at once while matrix, alpha, beta
 /// and `params` are those of the last build; the solvers bind the object natively; `mul` is storm_hip_amg_apply.  The
-/// operator it was built from must outlive it; after StencilMatrix::set_face_weights the object is stale: `reset()` it.
+/// operator it was built from must outlive it; after StencilMatrix::set_face_weights the object is stale: `reset()` it --
+/// or, if `refreshable` (set before the build; the matrix must come from from_face_weights_updatable), `refresh()` it: every
+/// number of the hierarchy is recomputed on the device on the structure the setup froze (storm_hip_amg_refresh).
 /// `params.reduced_records`: every level's smoother reads fp32-weight companion records (the matrix gets one if missing).
 class AmgPreconditioner final : public Preconditioner<DeviceVector> {
 public:
   storm_hip_amg_params params;
+  bool refreshable = false;  ///< read by build(): storm_hip_amg_create_refreshable instead of storm_hip_amg_create
 
   AmgPreconditioner() { storm_hip_amg_params_default(&params); }
   explicit AmgPreconditioner(int smoother_degree, bool reduced_records = false) : AmgPreconditioner() {
@@ -974,12 +977,20 @@ public:
         _built.strength_theta == params.strength_theta && _built.prolongator_omega == params.prolongator_omega &&
         _built.smoother_degree == params.smoother_degree && _built.smoother_ratio == params.smoother_ratio &&
         _built.max_levels == params.max_levels && _built.coarse_rows == params.coarse_rows &&
-        _built.reduced_records == params.reduced_records)
+        _built.reduced_records == params.reduced_records && _built_refreshable == refreshable)
       return;
     reset();
-    detail::check(storm_hip_amg_create(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params, &_h));
+    if (refreshable)
+      detail::check(storm_hip_amg_create_refreshable(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params, &_h));
+    else
+      detail::check(storm_hip_amg_create(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params, &_h));
     _op = hip_op->matrix().handle(), _alpha = hip_op->alpha(), _beta = hip_op->beta(), _built = params;
+    _built_refreshable = refreshable;
   }
+  /// Recompute every number of the hierarchy from the matrix's current records (a refreshable object; waits on the host).
+  void refresh() { detail::check(storm_hip_amg_refresh(_h)); }
+  /// Bring the host hierarchy (storm_hip_amg_get_hierarchy) up to date with what the cycle reads on the device.
+  void download() { detail::check(storm_hip_amg_download(_h)); }
   /// Drop the hierarchy: the next build() runs the setup again (after set_face_weights, for instance).
   void reset() noexcept {
     storm_hip_amg_destroy(_h);
@@ -1018,6 +1029,7 @@ private:
   const storm_hip_op* _op = nullptr;
   real_t _alpha = 0.0, _beta = 0.0;
   storm_hip_amg_params _built{};
+  bool _built_refreshable = false;
 };
 
 #ifndef STORM_HIP_NO_SOLVERS

@@ -211,6 +211,11 @@ SIGNATURES = {
     "storm_hip_amg_hierarchy_get_prolongator": (C.c_int, [vp, C.c_int, i64p, i64p, f64p]),
     "storm_hip_amg_hierarchy_get_coarse_inverse": (C.c_int, [vp, f64p]),
     "storm_hip_amg_hierarchy_get": (C.c_int, [vp, C.c_char_p, f64p]),
+    "storm_hip_amg_setup_csr_structural": (C.c_int, [C.c_int64, i64p, i64p, f64p, C.POINTER(AmgParams), C.POINTER(vp)]),
+    "storm_hip_amg_hierarchy_get_strong": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint8)]),
+    "storm_hip_amg_create_refreshable": (C.c_int, [vp, C.c_double, C.c_double, C.POINTER(AmgParams), C.POINTER(vp)]),
+    "storm_hip_amg_refresh": (C.c_int, [vp]),
+    "storm_hip_amg_download": (C.c_int, [vp]),
     "storm_hip_amg_create": (C.c_int, [vp, C.c_double, C.c_double, C.POINTER(AmgParams), C.POINTER(vp)]),
     "storm_hip_amg_apply": (C.c_int, [vp, vp, vp]),
     "storm_hip_amg_restrict": (C.c_int, [vp, C.c_int, vp, vp]),

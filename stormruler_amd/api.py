@@ -1017,17 +1017,20 @@ class AmgHierarchy:
         self._h, self._owned, self._keep = handle, owned, keep
 
     @classmethod
-    def from_csr(cls, a, **params) -> "AmgHierarchy":
+    def from_csr(cls, a, structural: bool = False, **params) -> "AmgHierarchy":
         """Keywords: ``strength_theta``, ``prolongator_omega``, ``smoother_degree``, ``smoother_ratio``, ``max_levels``,
-        ``coarse_rows``, ``reduced_records`` (defaults: ``storm_hip_amg_params_default``)."""
+        ``coarse_rows``, ``reduced_records`` (defaults: ``storm_hip_amg_params_default``).  ``structural``: the setup whose
+        patterns depend on no value (``storm_hip_amg_setup_csr_structural``): stored zeros of ``a`` stay, and so do entries of
+        P_l and A_{l+1} that cancel exactly."""
         a = a.tocsr()
         rp = np.ascontiguousarray(a.indptr, np.int64)
         col = np.ascontiguousarray(a.indices, np.int64)
         val = np.ascontiguousarray(a.data, np.float64)
         h = C.c_void_p()
         p = _amg_params(**params)
-        check(lib.storm_hip_amg_setup_csr(a.shape[0], rp.ctypes.data_as(_lib.i64p), col.ctypes.data_as(_lib.i64p),
-                                          val.ctypes.data_as(_lib.f64p), C.byref(p), C.byref(h)))
+        setup = lib.storm_hip_amg_setup_csr_structural if structural else lib.storm_hip_amg_setup_csr
+        check(setup(a.shape[0], rp.ctypes.data_as(_lib.i64p), col.ctypes.data_as(_lib.i64p), val.ctypes.data_as(_lib.f64p),
+                    C.byref(p), C.byref(h)))
         return cls(h)
 
     @property
@@ -1065,6 +1068,13 @@ class AmgHierarchy:
         check(lib.storm_hip_amg_hierarchy_get_aggregates(self._h, level, agg.ctypes.data_as(_lib.i64p)))
         return agg
 
+    def strong(self, level: int) -> np.ndarray:
+        """The strong mask of level ``level``: one byte per stored entry of ``operator(level)``, 1 where the pair is strong
+        (``storm_hip_amg_hierarchy_get_strong``); not on the coarsest level."""
+        mask = np.zeros(max(self.sizes(level)[1], 1), np.uint8)
+        check(lib.storm_hip_amg_hierarchy_get_strong(self._h, level, mask.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return mask[:self.sizes(level)[1]]
+
     def coarse_inverse(self) -> np.ndarray:
         n = self.sizes(self.levels - 1)[0]
         inv = np.zeros((n, n), np.float64)
@@ -1072,7 +1082,7 @@ class AmgHierarchy:
         return inv
 
     def get(self, key: str) -> float:
-        """``levels``, ``operator_complexity``, ``grid_complexity`` or ``setup_seconds``."""
+        """``levels``, ``operator_complexity``, ``grid_complexity``, ``setup_seconds`` or ``structural`` (0 or 1)."""
         v = C.c_double()
         check(lib.storm_hip_amg_hierarchy_get(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -1096,16 +1106,22 @@ class AmgPreconditioner(Preconditioner):
     host (seconds on a large mesh) and uploads the hierarchy -- once: a solver calls it before every solve, and it returns
     at once while the matrix handle, alpha, beta and the parameters are those of the last build; the solvers bind the
     object natively; :meth:`mul` is ``storm_hip_amg_apply``.  The operator it was built from must outlive it; after
-    :meth:`StencilMatrix.set_face_weights` the object is stale: :meth:`close` it, and the next build runs the setup again.  ``reduced_records``: every level's
-    smoother reads fp32-weight companion records (the matrix gets one if it has none)."""
+    :meth:`StencilMatrix.set_face_weights` the object is stale: :meth:`close` it, and the next build runs the setup again --
+    or, if ``refreshable``, :meth:`refresh` it.  ``reduced_records``: every level's smoother reads fp32-weight companion
+    records (the matrix gets one if it has none).  ``refreshable`` (``storm_hip_amg_create_refreshable``; the matrix must
+    come from ``from_face_weights_updatable``): the setup freezes aggregates, strong masks and patterns, and :meth:`refresh`
+    recomputes every number of the hierarchy on the device from the matrix's current weights; :meth:`build` keeps its
+    cache key, so the same handle and parameters mean no rebuild.  :meth:`download` brings :attr:`hierarchy` up to date."""
 
     def __init__(self, strength_theta: Optional[float] = None, prolongator_omega: Optional[float] = None,
                  smoother_degree: Optional[int] = None, smoother_ratio: Optional[float] = None,
-                 max_levels: Optional[int] = None, coarse_rows: Optional[int] = None, reduced_records: bool = False):
+                 max_levels: Optional[int] = None, coarse_rows: Optional[int] = None, reduced_records: bool = False,
+                 refreshable: bool = False):
         self.params = dict(strength_theta=strength_theta, prolongator_omega=prolongator_omega, smoother_degree=smoother_degree,
                            smoother_ratio=smoother_ratio, max_levels=max_levels, coarse_rows=coarse_rows,
                            reduced_records=int(bool(reduced_records)))
         self.reduced_records = bool(reduced_records)
+        self.refreshable = bool(refreshable)
         self._h, self._op, self.ctx, self._key = None, None, None, None
 
     def build(self, x_vec, b_vec, any_op) -> None:
@@ -1116,20 +1132,22 @@ class AmgPreconditioner(Preconditioner):
             raise TypeError("AmgPreconditioner needs a HipStencilOperator to build its hierarchy from")
         # a solver calls build() before every solve: the hierarchy is kept while operator and parameters are the same
         # (a matrix whose weights were refreshed is the same handle: close() first -- staleness is the caller's)
-        key = (x_vec.ctx, any_op.matrix._h.value, float(any_op.alpha), float(any_op.beta), tuple(sorted(self.params.items())))
+        key = (x_vec.ctx, any_op.matrix._h.value, float(any_op.alpha), float(any_op.beta), tuple(sorted(self.params.items())),
+               self.refreshable)
         if self._h is not None and self._key == key:
             return
         self._free()
         self.ctx, self._op = x_vec.ctx, any_op
         h = C.c_void_p()
         p = _amg_params(**self.params)
-        check(lib.storm_hip_amg_create(any_op.matrix._h, any_op.alpha, any_op.beta, C.byref(p), C.byref(h)))
+        create = lib.storm_hip_amg_create_refreshable if self.refreshable else lib.storm_hip_amg_create
+        check(create(any_op.matrix._h, any_op.alpha, any_op.beta, C.byref(p), C.byref(h)))
         self._h, self._key = h, key
         self.ctx._children.add(self)
 
     def get(self, key: str) -> float:
         """``levels``, ``operator_complexity``, ``grid_complexity``, ``setup_seconds``, ``upload_seconds``, ``device_bytes``,
-        ``transfer_padding``, ``smoother_degree`` or ``reduced``."""
+        ``transfer_padding``, ``smoother_degree``, ``reduced``, ``structural``, ``refreshable`` or ``refresh_bytes``."""
         v = C.c_double()
         check(lib.storm_hip_amg_get(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -1140,6 +1158,19 @@ class AmgPreconditioner(Preconditioner):
         h = C.c_void_p()
         check(lib.storm_hip_amg_get_hierarchy(self._h, C.byref(h)))
         return AmgHierarchy(h, owned=False, keep=self)
+
+    def refresh(self) -> None:
+        """Recompute every number of the hierarchy on the device from the matrix's current records
+        (``storm_hip_amg_refresh``; a ``refreshable`` object only).  Waits on the host, like a build."""
+        if self._h is None:
+            raise RuntimeError("AmgPreconditioner.refresh before build")
+        check(lib.storm_hip_amg_refresh(self._h))
+
+    def download(self) -> None:
+        """Bring :attr:`hierarchy` up to date with what the cycle reads on the device (``storm_hip_amg_download``)."""
+        if self._h is None:
+            raise RuntimeError("AmgPreconditioner.download before build")
+        check(lib.storm_hip_amg_download(self._h))
 
     def mul(self, y_vec, x_vec):
         check(lib.storm_hip_amg_apply(self._h, x_vec._h, y_vec._h))

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void amg_coarse_kernel(const double *__rest
 }
 
 int op_create_csr_fp64(storm_hip_ctx *c, int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
-                       storm_hip_op **out);  // spmv_build.hip
+                       bool source_map, storm_hip_op **out);  // spmv_build.hip
 
 static bool amg_residual_fused(const storm_hip_amg *h, const storm_hip_op *op) {
   return h->ctx->opt_amg_fused != 0 && op->pair == 0 && op->dict_size == 0 && op->offs_size == 0 && op->tail_rows == 0 &&
@@ -174,8 +174,9 @@ static int amg_cycle(const storm_hip_amg *h, size_t l, const storm_hip_vec *r, s
 
 // The operator's fp64 records (and CSR tail) as CSR of A = beta I + alpha M: a_ii = beta + alpha (ext_i - sum w_ik) over the
 // row's slots and tail entries in their order, a_ij = alpha sum w over the slots of column j; padding (weight 0) dropped.
-static int amg_decode(const storm_hip_op *op, double alpha, double beta, std::vector<int64_t> *ptr, std::vector<int64_t> *col,
-                      std::vector<double> *val) {
+// structural (an operator with a source map): a slot is real where its source id is >= 0, whatever its value.
+int amg_decode(const storm_hip_op *op, double alpha, double beta, bool structural, std::vector<int64_t> *ptr, std::vector<int64_t> *col,
+               std::vector<double> *val) {
   const int64_t n = op->n_rows, ns = op->n_slices;
   std::vector<int64_t> off((size_t)ns + 1, 0);
   HIP_TRY(hipStreamSynchronize(op->ctx->stream));
@@ -190,6 +191,12 @@ static int amg_decode(const storm_hip_op *op, double alpha, double beta, std::ve
     HIP_TRY(hipMemcpy(tptr.data(), op->d_tail_ptr, sizeof(int64_t) * tptr.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(tcol.data(), op->d_tail_col, sizeof(int) * tcol.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(tval.data(), op->d_tail_val, sizeof(double) * tval.size(), hipMemcpyDeviceToHost));
+  }
+  std::vector<int> src;
+  if (structural) {
+    STORM_REQUIRE(op->d_src != nullptr, "amg: the operator (%lld rows) has no source map", (long long)n);
+    src.resize((size_t)((off[(size_t)ns] - ns * kExtBytes) / (kSlotBytes / kWave)));
+    if (!src.empty()) HIP_TRY(hipMemcpy(src.data(), op->d_src, sizeof(int) * src.size(), hipMemcpyDeviceToHost));
   }
   std::vector<int64_t> tail_of((size_t)n, -1);
   for (int64_t t = 0; t < op->tail_rows; ++t) {
@@ -208,18 +215,19 @@ static int amg_decode(const storm_hip_op *op, double alpha, double beta, std::ve
     const double ext = reinterpret_cast<const double *>(rec)[l];
     const int *c_ = reinterpret_cast<const int *>(rec + kExtBytes);
     const double *v_ = reinterpret_cast<const double *>(rec + kExtBytes + (int64_t)W * (kWave * 4));
+    const int *s_ = structural ? src.data() + (off[(size_t)s] - s * kExtBytes) / (kSlotBytes / kWave) : nullptr;
     row.clear();
     double sum = 0.0;
     for (int k = 0; k < W; ++k) {
       const int at = (k < 2 * np2) ? ((k >> 1) * kWave + l) * 2 + (k & 1) : np2 * 2 * kWave + l;
-      if (v_[at] == 0.0) continue;
+      if (structural ? s_[at] < 0 : v_[at] == 0.0) continue;
       STORM_REQUIRE(c_[at] >= 0 && c_[at] < n, "amg_create: column %d of row %lld outside the operator", c_[at], (long long)i);
       sum += v_[at];
       row.emplace_back(c_[at], v_[at]);
     }
     if (tail_of[(size_t)i] >= 0)
       for (int64_t k = tptr[(size_t)tail_of[(size_t)i]]; k < tptr[(size_t)tail_of[(size_t)i] + 1]; ++k) {
-        if (tval[(size_t)k] == 0.0) continue;
+        if (!structural && tval[(size_t)k] == 0.0) continue;
         STORM_REQUIRE(tcol[(size_t)k] >= 0 && tcol[(size_t)k] < n, "amg_create: column %d of row %lld outside the operator",
                       tcol[(size_t)k], (long long)i);
         sum += tval[(size_t)k];
@@ -266,7 +274,7 @@ static int amg_upload_transfer(storm_hip_amg *h, const AmgCsr &M, storm_hip_amg:
   return STORM_HIP_OK;
 }
 
-static int amg_build_device(storm_hip_amg *h, storm_hip_op *op0) {
+int amg_build_device(storm_hip_amg *h, storm_hip_op *op0) {
   storm_hip_ctx *c = h->ctx;
   const storm_hip_amg_params &p = h->hier->params;
   const size_t nl = h->hier->levels.size();
@@ -285,7 +293,7 @@ static int amg_build_device(storm_hip_amg *h, storm_hip_op *op0) {
       L.op = op0, L.alpha = h->alpha, L.beta = h->beta;
     } else {
       std::vector<int64_t> col(H.A.col.begin(), H.A.col.end());
-      STORM_TRY(op_create_csr_fp64(c, L.n, H.A.ptr.data(), col.data(), H.A.val.data(), &L.own_op));
+      STORM_TRY(op_create_csr_fp64(c, L.n, H.A.ptr.data(), col.data(), H.A.val.data(), h->hier->structural, &L.own_op));
       L.op = L.own_op, L.alpha = 1.0, L.beta = 0.0;
       h->device_bytes += L.own_op->device_bytes;
     }
@@ -314,6 +322,19 @@ static int amg_build_device(storm_hip_amg *h, storm_hip_op *op0) {
   return STORM_HIP_OK;
 }
 
+int amg_create_checks(const storm_hip_op *op, double alpha, double beta, const char *who) {
+  STORM_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "%s: alpha and beta must be finite", who);
+  if (op->pair != 0 || op->dict_size > 0 || op->offs_size > 0 || op->d_bnd_pack != nullptr)
+    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "%s: the operator is on compact records (a value / offset dictionary, paired rows "
+                                        "or a mixed operator); the multigrid preconditioner reads fp64 records (what any mesh "
+                                        "gets; a box built with option spmv_dict = 0)", who);
+  if (op->halo.n_nbrs > 0 || op->n_halo > 0 || op->ctx->comm != nullptr)
+    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "%s: the multigrid preconditioner is single-rank (the operator has a halo plan or "
+                                        "halo columns, or the context a communicator)", who);
+  STORM_REQUIRE(op->n_rows >= 1, "%s: the operator has no rows", who);
+  return STORM_HIP_OK;
+}
+
 }  // namespace storm
 
 using namespace storm;
@@ -323,21 +344,13 @@ extern "C" {
 int storm_hip_amg_create(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params, storm_hip_amg **out) {
   STORM_REQUIRE(op && out, "amg_create: null argument");
   *out = nullptr;
-  STORM_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "amg_create: alpha and beta must be finite");
-  if (op->pair != 0 || op->dict_size > 0 || op->offs_size > 0 || op->d_bnd_pack != nullptr)
-    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "amg_create: the operator is on compact records (a value / offset dictionary, paired rows "
-                                        "or a mixed operator); the multigrid preconditioner reads fp64 records (what any mesh "
-                                        "gets; a box built with option spmv_dict = 0)");
-  if (op->halo.n_nbrs > 0 || op->n_halo > 0 || op->ctx->comm != nullptr)
-    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "amg_create: the multigrid preconditioner is single-rank (the operator has a halo plan or "
-                                        "halo columns, or the context a communicator)");
-  STORM_REQUIRE(op->n_rows >= 1, "amg_create: the operator has no rows");
+  STORM_TRY(amg_create_checks(op, alpha, beta, "amg_create"));
   storm_hip_ctx *c = op->ctx;
   HIP_TRY(hipSetDevice(c->device));
   STORM_TRY(lazy_sync(c));
   std::vector<int64_t> ptr, col;
   std::vector<double> val;
-  STORM_TRY(amg_decode(op, alpha, beta, &ptr, &col, &val));
+  STORM_TRY(amg_decode(op, alpha, beta, false, &ptr, &col, &val));
   storm_hip_amg_hierarchy *hier = nullptr;
   STORM_TRY(storm_hip_amg_setup_csr(op->n_rows, ptr.data(), col.data(), val.data(), params, &hier));
   storm_hip_amg *h = new storm_hip_amg();
@@ -363,6 +376,7 @@ int storm_hip_amg_destroy(storm_hip_amg *h) {
     (void)storm_hip_op_destroy(L.own_op);
   }
   (void)hipFree(h->d_ainv);
+  amg_refresh_free(h);
   (void)storm_hip_amg_hierarchy_destroy(h->hier);
   delete h;
   return STORM_HIP_OK;
@@ -374,6 +388,7 @@ int storm_hip_amg_apply(const storm_hip_amg *h, const storm_hip_vec *r, storm_hi
   STORM_REQUIRE(z != r && z->d != r->d, "amg_apply: z must not alias r");
   STORM_REQUIRE(r->n_owned == h->op->n_rows && z->n_owned == h->op->n_rows, "amg_apply: operator has %lld rows, r %lld, z %lld",
                 (long long)h->op->n_rows, (long long)r->n_owned, (long long)z->n_owned);
+  STORM_REQUIRE(!h->invalid, "amg_apply: the last storm_hip_amg_refresh of this object failed; it is invalid until one succeeds");
   storm_hip_ctx *c = h->ctx;
   HIP_TRY(hipSetDevice(c->device));
   STORM_TRY(lazy_sync(c));
@@ -429,6 +444,8 @@ int storm_hip_amg_get(const storm_hip_amg *h, const char *key, double *value) {
   else if (!strcmp(key, "transfer_padding"))
     *value = h->transfer_slots > 0 ? 1.0 - (double)h->transfer_nnz / (double)h->transfer_slots : 0.0;
   else if (!strcmp(key, "upload_seconds")) *value = h->upload_seconds;
+  else if (!strcmp(key, "refresh_bytes")) *value = (double)h->refresh_bytes;
+  else if (!strcmp(key, "refreshable")) *value = h->refresh.empty() ? 0.0 : 1.0;
   else if (!strcmp(key, "smoother_degree")) *value = (double)h->hier->params.smoother_degree;
   else if (!strcmp(key, "reduced")) *value = (double)h->hier->params.reduced_records;
   else return storm_hip_amg_hierarchy_get(h->hier, key, value);

@@ -21,6 +21,7 @@ struct AmgHostLevel {
   std::vector<int> agg;  // aggregate of every row (empty on the coarsest level)
   int64_t n_agg = 0;
   AmgCsr P, R;           // prolongator to this level from the next, and its explicit transpose
+  std::vector<uint8_t> strong;  // one byte per entry of A.col: 1 where the pair is strong (empty on the coarsest level)
 };
 
 constexpr int kAmgMaxCoarse = 1024;  // rows of a dense coarsest level
@@ -33,6 +34,17 @@ struct AmgTransferImage {
   std::vector<char> pack;
 };
 int amg_pack_transfer(const AmgCsr &T, AmgTransferImage *img);
+int amg_dense_inverse(const AmgCsr &A, std::vector<double> *inv_out);  // step 7 (amg_setup.hip)
+
+// What a refresh of level l needs beside the structural hierarchy, built once on the host (amg_setup.hip, no device):
+// r_of[k]: the entry of P_l that entry k of R_l = P_l^T carries; p_slot / r_slot: for every slot of the transfer records of
+// P_l / R_l (slot k x 64 + lane behind the slots of the slices before) the entry of P_l it carries, -1 for padding; AP: the
+// structural pattern of A_l P_l.
+struct AmgRefreshMaps {
+  std::vector<int> r_of, p_slot, r_slot;
+  AmgCsr AP;
+};
+int amg_refresh_maps(const storm_hip_amg_hierarchy &h, size_t l, AmgRefreshMaps *m);
 
 }  // namespace storm
 
@@ -41,6 +53,7 @@ struct storm_hip_amg_hierarchy {
   std::vector<storm::AmgHostLevel> levels;
   std::vector<double> ainv;  // the coarsest level's inverse, row-major
   double setup_seconds = 0.0;
+  bool structural = false;  // storm_hip_amg_setup_csr_structural: no pattern depends on a value
 };
 
 struct storm_hip_amg {
@@ -69,4 +82,43 @@ struct storm_hip_amg {
   int64_t n_coarse = 0;
   int64_t device_bytes = 0, transfer_slots = 0, transfer_nnz = 0;
   double upload_seconds = 0.0;
+  // storm_hip_amg_create_refreshable (amg_refresh.hip): per level the frozen structure and the value arrays of a refresh.
+  // All of it is counted in refresh_bytes (and in device_bytes).
+  struct RefreshLevel {
+    int64_t n = 0, nnz_a = 0, nnz_p = 0, nnz_ap = 0, p_slots = 0, r_slots = 0;
+    int64_t *d_a_ptr = nullptr;   // A_l as CSR: [n + 1], [nnz_a], [nnz_a]; the strong mask [nnz_a]; the diagonal's entry [n]
+    int *d_a_col = nullptr;
+    double *d_a_val = nullptr;
+    uint8_t *d_strong = nullptr;
+    int *d_a_diag = nullptr;
+    int *d_agg = nullptr;         // [n]
+    double *d_df = nullptr;       // [n] the filtered diagonal
+    double *d_wave_max = nullptr; // [slices of n] the wavefronts' maxima of the ratio
+    int64_t *d_p_ptr = nullptr;   // P_l as CSR
+    int *d_p_col = nullptr;
+    double *d_p_val = nullptr;
+    int64_t *d_r_ptr = nullptr;   // R_l's pattern and the entry of P_l behind each of its entries
+    int *d_r_col = nullptr, *d_r_of = nullptr;
+    int64_t *d_ap_ptr = nullptr;  // A_l P_l
+    int *d_ap_col = nullptr;
+    double *d_ap_val = nullptr;
+    int *d_p_slot = nullptr, *d_r_slot = nullptr;  // the transfer records' slot -> entry of P_l maps
+    // level 0: the records' slot -> entry of A_0 maps (-1: padding, -2: a real slot on the row's own column) and the row ->
+    // tail row map (null without a CSR tail)
+    int *d_slot_ent = nullptr, *d_tail_ent = nullptr, *d_tail_of = nullptr;
+  };
+  std::vector<RefreshLevel> refresh;  // empty: a plain object
+  int64_t refresh_bytes = 0;
+  double *d_scalars = nullptr;  // [0]: the folded maximum of a level's ratio
+  int *d_bad = nullptr;         // the lowest row whose filtered diagonal is zero or non-finite (INT32_MAX: none)
+  int invalid = 0;              // a refresh failed: apply and solves return STORM_HIP_E_INVALID until one succeeds
 };
+
+namespace storm {
+// amg.hip, shared with amg_refresh.hip
+int amg_decode(const storm_hip_op *op, double alpha, double beta, bool structural, std::vector<int64_t> *ptr, std::vector<int64_t> *col,
+               std::vector<double> *val);
+int amg_build_device(storm_hip_amg *h, storm_hip_op *op0);
+int amg_create_checks(const storm_hip_op *op, double alpha, double beta, const char *who);
+void amg_refresh_free(storm_hip_amg *h);  // amg_refresh.hip
+}  // namespace storm

@@ -42,9 +42,9 @@ static AmgCsr amg_transpose(const AmgCsr &A) {
   return T;
 }
 
-// The caller's CSR as a level operator: columns sorted, duplicates summed in their order, exact zeros dropped, the
-// diagonal kept even where it is zero.
-static int amg_normalise(int64_t n, const int64_t *row_ptr, const int64_t *col, const double *val, AmgCsr *out) {
+// The caller's CSR as a level operator: columns sorted, duplicates summed in their order, exact zeros dropped (structural:
+// kept -- every stored entry stays), the diagonal kept even where it is zero.
+static int amg_normalise(int64_t n, const int64_t *row_ptr, const int64_t *col, const double *val, bool structural, AmgCsr *out) {
   STORM_REQUIRE(n >= 1 && n < (int64_t)INT32_MAX, "amg_setup: %lld rows (1 .. 2^31 - 2)", (long long)n);
   STORM_REQUIRE(row_ptr[0] == 0, "amg_setup: row_ptr[0] != 0");
   AmgCsr A;
@@ -68,7 +68,7 @@ static int amg_normalise(int64_t n, const int64_t *row_ptr, const int64_t *col, 
       for (; e < row.size() && row[e].first == row[k].first; ++e) s += row[e].second;
       if (row[k].first == i) diag = true;
       if (!diag && row[k].first > i) A.col.push_back((int)i), A.val.push_back(0.0), diag = true;
-      if (s != 0.0 || row[k].first == i) A.col.push_back(row[k].first), A.val.push_back(s);
+      if (structural || s != 0.0 || row[k].first == i) A.col.push_back(row[k].first), A.val.push_back(s);
       k = e;
     }
     if (!diag) A.col.push_back((int)i), A.val.push_back(0.0);
@@ -147,13 +147,15 @@ static int64_t amg_aggregate(const AmgStrong &S, int64_t n, std::vector<int> *ag
   return n_agg;
 }
 
-// Steps 3 and 4: P = T - (omega / lambda_F) D_F^-1 A^F T, row by row.
+// Steps 3 and 4: P = T - (omega / lambda_F) D_F^-1 A^F T, row by row.  structural: an entry that comes out zero stays, so
+// that P lives on the pattern of T u A^F T whatever the values.  strong_out: the strong mask, one byte per entry of A.col.
 static int amg_prolongator(const AmgCsr &A, const AmgStrong &S, const std::vector<int> &agg, int64_t n_agg, double omega,
-                           AmgCsr *P_out) {
+                           bool structural, AmgCsr *P_out, std::vector<uint8_t> *strong_out) {
   const int64_t n = A.n_rows;
   // a^F: the row's strong entries and the diagonal plus its weak ones, on A's own pattern (weak slots marked)
   std::vector<double> dF((size_t)n, 0.0);
-  std::vector<char> keep(A.col.size(), 0);
+  std::vector<uint8_t> &keep = *strong_out;
+  keep.assign(A.col.size(), 0);
   std::vector<double> ratio((size_t)n, 0.0);
   int64_t bad_row = -1;
   for (int64_t i = 0; i < n; ++i) {
@@ -209,7 +211,7 @@ static int amg_prolongator(const AmgCsr &A, const AmgStrong &S, const std::vecto
       auto &row = rows[(size_t)i];
       for (const auto &a : acc) {
         const double p = (a.first == agg[(size_t)i] ? 1.0 : 0.0) - f * a.second;
-        if (p != 0.0) row.emplace_back(a.first, p);
+        if (structural || p != 0.0) row.emplace_back(a.first, p);
       }
       std::sort(row.begin(), row.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
     }
@@ -223,8 +225,8 @@ static int amg_prolongator(const AmgCsr &A, const AmgStrong &S, const std::vecto
 }
 
 // C = X Y by rows (Gustavson): every row accumulates in the order of X's entries; columns sorted; exact zeros dropped;
-// with keep_diag the diagonal stays even where it is zero.
-static AmgCsr amg_spgemm(const AmgCsr &X, const AmgCsr &Y, bool keep_diag) {
+// with keep_diag the diagonal stays even where it is zero; structural: every entry a product reaches stays.
+static AmgCsr amg_spgemm(const AmgCsr &X, const AmgCsr &Y, bool keep_diag, bool structural) {
   const int64_t n = X.n_rows, m = Y.n_cols;
   std::vector<std::vector<std::pair<int, double>>> rows((size_t)n);
   amg_parallel_rows(n, [&](int64_t r0, int64_t r1) {
@@ -246,7 +248,7 @@ static AmgCsr amg_spgemm(const AmgCsr &X, const AmgCsr &Y, bool keep_diag) {
       std::sort(cols.begin(), cols.end());
       auto &row = rows[(size_t)i];
       for (int cidx : cols)
-        if (acc[(size_t)cidx] != 0.0 || (keep_diag && cidx == i)) row.emplace_back(cidx, acc[(size_t)cidx]);
+        if (structural || acc[(size_t)cidx] != 0.0 || (keep_diag && cidx == i)) row.emplace_back(cidx, acc[(size_t)cidx]);
     }
   });
   AmgCsr Cm;
@@ -260,7 +262,7 @@ static AmgCsr amg_spgemm(const AmgCsr &X, const AmgCsr &Y, bool keep_diag) {
 }
 
 // Step 7: Gauss-Jordan with partial pivoting on [A | I].
-static int amg_dense_inverse(const AmgCsr &A, std::vector<double> *inv_out) {
+int amg_dense_inverse(const AmgCsr &A, std::vector<double> *inv_out) {
   const int64_t n = A.n_rows;
   std::vector<double> a((size_t)(n * n), 0.0), b((size_t)(n * n), 0.0);
   for (int64_t i = 0; i < n; ++i) {
@@ -337,10 +339,10 @@ static int amg_build(storm_hip_amg_hierarchy *h) {
                  (long long)n, kAmgMaxCoarse, amg_sizes(*h).c_str());
     }
     L.agg = std::move(agg), L.n_agg = n_agg;
-    STORM_TRY(amg_prolongator(L.A, S, L.agg, n_agg, p.prolongator_omega, &L.P));
+    STORM_TRY(amg_prolongator(L.A, S, L.agg, n_agg, p.prolongator_omega, h->structural, &L.P, &L.strong));
     L.R = amg_transpose(L.P);
     AmgHostLevel next;
-    next.A = amg_spgemm(L.R, amg_spgemm(L.A, L.P, false), true);
+    next.A = amg_spgemm(L.R, amg_spgemm(L.A, L.P, false, h->structural), true, h->structural);
     h->levels.push_back(std::move(next));  // (invalidates L)
   }
   return amg_dense_inverse(h->levels.back().A, &h->ainv);
@@ -380,6 +382,57 @@ static int amg_export_csr(const AmgCsr &M, int64_t *row_ptr, int64_t *col, doubl
   return STORM_HIP_OK;
 }
 
+// The host half of storm_hip_amg_create_refreshable: what a refresh needs beside the hierarchy (amg.hpp).  Host code only.
+int amg_refresh_maps(const storm_hip_amg_hierarchy &h, size_t l, AmgRefreshMaps *m) {
+  STORM_REQUIRE(l + 1 < h.levels.size(), "amg_refresh_maps: level %d has no transfer", (int)l);
+  const AmgHostLevel &L = h.levels[l];
+  const AmgCsr &A = L.A, &P = L.P, &R = L.R;
+  STORM_REQUIRE(L.strong.size() == A.col.size() && (int64_t)L.agg.size() == A.n_rows, "amg_refresh_maps: level %d is incomplete", (int)l);
+  STORM_REQUIRE(A.nnz() < (int64_t)INT32_MAX && P.nnz() < (int64_t)INT32_MAX, "amg_refresh_maps: more than 2^31 - 2 entries on level %d", (int)l);
+  // R_l = P_l^T: entry k of R (coarse row I, fine row i) is entry r_of[k] of P -- the walk of amg_transpose
+  m->r_of.assign(R.col.size(), 0);
+  std::vector<int64_t> at(R.ptr.begin(), R.ptr.end() - 1);
+  for (int64_t i = 0; i < P.n_rows; ++i)
+    for (int64_t k = P.ptr[(size_t)i]; k < P.ptr[(size_t)i + 1]; ++k) m->r_of[(size_t)at[(size_t)P.col[(size_t)k]]++] = (int)k;
+  for (int64_t I = 0; I < R.n_rows; ++I)
+    for (int64_t k = R.ptr[(size_t)I]; k < R.ptr[(size_t)I + 1]; ++k)
+      STORM_REQUIRE(P.col[(size_t)m->r_of[(size_t)k]] == I && R.col[(size_t)k] >= 0 && R.col[(size_t)k] < P.n_rows,
+                    "amg_refresh_maps: R_%d is not the transpose of P_%d", (int)l, (int)l);
+  // the slot -> entry maps of the transfer records (amg_pack_transfer's slot k x 64 + lane behind the slices before)
+  const AmgCsr *T[2] = {&P, &R};
+  std::vector<int> *slot[2] = {&m->p_slot, &m->r_slot};
+  for (int t = 0; t < 2; ++t) {
+    const AmgCsr &M = *T[t];
+    const int64_t ns = (M.n_rows + kWave - 1) / kWave;
+    int64_t total = 0;
+    std::vector<int64_t> first((size_t)ns + 1, 0);
+    for (int64_t s = 0; s < ns; ++s) {
+      int64_t w = 0;
+      for (int64_t i = s * kWave; i < std::min<int64_t>(M.n_rows, (s + 1) * kWave); ++i) w = std::max(w, M.ptr[(size_t)i + 1] - M.ptr[(size_t)i]);
+      total += w * kWave, first[(size_t)s + 1] = total;
+    }
+    slot[t]->assign((size_t)total, -1);
+    for (int64_t i = 0; i < M.n_rows; ++i) {
+      const int64_t s = i / kWave, lane = i % kWave;
+      for (int64_t k = M.ptr[(size_t)i], q = 0; k < M.ptr[(size_t)i + 1]; ++k, ++q)
+        (*slot[t])[(size_t)(first[(size_t)s] + q * kWave + lane)] = t == 0 ? (int)k : m->r_of[(size_t)k];
+    }
+  }
+  // A_l P_l on its structural pattern (values are the device's to fill)
+  m->AP = amg_spgemm(A, P, false, true);
+  STORM_REQUIRE(m->AP.nnz() < (int64_t)INT32_MAX, "amg_refresh_maps: more than 2^31 - 2 entries in A_%d P_%d", (int)l, (int)l);
+  // every contribution of R (A P) must find its column in the frozen A_{l+1}
+  const AmgCsr &N = h.levels[l + 1].A;
+  for (int64_t I = 0; I < R.n_rows; ++I)
+    for (int64_t k = R.ptr[(size_t)I]; k < R.ptr[(size_t)I + 1]; ++k) {
+      const int64_t i = R.col[(size_t)k];
+      for (int64_t q = m->AP.ptr[(size_t)i]; q < m->AP.ptr[(size_t)i + 1]; ++q)
+        STORM_REQUIRE(std::binary_search(N.col.begin() + N.ptr[(size_t)I], N.col.begin() + N.ptr[(size_t)I + 1], m->AP.col[(size_t)q]),
+                      "amg_refresh_maps: A_%d is not on the structural pattern of R (A P)", (int)l + 1);
+    }
+  return STORM_HIP_OK;
+}
+
 }  // namespace storm
 
 using namespace storm;
@@ -392,8 +445,8 @@ void storm_hip_amg_params_default(storm_hip_amg_params *p) {
   p->max_levels = 10, p->coarse_rows = 512, p->reduced_records = 0;
 }
 
-int storm_hip_amg_setup_csr(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
-                            const storm_hip_amg_params *params, storm_hip_amg_hierarchy **out) {
+static int amg_setup(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
+                     const storm_hip_amg_params *params, bool structural, storm_hip_amg_hierarchy **out) {
   STORM_REQUIRE(row_ptr && out && (n_rows < 1 || row_ptr[n_rows] == 0 || (col && val)), "amg_setup: null argument");
   *out = nullptr;
   storm_hip_amg_params p;
@@ -402,9 +455,9 @@ int storm_hip_amg_setup_csr(int64_t n_rows, const int64_t *row_ptr, const int64_
   STORM_TRY(amg_check_params(&p, "amg_setup"));
   const auto t0 = std::chrono::steady_clock::now();
   auto *h = new storm_hip_amg_hierarchy();
-  h->params = p;
+  h->params = p, h->structural = structural;
   h->levels.emplace_back();
-  int st = amg_normalise(n_rows, row_ptr, col, val, &h->levels[0].A);
+  int st = amg_normalise(n_rows, row_ptr, col, val, structural, &h->levels[0].A);
   if (st == STORM_HIP_OK) st = amg_build(h);
   if (st != STORM_HIP_OK) {
     delete h;
@@ -412,6 +465,25 @@ int storm_hip_amg_setup_csr(int64_t n_rows, const int64_t *row_ptr, const int64_
   }
   h->setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   *out = h;
+  return STORM_HIP_OK;
+}
+
+int storm_hip_amg_setup_csr(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
+                            const storm_hip_amg_params *params, storm_hip_amg_hierarchy **out) {
+  return amg_setup(n_rows, row_ptr, col, val, params, false, out);
+}
+
+int storm_hip_amg_setup_csr_structural(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
+                                       const storm_hip_amg_params *params, storm_hip_amg_hierarchy **out) {
+  return amg_setup(n_rows, row_ptr, col, val, params, true, out);
+}
+
+int storm_hip_amg_hierarchy_get_strong(const storm_hip_amg_hierarchy *h, int level, uint8_t *mask) {
+  STORM_REQUIRE(h && mask, "amg_hierarchy_get_strong: null argument");
+  STORM_REQUIRE(level >= 0 && level + 1 < (int)h->levels.size(), "amg_hierarchy_get_strong: level %d has no strong mask (%d levels)",
+                level, (int)h->levels.size());
+  const auto &m = h->levels[(size_t)level].strong;
+  if (!m.empty()) std::memcpy(mask, m.data(), m.size());
   return STORM_HIP_OK;
 }
 
@@ -471,6 +543,7 @@ int storm_hip_amg_hierarchy_get(const storm_hip_amg_hierarchy *h, const char *ke
   else if (!strcmp(key, "operator_complexity")) *value = nnz / (double)h->levels[0].A.nnz();
   else if (!strcmp(key, "grid_complexity")) *value = rows / (double)h->levels[0].A.n_rows;
   else if (!strcmp(key, "setup_seconds")) *value = h->setup_seconds;
+  else if (!strcmp(key, "structural")) *value = h->structural ? 1.0 : 0.0;
   else STORM_FAIL(STORM_HIP_E_INVALID, "amg_hierarchy_get: unknown key '%s'", key);
   return STORM_HIP_OK;
 }

@@ -258,6 +258,7 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "amg_applies")) *value = c->n_amg_applies;
   else if (!strcmp(key, "amg_fused_residuals")) *value = c->n_amg_fused_residuals;
   else if (!strcmp(key, "amg_statement_residuals")) *value = c->n_amg_statement_residuals;
+  else if (!strcmp(key, "amg_refreshes")) *value = c->n_amg_refreshes;
   else if (!strcmp(key, "op_reduced_builds")) *value = c->n_op_reduced_builds;
   else if (!strcmp(key, "op_reduced_refreshes")) *value = c->n_op_reduced_refreshes;
   else if (!strcmp(key, "jfnk_inner_solves")) *value = c->n_jfnk_inner_solves;

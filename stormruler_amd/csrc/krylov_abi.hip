@@ -35,6 +35,8 @@ int check_ready(K *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_
     STORM_REQUIRE(k->pre_amg->ctx == k->c, "krylov: the multigrid preconditioner belongs to another context");
     STORM_REQUIRE(rows == x->n_owned, "krylov: the multigrid preconditioner has %lld rows, x %lld", (long long)rows,
                   (long long)x->n_owned);
+    STORM_REQUIRE(!k->pre_amg->invalid, "krylov: the last storm_hip_amg_refresh of the multigrid preconditioner failed; it is "
+                                        "invalid until one succeeds");
   }
   if (op.is(Operator::FD)) {
     STORM_REQUIRE(op.x->ctx == k->c, "krylov: the finite-difference operator's vectors belong to another context");

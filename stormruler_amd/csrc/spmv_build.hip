@@ -116,14 +116,39 @@ static PackOptions pack_options(const storm_hip_ctx *c) {
 }
 
 // amg.hip: a coarse-level operator from assembled CSR, forced to fp64 records (the context's ell_cap holds; no latency copy)
+// source_map (amg_refresh.hip): the records carry a source map whose id is the CSR entry's index (off-diagonal entries; the
+// diagonal is in ext), so that they can be rewritten from a value array; the packing is op_pack_csr's.
 int op_create_csr_fp64(storm_hip_ctx *c, int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
-                       storm_hip_op **out) {
+                       bool source_map, storm_hip_op **out) {
   *out = nullptr;
   PackOptions o = pack_options(c);
   o.spmv_dict = 0, o.latency_path = 0;
   OpImage img;
-  STORM_TRY(op_pack_csr(o, n_rows, 0, row_ptr, col, val, &img));
-  return op_upload(c, std::move(img), out);
+  if (!source_map) {
+    STORM_TRY(op_pack_csr(o, n_rows, 0, row_ptr, col, val, &img));
+    return op_upload(c, std::move(img), out);
+  }
+  STORM_REQUIRE(n_rows >= 0 && row_ptr[n_rows] < (int64_t)INT32_MAX, "amg: a level operator of %lld entries exceeds int32 source ids",
+                (long long)row_ptr[n_rows]);
+  std::vector<int64_t> rp((size_t)n_rows + 1, 0);
+  std::vector<int> oc, src;
+  std::vector<double> ov, ext((size_t)n_rows, 0.0);
+  for (int64_t i = 0; i < n_rows; ++i) {
+    double rowsum = 0.0;
+    for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
+      STORM_REQUIRE(col[k] >= 0 && col[k] < n_rows, "amg: column %lld of row %lld outside [0, %lld)", (long long)col[k], (long long)i,
+                    (long long)n_rows);
+      rowsum += val[k];
+      if (col[k] != i) oc.push_back((int)col[k]), ov.push_back(val[k]), src.push_back((int)k);
+    }
+    ext[(size_t)i] = rowsum;
+    rp[(size_t)i + 1] = (int64_t)oc.size();
+  }
+  STORM_TRY(op_pack(o, n_rows, 0, rp, oc, ov, ext, &img, &src));
+  img.updatable = 1, img.n_faces = 0;  // (uploads the source map; no face lists)
+  STORM_TRY(op_upload(c, std::move(img), out));
+  (*out)->updatable = 0;  // not a face-weight operator: storm_hip_op_set_face_weights must refuse it
+  return STORM_HIP_OK;
 }
 
 }  // namespace storm
