@@ -274,6 +274,7 @@ struct storm_hip_ctx {
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_cg_pz_consumer_folds = 0;  // ... of those, the solves whose plane march folded <p,z> itself (option cg_pz_fold)
   int64_t n_mgs_chain_steps = 0, n_mgs_quad_steps = 0;  // Gram-Schmidt steps run as a chain kernel (mgs_chain.hip); ... as mgs_chain_quad_kernel
+  int64_t n_mgs_lds_steps = 0;                          // ... as mgs_chain_lds_kernel (the rest: the register chain)
   // communicator
   storm::Comm *comm = nullptr;
   int n_ranks = 1, rank = 0;

@@ -269,6 +269,7 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "cg_pz_consumer_folds")) *value = c->n_cg_pz_consumer_folds;
   else if (!strcmp(key, "mgs_chain_steps")) *value = c->n_mgs_chain_steps;
   else if (!strcmp(key, "mgs_quad_steps")) *value = c->n_mgs_quad_steps;
+  else if (!strcmp(key, "mgs_lds_steps")) *value = c->n_mgs_lds_steps;
   else if (!strcmp(key, "lazy_fused_dots")) *value = c->n_lazy_fused_dots;
   else if (!strcmp(key, "lazy_fused_pairs")) *value = c->n_lazy_fused_pairs;
   else if (!strcmp(key, "lazy_apply_dots")) *value = c->n_lazy_apply_dots;

@@ -619,6 +619,7 @@ struct MgsChoice {
   int64_t blocks = 0;
   size_t dyn_lds = 0;
   bool quad = false;        // mgs_chain_quad_kernel: its slots, its step counter
+  bool lds = false;         // mgs_chain_lds_kernel: its step counter
   bool with_apply = false;  // ... which forms w = beta x + alpha M(x) itself
   bool laps = false;        // the kernel records its phases (option resident_profile): every one but the register chain
   int pairs = 0;            // the register chain: two steps per synchronisation point
@@ -669,7 +670,7 @@ static MgsChoice mgs_choose(storm_hip_ctx *c, int64_t n, const double *qk, const
     const void *lf = sv == 1 ? (const void *)mgs_chain_lds_kernel<1> : sv == 2 ? (const void *)mgs_chain_lds_kernel<2> : (const void *)mgs_chain_lds_kernel<4>;
     const size_t ring = sizeof(double) * 2 * (size_t)sv * kMgsSub;
     if (occupancy_cached(c, lf, kLatBlock, ring) >= 1) {
-      ch.fn = lf, ch.blocks = (subs_total + sv - 1) / sv, ch.dyn_lds = ring, ch.laps = true;
+      ch.fn = lf, ch.blocks = (subs_total + sv - 1) / sv, ch.dyn_lds = ring, ch.laps = ch.lds = true;
       return ch;
     }
   }
@@ -741,7 +742,7 @@ int gmres_mgs_chain_coop(storm_hip_ctx *c, int64_t n, const int *done, double *w
   void *args[] = {&a};
   *taken = coop_launch(c, ch.fn, (unsigned)ch.blocks, args, ch.dyn_lds, ch.threads);
   if (!*taken) c->lat_seq -= (unsigned long long)k + 2;
-  else ++c->n_mgs_chain_steps, c->n_mgs_quad_steps += ch.quad;
+  else ++c->n_mgs_chain_steps, c->n_mgs_quad_steps += ch.quad, c->n_mgs_lds_steps += ch.lds;
   if (applied) *applied = formed || (*taken && ch.with_apply);
   return STORM_HIP_OK;
 }

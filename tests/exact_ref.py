@@ -14,6 +14,15 @@ are restated from the reference's headers on coefficient columns over the intege
 high-precision decimals (``Space`` and the method functions); ``Pins`` turns their exact histories into the values and
 tolerances the tests assert.
 
+GMRES(m) beyond its first step is pinned on a NON-symmetric integer operator -- convection-diffusion on the unit box
+(``convdiff_box``, ``IntOperator``): on the symmetric Poisson box H is tridiagonal, the projections on q_0 ... q_{k-2}
+are rounding noise, and a Gram-Schmidt kernel that skipped them could not be told from a correct one.  ``OpBasis`` is
+the chain of a general integer operator (no Hankel shortcut in its Gram matrix), ``gmres`` the restatement of
+SolverGmres.hpp with its inner_finalize, ``GmresPins`` the pins of history[0..K] and of x_K (``true_residual``), with a
+precision guard: the power basis loses digits with K, so every pinned case is run at PREC and at 2 PREC digits and must
+agree to 1e-40, and K stays at 12 or below.  ``mgs_float64`` is the same step in fp64 numpy, with the grouped evaluation
+of the device's chain kernels and with the defects the pins must reject.
+
 Plain module, not a conftest: the tests import it by name.
 """
 import math
@@ -336,6 +345,98 @@ class Basis:
         return Fraction(int(u[-1]), d)
 
 
+class IntOperator:
+    """A square integer matrix held as CSR, applied exactly: int64 vectors while no partial sum can wrap (asserted
+    from the largest row sum of |A|, as ``int_apply`` does), object vectors (Python ints, Fractions, decimals)
+    without a limit.  ``from_face_weights`` assembles the device operator's difference form
+    ``(A x)_i = sum_f w_if (x_other - x_i) + diag_extra_i x_i`` of a face graph -- what
+    ``StencilMatrix.from_face_weights`` applies with alpha = 1, beta = 0 -- and asserts that every weight is an
+    integer (true of ``mesh.convection_diffusion_weights`` on unit spacing with integer nu and velocity)."""
+
+    def __init__(self, n, rows, cols, vals):
+        import scipy.sparse as sps
+
+        vals = np.asarray(vals)
+        assert np.array_equal(vals, np.rint(vals)), "the operator is not integer"
+        a = sps.coo_matrix((vals.astype(np.int64), (rows, cols)), shape=(n, n)).tocsr()
+        a.sum_duplicates()
+        a.eliminate_zeros()
+        a.sort_indices()
+        self.n, self.csr = n, a
+        self.rowsum = int(abs(a).sum(axis=1).max())
+        assert int(np.diff(a.indptr).min()) > 0  # (no empty row: ``true_residual`` reduces row by row)
+        self._rows = np.repeat(np.arange(n), np.diff(a.indptr))
+        self._obj = a.data.astype(object)
+
+    @classmethod
+    def from_face_weights(cls, g, w_inner, w_outer, diag_extra):
+        n = g.n_cells
+        assert g.n_halo == 0
+        i, o = np.asarray(g.inner), np.asarray(g.outer)
+        cells = np.arange(n)
+        return cls(n, np.concatenate([i, i, o, o, cells]), np.concatenate([o, i, i, o, cells]),
+                   np.concatenate([w_inner, -w_inner, w_outer, -w_outer, diag_extra]))
+
+    def apply(self, w):
+        w = np.asarray(w)
+        if w.dtype == object:
+            out = np.zeros(self.n, dtype=object)
+            np.add.at(out, self._rows, self._obj * w[self.csr.indices])
+            return out
+        assert w.dtype == np.int64 and int(np.abs(w).max(initial=0)) * self.rowsum < (1 << 62)
+        return self.csr @ w
+
+    def float64(self):
+        """The same matrix with fp64 entries (the float64 restatements)."""
+        return self.csr.astype(np.float64)
+
+
+def true_residual(A, b, x):
+    """||b - A x||_2 in ``np.longdouble`` for an fp64 x and an ``IntOperator`` A: every product is exact there (an
+    integer of a few bits times 53 bits), the sums carry the long double's rounding."""
+    a = A.csr
+    ld = np.longdouble
+    prod = a.data.astype(ld) * np.asarray(x, np.float64).astype(ld)[a.indices]
+    r = np.asarray(b).astype(ld) - np.add.reduceat(prod, a.indptr[:-1])
+    return float(np.sqrt(np.dot(r, r)))
+
+
+class OpBasis(Basis):
+    """``Basis`` over a general integer operator: W_0 = b, W_{t+1} = A W_t with A an ``IntOperator``.  int64 while
+    max|W_t| * rowsum < 2^62 (3 * 20^t fits for t <= 13 with row sums of 20), Python integers beyond.  No
+    preconditioner.  ``gram`` is the parent's: ``big_dot(W_i, W_j)`` for every pair -- A need not be symmetric, so
+    <W_i, W_j> is no function of i + j."""
+
+    def __init__(self, op, b):
+        self.op, self.shape, self.n, self.pre = op, None, int(np.asarray(b).size), False
+        assert op.n == self.n
+        self.W = [np.asarray(b, np.int64)]
+        self.R = []
+        self._fixed, self._g, self._limb = {}, {}, {}
+
+    def grow(self, t):
+        while len(self.W) <= t:
+            w = self.W[-1]
+            if w.dtype != object and int(np.abs(w).max(initial=0)) * self.op.rowsum >= (1 << 62):
+                w = w.astype(object)
+            self.W.append(self.op.apply(w))
+
+    def gram(self, i, j):
+        """``big_dot(W_i, W_j)`` with the limbs of every int64 chain vector split once (all pairs are asked for)."""
+        key = (min(i, j), max(i, j))
+        if key not in self._g:
+            self.grow(max(key[1], 0))
+            bits = (62 - max(1, self.n).bit_length()) // 2
+            if key[0] < 0 or self.W[key[1]].dtype == object or bits > 31:
+                return Basis.gram(self, i, j)
+            for t in key:
+                if t not in self._limb:
+                    self._limb[t] = [a.astype(np.int32) for a in _limbs(self.W[t], bits)]  # (|limb| < 2^bits)
+            self._g[key] = Fraction(sum(int(np.dot(a.astype(np.int64), b.astype(np.int64))) << (bits * (s + t))
+                                        for s, a in enumerate(self._limb[i]) for t, b in enumerate(self._limb[j])))
+        return self._g[key]
+
+
 class Space:
     """The coefficient-form vectors of a Basis.  ``drop_at``: the ordinal of one dot product (counted from 1 in call
     order) that leaves the last row out -- the defect a lost partial sum would make."""
@@ -395,10 +496,11 @@ class Space:
 
 
 class ElemSpace:
-    """The same interface with every element held exactly (Fraction) or in PREC-digit decimals: the brute force."""
+    """The same interface with every element held exactly (Fraction) or in PREC-digit decimals: the brute force.
+    ``op``: an ``IntOperator`` in place of the unit box's ``-L`` (then ``shape`` is None)."""
 
-    def __init__(self, shape, b, dinv=None, decimal=False):
-        self.shape, self.decimal = tuple(shape), decimal
+    def __init__(self, shape, b, dinv=None, decimal=False, op=None):
+        self.shape, self.decimal, self.op = (None if shape is None else tuple(shape)), decimal, op
         conv = _dec if decimal else Fraction
         with localcontext() as ctx:
             ctx.prec = PREC
@@ -413,7 +515,7 @@ class ElemSpace:
         return np.zeros(self._b.size, dtype=object)
 
     def A(self, v):
-        return exact_apply(self.shape, v)
+        return exact_apply(self.shape, v) if self.op is None else self.op.apply(v)
 
     def P(self, v):
         return self._dinv * v
@@ -781,6 +883,135 @@ def fgmres(sp, K, m):
     return Run(hist, x, feeds)
 
 
+def gmres(sp, K, m, prec=None):
+    """SolverGmres.hpp:51-249 with Flexible = false and no preconditioner: ``fgmres`` with z_k = q_k, and with
+    inner_finalize where the solver calls it -- at the end of every cycle (Solver.hpp:244-246) and at exit after K
+    steps when the last cycle is unfinished (Solver.hpp:253-255) -- so x is what the solver leaves.  ``prec``: the
+    decimal digits (PREC).  Besides ``Run``'s fields the result carries ``ratio[k]``, sqrt(M) / h for history[k] as
+    ``floor_tol`` takes it: the vector a step forms is w = A q_k - sum_i H_ik q_i, its terms have the squared norms
+    |A q_k|^2 and H_ik^2 (|q_i| = 1), and h is |w| = H_{k+1,k}; the largest over the steps of the cycle so far, since
+    history[k + 1] is a product of all their rotations."""
+    with localcontext() as ctx:
+        ctx.prec = prec or PREC
+        b = sp.b()
+        x = sp.zero()
+        q, H, cs, sn, beta = [None] * (m + 1), {}, [None] * m, [None] * m, [Decimal(0)] * (m + 1)
+        hist, feeds, ratio = [], [], [Decimal(1)]
+
+        def finalize(k):  # inner_finalize, :207-236
+            nonlocal x
+            for i in range(k, -1, -1):
+                for j in range(i + 1, k + 1):
+                    beta[i] -= H[i, j] * beta[j]  # :209
+                beta[i] /= H[i, i]  # :211
+            for i in range(k + 1):
+                x = x + beta[i] * q[i]  # :234-236
+
+        for it in range(K):
+            k = it % m  # Solver.hpp:239
+            if k == 0:  # outer_init (:82-88) at it = 0, inner_init (:110-116) at the head of every cycle
+                q[0] = b - sp.A(x) if it else b  # :82, :110
+                beta[0] = _root(sp.dot(q[0], q[0]))  # :87, :115
+                if it == 0:
+                    hist.append(beta[0] * beta[0])  # :90
+                    feeds.append([q[0]])
+                q[0] = q[0] / beta[0]  # :88, :116
+                worst = Decimal(0)
+            w = sp.A(q[k])  # :155
+            mag = _dec(sp.dot(w, w))
+            for i in range(k + 1):  # :157-160
+                H[i, k] = _dec(sp.dot(w, q[i]))  # :158
+                w = w - H[i, k] * q[i]  # :159
+                mag += H[i, k] * H[i, k]
+            H[k + 1, k] = _root(sp.dot(w, w))  # :161
+            q[k + 1] = w / H[k + 1, k]  # :162
+            worst = max(worst, mag.sqrt() / H[k + 1, k])
+            for i in range(k):  # :176-180
+                chi = cs[i] * H[i, k] + sn[i] * H[i + 1, k]  # :177
+                H[i + 1, k] = -sn[i] * H[i, k] + cs[i] * H[i + 1, k]  # :178
+                H[i, k] = chi  # :179
+            rr = (H[k, k] ** 2 + H[k + 1, k] ** 2).sqrt()  # :181, MathUtils.hpp:165-179
+            cs[k], sn[k] = (H[k, k] / rr, H[k + 1, k] / rr) if rr > 0 else (Decimal(1), Decimal(0))
+            H[k, k] = cs[k] * H[k, k] + sn[k] * H[k + 1, k]  # :182
+            H[k + 1, k] = Decimal(0)  # :183
+            beta[k + 1], beta[k] = -sn[k] * beta[k], cs[k] * beta[k]  # :189
+            hist.append(beta[k + 1] * beta[k + 1])  # :191
+            feeds.append([w])
+            ratio.append(worst)
+            if k == m - 1:
+                finalize(k)  # Solver.hpp:244-246
+        if K and (K - 1) % m != m - 1:
+            finalize((K - 1) % m)  # Solver.hpp:253-255
+    run = Run(hist, x, feeds)
+    run.ratio = [float(r) for r in ratio]
+    return run
+
+
+def mgs_float64(a, b, K, m, defect=None, group=None, drop=(3, 1)):
+    """GMRES(m)'s history[0..K] in plain fp64 numpy (``a``: scipy CSR, fp64), the same statements as ``gmres``.
+
+    ``group`` = T: the projections of a step taken T at a time the way the device's chain kernels take them -- the T
+    dots of a group against the SAME w, the one from before the group, then regrouped by bilinearity,
+    h_{i+v} = <w, q_{i+v}> - sum_{u<v} h_{i+u} <q_{i+u}, q_{i+v}>, then w -= sum_v h_{i+v} q_{i+v}.  Not a defect.
+
+    ``defect`` (what the pins must reject):
+      "skip_q0"     the projection on q_0 dropped for k >= 2
+      "skip_in_group" the projection on q_2 dropped for k >= 4 (one of a group of four)
+      "drop_row"    the dot <w, q_i> of step k, (k, i) = ``drop``, without its last row
+      "rotation_order" the earlier rotations of a column applied last first"""
+    b = np.asarray(b, np.float64)
+    n = b.size
+    x = np.zeros(n)
+    q, H = [None] * (m + 1), np.zeros((m + 1, m))
+    cs, sn, beta = np.zeros(m), np.zeros(m), np.zeros(m + 1)
+    hist = []
+    for it in range(K):
+        k = it % m
+        if k == 0:
+            q[0] = b - a @ x if it else b.copy()
+            beta[0] = math.sqrt(np.dot(q[0], q[0]))
+            if it == 0:
+                hist.append(beta[0])
+            q[0] = q[0] / beta[0]
+        w = a @ q[k]
+        i = 0
+        while i <= k:
+            T = min(group or 1, k + 1 - i)
+            w0 = w
+            for v in range(T):
+                j = i + v
+                if defect == "drop_row" and (k, j) == tuple(drop):
+                    h = np.dot(w0[:-1], q[j][:-1])
+                else:
+                    h = np.dot(w0, q[j])
+                for u in range(v):
+                    h -= H[i + u, k] * np.dot(q[i + u], q[j])
+                if (defect == "skip_q0" and j == 0 and k >= 2) or (defect == "skip_in_group" and j == 2 and k >= 4):
+                    h = 0.0
+                H[j, k] = h
+            for v in range(T):
+                w = w - H[i + v, k] * q[i + v]
+            i += T
+        H[k + 1, k] = math.sqrt(np.dot(w, w))
+        q[k + 1] = w / H[k + 1, k]
+        order = range(k - 1, -1, -1) if defect == "rotation_order" else range(k)
+        for i in order:
+            chi = cs[i] * H[i, k] + sn[i] * H[i + 1, k]
+            H[i + 1, k] = -sn[i] * H[i, k] + cs[i] * H[i + 1, k]
+            H[i, k] = chi
+        rr = math.hypot(H[k, k], H[k + 1, k])
+        cs[k], sn[k] = (H[k, k] / rr, H[k + 1, k] / rr) if rr > 0 else (1.0, 0.0)
+        H[k, k] = cs[k] * H[k, k] + sn[k] * H[k + 1, k]
+        H[k + 1, k] = 0.0
+        beta[k + 1], beta[k] = -sn[k] * beta[k], cs[k] * beta[k]
+        hist.append(abs(beta[k + 1]))
+        if k == m - 1 and it + 1 < K:
+            y = np.linalg.solve(np.triu(H[:m, :m]), beta[:m])
+            for i in range(m):
+                x = x + y[i] * q[i]
+    return np.array(hist)
+
+
 # ---- what the tests pin, and how tightly -----------------------------------------------------------------------------
 
 DECIMAL_METHODS = ("idrs", "fgmres")
@@ -836,10 +1067,13 @@ def exact_run(sp, method, param, K, side=None, shadow=()):
 #   s > 1   r -= beta g_0 2 + 1                                                                            -> 7
 #   IDR(1)  then v = A r 13 + 12 * 7; omega 1; r -= omega v 2 + 7                                          -> 107
 #   Richardson: every vector exact (``richardson_integers``)                                               -> 0
+#   GMRES   q_0 = b / beta 1 + 1; w = A q_k 13; per projection h 1, w -= h q_i 2 (the terms of M count every one);
+#   FGMRES  |w| 1, q_{k+1} = w / |w| 1; the rotation's hypot, divisions and products ~8                   -> 32
+#           (``gmres`` takes sqrt(M) / h from the step's own terms -- A q_k and the H_ik q_i -- not from the chain)
 # Later iterations and the preconditioned cases repeat these statements: c_k = k c_1 (+ 4k + 1 with the elementwise
 # products of a preconditioner) is their floor; there the measured error of the oracle decides (``Pins``).
 C1 = {"cgs": 64, "tfqmr": 59, "tfqmr1": 54, "idrs": 7, "idrs1": 107, "richardson": 0, "bicgstabl": 64, "cg": 16,
-      "fgmres": 32}
+      "fgmres": 32, "gmres": 32}
 
 
 def _c(method, param, k, pre):
@@ -944,6 +1178,121 @@ class Pins:
                                          f"{tol:.3e} ({self.rule[k]})"
             ratios.append(abs(h - x) / (x * self.e[k]) if self.e[k] > 0 else (0.0 if h == x else math.inf))
         return ratios
+
+
+def convdiff_box(mesh, nx, ny, nz, vel=(2.0, 1.0, -1.0)):
+    """The non-symmetric integer operator of the GMRES pins: A = -L + C(v) on the unit box, nu = 1, v = (2, 1, -1),
+    first-order upwind.  Every face weight is an integer; row sums of |A| <= 20, |A - A^T| = 2.  Returns the face
+    graph, the weights for ``StencilMatrix.from_face_weights`` (apply with alpha = 1, beta = 0) and the
+    ``IntOperator``; the oracle's operator of it is ``oracle.StencilOperator(g, -1.0, 0.0, conv=1.0, vel=vel)``."""
+    g = unit_box(mesh, nx, ny, nz)
+    w = mesh.convection_diffusion_weights(g, 1.0, vel)
+    op = IntOperator.from_face_weights(g, *w)
+    assert op.rowsum <= 20
+    return g, w, op
+
+
+GMRES_VEL = (2.0, 1.0, -1.0)
+GMRES_SEED, GMRES_RANGE = 31, (-3, 3)  # b = int_vector(n, 31, -3, 3): W_t stays in int64 through t = 13
+# shape -> the (K, m) pinned on it (tests/test_gpu_exact_gmres.py names the kernel width each shape is there for).
+# K = 9 = m: 1 ... 9 basis vectors per step, every remainder of groups of 2, 3 and 4; K = 12, m = 5: inner_finalize
+# twice and the exit in the middle of a cycle
+GMRES_CASES = {(7, 5, 3): [(12, 5)], (37, 21, 19): [(12, 5), (9, 9)], (64, 64, 65): [(9, 9)], (64, 64, 129): [(9, 9)],
+               (128, 128, 65): [(9, 9)], (128, 128, 129): [(9, 9)]}
+GMRES_X_ROWS = 20000  # at or below: x itself is compared with the exact x (``Space.materialize`` is elementwise Python)
+
+
+class GmresProblem:
+    """One shape of the GMRES pins: the convection-diffusion box, b, the chain, and the pins of its (K, m), built on
+    demand and kept."""
+
+    def __init__(self, oracle, mesh, shape):
+        self.oracle, self.shape = oracle, shape
+        self.g, self.weights, self.A = convdiff_box(mesh, *shape, vel=GMRES_VEL)
+        self.b = int_vector(self.g.n_cells, GMRES_SEED, *GMRES_RANGE)
+        self.basis = OpBasis(self.A, self.b)
+        self._pins = {}
+
+    def oracle_op(self, variant):
+        return self.oracle.StencilOperator(self.g, -1.0, 0.0, conv=1.0, vel=GMRES_VEL, variant=variant)
+
+    def pins(self, K, m):
+        if (K, m) not in self._pins:
+            self._pins[K, m] = GmresPins(self.oracle, self.oracle_op, self.basis, self.A, self.b, K, m,
+                                         with_x=self.b.size <= GMRES_X_ROWS)
+        return self._pins[K, m]
+
+
+class GmresPins:
+    """history[0..K] and x_K of unpreconditioned GMRES(m) from x0 = 0 on an integer operator, with ``Pins``' rule
+    unchanged: history[0] bitwise (the root of an exact integer below 2^53); for k >= 1 tol_k = max(floor_k, 16 e_k),
+    e_k the larger relative distance of the oracle's strict and fma builds from the exact value, floor_k =
+    ``floor_tol`` with c = k C1["gmres"] and the ratio ``gmres`` records; every tol_k at most TOL_CAP (asserted).
+
+    The coefficient form over the power basis loses digits with K (at PREC = 80 it is wrong in the second digit by
+    K = 64 on the convection-diffusion box): the restatement is run at PREC and at 2 PREC digits and the two histories
+    must agree to 1e-40 (asserted), and K is held at 12 or below.
+
+    x: ``tol_res`` for ``true_residual(A, b, x)`` against the exact history[K] -- max(floor_K, 16 e_x), e_x the same
+    quantity of the oracle's two x; with ``with_x`` also ``x`` (the exact x_K, each element rounded once) and
+    ``tol_x`` for the relative 2-norm distance from it, by the same rule on the oracle's two x."""
+
+    MAX_K = 12
+
+    def __init__(self, oracle, make_op, basis, A, b, K, m, with_x=False):
+        b = np.asarray(b, np.int64)
+        assert 1 <= K <= self.MAX_K, "the power basis does not carry more steps at PREC digits"
+        self.n, self.K, self.m, self.A, self.b = b.size, K, m, A, b
+        self.run = run = gmres(Space(basis, decimal=True), K, m)
+        fine = gmres(Space(basis, decimal=True), K, m, prec=2 * PREC)
+        with localcontext() as ctx:
+            ctx.prec = 2 * PREC
+            for k, (c, f) in enumerate(zip(run.hist_sq, fine.hist_sq)):
+                assert abs(c - f) <= abs(f) * Decimal(10) ** -40, f"history[{k}]^2 depends on the precision: {c} {f}"
+        self.exact = exact = run.history
+        rr = exact_dot(b, b)
+        assert exact[0] == math.sqrt(float(rr))
+        self.oracle, self.oracle_x = {}, {}
+        bf = b.astype(np.float64)
+        for variant in ("strict", "fma"):
+            r = oracle.solve("gmres", make_op(variant), bf, num_iterations=K, abs_tol=0.0, rel_tol=0.0,
+                             num_inner_iterations=m, variant=variant)
+            assert r.history.size == K + 1, r.history
+            self.oracle[variant], self.oracle_x[variant] = r.history, r.x
+        self.e = [max(abs(h[k] - exact[k]) / exact[k] for h in self.oracle.values()) for k in range(K + 1)]
+        self.tol, self.rule = [None], ["exact"]
+        for k in range(1, K + 1):
+            floor = floor_tol(self.n, run.ratio[k], _c("gmres", m, k, False))
+            self.tol.append(self._cap(max(floor, 16 * self.e[k]), f"tol_{k}"))
+            self.rule.append("16 e_k" if self.tol[k] > floor else "floor")
+        floor = floor_tol(self.n, run.ratio[K], _c("gmres", m, K, False))
+        self.e_res = max(abs(true_residual(A, b, x) - exact[K]) / exact[K] for x in self.oracle_x.values())
+        self.tol_res = self._cap(max(floor, 16 * self.e_res), "tol_res")
+        self.rule_res = "16 e_x" if self.tol_res > floor else "floor"
+        self.x = None
+        if with_x:
+            self.x = Space(basis).materialize(run.x)
+            nx = float(np.linalg.norm(self.x))
+            self.e_x = max(float(np.linalg.norm(x - self.x)) / nx for x in self.oracle_x.values())
+            self.tol_x = self._cap(max(floor, 16 * self.e_x), "tol_x")
+
+    def _cap(self, tol, what):
+        assert tol <= TOL_CAP, f"gmres({self.m}) K={self.K} n={self.n}: {what} = {tol:.3e} above the cap {TOL_CAP}"
+        return tol
+
+    check = Pins.check
+
+    def check_x(self, x, label=""):
+        """Assert a solution against the pins; returns |res - exact| / (exact e_x) (and the same for x itself)."""
+        res, want = true_residual(self.A, self.b, x), self.exact[self.K]
+        assert close(res, want, self.tol_res), f"{label} |b - A x| = {res!r}, exact history[{self.K}] {want!r}: rel " \
+                                               f"{abs(res - want) / want:.3e} > tol {self.tol_res:.3e} ({self.rule_res})"
+        out = [abs(res - want) / (want * self.e_res) if self.e_res > 0 else 0.0]
+        if self.x is not None:
+            d = float(np.linalg.norm(x - self.x)) / float(np.linalg.norm(self.x))
+            assert d <= self.tol_x, f"{label} |x - exact| / |exact| = {d:.3e} > tol {self.tol_x:.3e}"
+            out.append(d / self.e_x if self.e_x > 0 else 0.0)
+        return out
 
 
 def richardson_integers(shape, b, k):

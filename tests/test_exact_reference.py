@@ -515,3 +515,159 @@ def test_loop_edits_are_caught_at_the_row_counts_the_gpu_tests_use():
             else:
                 got = er.forms_axpbz(er.R_XPAY, vecs[0], 1.0, vecs[1])["fuse_x"]  # fma(b, y, fl(1 x))
             assert er.classify(got, forms) == [swapped], (name, n)
+
+
+# ---- GMRES(m) on the non-symmetric integer operator (exact_ref.gmres, GmresPins) ----------------------------------------
+
+GMRES_ODD = (37, 21, 19)
+DEFECTS = ["skip_q0", "skip_in_group", "drop_row", "rotation_order"]
+_gmres_problems = {}
+
+
+def _gmres_problem(env, shape):
+    oracle, mesh = env
+    if shape not in _gmres_problems:
+        _gmres_problems[shape] = er.GmresProblem(oracle, mesh, shape)
+    return _gmres_problems[shape]
+
+
+def _rel(h, pins):
+    return [abs(a - x) / x for a, x in zip(h, pins.exact)]
+
+
+@pytest.mark.parametrize("shape", [(5, 4, 3), GMRES_ODD])
+def test_convection_diffusion_box_is_an_integer_operator(env, shape):
+    """The operator of the GMRES pins: integer face weights, row sums of |A| <= 20, |A - A^T| = 2 -- and the oracle's
+    face loops, the operator the device gets and ``IntOperator`` are the same matrix, bit for bit on integers."""
+    oracle, mesh = env
+    p = _gmres_problem(env, shape)
+    for w in p.weights:
+        assert np.array_equal(w, np.rint(w))
+    assert p.A.rowsum <= 20 and abs(p.A.csr - p.A.csr.T).max() == 2
+    z = p.A.apply(p.b)
+    assert np.array_equal(p.oracle_op("strict").apply(p.b.astype(np.float64)), z.astype(np.float64))
+    assert np.array_equal(p.A.apply(p.b.astype(object)).astype(np.int64), z)
+    # nu = 1, v = 0 is -L of the unit box: the Poisson chain of ``Basis`` is the same chain
+    lap = er.IntOperator.from_face_weights(p.g, *mesh.convection_diffusion_weights(p.g, 1.0, (0.0, 0.0, 0.0)))
+    assert np.array_equal(lap.apply(p.b), er.int_apply(shape, p.b))
+    r = er.true_residual(p.A, p.b, np.zeros(p.b.size))
+    assert r == math.sqrt(float(er.exact_dot(p.b, p.b)))
+
+
+def test_chain_of_a_general_operator_leaves_int64_when_it_must(env):
+    p = _gmres_problem(env, (5, 4, 3))
+    basis = er.OpBasis(p.A, p.b)
+    basis.grow(16)
+    kinds = [w.dtype == object for w in basis.W]
+    assert not any(kinds[:13]) and kinds[-1] and kinds == sorted(kinds)
+    w = basis.W[0].astype(object)
+    for t in range(1, 17):
+        w = p.A.apply(w)
+        assert [int(v) for v in basis.W[t]] == list(w), t
+
+
+@pytest.mark.parametrize("m", [3, 7])
+def test_gmres_coefficient_form_against_a_brute_force(env, m):
+    """``gmres`` on coefficient columns over the chain of the non-symmetric operator against ``gmres`` with every
+    element a PREC-digit decimal: history and x_K to 1e-60, through restarts (m = 3: two inner_finalize and the exit
+    inside the third cycle) and without (m = 7)."""
+    from decimal import localcontext
+
+    p = _gmres_problem(env, (5, 4, 3))
+    sp = er.Space(er.OpBasis(p.A, p.b), decimal=True)
+    el = er.ElemSpace(None, p.b, decimal=True, op=p.A)
+    coef, brute = er.gmres(sp, 7, m), er.gmres(el, 7, m)
+    assert len(coef.hist_sq) == len(brute.hist_sq) == 8
+    with localcontext() as ctx:
+        ctx.prec = er.PREC
+        tiny = er._dec(Fraction(1, 10 ** 60))
+        for c, e in zip(coef.hist_sq, brute.hist_sq):
+            assert abs(c - e) <= abs(e) * tiny
+        xc = sum((er._dec(c) * sp.basis.W[k].astype(object) for k, c in coef.x.c.items()), np.zeros(p.b.size, dtype=object))
+        assert max(abs(a - e) for a, e in zip(xc, brute.x)) <= max(abs(v) for v in brute.x) * tiny
+        # x is the solver's: the true residual of the exact x is the last history entry
+        r = p.b.astype(object) - p.A.apply(brute.x)
+        assert abs(sum(v * v for v in r) - brute.hist_sq[7]) <= brute.hist_sq[7] * tiny
+
+
+@pytest.mark.parametrize("shape", list(er.GMRES_CASES), ids=lambda s: "x".join(map(str, s)))
+def test_gmres_pins_of_every_gpu_case(env, shape):
+    """Every case of tests/test_gpu_exact_gmres.py: the precision guard (PREC against 2 PREC digits) and the cap
+    (tol_k, tol_res, tol_x <= TOL_CAP) are asserted as ``GmresPins`` is built; both oracle builds lie inside."""
+    p = _gmres_problem(env, shape)
+    for K, m in er.GMRES_CASES[shape]:
+        pins = p.pins(K, m)
+        assert pins.tol[0] is None and max(pins.tol[1:]) <= er.TOL_CAP and pins.tol_res <= er.TOL_CAP
+        assert (pins.x is not None) == (p.b.size <= er.GMRES_X_ROWS)
+        for variant, hist in pins.oracle.items():
+            pins.check(list(hist), f"gmres({m}) {shape} {variant}")
+            pins.check_x(pins.oracle_x[variant], f"gmres({m}) {shape} {variant}")
+    if p.b.size > er.GMRES_X_ROWS:
+        del _gmres_problems[shape]  # (hundreds of MB of chain that no other test here needs)
+
+
+def test_gmres_pins_refuse_more_steps_than_the_power_basis_carries(env):
+    p = _gmres_problem(env, (5, 4, 3))
+    with pytest.raises(AssertionError):
+        er.GmresPins(p.oracle, p.oracle_op, p.basis, p.A, p.b, 13, 13)
+    from decimal import InvalidOperation, localcontext
+
+    # ... and what the guard is for: with too few digits the K = 12 history is not the 80-digit one to 1e-40 (or a
+    # squared norm comes out negative)
+    sp = er.Space(er.OpBasis(p.A, p.b), decimal=True)
+    fine = er.gmres(sp, 12, 12)
+    for digits in (12, 30):
+        try:
+            coarse = er.gmres(sp, 12, 12, prec=digits)
+            with localcontext() as ctx:
+                ctx.prec = er.PREC
+                lost = abs(coarse.hist_sq[12] - fine.hist_sq[12]) > abs(fine.hist_sq[12]) * er._dec(Fraction(1, 10 ** 40))
+        except InvalidOperation:
+            lost = True
+        assert lost, digits
+
+
+@pytest.mark.parametrize("defect", DEFECTS)
+def test_gmres_defects_fall_outside_the_pins(env, defect):
+    """What the pins are for, on 37 x 21 x 19 with K = m = 9: a float64 restatement of the Gram-Schmidt step with one
+    defect -- the projection on q_0 dropped from the third step on; one projection of a group of four dropped; one
+    dot without its last row; the earlier rotations in the wrong order -- leaves the pins at some k by a factor of
+    1000 or more.  The same restatement without a defect lies inside (the grouped test below, T = 1)."""
+    p = _gmres_problem(env, GMRES_ODD)
+    pins = p.pins(9, 9)
+    h = er.mgs_float64(p.A.float64(), p.b, 9, 9, defect=defect)
+    out = [d / t for d, t in zip(_rel(h, pins)[1:], pins.tol[1:])]
+    assert max(out) >= 1e3, (defect, out)
+    with pytest.raises(AssertionError):
+        pins.check(list(h), defect)
+
+
+def test_poisson_cannot_see_a_dropped_old_projection(env):
+    """Why the operator had to change.  On the symmetric Poisson box H is tridiagonal: the projections on
+    q_0 ... q_{k-2} are rounding noise, and GMRES with the projection on q_0 dropped for k >= 2 stays inside Poisson's
+    own pins -- the same defect that leaves the convection-diffusion pins by a factor of 1e3 (above)."""
+    oracle, mesh = env
+    g = er.unit_box(mesh, *GMRES_ODD)
+    b = er.int_vector(g.n_cells, er.GMRES_SEED, *er.GMRES_RANGE)
+    lap = er.IntOperator.from_face_weights(g, *mesh.convection_diffusion_weights(g, 1.0, (0.0, 0.0, 0.0)))
+    assert np.array_equal(lap.apply(b), er.int_apply(GMRES_ODD, b))
+    pins = er.GmresPins(oracle, lambda v: oracle.StencilOperator(g, -1.0, 0.0, variant=v), er.Basis(GMRES_ODD, b), lap, b,
+                        9, 9)
+    good = er.mgs_float64(lap.float64(), b, 9, 9)
+    bad = er.mgs_float64(lap.float64(), b, 9, 9, defect="skip_q0")
+    pins.check(list(good), "poisson")
+    pins.check(list(bad), "poisson, q_0 skipped")  # invisible
+    assert max(_rel(bad, pins)) < 1e-13
+
+
+@pytest.mark.parametrize("T", [1, 2, 3, 4])
+def test_grouped_gram_schmidt_is_no_defect(env, T):
+    """The chain kernels take T projections per synchronisation point: the T dots of a group against the w from
+    before the group, regrouped by bilinearity (``mgs_float64``).  In fp64 that form stays within 1e-14 of the exact
+    history on 37 x 21 x 19 -- inside the pins, and no further from the exact value than the plain form (T = 1)."""
+    p = _gmres_problem(env, GMRES_ODD)
+    for K, m in er.GMRES_CASES[GMRES_ODD]:
+        pins = p.pins(K, m)
+        h = er.mgs_float64(p.A.float64(), p.b, K, m, group=T)
+        pins.check(list(h), f"grouped T={T}")
+        assert max(_rel(h, pins)) <= 1e-14, _rel(h, pins)
