@@ -452,7 +452,8 @@ int storm_hip_ctx_set_option(storm_hip_ctx *ctx, const char *key, int64_t value)
  * "rccl_prof_pack_ticks", "rccl_prof_sendrecv_ticks", "rccl_prof_unhidden_wait_ticks" (the exchange still running when the
  * interior rows had ended), "rccl_prof_resume_ticks" (exchange and interior rows done -> the boundary rows start),
  * "rccl_prof_allreduces", "rccl_prof_allreduce_ticks".  With option "resident_profile" = 1:
- * "resident_phase_mean_<k>" / "resident_phase_max_<k>" (csrc/resident.hip). */
+ * "resident_phase_mean_<k>" / "resident_phase_max_<k>" (csrc/resident.hip).  "option_spmv_dict": no counter but the
+ * current value of option "spmv_dict", for a caller that builds one operator on fp64 records and restores the option. */
 int storm_hip_ctx_get_counter(storm_hip_ctx *ctx, const char *key, int64_t *value);
 
 /* A cell ordering from geometry: host preprocessing in the role METIS plays in the north star; the reference's hook
@@ -876,8 +877,10 @@ int storm_hip_cheb_create_reduced(const storm_hip_op *op, double alpha, double b
  *   6. Stop when n_l <= coarse_rows; also when the next level would keep more than 90 % of the rows, or when max_levels
  *      is reached -- in these two cases a level of at most 1024 rows becomes the coarsest, otherwise the result is
  *      STORM_HIP_E_UNSUPPORTED with the level sizes in the message.
- *   7. The coarsest level's dense inverse is formed on the host by Gauss-Jordan with partial pivoting.  A zero pivot or a
- *      non-finite entry (a pure-Neumann operator, for instance): STORM_HIP_E_INVALID, and the message says so.
+ *   7. The coarsest level's dense inverse is formed on the host by Gauss-Jordan with partial pivoting.  A zero pivot, a
+ *      pivot below 2^-40 max_i |a_ii| in magnitude (singular to working precision: what rounding leaves of a zero pivot) or
+ *      a non-finite entry -- a pure-Neumann operator, for instance --: STORM_HIP_E_INVALID, and the message says so.  (For
+ *      operators whose kernel is the constants there is storm_hip_amg_setup_csr_nullspace below.)
  *
  * THE CYCLE for level l with right-hand side r and output z (S_l: the level's Chebyshev smoother with the Jacobi scale,
  * degree smoother_degree, on [lmax / smoother_ratio, lmax] with Gershgorin's lmax; t, e: the level's work vectors):
@@ -1013,6 +1016,56 @@ int storm_hip_amg_destroy(storm_hip_amg *h);
 /* pre_op as the library's multigrid preconditioner (h == NULL removes it): bound natively, no callback.  A size that differs
  * from the solve's vectors: STORM_HIP_E_INVALID from the solve. */
 int storm_hip_krylov_set_preconditioner_amg(storm_hip_krylov *k, const storm_hip_amg *h, int side);
+/* ---- Singular operators with the constants as their kernel (STORM_HIP_HAS_AMG_NULLSPACE, added within ABI 6) ----------------
+ * The pressure equation of a projection method, -L_N p = rhs with Neumann walls, is symmetric positive SEMI-definite: A 1 = 0.
+ * The entry points above refuse it at step 7 (they still do); the ones below build B = Pi V Pi, the V-cycle between two
+ * projections onto the mean-free vectors, Pi = I - 1 1^T / n.  Strictly opt-in: nothing above changes its behaviour.
+ *
+ * storm_hip_amg_setup_csr_nullspace is THE RECIPE (structural != 0: its structural variant) with three differences
+ * (normative; tests/amg_nullspace_ref.py restates them):
+ *   N1. Row sums.  After normalisation every level-0 row must satisfy |sum_j a_ij| <= 2^-40 sum_j |a_ij| (both sums in column
+ *       order).  Otherwise STORM_HIP_E_INVALID; the message names the first such row.  2^-40 classifies, it is no tolerance: a
+ *       decoded Neumann row sits at a few eps, one Dirichlet face or beta != 0 gives O(0.1).
+ *   N2. Connectivity.  The graph of the non-zero off-diagonal entries of level 0, both directions joined, must have ONE
+ *       connected component (a row without an off-diagonal entry is a component of its own).  Otherwise STORM_HIP_E_INVALID
+ *       with "component" and the count in the message.  (A disconnected operator coarsens to a numerically zero coarsest
+ *       matrix, which no pivot test sees.)
+ *   N3. Coarsest level, instead of step 7.  n_c = 1: Ainv = (0).  Otherwise s = max_i a_ii (s <= 0: STORM_HIP_E_INVALID),
+ *       G = A_c + (s / n_c) 1 1^T entrywise, G^-1 by the Gauss-Jordan of step 7 -- a pivot below 2^-30 s in magnitude or a
+ *       non-finite entry: STORM_HIP_E_INVALID, "singular beyond the constants" -- and Ainv = Pi G^-1 Pi, formed as: from every
+ *       column its mean is subtracted (the sum over the rows in ascending order, divided by n_c), then from every row its
+ *       mean (the sum over the columns in ascending order, divided by n_c).  Ainv is the pseudo-inverse of A_c up to rounding.
+ * storm_hip_amg_hierarchy_get keys "nullspace" (0 / 1) and "coarse_shift" (s; 0 on a plain hierarchy and on a one-row
+ * coarsest level); storm_hip_amg_hierarchy_get_coarse_inverse exports Ainv.
+ *
+ * storm_hip_amg_create_nullspace: storm_hip_amg_create on the setup above; refreshable != 0: storm_hip_amg_create_refreshable
+ * on it (structural = 1).  The refusals of those two apply (compact records, halo, communicator, a non-updatable operator).
+ * storm_hip_amg_refresh on such an object runs N3 in step 6 of the frozen-structure recipe; N1 AND N2 ARE NOT REPEATED AT A
+ * REFRESH (the weights the caller sets must keep the operator a connected Neumann operator); a pivot failure leaves the
+ * object invalid as on a plain one.  _download, _get_hierarchy and the grid-transfer entry points work as on a plain object;
+ * storm_hip_amg_get key "nullspace".
+ *
+ * THE CYCLE of a null-space object (V: THE CYCLE above with Ainv from N3; Pi acts on level 0 only):
+ *     rp = r - mu_r,  mu_r = fl(S_r / n)     r is not written; rp is one more level-0 work vector
+ *     z  = V(rp)                             exactly the launches of a plain object, ending in z = z + e
+ *     z  = z - mu_z,  mu_z = fl(S_z / n)
+ * S is the sum of the vector's n entries by the library's streaming reduction: the stream_blocks(n) grid (a block owns 2048
+ * consecutive entries, a thread its four 16-byte words in ascending order), the block sum, then the two-level ticket fold.
+ * It depends on n only.  The block that draws the last ticket stores mu = S / n (an IEEE division) into a slot the object
+ * owns; the next kernel on the stream reads it.  No host wait, no floating-point atomic.  Kernels (all predicated on the
+ * solve's done flag): amg_mean_kernel (S, mu), amg_shift_kernel (out_i = v_i - mu), amg_axpy_mean_kernel (level 0's closing
+ * z_i = z_i + e_i accumulating the stored values into amg_mean_kernel's partition: with option amg_fused = 1 it replaces
+ * storm_hip_axpy + amg_mean_kernel; amg_fused = 0 runs the two; the same bits either way).  A one-level object is
+ * Pi Ainv Pi from the same kernels.  Counters "amg_projections" (+2 per apply, +1 per storm_hip_amg_project) and
+ * "amg_fused_projections" (+1 per apply that closed with the fused kernel).
+ * storm_hip_amg_project: v <- v - mean(v) in place, v of level 0's size (anything else: STORM_HIP_E_INVALID); on a plain
+ * object STORM_HIP_E_UNSUPPORTED.  Enqueued like an apply. */
+#define STORM_HIP_HAS_AMG_NULLSPACE 1
+int storm_hip_amg_setup_csr_nullspace(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
+                                      const storm_hip_amg_params *params, int structural, storm_hip_amg_hierarchy **out);
+int storm_hip_amg_create_nullspace(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params,
+                                   int refreshable, storm_hip_amg **out);
+int storm_hip_amg_project(const storm_hip_amg *h, storm_hip_vec *v);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

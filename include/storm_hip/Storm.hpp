@@ -952,10 +952,14 @@ private:
 /// or, if `refreshable` (set before the build; the matrix must come from from_face_weights_updatable), `refresh()` it: every
 /// number of the hierarchy is recomputed on the device on the structure the setup froze (storm_hip_amg_refresh).
 /// `params.reduced_records`: every level's smoother reads fp32-weight companion records (the matrix gets one if missing).
+/// `nullspace_constant` (set before the build): for a singular operator whose kernel is the constants -- a pure-Neumann
+/// pressure equation -- the object is storm_hip_amg_create_nullspace's: the cycle between two projections onto the mean-free
+/// vectors, and `project(v)` is v <- v - mean(v).
 class AmgPreconditioner final : public Preconditioner<DeviceVector> {
 public:
   storm_hip_amg_params params;
   bool refreshable = false;  ///< read by build(): storm_hip_amg_create_refreshable instead of storm_hip_amg_create
+  bool nullspace_constant = false;  ///< read by build(): storm_hip_amg_create_nullspace (with `refreshable` as its flag)
 
   AmgPreconditioner() { storm_hip_amg_params_default(&params); }
   explicit AmgPreconditioner(int smoother_degree, bool reduced_records = false) : AmgPreconditioner() {
@@ -977,16 +981,22 @@ public:
         _built.strength_theta == params.strength_theta && _built.prolongator_omega == params.prolongator_omega &&
         _built.smoother_degree == params.smoother_degree && _built.smoother_ratio == params.smoother_ratio &&
         _built.max_levels == params.max_levels && _built.coarse_rows == params.coarse_rows &&
-        _built.reduced_records == params.reduced_records && _built_refreshable == refreshable)
+        _built.reduced_records == params.reduced_records && _built_refreshable == refreshable &&
+        _built_nullspace == nullspace_constant)
       return;
     reset();
-    if (refreshable)
+    if (nullspace_constant)
+      detail::check(storm_hip_amg_create_nullspace(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params,
+                                                   refreshable ? 1 : 0, &_h));
+    else if (refreshable)
       detail::check(storm_hip_amg_create_refreshable(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params, &_h));
     else
       detail::check(storm_hip_amg_create(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params, &_h));
     _op = hip_op->matrix().handle(), _alpha = hip_op->alpha(), _beta = hip_op->beta(), _built = params;
-    _built_refreshable = refreshable;
+    _built_refreshable = refreshable, _built_nullspace = nullspace_constant;
   }
+  /// v <- v - mean(v) in place (a `nullspace_constant` object; storm_hip_amg_project).
+  void project(DeviceVector& v) const { detail::check(storm_hip_amg_project(_h, v.handle())); }
   /// Recompute every number of the hierarchy from the matrix's current records (a refreshable object; waits on the host).
   void refresh() { detail::check(storm_hip_amg_refresh(_h)); }
   /// Bring the host hierarchy (storm_hip_amg_get_hierarchy) up to date with what the cycle reads on the device.
@@ -1003,7 +1013,7 @@ public:
     detail::check(storm_hip_amg_apply(_h, y_vec.handle(), x_vec.handle()));
   }
   /// "levels", "operator_complexity", "grid_complexity", "setup_seconds", "upload_seconds", "device_bytes",
-  /// "transfer_padding", "smoother_degree" or "reduced".
+  /// "transfer_padding", "smoother_degree", "reduced", "nullspace" or "coarse_shift".
   real_t get(const char* key) const {
     double v = 0.0;
     detail::check(storm_hip_amg_get(_h, key, &v));
@@ -1029,7 +1039,7 @@ private:
   const storm_hip_op* _op = nullptr;
   real_t _alpha = 0.0, _beta = 0.0;
   storm_hip_amg_params _built{};
-  bool _built_refreshable = false;
+  bool _built_refreshable = false, _built_nullspace = false;
 };
 
 #ifndef STORM_HIP_NO_SOLVERS

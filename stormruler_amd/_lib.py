@@ -225,6 +225,9 @@ SIGNATURES = {
     "storm_hip_amg_get_hierarchy": (C.c_int, [vp, C.POINTER(vp)]),
     "storm_hip_amg_destroy": (C.c_int, [vp]),
     "storm_hip_krylov_set_preconditioner_amg": (C.c_int, [vp, vp, C.c_int]),
+    "storm_hip_amg_setup_csr_nullspace": (C.c_int, [C.c_int64, i64p, i64p, f64p, C.POINTER(AmgParams), C.c_int, C.POINTER(vp)]),
+    "storm_hip_amg_create_nullspace": (C.c_int, [vp, C.c_double, C.c_double, C.POINTER(AmgParams), C.c_int, C.POINTER(vp)]),
+    "storm_hip_amg_project": (C.c_int, [vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

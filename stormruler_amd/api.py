@@ -1018,20 +1018,27 @@ class AmgHierarchy:
         self._h, self._owned, self._keep = handle, owned, keep
 
     @classmethod
-    def from_csr(cls, a, structural: bool = False, **params) -> "AmgHierarchy":
+    def from_csr(cls, a, structural: bool = False, nullspace: Optional[str] = None, **params) -> "AmgHierarchy":
         """Keywords: ``strength_theta``, ``prolongator_omega``, ``smoother_degree``, ``smoother_ratio``, ``max_levels``,
         ``coarse_rows``, ``reduced_records`` (defaults: ``storm_hip_amg_params_default``).  ``structural``: the setup whose
         patterns depend on no value (``storm_hip_amg_setup_csr_structural``): stored zeros of ``a`` stay, and so do entries of
-        P_l and A_{l+1} that cancel exactly."""
+        P_l and A_{l+1} that cancel exactly.  ``nullspace="constant"``: the setup for a singular operator whose kernel is the
+        constants (``storm_hip_amg_setup_csr_nullspace``: row sums and connectivity are checked, the coarsest level gets
+        its pseudo-inverse)."""
+        if nullspace not in (None, "constant"):
+            raise ValueError(f"nullspace={nullspace!r}: None or 'constant'")
         a = a.tocsr()
         rp = np.ascontiguousarray(a.indptr, np.int64)
         col = np.ascontiguousarray(a.indices, np.int64)
         val = np.ascontiguousarray(a.data, np.float64)
         h = C.c_void_p()
         p = _amg_params(**params)
+        args = (a.shape[0], rp.ctypes.data_as(_lib.i64p), col.ctypes.data_as(_lib.i64p), val.ctypes.data_as(_lib.f64p), C.byref(p))
+        if nullspace is not None:
+            check(lib.storm_hip_amg_setup_csr_nullspace(*args, int(bool(structural)), C.byref(h)))
+            return cls(h)
         setup = lib.storm_hip_amg_setup_csr_structural if structural else lib.storm_hip_amg_setup_csr
-        check(setup(a.shape[0], rp.ctypes.data_as(_lib.i64p), col.ctypes.data_as(_lib.i64p), val.ctypes.data_as(_lib.f64p),
-                    C.byref(p), C.byref(h)))
+        check(setup(*args, C.byref(h)))
         return cls(h)
 
     @property
@@ -1083,7 +1090,8 @@ class AmgHierarchy:
         return inv
 
     def get(self, key: str) -> float:
-        """``levels``, ``operator_complexity``, ``grid_complexity``, ``setup_seconds`` or ``structural`` (0 or 1)."""
+        """``levels``, ``operator_complexity``, ``grid_complexity``, ``setup_seconds``, ``structural`` (0 or 1), ``nullspace``
+        (0 or 1) or ``coarse_shift`` (the shift of a null-space hierarchy's coarsest level)."""
         v = C.c_double()
         check(lib.storm_hip_amg_hierarchy_get(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -1112,12 +1120,20 @@ class AmgPreconditioner(Preconditioner):
     records (the matrix gets one if it has none).  ``refreshable`` (``storm_hip_amg_create_refreshable``; the matrix must
     come from ``from_face_weights_updatable``): the setup freezes aggregates, strong masks and patterns, and :meth:`refresh`
     recomputes every number of the hierarchy on the device from the matrix's current weights; :meth:`build` keeps its
-    cache key, so the same handle and parameters mean no rebuild.  :meth:`download` brings :attr:`hierarchy` up to date."""
+    cache key, so the same handle and parameters mean no rebuild.  :meth:`download` brings :attr:`hierarchy` up to date.
+    ``nullspace="constant"`` (``storm_hip_amg_create_nullspace``): for a singular operator whose kernel is the constants --
+    a pure-Neumann pressure equation -- the cycle runs between two projections onto the mean-free vectors, and
+    :meth:`project` applies that projection to a vector.  ``matrix``: a :class:`StencilMatrix` on fp64 records holding the
+    SAME operator as the solve's; the hierarchy is built from it (and level 0 of the cycle applies it), so that the solve's
+    own operator may stay on compact records.  Both are part of the cache key."""
 
     def __init__(self, strength_theta: Optional[float] = None, prolongator_omega: Optional[float] = None,
                  smoother_degree: Optional[int] = None, smoother_ratio: Optional[float] = None,
                  max_levels: Optional[int] = None, coarse_rows: Optional[int] = None, reduced_records: bool = False,
-                 refreshable: bool = False):
+                 refreshable: bool = False, nullspace: Optional[str] = None, matrix=None):
+        if nullspace not in (None, "constant"):
+            raise ValueError(f"nullspace={nullspace!r}: None or 'constant'")
+        self.nullspace, self.matrix = nullspace, matrix
         self.params = dict(strength_theta=strength_theta, prolongator_omega=prolongator_omega, smoother_degree=smoother_degree,
                            smoother_ratio=smoother_ratio, max_levels=max_levels, coarse_rows=coarse_rows,
                            reduced_records=int(bool(reduced_records)))
@@ -1133,22 +1149,28 @@ class AmgPreconditioner(Preconditioner):
             raise TypeError("AmgPreconditioner needs a HipStencilOperator to build its hierarchy from")
         # a solver calls build() before every solve: the hierarchy is kept while operator and parameters are the same
         # (a matrix whose weights were refreshed is the same handle: close() first -- staleness is the caller's)
-        key = (x_vec.ctx, any_op.matrix._h.value, float(any_op.alpha), float(any_op.beta), tuple(sorted(self.params.items())),
-               self.refreshable)
+        source = any_op.matrix if self.matrix is None else self.matrix
+        key = (x_vec.ctx, source._h.value, float(any_op.alpha), float(any_op.beta), tuple(sorted(self.params.items())),
+               self.refreshable, self.nullspace, None if self.matrix is None else self.matrix._h.value)
         if self._h is not None and self._key == key:
             return
         self._free()
         self.ctx, self._op = x_vec.ctx, any_op
         h = C.c_void_p()
         p = _amg_params(**self.params)
-        create = lib.storm_hip_amg_create_refreshable if self.refreshable else lib.storm_hip_amg_create
-        check(create(any_op.matrix._h, any_op.alpha, any_op.beta, C.byref(p), C.byref(h)))
+        if self.nullspace is not None:
+            check(lib.storm_hip_amg_create_nullspace(source._h, any_op.alpha, any_op.beta, C.byref(p), int(self.refreshable),
+                                                     C.byref(h)))
+        else:
+            create = lib.storm_hip_amg_create_refreshable if self.refreshable else lib.storm_hip_amg_create
+            check(create(source._h, any_op.alpha, any_op.beta, C.byref(p), C.byref(h)))
         self._h, self._key = h, key
         self.ctx._children.add(self)
 
     def get(self, key: str) -> float:
         """``levels``, ``operator_complexity``, ``grid_complexity``, ``setup_seconds``, ``upload_seconds``, ``device_bytes``,
-        ``transfer_padding``, ``smoother_degree``, ``reduced``, ``structural``, ``refreshable`` or ``refresh_bytes``."""
+        ``transfer_padding``, ``smoother_degree``, ``reduced``, ``structural``, ``refreshable``, ``refresh_bytes``,
+        ``nullspace`` or ``coarse_shift``."""
         v = C.c_double()
         check(lib.storm_hip_amg_get(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -1175,6 +1197,12 @@ class AmgPreconditioner(Preconditioner):
 
     def mul(self, y_vec, x_vec):
         check(lib.storm_hip_amg_apply(self._h, x_vec._h, y_vec._h))
+
+    def project(self, v) -> None:
+        """``v <- v - mean(v)`` in place (``storm_hip_amg_project``; a ``nullspace="constant"`` object only)."""
+        if self._h is None:
+            raise RuntimeError("AmgPreconditioner.project before build")
+        check(lib.storm_hip_amg_project(self._h, v._h))
 
     def restrict(self, level: int, fine, coarse) -> None:
         """``coarse = R_l fine`` (``storm_hip_amg_restrict``)."""

@@ -94,10 +94,19 @@ def build_cavity_operators(n: int, graph: FaceGraph = None, lid_coord: float = 1
 class CavityProjection:
     """Device-resident projection stepper.  ``step()`` returns (cg_iterations, seconds)."""
 
-    def __init__(self, ctx, n: int, nu: float = 0.01, dt: float = None, graph: FaceGraph = None, plan=None):
+    def __init__(self, ctx, n: int, nu: float = 0.01, dt: float = None, graph: FaceGraph = None, plan=None,
+                 pressure_preconditioner: str = None):
         """``graph``/``plan``: this rank's local face graph and halo plan (``stormruler_amd.partition``)
-        for a row-partitioned run (config 5 is 4 GPUs); ``ctx`` must then carry a communicator."""
+        for a row-partitioned run (config 5 is 4 GPUs); ``ctx`` must then carry a communicator.
+        ``pressure_preconditioner``: ``None`` (plain CG, the default) or ``"amg"``: the multigrid preconditioner for the
+        pure-Neumann pressure operator (``AmgPreconditioner(nullspace="constant")``), single rank only.  Its hierarchy is
+        built from a second copy of ``L_N`` on fp64 records; the solve's own ``L_N`` keeps its compact records."""
         from . import api
+
+        if pressure_preconditioner not in (None, "amg"):
+            raise ValueError(f"pressure_preconditioner={pressure_preconditioner!r}: None or 'amg'")
+        if pressure_preconditioner == "amg" and (graph is not None or plan is not None or ctx.n_ranks != 1):
+            raise ValueError("pressure_preconditioner='amg' is single-rank: no graph, no plan, no communicator")
 
         self.api, self.ctx, self.n, self.nu = api, ctx, n, nu
         h = 1.0 / n
@@ -122,6 +131,16 @@ class CavityProjection:
         self.p, self.rhs, self.t1, self.t2 = vec(), vec(), vec(), vec()
         self.A_p = api.HipStencilOperator(self.L_N, alpha=-1.0, beta=0.0)  # -L_N p = -rhs  (SPD on the mean-free space)
         self.solver = api.CgSolver()
+        self.pressure_preconditioner = pressure_preconditioner
+        if pressure_preconditioner == "amg":
+            before = ctx.counter("option_spmv_dict")
+            ctx.set_option("spmv_dict", 0)
+            try:
+                self.L_N64 = api.StencilMatrix.from_face_graph(ctx, ops.g_neumann)
+            finally:
+                ctx.set_option("spmv_dict", before)
+            self.solver.pre_op = api.AmgPreconditioner(nullspace="constant", matrix=self.L_N64)
+            self.solver.pre_op.build(self.p, self.rhs, self.A_p)  # once, here: not inside the first step
         # The reference's relative test is relative to the INITIAL residual |b - A x0| (Solver.hpp:135),
         # which a warm start makes tiny; a warm-started loop therefore stops on the absolute test, set
         # per step to `tol` x |rhs|.

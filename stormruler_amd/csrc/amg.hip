@@ -13,13 +13,20 @@
 //                           of 64 rows, one row per lane, acc = fma(w_k, x[c_k], acc) in slot order.
 //   amg_coarse_kernel       z = Ainv r, dense: one wavefront per row, lane j takes columns j, j + 64, ... by fma, then the
 //                           wavefront's sum (wave_device.hpp).
+// A null-space object (storm_hip_amg_create_nullspace) is B = Pi V Pi, Pi = I - 1 1^T / n on level 0; streaming kernels of
+// blas1.hip's shape, the one reduction finished by tickets inside the kernel that formed its partial sums:
+//   amg_mean_kernel         S = sum v, then mu = S / n into the object's slot by the block that drew the last ticket
+//   amg_shift_kernel        out_i = v_i - mu
+//   amg_axpy_mean_kernel    level 0's closing z = z + e with S of the stored z in the same launch (option amg_fused)
 // Every kernel loads the context's api_done word first and tests it before its first store.
 #include <chrono>
 #include <cmath>
 #include <cstring>
 
 #include "amg.hpp"
+#include "blas1_device.hpp"
 #include "sell_device.hpp"
+#include "ticket_device.hpp"
 #include "wave_device.hpp"
 
 namespace storm {
@@ -104,6 +111,126 @@ __global__ __launch_bounds__(kBlock) void amg_coarse_kernel(const double *__rest
   if (lane == 0 && !done_flag) z[row] = acc;
 }
 
+// ---- the projection Pi = I - 1 1^T / n of a null-space object ---------------------------------------------------------------
+// This thread's share of S = sum_i v_i on the stream_blocks(n) grid (blas1.hip's shape: a block owns 2048 consecutive
+// entries per trip, a thread four 16-byte words of them; the odd last entry goes to thread 0 of block 0 behind its words).
+// AXPY: v_i = z_i + e_i is formed and STORED first and the stored value is what is summed -- ONE loop for amg_mean_kernel and
+// amg_axpy_mean_kernel, so the partition and the order, hence the bits of S, do not depend on which of them ran.
+template <bool AXPY>
+__device__ __forceinline__ double amg_sum_accumulate(int64_t n, double *z, const double *__restrict__ e, int nt) {
+  const int64_t n2 = n >> 1;
+  double2v *z2 = reinterpret_cast<double2v *>(z);
+  const double2v *__restrict__ e2 = reinterpret_cast<const double2v *>(e);
+  double acc = 0.0;
+  nt_dispatch(nt, [&](auto nt) {
+    for (int64_t base = (int64_t)blockIdx.x * (kBlock * kUnroll) + threadIdx.x; base < n2;
+         base += (int64_t)gridDim.x * (kBlock * kUnroll)) {
+      double2v v[kUnroll];
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int64_t i = base + u * kBlock;
+        if (i < n2) {
+          v[u] = ld2(z2 + i, nt);
+          if (AXPY) v[u] = v[u] + ld2(e2 + i, nt);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int64_t i = base + u * kBlock;
+        if (i < n2) {
+          if (AXPY) st2(z2 + i, v[u], nt);
+          acc += v[u].x;
+          acc += v[u].y;
+        }
+      }
+    }
+  });
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    double last = z[n - 1];
+    if (AXPY) last = last + e[n - 1], z[n - 1] = last;
+    acc += last;
+  }
+  return acc;
+}
+
+// The block sum, the two-level ticket fold (ticket_device.hpp), and mu = S / n by the block that drew the last ticket.
+__device__ __forceinline__ void amg_mean_finish(double acc, int64_t n, const TicketArgs &t, double *mu) {
+  __shared__ double lds[1][4];
+  const double a1[1] = {acc};
+  double mine[1], total[1];
+  block_sum_multi<1>(a1, lds, mine);
+  if (threadIdx.x >= kWave) return;
+  if (ticket_reduce_wave0<1>(t, mine, 1, blockIdx.x, gridDim.x, total) && threadIdx.x == 0) *mu = __ddiv_rn(total[0], (double)n);
+}
+
+// (the done flag is the same for every block of a launch -- it is written by kernels earlier on the stream only -- so either
+//  all blocks draw their tickets or none does)
+__global__ __launch_bounds__(kBlock) void amg_mean_kernel(int64_t n, const double *v, TicketArgs t, double *mu, const int *done, int nt) {
+  const int done_flag = done ? *done : 0;
+  if (done_flag) return;
+  amg_mean_finish(amg_sum_accumulate<false>(n, const_cast<double *>(v), nullptr, nt), n, t, mu);
+}
+
+__global__ __launch_bounds__(kBlock) void amg_axpy_mean_kernel(int64_t n, double *z, const double *e, TicketArgs t, double *mu,
+                                                               const int *done, int nt) {
+  const int done_flag = done ? *done : 0;
+  if (done_flag) return;
+  amg_mean_finish(amg_sum_accumulate<true>(n, z, e, nt), n, t, mu);
+}
+
+// out_i = v_i - mu (out == v: in place)
+__global__ __launch_bounds__(kBlock) void amg_shift_kernel(int64_t n, const double *v, const double *mu, double *out, const int *done,
+                                                           int nt) {
+  const int done_flag = done ? *done : 0;
+  if (done_flag) return;
+  const double m = *mu;
+  const int64_t n2 = n >> 1;
+  const double2v *v2 = reinterpret_cast<const double2v *>(v);
+  double2v *o2 = reinterpret_cast<double2v *>(out);
+  nt_dispatch(nt, [&](auto nt) {
+    for (int64_t base = (int64_t)blockIdx.x * (kBlock * kUnroll) + threadIdx.x; base < n2;
+         base += (int64_t)gridDim.x * (kBlock * kUnroll)) {
+      double2v w[kUnroll];
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int64_t i = base + u * kBlock;
+        if (i < n2) w[u] = ld2(v2 + i, nt);
+      }
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int64_t i = base + u * kBlock;
+        if (i < n2) st2(o2 + i, w[u] - m, nt);
+      }
+    }
+  });
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) out[n - 1] = v[n - 1] - m;
+}
+
+static TicketArgs amg_tickets(const storm_hip_amg *h) { return TicketArgs{h->d_mean_cnt, h->d_mean_part1, h->d_mean_part2}; }
+
+// mu[slot] = fl(sum(v) / n); with e: v = v + e first (the closing statement of level 0)
+static int amg_mean(const storm_hip_amg *h, storm_hip_vec *v, const storm_hip_vec *e, int slot) {
+  storm_hip_ctx *c = h->ctx;
+  const int64_t n = v->n_owned;
+  const dim3 grid(stream_blocks(n)), block(kBlock);
+  if (e)
+    hipLaunchKernelGGL(amg_axpy_mean_kernel, grid, block, 0, c->stream, n, v->d, e->d, amg_tickets(h), h->d_mu + slot, c->api_done,
+                       stream_nt(c, n));
+  else
+    hipLaunchKernelGGL(amg_mean_kernel, grid, block, 0, c->stream, n, v->d, amg_tickets(h), h->d_mu + slot, c->api_done, stream_nt(c, n));
+  HIP_TRY(hipGetLastError());
+  return STORM_HIP_OK;
+}
+
+static int amg_shift(const storm_hip_amg *h, const storm_hip_vec *v, int slot, storm_hip_vec *out) {
+  storm_hip_ctx *c = h->ctx;
+  const int64_t n = v->n_owned;
+  hipLaunchKernelGGL(amg_shift_kernel, dim3(stream_blocks(n)), dim3(kBlock), 0, c->stream, n, v->d, h->d_mu + slot, out->d, c->api_done,
+                     stream_nt(c, n));
+  HIP_TRY(hipGetLastError());
+  return STORM_HIP_OK;
+}
+
 int op_create_csr_fp64(storm_hip_ctx *c, int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
                        bool source_map, storm_hip_op **out);  // spmv_build.hip
 
@@ -169,6 +296,14 @@ static int amg_cycle(const storm_hip_amg *h, size_t l, const storm_hip_vec *r, s
   STORM_TRY(amg_transfer(h, L.P, true, N.z, z));
   STORM_TRY(amg_residual(h, L, r, z, L.t));
   STORM_TRY(storm_hip_cheb_apply(L.cheb, L.t, L.e));
+  if (l == 0 && h->nullspace) {  // z = z + e and the mean of z: one launch, or the statement and amg_mean_kernel
+    if (c->opt_amg_fused != 0) {
+      ++c->n_amg_fused_projections;
+      return amg_mean(h, z, L.e, 1);
+    }
+    STORM_TRY(storm_hip_axpy(z, 1.0, L.e));
+    return amg_mean(h, z, nullptr, 1);
+  }
   return storm_hip_axpy(z, 1.0, L.e);
 }
 
@@ -319,6 +454,19 @@ int amg_build_device(storm_hip_amg *h, storm_hip_op *op0) {
   }
   h->n_coarse = h->hier->levels.back().A.n_rows;
   STORM_TRY(amg_upload(&h->d_ainv, h->hier->ainv.data(), h->hier->ainv.size(), &h->device_bytes));
+  if (h->hier->nullspace) {  // the projected residual, the two means, the mean's own ticket buffers (counters start at 0)
+    const int64_t n = h->levels[0].n;
+    const size_t nb = (size_t)stream_blocks(n), ng = (nb + kTicketGroup - 1) / kTicketGroup;
+    h->nullspace = 1;
+    STORM_TRY(storm_hip_vec_create(c, n, 0, &h->rp));
+    h->device_bytes += (int64_t)h->rp->bytes;
+    const std::vector<double> zeros(std::max(nb, (size_t)2), 0.0);
+    const std::vector<int> zero_cnt((1 + ng) * kTicketStride, 0);
+    STORM_TRY(amg_upload(&h->d_mu, zeros.data(), 2, &h->device_bytes));
+    STORM_TRY(amg_upload(&h->d_mean_part1, zeros.data(), nb, &h->device_bytes));
+    STORM_TRY(amg_upload(&h->d_mean_part2, zeros.data(), ng, &h->device_bytes));
+    STORM_TRY(amg_upload(&h->d_mean_cnt, zero_cnt.data(), zero_cnt.size(), &h->device_bytes));
+  }
   return STORM_HIP_OK;
 }
 
@@ -376,6 +524,8 @@ int storm_hip_amg_destroy(storm_hip_amg *h) {
     (void)storm_hip_op_destroy(L.own_op);
   }
   (void)hipFree(h->d_ainv);
+  (void)storm_hip_vec_destroy(h->rp);
+  (void)hipFree(h->d_mu), (void)hipFree(h->d_mean_part1), (void)hipFree(h->d_mean_part2), (void)hipFree(h->d_mean_cnt);
   amg_refresh_free(h);
   (void)storm_hip_amg_hierarchy_destroy(h->hier);
   delete h;
@@ -399,7 +549,29 @@ int storm_hip_amg_apply(const storm_hip_amg *h, const storm_hip_vec *r, storm_hi
     ~Depth() { --c->callback_depth; }
   } depth(c);
   ++c->n_amg_applies;
-  return amg_cycle(h, 0, r, z);
+  if (!h->nullspace) return amg_cycle(h, 0, r, z);
+  // B = Pi V Pi: rp = r - mean(r); z = V(rp), whose closing statement leaves mean(z) in the second slot; z = z - mean(z)
+  c->n_amg_projections += 2;
+  STORM_TRY(amg_mean(h, const_cast<storm_hip_vec *>(r), nullptr, 0));  // (reads r only)
+  STORM_TRY(amg_shift(h, r, 0, h->rp));
+  STORM_TRY(amg_cycle(h, 0, h->rp, z));
+  if (h->levels.size() == 1) STORM_TRY(amg_mean(h, z, nullptr, 1));  // one level: z = Ainv rp has no closing statement
+  return amg_shift(h, z, 1, z);
+}
+
+int storm_hip_amg_project(const storm_hip_amg *h, storm_hip_vec *v) {
+  STORM_REQUIRE(h && v, "amg_project: null argument");
+  if (!h->nullspace)
+    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "amg_project: the object was not created by storm_hip_amg_create_nullspace (it has no "
+                                        "null space to project out)");
+  STORM_REQUIRE(v->ctx == h->ctx, "amg_project: context mismatch");
+  STORM_REQUIRE(v->n_owned == h->op->n_rows, "amg_project: operator has %lld rows, v %lld", (long long)h->op->n_rows, (long long)v->n_owned);
+  storm_hip_ctx *c = h->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  STORM_TRY(lazy_sync(c));
+  ++c->n_amg_projections;
+  STORM_TRY(amg_mean(h, v, nullptr, 0));
+  return amg_shift(h, v, 0, v);
 }
 
 static int amg_level_check(const storm_hip_amg *h, int level, const storm_hip_vec *fine, const storm_hip_vec *coarse, const char *who) {
@@ -446,6 +618,7 @@ int storm_hip_amg_get(const storm_hip_amg *h, const char *key, double *value) {
   else if (!strcmp(key, "upload_seconds")) *value = h->upload_seconds;
   else if (!strcmp(key, "refresh_bytes")) *value = (double)h->refresh_bytes;
   else if (!strcmp(key, "refreshable")) *value = h->refresh.empty() ? 0.0 : 1.0;
+  else if (!strcmp(key, "nullspace")) *value = h->nullspace ? 1.0 : 0.0;
   else if (!strcmp(key, "smoother_degree")) *value = (double)h->hier->params.smoother_degree;
   else if (!strcmp(key, "reduced")) *value = (double)h->hier->params.reduced_records;
   else return storm_hip_amg_hierarchy_get(h->hier, key, value);

@@ -35,6 +35,8 @@ struct AmgTransferImage {
 };
 int amg_pack_transfer(const AmgCsr &T, AmgTransferImage *img);
 int amg_dense_inverse(const AmgCsr &A, std::vector<double> *inv_out);  // step 7 (amg_setup.hip)
+// N3 of a null-space hierarchy instead of step 7: Ainv = Pi (A + (s / n) 1 1^T)^-1 Pi, s = max a_ii (0 for one row)
+int amg_coarse_nullspace(const AmgCsr &A, std::vector<double> *inv_out, double *shift_out);
 
 // What a refresh of level l needs beside the structural hierarchy, built once on the host (amg_setup.hip, no device):
 // r_of[k]: the entry of P_l that entry k of R_l = P_l^T carries; p_slot / r_slot: for every slot of the transfer records of
@@ -54,6 +56,8 @@ struct storm_hip_amg_hierarchy {
   std::vector<double> ainv;  // the coarsest level's inverse, row-major
   double setup_seconds = 0.0;
   bool structural = false;  // storm_hip_amg_setup_csr_structural: no pattern depends on a value
+  bool nullspace = false;   // storm_hip_amg_setup_csr_nullspace: the constants are A's kernel (N1 - N3)
+  double coarse_shift = 0.0;  // N3's s (0 on a plain hierarchy and on a one-row coarsest level)
 };
 
 struct storm_hip_amg {
@@ -112,6 +116,13 @@ struct storm_hip_amg {
   double *d_scalars = nullptr;  // [0]: the folded maximum of a level's ratio
   int *d_bad = nullptr;         // the lowest row whose filtered diagonal is zero or non-finite (INT32_MAX: none)
   int invalid = 0;              // a refresh failed: apply and solves return STORM_HIP_E_INVALID until one succeeds
+  // storm_hip_amg_create_nullspace: B = Pi V Pi.  The projected residual, the two means (d_mu[0]: of r, or of a projected
+  // vector; d_mu[1]: of z) and the object's own ticket buffers (the context's may hold a solver's partials across an apply).
+  int nullspace = 0;
+  storm_hip_vec *rp = nullptr;
+  double *d_mu = nullptr;
+  int *d_mean_cnt = nullptr;
+  double *d_mean_part1 = nullptr, *d_mean_part2 = nullptr;
 };
 
 namespace storm {

@@ -484,7 +484,8 @@ static int rf_run(storm_hip_amg *h) {
     for (double v : Ac.val)
       if (!std::isfinite(v)) STORM_FAIL(STORM_HIP_E_INVALID, "amg_refresh: level %d (the coarsest) has a non-finite entry", (int)nl - 1);
     std::vector<double> inv;
-    STORM_TRY(amg_dense_inverse(Ac, &inv));
+    if (h->hier->nullspace) STORM_TRY(amg_coarse_nullspace(Ac, &inv, &h->hier->coarse_shift));  // N3 (N1 and N2 are the build's)
+    else STORM_TRY(amg_dense_inverse(Ac, &inv));
     HIP_TRY(hipMemcpyAsync(h->d_ainv, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // (inv leaves scope)
   }
@@ -541,6 +542,40 @@ int storm_hip_amg_create_refreshable(storm_hip_op *op, double alpha, double beta
   const auto t0 = std::chrono::steady_clock::now();
   int st = amg_build_device(h, op);
   if (st == STORM_HIP_OK) st = rf_build(h);
+  if (st != STORM_HIP_OK) {
+    (void)storm_hip_amg_destroy(h);
+    return st;
+  }
+  h->upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  *out = h;
+  return STORM_HIP_OK;
+}
+
+int storm_hip_amg_create_nullspace(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params, int refreshable,
+                                   storm_hip_amg **out) {
+  STORM_REQUIRE(op && out, "amg_create_nullspace: null argument");
+  *out = nullptr;
+  const bool rf = refreshable != 0;
+  if (rf && !op->updatable)
+    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "amg_create_nullspace: refreshable, but the operator (%lld rows) was not created by "
+                                        "storm_hip_op_create_from_face_weights_updatable (its source map says which slots are real)",
+               (long long)op->n_rows);
+  STORM_TRY(amg_create_checks(op, alpha, beta, "amg_create_nullspace"));
+  if (rf)
+    STORM_REQUIRE(op->pack_bytes < ((int64_t)1 << 33), "amg_create_nullspace: %lld bytes of records exceed the int32 slot maps", (long long)op->pack_bytes);
+  storm_hip_ctx *c = op->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  STORM_TRY(lazy_sync(c));
+  std::vector<int64_t> ptr, col;
+  std::vector<double> val;
+  STORM_TRY(amg_decode(op, alpha, beta, rf, &ptr, &col, &val));
+  storm_hip_amg_hierarchy *hier = nullptr;
+  STORM_TRY(storm_hip_amg_setup_csr_nullspace(op->n_rows, ptr.data(), col.data(), val.data(), params, rf ? 1 : 0, &hier));
+  storm_hip_amg *h = new storm_hip_amg();
+  h->ctx = c, h->op = op, h->alpha = alpha, h->beta = beta, h->hier = hier;
+  const auto t0 = std::chrono::steady_clock::now();
+  int st = amg_build_device(h, op);
+  if (st == STORM_HIP_OK && rf) st = rf_build(h);
   if (st != STORM_HIP_OK) {
     (void)storm_hip_amg_destroy(h);
     return st;

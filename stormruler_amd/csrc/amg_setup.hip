@@ -261,22 +261,41 @@ static AmgCsr amg_spgemm(const AmgCsr &X, const AmgCsr &Y, bool keep_diag, bool 
   return Cm;
 }
 
-// Step 7: Gauss-Jordan with partial pivoting on [A | I].
-int amg_dense_inverse(const AmgCsr &A, std::vector<double> *inv_out) {
+// Step 7: Gauss-Jordan with partial pivoting on [A | I].  shift is added to every entry of A and a pivot below floor is
+// refused (N3 of a null-space hierarchy).  The plain step 7 passes 0 and 0: a zero pivot is refused, and so is one below
+// 2^-40 max_i |a_ii| -- what the elimination of a SINGULAR matrix leaves in floating point (a few n eps of the scale: 1e-15 ..
+// 7e-15 on the pure-Neumann boxes of tests/test_amg_nullspace_host.py, whose "inverse" then has entries of 1e11 .. 1e13),
+// eleven orders of magnitude below the smallest pivot of the definite test operators (0.07).
+static int amg_gauss_jordan(const AmgCsr &A, double shift, double floor, std::vector<double> *inv_out) {
   const int64_t n = A.n_rows;
-  std::vector<double> a((size_t)(n * n), 0.0), b((size_t)(n * n), 0.0);
+  const bool ns = floor > 0.0;
+  double scale = 0.0;
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t k = A.ptr[(size_t)i]; k < A.ptr[(size_t)i + 1]; ++k)
+      if (A.col[(size_t)k] == i && std::isfinite(A.val[(size_t)k])) scale = std::max(scale, std::fabs(A.val[(size_t)k]));
+  const double plain_floor = std::ldexp(scale, -40);
+  std::vector<double> a((size_t)(n * n), shift), b((size_t)(n * n), 0.0);
   for (int64_t i = 0; i < n; ++i) {
     b[(size_t)(i * n + i)] = 1.0;
-    for (int64_t k = A.ptr[(size_t)i]; k < A.ptr[(size_t)i + 1]; ++k) a[(size_t)(i * n + A.col[(size_t)k])] = A.val[(size_t)k];
+    for (int64_t k = A.ptr[(size_t)i]; k < A.ptr[(size_t)i + 1]; ++k) a[(size_t)(i * n + A.col[(size_t)k])] = ns ? A.val[(size_t)k] + shift : A.val[(size_t)k];
   }
   for (int64_t c = 0; c < n; ++c) {
     int64_t p = c;
     for (int64_t i = c + 1; i < n; ++i)
       if (std::fabs(a[(size_t)(i * n + c)]) > std::fabs(a[(size_t)(p * n + c)])) p = i;
     const double piv = a[(size_t)(p * n + c)];
+    if (ns && (!std::isfinite(piv) || std::fabs(piv) < floor))
+      STORM_FAIL(STORM_HIP_E_INVALID, "amg_setup: the coarsest level (%lld rows) is singular beyond the constants: pivot %g in "
+                                      "column %lld is below 2^-30 of the largest diagonal entry", (long long)n, piv, (long long)c);
     if (piv == 0.0 || !std::isfinite(piv))
       STORM_FAIL(STORM_HIP_E_INVALID, "amg_setup: the coarsest level (%lld rows) is singular: zero pivot in column %lld (a "
-                                      "pure-Neumann operator, for instance, has no inverse)", (long long)n, (long long)c);
+                                      "pure-Neumann operator, for instance, has no inverse; storm_hip_amg_setup_csr_nullspace "
+                                      "/ storm_hip_amg_create_nullspace take one)", (long long)n, (long long)c);
+    if (!ns && std::fabs(piv) < plain_floor)
+      STORM_FAIL(STORM_HIP_E_INVALID, "amg_setup: the coarsest level (%lld rows) is singular to working precision: pivot %g in "
+                                      "column %lld is below 2^-40 of the largest diagonal entry (a pure-Neumann operator, for "
+                                      "instance, has no inverse; storm_hip_amg_setup_csr_nullspace / "
+                                      "storm_hip_amg_create_nullspace take one)", (long long)n, piv, (long long)c);
     if (p != c)
       for (int64_t j = 0; j < n; ++j) std::swap(a[(size_t)(p * n + j)], a[(size_t)(c * n + j)]), std::swap(b[(size_t)(p * n + j)], b[(size_t)(c * n + j)]);
     for (int64_t j = 0; j < n; ++j) a[(size_t)(c * n + j)] /= piv, b[(size_t)(c * n + j)] /= piv;
@@ -288,10 +307,90 @@ int amg_dense_inverse(const AmgCsr &A, std::vector<double> *inv_out) {
     }
   }
   for (double v : b)
-    if (!std::isfinite(v))
+    if (!std::isfinite(v)) {
+      if (ns)
+        STORM_FAIL(STORM_HIP_E_INVALID, "amg_setup: the coarsest level (%lld rows) is singular beyond the constants: the "
+                                        "inverse of the shifted matrix has a non-finite entry", (long long)n);
       STORM_FAIL(STORM_HIP_E_INVALID, "amg_setup: the coarsest level (%lld rows) is singular: its inverse has a non-finite "
                                       "entry (a pure-Neumann operator, for instance, has no inverse)", (long long)n);
+    }
   *inv_out = std::move(b);
+  return STORM_HIP_OK;
+}
+
+int amg_dense_inverse(const AmgCsr &A, std::vector<double> *inv_out) { return amg_gauss_jordan(A, 0.0, 0.0, inv_out); }
+
+// N3: the coarsest level of a null-space hierarchy.  One row: Ainv = (0).  Otherwise s = max a_ii, G = A + (s / n) 1 1^T,
+// Ainv = Pi G^-1 Pi with Pi = I - 1 1^T / n: every column less its mean (rows summed in ascending order), then every row.
+int amg_coarse_nullspace(const AmgCsr &A, std::vector<double> *inv_out, double *shift_out) {
+  const int64_t n = A.n_rows;
+  *shift_out = 0.0;
+  if (n == 1) {
+    inv_out->assign(1, 0.0);
+    return STORM_HIP_OK;
+  }
+  double s = -HUGE_VAL;
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t k = A.ptr[(size_t)i]; k < A.ptr[(size_t)i + 1]; ++k) {
+      if (!std::isfinite(A.val[(size_t)k]))
+        STORM_FAIL(STORM_HIP_E_INVALID, "amg_setup: the coarsest level (%lld rows) has a non-finite entry", (long long)n);
+      if (A.col[(size_t)k] == i) s = std::max(s, A.val[(size_t)k]);
+    }
+  if (!(s > 0.0))
+    STORM_FAIL(STORM_HIP_E_INVALID, "amg_setup: the coarsest level (%lld rows) has no positive diagonal entry (max a_ii = %g)",
+               (long long)n, s);
+  std::vector<double> g;
+  STORM_TRY(amg_gauss_jordan(A, s / (double)n, std::ldexp(s, -30), &g));
+  for (int64_t j = 0; j < n; ++j) {
+    double sum = 0.0;
+    for (int64_t i = 0; i < n; ++i) sum += g[(size_t)(i * n + j)];
+    const double mean = sum / (double)n;
+    for (int64_t i = 0; i < n; ++i) g[(size_t)(i * n + j)] -= mean;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    double sum = 0.0;
+    for (int64_t j = 0; j < n; ++j) sum += g[(size_t)(i * n + j)];
+    const double mean = sum / (double)n;
+    for (int64_t j = 0; j < n; ++j) g[(size_t)(i * n + j)] -= mean;
+  }
+  *shift_out = s;
+  *inv_out = std::move(g);
+  return STORM_HIP_OK;
+}
+
+// N1: the constants are in the kernel of level 0 -- every row sum is zero to 2^-40 of the row's absolute sum.
+static int amg_check_row_sums(const AmgCsr &A) {
+  for (int64_t i = 0; i < A.n_rows; ++i) {
+    double sum = 0.0, sum_abs = 0.0;
+    for (int64_t k = A.ptr[(size_t)i]; k < A.ptr[(size_t)i + 1]; ++k) sum += A.val[(size_t)k], sum_abs += std::fabs(A.val[(size_t)k]);
+    if (!(std::fabs(sum) <= std::ldexp(sum_abs, -40)))
+      STORM_FAIL(STORM_HIP_E_INVALID, "amg_setup: row %lld sums to %g (its absolute sum is %g): the operator does not have the "
+                                      "constants in its kernel (a Dirichlet face or beta != 0: use storm_hip_amg_setup_csr / "
+                                      "storm_hip_amg_create)", (long long)i, sum, sum_abs);
+  }
+  return STORM_HIP_OK;
+}
+
+// N2: the graph of the non-zero off-diagonal entries of level 0, both directions joined, is connected.
+static int amg_check_connected(const AmgCsr &A) {
+  const int64_t n = A.n_rows;
+  std::vector<int> parent((size_t)n);
+  for (int64_t i = 0; i < n; ++i) parent[(size_t)i] = (int)i;
+  auto find = [&](int x) {
+    while (parent[(size_t)x] != x) x = parent[(size_t)x] = parent[(size_t)parent[(size_t)x]];
+    return x;
+  };
+  int64_t components = n;
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t k = A.ptr[(size_t)i]; k < A.ptr[(size_t)i + 1]; ++k) {
+      if (A.col[(size_t)k] == i || A.val[(size_t)k] == 0.0) continue;
+      const int a = find((int)i), b = find(A.col[(size_t)k]);
+      if (a != b) parent[(size_t)std::max(a, b)] = std::min(a, b), --components;
+    }
+  if (components != 1)
+    STORM_FAIL(STORM_HIP_E_INVALID, "amg_setup: the operator's graph has %lld connected components; the null-space setup "
+                                    "takes one (every component adds a kernel vector the constants do not span)",
+               (long long)components);
   return STORM_HIP_OK;
 }
 
@@ -345,6 +444,7 @@ static int amg_build(storm_hip_amg_hierarchy *h) {
     next.A = amg_spgemm(L.R, amg_spgemm(L.A, L.P, false, h->structural), true, h->structural);
     h->levels.push_back(std::move(next));  // (invalidates L)
   }
+  if (h->nullspace) return amg_coarse_nullspace(h->levels.back().A, &h->ainv, &h->coarse_shift);  // N3
   return amg_dense_inverse(h->levels.back().A, &h->ainv);
 }
 
@@ -446,7 +546,7 @@ void storm_hip_amg_params_default(storm_hip_amg_params *p) {
 }
 
 static int amg_setup(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
-                     const storm_hip_amg_params *params, bool structural, storm_hip_amg_hierarchy **out) {
+                     const storm_hip_amg_params *params, bool structural, bool nullspace, storm_hip_amg_hierarchy **out) {
   STORM_REQUIRE(row_ptr && out && (n_rows < 1 || row_ptr[n_rows] == 0 || (col && val)), "amg_setup: null argument");
   *out = nullptr;
   storm_hip_amg_params p;
@@ -455,9 +555,11 @@ static int amg_setup(int64_t n_rows, const int64_t *row_ptr, const int64_t *col,
   STORM_TRY(amg_check_params(&p, "amg_setup"));
   const auto t0 = std::chrono::steady_clock::now();
   auto *h = new storm_hip_amg_hierarchy();
-  h->params = p, h->structural = structural;
+  h->params = p, h->structural = structural, h->nullspace = nullspace;
   h->levels.emplace_back();
   int st = amg_normalise(n_rows, row_ptr, col, val, structural, &h->levels[0].A);
+  if (st == STORM_HIP_OK && nullspace) st = amg_check_row_sums(h->levels[0].A);
+  if (st == STORM_HIP_OK && nullspace) st = amg_check_connected(h->levels[0].A);
   if (st == STORM_HIP_OK) st = amg_build(h);
   if (st != STORM_HIP_OK) {
     delete h;
@@ -470,12 +572,17 @@ static int amg_setup(int64_t n_rows, const int64_t *row_ptr, const int64_t *col,
 
 int storm_hip_amg_setup_csr(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
                             const storm_hip_amg_params *params, storm_hip_amg_hierarchy **out) {
-  return amg_setup(n_rows, row_ptr, col, val, params, false, out);
+  return amg_setup(n_rows, row_ptr, col, val, params, false, false, out);
 }
 
 int storm_hip_amg_setup_csr_structural(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
                                        const storm_hip_amg_params *params, storm_hip_amg_hierarchy **out) {
-  return amg_setup(n_rows, row_ptr, col, val, params, true, out);
+  return amg_setup(n_rows, row_ptr, col, val, params, true, false, out);
+}
+
+int storm_hip_amg_setup_csr_nullspace(int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
+                                      const storm_hip_amg_params *params, int structural, storm_hip_amg_hierarchy **out) {
+  return amg_setup(n_rows, row_ptr, col, val, params, structural != 0, true, out);
 }
 
 int storm_hip_amg_hierarchy_get_strong(const storm_hip_amg_hierarchy *h, int level, uint8_t *mask) {
@@ -544,6 +651,8 @@ int storm_hip_amg_hierarchy_get(const storm_hip_amg_hierarchy *h, const char *ke
   else if (!strcmp(key, "grid_complexity")) *value = rows / (double)h->levels[0].A.n_rows;
   else if (!strcmp(key, "setup_seconds")) *value = h->setup_seconds;
   else if (!strcmp(key, "structural")) *value = h->structural ? 1.0 : 0.0;
+  else if (!strcmp(key, "nullspace")) *value = h->nullspace ? 1.0 : 0.0;
+  else if (!strcmp(key, "coarse_shift")) *value = h->coarse_shift;
   else STORM_FAIL(STORM_HIP_E_INVALID, "amg_hierarchy_get: unknown key '%s'", key);
   return STORM_HIP_OK;
 }

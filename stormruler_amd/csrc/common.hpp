@@ -270,6 +270,7 @@ struct storm_hip_ctx {
   int64_t opt_amg_fused = 1;  // storm_hip_amg_apply: the fused residual kernel where it applies (fp64 records, no CSR tail); 0: the two library statements
   int64_t n_amg_applies = 0, n_amg_fused_residuals = 0, n_amg_statement_residuals = 0;  // amg.hip: applies; which path a residual took
   int64_t n_amg_refreshes = 0;  // storm_hip_amg_refresh (amg_refresh.hip)
+  int64_t n_amg_projections = 0, n_amg_fused_projections = 0;  // a null-space object's Pi (two per apply); the closing axpy fused with its sum
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_cg_pz_consumer_folds = 0;  // ... of those, the solves whose plane march folded <p,z> itself (option cg_pz_fold)

@@ -259,6 +259,9 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "amg_fused_residuals")) *value = c->n_amg_fused_residuals;
   else if (!strcmp(key, "amg_statement_residuals")) *value = c->n_amg_statement_residuals;
   else if (!strcmp(key, "amg_refreshes")) *value = c->n_amg_refreshes;
+  else if (!strcmp(key, "option_spmv_dict")) *value = c->opt_spmv_dict;  // (the option's value, for a caller that restores it)
+  else if (!strcmp(key, "amg_projections")) *value = c->n_amg_projections;
+  else if (!strcmp(key, "amg_fused_projections")) *value = c->n_amg_fused_projections;
   else if (!strcmp(key, "op_reduced_builds")) *value = c->n_op_reduced_builds;
   else if (!strcmp(key, "op_reduced_refreshes")) *value = c->n_op_reduced_refreshes;
   else if (!strcmp(key, "jfnk_inner_solves")) *value = c->n_jfnk_inner_solves;

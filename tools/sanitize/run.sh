@@ -10,7 +10,9 @@
 # 4. pack_digest: the operator packer on the corpus of tests/test_op_pack.py, threaded down to chunks of 5 rows;
 # 5. pack_srcmap: the source map of updatable operators decoded slot by slot (tests/test_op_srcmap.py), 1, 3 and 7 threads;
 # 6. amg_setup: the multigrid preconditioner's host setup (csrc/amg_setup.hip): hierarchies, transfer records, refusals;
-# 7. amg_structural: the structural setup and the host-built maps of a refreshable object, each checked against its hierarchy.
+# 7. amg_structural: the structural setup and the host-built maps of a refreshable object, each checked against its hierarchy;
+# 8. amg_nullspace: the null-space setup (storm_hip_amg_setup_csr_nullspace): row sums, connectivity, the coarsest level's
+#    pseudo-inverse on a chain, Neumann boxes, a two-component operator and a one-row coarsest level.
 set -eu
 HERE=$(cd "$(dirname "$0")" && pwd)
 ROOT=$(cd "$HERE/../.." && pwd)
@@ -33,6 +35,7 @@ $CXX "$HERE/pack_digest.cpp" "$WORK/op_pack.o" -o "$WORK/pack_digest" -lpthread
 $CXX "$HERE/pack_srcmap.cpp" "$WORK/op_pack.o" -o "$WORK/pack_srcmap" -lpthread
 $CXX "$HERE/amg_setup.cpp" -x c++ "$ROOT/stormruler_amd/csrc/amg_setup.hip" -o "$WORK/amg_setup" -lpthread
 $CXX "$HERE/amg_structural.cpp" -x c++ "$ROOT/stormruler_amd/csrc/amg_setup.hip" -o "$WORK/amg_structural" -lpthread
+$CXX "$HERE/amg_nullspace.cpp" -x c++ "$ROOT/stormruler_amd/csrc/amg_setup.hip" -o "$WORK/amg_nullspace" -lpthread
 export STORM_HIP_BUILD_THREADS=${STORM_HIP_BUILD_THREADS:-4}
 # (ThreadSanitizer: a box large enough for the threaded parse / sort / bisection paths -- 384 000 tetrahedra)
 EDGE=${BOX_EDGE:-9}
@@ -45,4 +48,5 @@ STORM_HIP_BUILD_MIN_CHUNK=5 "$WORK/pack_digest" | tail -1
 "$WORK/pack_srcmap" "$ROOT" | tail -1
 "$WORK/amg_setup" | tail -1
 "$WORK/amg_structural" | tail -1
+"$WORK/amg_nullspace" | tail -1
 echo "sanitizers: clean"
