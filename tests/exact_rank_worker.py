@@ -5,8 +5,10 @@ box (integer stencil coefficients, tests/exact_ref.py) and connects the host-sta
 STORM_TRANSPORT=ipc, the peer-window transport.  On integer data every all-reduce is exact whatever its order, so each
 rank must reproduce the closed forms of the whole box: the global <b,b>, <b,z> and z = A b bitwise, CG's x1 =
 fl(fl(rr/pz) * b_local) bitwise, history[0] bitwise and history[1] of CG, BiCGStab and GMRES(30) within the derived
-tolerance -- on fp64 records and on format 4 (mixed records on a slab).  On the host-staged transport the engine's CGS
-and TFQMR also run to K = 2 against exact_ref.Pins of the whole box."""
+tolerance -- on fp64 records and on format 4 (mixed records on a slab).  CG and BiCGStab also run K = 4 iterations
+against the step pins of the whole box (exact_ref.StepPins): history[0..4] on every rank, and on rank 0 the residual of
+the x gathered from all ranks (and, on a box of at most 20 000 rows, that x against the exact x_4).  On the host-staged
+transport the engine's CGS and TFQMR also run to K = 2 against exact_ref.Pins of the whole box."""
 import json
 import math
 import os
@@ -23,9 +25,9 @@ import exact_ref as er  # noqa: E402
 from stormruler_amd import api, dist, mesh, partition  # noqa: E402
 
 
-def _solve(ctx, cls, mat, b, n, n_halo, counted=True, **knobs):
+def _solve(ctx, cls, mat, b, n, n_halo, counted=True, iters=1, **knobs):
     s = cls()
-    s.num_iterations, s.absolute_error_tolerance, s.relative_error_tolerance = 1, 0.0, 0.0
+    s.num_iterations, s.absolute_error_tolerance, s.relative_error_tolerance = iters, 0.0, 0.0
     s.record_history = True
     for k, v in knobs.items():
         setattr(s, k, v)
@@ -33,7 +35,7 @@ def _solve(ctx, cls, mat, b, n, n_halo, counted=True, **knobs):
     before = ctx.counter("throughput_solves"), ctx.counter("cg_fused_steps")
     s.solve(x, b, api.HipStencilOperator(mat, -1.0, 0.0))
     # (a partitioned operator: the throughput loops, with their all-reduces; the fused GMRES loop counts no path)
-    assert ctx.counter("throughput_solves") == before[0] + int(counted) and s.iteration == 1 and s.path_fallback == 0
+    assert ctx.counter("throughput_solves") == before[0] + int(counted) and s.iteration == iters and s.path_fallback == 0
     return s, x.to_numpy(), ctx.counter("cg_fused_steps") - before[1]
 
 
@@ -72,9 +74,12 @@ def main():
     z_loc = er.int_apply(shape, b_glob, k0, k1)
     report = {"rank": rank, "world": world, "nbrs": [int(r) for r in plan.nbr_rank], "fused": {}, "history": {}}
     pins = {}
-    if transport == "host":  # the engine's CGS and TFQMR to K = 2 against the exact reference of the whole box
-        from oracle import oracle
+    from oracle import oracle
 
+    # CG and BiCGStab to K = 4 against the step pins of the whole box (exact_ref.StepPins), on both transports
+    steps = er.StepProblem(oracle, mesh, shape)
+    assert np.array_equal(steps.b, b_glob)
+    if transport == "host":  # the engine's CGS and TFQMR to K = 2 against the exact reference of the whole box
         g, basis = er.unit_box(mesh, *shape), er.Basis(shape, b_glob)
         pins = {kind: er.Pins(oracle, g, shape, b_glob, kind, fs=fs, basis=basis) for kind in ("cgs", "tfqmr")}
 
@@ -108,6 +113,18 @@ def main():
         assert er.close(s.history[1], fs.gmres_h1, fs.gmres_tol), ("gmres h1", fmt, s.history[1], fs.gmres_h1)
         report["history"][f"gmres{fmt}"] = [float(v) for v in s.history]
         assert math.isfinite(s.history[1])
+        for kind, cls in (("cg", api.CgSolver), ("bicgstab", api.BiCgStabSolver)):
+            sp = steps.pins(kind, er.STEP_RANK_K)
+            s, x, _ = _solve(ctx, cls, mat, b, n, n_halo, iters=sp.K)
+            sp.check(list(s.history), f"{kind} K={sp.K} rank {rank} format {fmt}")
+            report["history"][f"{kind}{fmt}K{sp.K}"] = [float(v) for v in s.history]
+            parts = [None] * world
+            td.all_gather_object(parts, (np.asarray(loc.global_id[:n]), x))
+            if rank == 0:  # the residual of the gathered x against the exact history[K] (and x itself on a small box)
+                x_glob = np.full(b_glob.size, np.nan)
+                for ids, part in parts:
+                    x_glob[ids] = part
+                report.setdefault("x", {})[f"{kind}{fmt}"] = sp.check_x(x_glob, sp.K, f"{kind} K={sp.K} format {fmt}")
         for kind, cls in (("cgs", api.CgsSolver), ("tfqmr", api.TfqmrSolver)):
             if kind in pins:
                 s = _engine_solve(ctx, cls, mat, b, n, n_halo, pins[kind].K)

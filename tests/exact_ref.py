@@ -23,6 +23,12 @@ precision guard: the power basis loses digits with K, so every pinned case is ru
 agree to 1e-40, and K stays at 12 or below.  ``mgs_float64`` is the same step in fp64 numpy, with the grouped evaluation
 of the device's chain kernels and with the defects the pins must reject.
 
+CG and BiCGStab past their first step: ``cg`` and ``bicgstab`` (SolverCg.hpp, SolverBiCgStab.hpp in Fractions; CG on
+the two-stage operator (I + A)^2 through ``TwoStageSpace``) keep every iterate x_k and the ratio sqrt(M) / h of each
+step's own terms; ``StepPins`` holds history[0..K], x_k and their tolerances by ``Pins``' rule, ``StepProblem`` one box
+with its chain and operator.  The same bodies run on ``Float64Space`` (``cg_float64``, ``bicgstab_float64``) with the
+defects the pins must reject.
+
 Plain module, not a conftest: the tests import it by name.
 """
 import math
@@ -365,8 +371,7 @@ class IntOperator:
         self.n, self.csr = n, a
         self.rowsum = int(abs(a).sum(axis=1).max())
         assert int(np.diff(a.indptr).min()) > 0  # (no empty row: ``true_residual`` reduces row by row)
-        self._rows = np.repeat(np.arange(n), np.diff(a.indptr))
-        self._obj = a.data.astype(object)
+        self._rows = self._obj = None  # (the object form: built when first applied to an object vector)
 
     @classmethod
     def from_face_weights(cls, g, w_inner, w_outer, diag_extra):
@@ -380,6 +385,9 @@ class IntOperator:
     def apply(self, w):
         w = np.asarray(w)
         if w.dtype == object:
+            if self._obj is None:
+                self._rows = np.repeat(np.arange(self.n), np.diff(self.csr.indptr))
+                self._obj = self.csr.data.astype(object)
             out = np.zeros(self.n, dtype=object)
             np.add.at(out, self._rows, self._obj * w[self.csr.indices])
             return out
@@ -736,8 +744,41 @@ def richardson(sp, K, omega, pre=False):
     return Run(hist, x, feeds)
 
 
-def cg(sp, K, pre=False):
-    """SolverCg.hpp:54-126; the preconditioner has no side (z = P r)."""
+def _own_ratio(sp, terms, h_sq):
+    """M / h^2 of one step: M the sum of the squared norms of the step's own terms, h^2 the squared norm of the vector
+    they form.  The dots are not counted (``ndots``, ``drop_at`` are the method's)."""
+    n, drop, sp.drop_at = sp.ndots, sp.drop_at, None
+    m = sum((sp.dot(t, t) for t in terms), 0)
+    sp.ndots, sp.drop_at = n, drop
+    return m / h_sq if h_sq else 0 * m
+
+
+def _dot_without_last_row(sp, u, v):
+    sp.drop_at = sp.ndots + 1
+    d = sp.dot(u, v)
+    sp.drop_at = None
+    return d
+
+
+CG_DEFECTS = ("stale_gamma", "old_r", "skip_x", "double_x", "stale_pz", "old_p", "drop_row")
+BICGSTAB_DEFECTS = ("beta_no_ratio", "stale_omega", "skip_x_omega", "old_v", "rho_early")
+
+
+def cg(sp, K, pre=False, defect=None, at=2):
+    """SolverCg.hpp:54-126; the preconditioner has no side (z = P r).  Besides ``Run``'s fields the result carries
+    ``xs`` (x_0 ... x_K) and ``ratio_sq[k]``, M / h^2 of history[k] from the step's OWN terms: r_k = r_{k-1} - alpha z,
+    M = |r_{k-1}|^2 + alpha^2 |z|^2, h = |r_k| -- what ``floor_tol`` takes after a root (``StepPins``).
+
+    ``defect`` (the separation tests only; none acts before the second iteration, so history[0..1] and x_1 keep their
+    values -- ``at`` is the 0-based iteration of the one-shot ones):
+      "stale_gamma"  beta = gamma_k / gamma_0: the gamma-bar register never refreshed
+      "old_r"        p' = r + beta p with the r of before r -= alpha z
+      "skip_x"       x += alpha p left out at iteration ``at``
+      "double_x"     x += alpha p applied twice at the last iteration (the tail kernel after a fused step)
+      "stale_pz"     alpha from the previous iteration's <p, z>
+      "old_p"        p' = r + beta p_{k-2} at iteration ``at`` (the wrong buffer of the ping-pong)
+      "drop_row"     <r, r> of iteration ``at`` - 1 without its last row (history[``at``])"""
+    assert defect is None or (defect in CG_DEFECTS and at >= 1 and not pre)
     b = sp.b()
     x, r = sp.zero(), b  # :73 (x0 = 0)
     if pre:
@@ -748,22 +789,124 @@ def cg(sp, K, pre=False):
         p = r  # :79-80
         gamma = sp.dot(r, r)
     hist, feeds = [sp.dot(r, r) if pre else gamma], [[r]]  # :83
-    for _ in range(K):
+    xs, ratio = [x], [1]
+    gamma_0, pz_prev, p_prev = gamma, None, None
+    for it in range(K):
         z = sp.A(p)  # :96
-        alpha = _sdiv(gamma, sp.dot(p, z))  # :97
-        x = x + alpha * p  # :98
-        r = r - alpha * z  # :99
+        pz = sp.dot(p, z)
+        alpha = _sdiv(gamma, pz_prev if defect == "stale_pz" and it >= 1 else pz)  # :97
+        pz_prev = pz
+        if not (defect == "skip_x" and it == at):
+            x = x + alpha * p  # :98
+        if defect == "double_x" and it == K - 1 and it >= 1:
+            x = x + alpha * p
+        r_old, az = r, alpha * z
+        r = r - az  # :99
         gamma_bar = gamma  # :110
         if pre:
             z = sp.P(r)  # :111-113
             gamma = sp.dot(r, z)
+        elif defect == "drop_row" and it == at - 1:
+            gamma = _dot_without_last_row(sp, r, r)
         else:
             gamma = sp.dot(r, r)  # :115
-        beta = _sdiv(gamma, gamma_bar)  # :122
-        p = (z if pre else r) + beta * p  # :123
+        beta = _sdiv(gamma, gamma_0 if defect == "stale_gamma" else gamma_bar)  # :122
+        lead = z if pre else (r_old if defect == "old_r" and it >= 1 else r)
+        p_prev, p = p, lead + beta * (p_prev if defect == "old_p" and it == at else p)  # :123
         hist.append(sp.dot(r, r) if pre else gamma)  # :125
         feeds.append([r])
-    return Run(hist, x, feeds)
+        xs.append(x)
+        ratio.append(_own_ratio(sp, [r_old, az], hist[-1]))
+    run = Run(hist, x, feeds)
+    run.xs, run.ratio_sq = xs, ratio
+    return run
+
+
+def bicgstab(sp, K, defect=None, at=2):
+    """SolverBiCgStab.hpp:53-167, plain BiCGStab from x0 = 0 without a preconditioner -- what api.BiCgStabSolver and
+    oracle.solve("bicgstab", ...) implement.  Rational throughout; only the history takes a root.  ``xs`` and
+    ``ratio_sq`` as ``cg`` records them: r_k = r_{k-1} - alpha v - omega t, M = |r_{k-1}|^2 + alpha^2 |v|^2 +
+    omega^2 |t|^2.
+
+    ``defect`` (none acts before the second iteration; ``at``: the 0-based iteration of the one-shot ones):
+      "beta_no_ratio" beta = rho / rho-bar, the factor alpha / omega left out
+      "stale_omega"   p = r + beta (p - omega v) with the omega of the iteration before the last (from iteration 2 on)
+      "skip_x_omega"  x += omega r left out at iteration ``at``
+      "old_v"         v_{k-2} read for v_{k-1} in p at iteration ``at`` (the wrong parity buffer)
+      "rho_early"     rho = <r~, r> with the r of before r -= omega t"""
+    assert defect is None or (defect in BICGSTAB_DEFECTS and at >= 2)
+    r = sp.b()  # :82 (x0 = 0)
+    rt = r  # :87
+    rho = sp.dot(rt, r)  # :88
+    x, hist, feeds = sp.zero(), [rho], [[r]]
+    xs, ratio = [x], [1]
+    alpha = omega = omega_prev = v = v_prev = s = None
+    for it in range(K):
+        if it == 0:
+            p = r  # :114
+        else:
+            rho_bar, rho = rho, sp.dot(rt, s if defect == "rho_early" else r)  # :116-117
+            beta = _sdiv(rho, rho_bar) if defect == "beta_no_ratio" else _sdiv(alpha * rho, omega * rho_bar)  # :118
+            om = omega_prev if defect == "stale_omega" and it >= 2 else omega
+            p = r + beta * (p - om * (v_prev if defect == "old_v" and it == at else v))  # :119
+        v_prev, v = v, sp.A(p)  # :137
+        alpha = _sdiv(rho, sp.dot(rt, v))  # :139
+        x = x + alpha * p  # :140
+        r_old, av = r, alpha * v
+        r = s = r - av  # :141
+        t = sp.A(r)  # :158
+        omega_prev, omega = omega, _sdiv(sp.dot(t, r), sp.dot(t, t))  # :159-160
+        if not (defect == "skip_x_omega" and it == at):
+            x = x + omega * r  # :161
+        ot = omega * t
+        r = r - ot  # :162
+        hist.append(sp.dot(r, r))  # :164
+        feeds.append([r])
+        xs.append(x)
+        ratio.append(_own_ratio(sp, [r_old, av, ot], hist[-1]))
+    run = Run(hist, x, feeds)
+    run.xs, run.ratio_sq = xs, ratio
+    return run
+
+
+class Float64Space:
+    """The vector interface in plain fp64 numpy over a scipy CSR matrix: the method bodies above become float64
+    restatements, with their defects."""
+
+    def __init__(self, a, b):
+        self.a, self._b = a, np.asarray(b, np.float64)
+        self.ndots, self.drop_at = 0, None
+
+    def b(self):
+        return self._b.copy()
+
+    def zero(self):
+        return np.zeros(self._b.size)
+
+    def A(self, v):
+        return self.a @ v
+
+    def dot(self, u, v):
+        self.ndots += 1
+        if self.ndots == self.drop_at:
+            return float(np.dot(u[:-1], v[:-1]))
+        return float(np.dot(u, v))
+
+
+def _float64_run(method, a, b, K, defect, at):
+    run = method(Float64Space(a, b), K, defect=defect, at=at)
+    return np.sqrt(np.array(run.hist_sq, np.float64)), run.xs
+
+
+def cg_float64(a, b, K, defect=None, at=2):
+    """CG's history[0..K] and x_0 ... x_K in plain fp64 numpy (``a``: scipy CSR, fp64): ``cg``'s statements, and the
+    defects the pins must reject (``CG_DEFECTS``)."""
+    return _float64_run(cg, a, b, K, defect, at)
+
+
+def bicgstab_float64(a, b, K, defect=None, at=2):
+    """BiCGStab's history[0..K] and x_0 ... x_K in plain fp64 numpy, with ``BICGSTAB_DEFECTS``."""
+    return _float64_run(bicgstab, a, b, K, defect, at)
 
 
 def _root(v):
@@ -1070,10 +1213,13 @@ def exact_run(sp, method, param, K, side=None, shadow=()):
 #   GMRES   q_0 = b / beta 1 + 1; w = A q_k 13; per projection h 1, w -= h q_i 2 (the terms of M count every one);
 #   FGMRES  |w| 1, q_{k+1} = w / |w| 1; the rotation's hypot, divisions and products ~8                   -> 32
 #           (``gmres`` takes sqrt(M) / h from the step's own terms -- A q_k and the H_ik q_i -- not from the chain)
+#   BiCGStab v = A p exact (p = b); alpha 1; s = r - alpha v 2; t = A s 13 + 12 (1 + 2); omega 1;
+#           r = s - omega t 2 on top of s's 3                                                             -> 55
+#           (``cg`` and ``bicgstab`` record sqrt(M) / h from the step's own terms as well: ``StepPins``)
 # Later iterations and the preconditioned cases repeat these statements: c_k = k c_1 (+ 4k + 1 with the elementwise
 # products of a preconditioner) is their floor; there the measured error of the oracle decides (``Pins``).
 C1 = {"cgs": 64, "tfqmr": 59, "tfqmr1": 54, "idrs": 7, "idrs1": 107, "richardson": 0, "bicgstabl": 64, "cg": 16,
-      "fgmres": 32, "gmres": 32}
+      "fgmres": 32, "gmres": 32, "bicgstab": 55}
 
 
 def _c(method, param, k, pre):
@@ -1293,6 +1439,208 @@ class GmresPins:
             assert d <= self.tol_x, f"{label} |x - exact| / |exact| = {d:.3e} > tol {self.tol_x:.3e}"
             out.append(d / self.e_x if self.e_x > 0 else 0.0)
         return out
+
+
+# ---- CG and BiCGStab past their first step ---------------------------------------------------------------------------
+
+STEP_K = {"cg": 8, "bicgstab": 5, "cg2": 4}  # the iterations pinned; BiCGStab at 5 reaches each parity buffer at least twice
+TWO_STAGE = (-1.0, 2.0, -1.0, 1.0)  # (alpha1, beta1, alpha2, beta2) over M = L: y = x - L (2 x - L x) = (I + A)^2 x, A = -L
+
+
+class TwoStageSpace(Space):
+    """``Space`` whose operator is (I + A)^2 = I + 2 A + A^2 -- the two-stage operator with the integer constants
+    ``TWO_STAGE``: a polynomial in A, so its Krylov vectors are columns over the same chain."""
+
+    def A(self, v):
+        a = Space.A(self, v)
+        return v + 2 * a + Space.A(self, a)
+
+
+def two_stage_operator(A):
+    """(I + A)^2 of an ``IntOperator`` as an ``IntOperator``."""
+    import scipy.sparse as sps
+
+    m = sps.identity(A.n, dtype=np.int64, format="csr") + A.csr
+    c = (m @ m).tocoo()
+    return IntOperator(A.n, c.row, c.col, c.data)
+
+
+def two_stage_oracle_op(oracle, g, variant="strict"):
+    """The oracle's two-stage operator: a callback that applies its one-stage operator M = L twice."""
+    m = oracle.StencilOperator(g, 1.0, 0.0, variant=variant)
+    a1, b1, a2, b2 = TWO_STAGE
+    return oracle.CallbackOperator(g.n_cells, lambda x: b2 * x + a2 * m.apply(b1 * x + a1 * m.apply(x)))
+
+
+def poisson_operator(mesh, g):
+    """``-L`` of the unit box as an ``IntOperator`` (convection-diffusion with nu = 1, v = 0)."""
+    return IntOperator.from_face_weights(g, *mesh.convection_diffusion_weights(g, 1.0, (0.0, 0.0, 0.0)))
+
+
+class StepPins:
+    """history[0..K] and x_0 ... x_K of unpreconditioned CG ("cg"; "cg2": CG on the two-stage operator) or BiCGStab from
+    x0 = 0, with ``Pins``' rule unchanged: history[0] bitwise; tol_k = max(floor_k, 16 e_k), e_k the larger relative
+    distance of the oracle's strict and fma builds from the exact value, floor_k = ``floor_tol`` with c = k C1[method]
+    and the ratio sqrt(M) / h of the step's own terms (``cg``, ``bicgstab``); every tol_k at most TOL_CAP (asserted).
+    With ``fs`` (the Poisson box's ``FirstStep``) history[1] keeps the closed form's tolerance where that is tighter.
+
+    ``check_x(x, k)``: ||b - A x|| (``true_residual``) against the exact history[k] within max(floor_k, 16 e_x), e_x
+    the same quantity of the oracle's two x after k iterations; at or below GMRES_X_ROWS rows also x against the exact
+    x_k (``Space.materialize``) by relative 2-norm under the same rule.  The oracle's x_k and the exact x_k are formed
+    when first asked for and kept."""
+
+    def __init__(self, oracle, make_op, space, A, b, method, K=None, fs=None):
+        b = np.asarray(b, np.int64)
+        self.method, self.K = method, STEP_K[method] if K is None else K
+        self.n, self.A, self.b, self.space = b.size, A, b, space
+        self._oracle, self._make_op = oracle, make_op
+        self.kind = "bicgstab" if method == "bicgstab" else "cg"
+        K = self.K
+        self.run = run = (bicgstab if self.kind == "bicgstab" else cg)(space, K)
+        self.exact = exact = run.history
+        assert exact[0] == math.sqrt(float(exact_dot(b, b)))
+        self.oracle, self._ox, self._x, self._res, self._xt = {}, {}, {}, {}, {}
+        for variant in ("strict", "fma"):
+            r = self._solve(variant, K)
+            self.oracle[variant], self._ox[K, variant] = r.history, r.x
+        self.e = [max(abs(h[k] - exact[k]) / exact[k] for h in self.oracle.values()) for k in range(K + 1)]
+        self.floor = [0.0] + [floor_tol(self.n, math.sqrt(float(run.ratio_sq[k])), k * C1[self.kind])
+                              for k in range(1, K + 1)]
+        self.tol, self.rule = [None], ["exact"]
+        for k in range(1, K + 1):
+            tol = self._cap(max(self.floor[k], 16 * self.e[k]), f"tol_{k}")
+            rule = "16 e_k" if tol > self.floor[k] else "floor"
+            if k == 1 and fs is not None:
+                h1, t1 = (fs.cg_h1, fs.cg_tol) if self.kind == "cg" else (fs.bicgstab_h1, fs.bicgstab_tol)
+                assert close(exact[1], h1, 1e-15)
+                if t1 < tol:
+                    tol, rule = t1, "closed form"
+            self.tol.append(tol), self.rule.append(rule)
+
+    def _solve(self, variant, k):
+        r = self._oracle.solve(self.kind, self._make_op(variant), self.b.astype(np.float64), num_iterations=k,
+                               abs_tol=0.0, rel_tol=0.0, variant=variant)
+        assert r.history.size == k + 1, (self.method, r.history)
+        return r
+
+    def _cap(self, tol, what):
+        assert tol <= TOL_CAP, f"{self.method} K={self.K} n={self.n}: {what} = {tol:.3e} above the cap {TOL_CAP}"
+        return tol
+
+    def check(self, history, label="", k=None):
+        """Assert history[0..k] (K by default; a solve that stopped at iteration k leaves k + 1 entries) against the
+        pins; returns |h - exact| / exact per entry."""
+        k = self.K if k is None else k
+        assert len(history) == k + 1, (label, history)
+        far = []
+        for j, (h, x, tol) in enumerate(zip(history, self.exact, self.tol)):
+            if tol is None:
+                assert h == x, f"{label} history[{j}] = {h!r}, exact {x!r} (bitwise)"
+            else:
+                assert close(h, x, tol), f"{label} history[{j}] = {h!r}, exact {x!r}: rel {abs(h - x) / x:.3e} > tol " \
+                                         f"{tol:.3e} ({self.rule[j]})"
+            far.append(abs(h - x) / x)
+        return far
+
+    def stop_between(self, k):
+        """An absolute tolerance that iteration k is the first to meet: the midpoint of the exact history[k] and
+        history[k - 1] (they differ by orders of magnitude more than any tol)."""
+        mid = 0.5 * (self.exact[k] + self.exact[k - 1])
+        assert self.exact[k] * 1.05 < mid < min(self.exact[:k]) / 1.05
+        return mid
+
+    def oracle_x(self, variant, k):
+        if (k, variant) not in self._ox:
+            self._ox[k, variant] = self._solve(variant, k).x
+        return self._ox[k, variant]
+
+    def x(self, k):
+        """The exact x_k, each element rounded once (None above GMRES_X_ROWS rows)."""
+        if self.n > GMRES_X_ROWS:
+            return None
+        if k not in self._x:
+            self._x[k] = self.space.materialize(self.run.xs[k])
+        return self._x[k]
+
+    def x_tolerances(self, k):
+        """(e_res, tol_res, rule, e_x, tol_x) of x_k; the last two None where the exact x is not formed."""
+        if k not in self._xt:
+            assert 1 <= k <= self.K
+            want = self.exact[k]
+            xs = [self.oracle_x(v, k) for v in ("strict", "fma")]
+            e_res = max(abs(true_residual(self.A, self.b, x) - want) / want for x in xs)
+            tol_res = self._cap(max(self.floor[k], 16 * e_res), f"tol_res({k})")
+            e_x = tol_x = None
+            if self.x(k) is not None:
+                nx = float(np.linalg.norm(self.x(k)))
+                e_x = max(float(np.linalg.norm(x - self.x(k))) / nx for x in xs)
+                tol_x = self._cap(max(self.floor[k], 16 * e_x), f"tol_x({k})")
+            self._xt[k] = (e_res, tol_res, "16 e_x" if tol_res > self.floor[k] else "floor", e_x, tol_x)
+        return self._xt[k]
+
+    def check_x(self, x, k=None, label=""):
+        """Assert a solution after k iterations (K by default); returns |res - exact| / exact (and |x - exact| / |exact|)."""
+        k = self.K if k is None else k
+        e_res, tol_res, rule, e_x, tol_x = self.x_tolerances(k)
+        res, want = true_residual(self.A, self.b, x), self.exact[k]
+        assert close(res, want, tol_res), f"{label} |b - A x_{k}| = {res!r}, exact history[{k}] {want!r}: rel " \
+                                          f"{abs(res - want) / want:.3e} > tol {tol_res:.3e} ({rule})"
+        out = [abs(res - want) / want]
+        if tol_x is not None:
+            d = float(np.linalg.norm(x - self.x(k))) / float(np.linalg.norm(self.x(k)))
+            assert d <= tol_x, f"{label} |x_{k} - exact| / |exact| = {d:.3e} > tol {tol_x:.3e}"
+            out.append(d)
+        return out
+
+
+STEP_SEED = 31  # b = int_vector(n, 31) on the Poisson boxes: the data of the first-step pins
+# method -> the (shape, box) the GPU tests pin it on, and the iterations k whose x_k they check (K and the early exit);
+# tests/test_exact_reference.py asserts every cap of every one on the reference alone
+STEP_CASES = {
+    "cg": [((64, 48, 40), "poisson"), ((37, 21, 19), "poisson"), ((36, 30, 8), "poisson"), ((64, 64, 12), "poisson"),
+           ((256, 128, 130), "poisson"), ((200, 100, 211), "poisson")],
+    "bicgstab": [((64, 48, 40), "poisson"), ((37, 21, 19), "poisson"), ((40, 30, 17), "convdiff")],
+    "cg2": [((24, 24, 24), "poisson"), ((9, 7, 1), "poisson")],
+}
+STEP_STOP = 3  # the early-exit tests stop at this iteration
+STEP_RANK_SHAPES, STEP_RANK_K = [(64, 16, 24), (32, 16, 18)], 4  # tests/test_gpu_exact_ranks.py: the whole boxes (2 and 3 slabs)
+STEP_BLOCK_SEEDS = (31, 32, 33, 34)  # tests/test_gpu_block.py: the columns of the block CG on 64 x 48 x 40, K = 8
+
+
+class StepProblem:
+    """One box of the step pins -- "poisson": -L on the unit box, b = int_vector(n, 31); "convdiff": the GMRES pins'
+    non-symmetric box and b -- with its chain, its ``IntOperator`` (built once) and the pins per method, kept."""
+
+    def __init__(self, oracle, mesh, shape, kind="poisson", seed=STEP_SEED):
+        self.oracle, self.shape, self.kind = oracle, tuple(shape), kind
+        if kind == "convdiff":
+            self.g, self.weights, self.A = convdiff_box(mesh, *shape, vel=GMRES_VEL)
+            self.b = int_vector(self.g.n_cells, GMRES_SEED, *GMRES_RANGE)
+            self.basis, self.fs = OpBasis(self.A, self.b), None
+        else:
+            self.g = unit_box(mesh, *shape)
+            self.A = poisson_operator(mesh, self.g)
+            self.b = int_vector(self.g.n_cells, seed)
+            self.basis, self.fs = Basis(shape, self.b), FirstStep(Sums(shape, self.b))
+        self._pins, self._A2 = {}, None
+
+    def oracle_op(self, variant):
+        if self.kind == "convdiff":
+            return self.oracle.StencilOperator(self.g, -1.0, 0.0, conv=1.0, vel=GMRES_VEL, variant=variant)
+        return self.oracle.StencilOperator(self.g, -1.0, 0.0, variant=variant)
+
+    def pins(self, method, K=None):
+        key = (method, STEP_K[method] if K is None else K)
+        if key not in self._pins:
+            if method == "cg2":
+                assert self.kind == "poisson"
+                self._A2 = self._A2 or two_stage_operator(self.A)
+                self._pins[key] = StepPins(self.oracle, lambda v: two_stage_oracle_op(self.oracle, self.g, v),
+                                           TwoStageSpace(self.basis), self._A2, self.b, method, key[1])
+            else:
+                self._pins[key] = StepPins(self.oracle, self.oracle_op, Space(self.basis), self.A, self.b, method,
+                                           key[1], fs=self.fs)
+        return self._pins[key]
 
 
 def richardson_integers(shape, b, k):

@@ -294,6 +294,21 @@ def test_block_cg_two_iterations_against_the_exact_pins(env):
         pins = er.Pins(oracle, g, shape, b[j], "cg")
         ratios = pins.check(list(s.history[j]), label=f"column {j}")
         print(f"column {j}: |h - exact| / (exact e_k) = {ratios}")
+    # ... and K = 8 per column against the step pins (exact_ref.StepPins): history[0..8], ||b_j - A x_j|| of the x the
+    # block solve leaves; iterations 2 ... 8 are the first to run the batched p' = r + beta p and x += alpha p with the
+    # per-column scalars of an earlier iteration in the slab
+    assert tuple(31 + j for j in range(k)) == er.STEP_BLOCK_SEEDS
+    s, x, _ = _block_solve(api, ctx, mat, b, er.STEP_K["cg"])
+    for j, seed in enumerate(er.STEP_BLOCK_SEEDS):
+        p = er.StepProblem(oracle, mesh, shape, seed=seed)
+        assert np.array_equal(p.b, b[j])
+        pins = p.pins("cg")
+        assert s.iterations[j] == pins.K
+        far = pins.check(list(s.history[j]), f"column {j}")
+        xr = pins.check_x(x[:, j], pins.K, f"column {j}")
+        print(f"steps block-cg 64x48x40 column {j}: far {max(far):.1e} at {int(np.argmax(far))}   x {xr[0]:.1e}   tol " +
+              " ".join("bitwise" if t is None else f"{t:.1e}/{r}" for t, r in zip(pins.tol, pins.rule)) +
+              f"   tol_res {pins.x_tolerances(pins.K)[1]:.1e}/{pins.x_tolerances(pins.K)[2]}")
     mat.close()
 
 

@@ -10,7 +10,12 @@ correct path, so:
                             against the exact coefficient-form reference (exact_ref.Pins)
 Each case asserts the path it is meant to reach from the context's path counters and the operator's stats; the
 comment names the <p,z> branch of the fused CG loop (solver_cg.hip, storm_hip_solve_cg; the branches themselves:
-Driver::finish_dots, solver_fused.hip) it takes."""
+Driver::finish_dots, solver_fused.hip) it takes.
+
+What one iteration cannot reach -- the step kernel that ends iteration k - 1 inside iteration k's SpMV, the residual
+recompute and its plane march, the <p,z> fold inside it, the tail x update, BiCGStab's beta and parity buffers -- is
+pinned by tests/test_gpu_exact_steps.py: the rows of CG_SMALL and BICG below for 8 (CG) and 5 (BiCGStab) iterations, the
+fused step on 4 M rows, CG on the two-stage operator for 4, against exact_ref.StepPins (history[0..K] and x_K)."""
 import math
 
 import numpy as np

@@ -21,7 +21,12 @@ and share that error, so they agree with each other far better than either agree
 exact Arnoldi reference (tests/test_gpu_exact_gmres.py, K = 9 on 0.27 ... 2.1 M rows of an integer convection-diffusion
 operator) the oracle is 4e-13 ... 6e-12 away and every device variant -- the chains of csrc/mgs_chain.hip with their
 steps grouped by bilinearity included -- at most 1.3e-15: a few ulps.  A float64 restatement of the grouped form on
-the CPU is no further from the exact value than the ungrouped one either (tests/test_exact_reference.py)."""
+the CPU is no further from the exact value than the ungrouped one either (tests/test_exact_reference.py).
+
+This file has no CG case.  CG -- and BiCGStab once more -- are held to an EXACT value, not to the oracle, for their first
+8 (BiCGStab: 5) iterations in tests/test_gpu_exact_steps.py (exact_ref.StepPins, integer boxes of 15 k ... 4.3 M rows):
+there the oracle's two builds lie 1e-15 ... 3e-13 from the exact history (the serial chain again, growing with n) and
+every device path at most 6e-16."""
 import numpy as np
 import pytest
 
