@@ -856,8 +856,9 @@ int storm_hip_cheb_create_reduced(const storm_hip_op *op, double alpha, double b
  * z = B r: one symmetric V-cycle of smoothed-aggregation multigrid (Vanek, Mandel, Brezina 1996) for A = beta I + alpha M,
  * the one preconditioner of this library that removes operator products instead of making them cheaper.  Usable as pre_op
  * of every method and side like storm_hip_cheb: it enqueues and never waits, has no reduction and no host wait inside an
- * apply.  Single rank.  For symmetric (or diagonally symmetrisable) operators: a strongly non-symmetric operator, upwind
- * convection-diffusion for instance, is outside what it claims.  Added within ABI 6 (STORM_HIP_HAS_AMG).
+ * apply.  Single rank.  For symmetric (or diagonally symmetrisable) operators: for a strongly non-symmetric operator, upwind
+ * convection-diffusion for instance, use the Jacobi smoother (storm_hip_amg_create_smoother below).  Added within ABI 6
+ * (STORM_HIP_HAS_AMG).
  *
  * THE RECIPE (normative; tests/amg_ref.py restates it).  A level operator A_l is CSR with sorted columns, duplicates
  * merged, exact zeros dropped and an explicit diagonal.
@@ -1066,6 +1067,57 @@ int storm_hip_amg_setup_csr_nullspace(int64_t n_rows, const int64_t *row_ptr, co
 int storm_hip_amg_create_nullspace(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params,
                                    int refreshable, storm_hip_amg **out);
 int storm_hip_amg_project(const storm_hip_amg *h, storm_hip_vec *v);
+/* ---- Non-symmetric operators: the damped-Jacobi smoother (STORM_HIP_HAS_AMG_JACOBI, added within ABI 6) ---------------------
+ * The setup above needs no symmetry (strength on the union of A and A^T, A_{l+1} = P^T A_l P, a pivoting inverse); the
+ * Chebyshev smoother does: a polynomial on [lmax / ratio, lmax] assumes a real positive spectrum, and on first-order upwind
+ * convection-diffusion its cycle is not a convergent preconditioner.  storm_hip_amg_create_smoother with kind 1 builds the
+ * same hierarchy with damped Jacobi sweeps as the smoother.  Strictly opt-in: nothing above changes its behaviour or its bits.
+ *
+ * THE SMOOTHER (normative; tests/amg_jacobi_ref.py restates it).  Per level l: s_i = 1 / a_ii, the Jacobi scale as the
+ * Chebyshev smoother obtains it (storm_hip_op_get_diagonal); lmax = Gershgorin's bound of diag(s) A_l, the one the Chebyshev
+ * object uses (from the companion records with reduced_records); sigma_l = 2 omega / lmax, computed on the host in double.
+ * One sweep is z' = z + sigma (s .* (r - A_l z)); a sweep from the zero guess is z = sigma (s .* r).
+ *
+ * THE CYCLE with nu = sweeps (t, e: the level's work vectors):
+ *     z  = sigma (s .* r);  nu - 1 sweeps on z        pre-smoothing (nu = 1: no operator product)
+ *     t  = r - A_l z                                   the residual of THE CYCLE above
+ *     rc = R_l t;  zc = cycle(l + 1, rc);  z = z + P_l zc     unchanged
+ *     nu sweeps on z                                   post-smoothing
+ * 2 nu + 3 launches per level.  For a symmetric A this B is symmetric.  A sweep gathers its neighbours' old z, so it stores
+ * into the other of two buffers, the caller's z and e: the sweep from the zero guess stores into e, which for every nu makes
+ * the last sweep store into the caller's z.  No copy kernel; r is never written.
+ *
+ * THE ROUNDING of a sweep is that of the statement sequence
+ *     storm_hip_op_apply(op_l, alpha_l, beta_l, z, t)          (storm_hip_op_apply_reduced with reduced_records)
+ *     storm_hip_axpbz(t, 1, r, -1, t)
+ *     storm_hip_vmul(t, s, t)
+ *     storm_hip_axpbz(z', sigma, t, 1, z)                      the kernel of storm_hip_axpy: fma(sigma, t_i, z_i)
+ * and of storm_hip_vmul(z, s, r); storm_hip_axpbz(z, sigma, z, 0, z) for the sweep from the zero guess.  A level on fp64
+ * records without a CSR tail runs ONE kernel per sweep instead (amg_jacobi_sweep_kernel: records + 32 bytes per row where
+ * the statements move 88) with the same bits; a level with a CSR tail, or option amg_fused = 0, runs the statements
+ * (tests/test_gpu_amg_jacobi.py).  With reduced_records the sweep reads the level's fp32-weight companion records; the
+ * residual keeps the fp64 records, as in a Chebyshev object.  Counters "amg_fused_sweeps" and "amg_statement_sweeps".
+ *
+ * storm_hip_amg_create_smoother: storm_hip_amg_create with the smoother chosen.  kind 0: exactly storm_hip_amg_create's
+ *   object.  kind 1: smoother_degree and smoother_ratio of `params` are ignored; the object holds no Chebyshev object (three
+ *   work vectors fewer per level).  STORM_HIP_E_INVALID: kind other than 0 / 1, sweeps outside 1 .. 16, omega outside (0, 1],
+ *   a zero or non-finite diagonal on any level (the message names level and row).  The refusals of storm_hip_amg_create apply.
+ *   There is no refreshable and no null-space object with this smoother: storm_hip_amg_refresh and storm_hip_amg_project on
+ *   it return STORM_HIP_E_UNSUPPORTED, as on any plain object.  Single rank, fp64 records on level 0.
+ * storm_hip_amg_smooth: one sweep on its own, z_out = z_in + sigma_l (s .* (r - A_l z_in)) on level l (not the coarsest),
+ *   enqueued like an apply; z_out must alias neither z_in nor r.  On a Chebyshev object: STORM_HIP_E_UNSUPPORTED.
+ * storm_hip_amg_get keys: "smoother_kind", "jacobi_sweeps", "jacobi_omega", "jacobi_sigma_<level>". */
+#define STORM_HIP_HAS_AMG_JACOBI 1
+typedef struct storm_hip_amg_smoother {
+  int32_t kind;   /* 1; 0: the Chebyshev smoother, 1: damped Jacobi sweeps */
+  int32_t sweeps; /* 2 (1 .. 16) */
+  double omega;   /* 2/3, in (0, 1] */
+} storm_hip_amg_smoother;
+void storm_hip_amg_smoother_default(storm_hip_amg_smoother *smoother);
+int storm_hip_amg_create_smoother(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params,
+                                  const storm_hip_amg_smoother *smoother, storm_hip_amg **out);
+int storm_hip_amg_smooth(const storm_hip_amg *h, int level, const storm_hip_vec *r, const storm_hip_vec *z_in,
+                         storm_hip_vec *z_out);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -955,13 +955,26 @@ private:
 /// `nullspace_constant` (set before the build): for a singular operator whose kernel is the constants -- a pure-Neumann
 /// pressure equation -- the object is storm_hip_amg_create_nullspace's: the cycle between two projections onto the mean-free
 /// vectors, and `project(v)` is v <- v - mean(v).
+/// `smoother.kind = 1` (set before the build; `use_jacobi(sweeps, omega)`): damped Jacobi sweeps instead of the Chebyshev
+/// polynomial (storm_hip_amg_create_smoother) -- the smoother for a non-symmetric operator such as upwind
+/// convection-diffusion; `smooth` is one sweep on its own.  Not with `refreshable` or `nullspace_constant`: build() throws.
 class AmgPreconditioner final : public Preconditioner<DeviceVector> {
 public:
   storm_hip_amg_params params;
   bool refreshable = false;  ///< read by build(): storm_hip_amg_create_refreshable instead of storm_hip_amg_create
   bool nullspace_constant = false;  ///< read by build(): storm_hip_amg_create_nullspace (with `refreshable` as its flag)
+  storm_hip_amg_smoother smoother;  ///< read by build(): kind 0 (the default here) Chebyshev, 1 Jacobi with `sweeps`, `omega`
 
-  AmgPreconditioner() { storm_hip_amg_params_default(&params); }
+  AmgPreconditioner() {
+    storm_hip_amg_params_default(&params);
+    storm_hip_amg_smoother_default(&smoother);
+    smoother.kind = 0;  // (every default keeps its behaviour: the Jacobi smoother is opt-in)
+  }
+  /// Smooth by `sweeps` damped Jacobi sweeps with `omega` before and after the coarse correction.
+  AmgPreconditioner& use_jacobi(int sweeps = 2, real_t omega = 2.0 / 3.0) {
+    smoother.kind = 1, smoother.sweeps = sweeps, smoother.omega = omega;
+    return *this;
+  }
   explicit AmgPreconditioner(int smoother_degree, bool reduced_records = false) : AmgPreconditioner() {
     params.smoother_degree = smoother_degree;
     params.reduced_records = reduced_records ? 1 : 0;
@@ -982,10 +995,15 @@ public:
         _built.smoother_degree == params.smoother_degree && _built.smoother_ratio == params.smoother_ratio &&
         _built.max_levels == params.max_levels && _built.coarse_rows == params.coarse_rows &&
         _built.reduced_records == params.reduced_records && _built_refreshable == refreshable &&
-        _built_nullspace == nullspace_constant)
+        _built_nullspace == nullspace_constant && _built_smoother.kind == smoother.kind &&
+        (smoother.kind == 0 || (_built_smoother.sweeps == smoother.sweeps && _built_smoother.omega == smoother.omega)))
       return;
     reset();
-    if (nullspace_constant)
+    if (smoother.kind != 0) {
+      if (refreshable || nullspace_constant)
+        throw std::runtime_error("AmgPreconditioner: the Jacobi smoother cannot be combined with refreshable or nullspace_constant");
+      detail::check(storm_hip_amg_create_smoother(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params, &smoother, &_h));
+    } else if (nullspace_constant)
       detail::check(storm_hip_amg_create_nullspace(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params,
                                                    refreshable ? 1 : 0, &_h));
     else if (refreshable)
@@ -993,7 +1011,11 @@ public:
     else
       detail::check(storm_hip_amg_create(hip_op->matrix().handle(), hip_op->alpha(), hip_op->beta(), &params, &_h));
     _op = hip_op->matrix().handle(), _alpha = hip_op->alpha(), _beta = hip_op->beta(), _built = params;
-    _built_refreshable = refreshable, _built_nullspace = nullspace_constant;
+    _built_refreshable = refreshable, _built_nullspace = nullspace_constant, _built_smoother = smoother;
+  }
+  /// One Jacobi sweep z_out = z_in + sigma_l (s .* (r - A_l z_in)) on level l (a Jacobi object; storm_hip_amg_smooth).
+  void smooth(int level, const DeviceVector& r, const DeviceVector& z_in, DeviceVector& z_out) const {
+    detail::check(storm_hip_amg_smooth(_h, level, r.handle(), z_in.handle(), z_out.handle()));
   }
   /// v <- v - mean(v) in place (a `nullspace_constant` object; storm_hip_amg_project).
   void project(DeviceVector& v) const { detail::check(storm_hip_amg_project(_h, v.handle())); }
@@ -1013,7 +1035,8 @@ public:
     detail::check(storm_hip_amg_apply(_h, y_vec.handle(), x_vec.handle()));
   }
   /// "levels", "operator_complexity", "grid_complexity", "setup_seconds", "upload_seconds", "device_bytes",
-  /// "transfer_padding", "smoother_degree", "reduced", "nullspace" or "coarse_shift".
+  /// "transfer_padding", "smoother_degree", "reduced", "nullspace", "coarse_shift", "smoother_kind", "jacobi_sweeps",
+  /// "jacobi_omega" or "jacobi_sigma_<level>".
   real_t get(const char* key) const {
     double v = 0.0;
     detail::check(storm_hip_amg_get(_h, key, &v));
@@ -1040,6 +1063,7 @@ private:
   real_t _alpha = 0.0, _beta = 0.0;
   storm_hip_amg_params _built{};
   bool _built_refreshable = false, _built_nullspace = false;
+  storm_hip_amg_smoother _built_smoother{};
 };
 
 #ifndef STORM_HIP_NO_SOLVERS

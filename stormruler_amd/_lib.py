@@ -65,6 +65,10 @@ class AmgParams(C.Structure):
                 ("reduced_records", C.c_int32)]
 
 
+class AmgSmoother(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("sweeps", C.c_int32), ("omega", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                           C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double))
@@ -228,6 +232,10 @@ SIGNATURES = {
     "storm_hip_amg_setup_csr_nullspace": (C.c_int, [C.c_int64, i64p, i64p, f64p, C.POINTER(AmgParams), C.c_int, C.POINTER(vp)]),
     "storm_hip_amg_create_nullspace": (C.c_int, [vp, C.c_double, C.c_double, C.POINTER(AmgParams), C.c_int, C.POINTER(vp)]),
     "storm_hip_amg_project": (C.c_int, [vp, vp]),
+    "storm_hip_amg_smoother_default": (None, [C.POINTER(AmgSmoother)]),
+    "storm_hip_amg_create_smoother": (C.c_int, [vp, C.c_double, C.c_double, C.POINTER(AmgParams), C.POINTER(AmgSmoother),
+                                                C.POINTER(vp)]),
+    "storm_hip_amg_smooth": (C.c_int, [vp, C.c_int, vp, vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1125,14 +1125,25 @@ class AmgPreconditioner(Preconditioner):
     a pure-Neumann pressure equation -- the cycle runs between two projections onto the mean-free vectors, and
     :meth:`project` applies that projection to a vector.  ``matrix``: a :class:`StencilMatrix` on fp64 records holding the
     SAME operator as the solve's; the hierarchy is built from it (and level 0 of the cycle applies it), so that the solve's
-    own operator may stay on compact records.  Both are part of the cache key."""
+    own operator may stay on compact records.  Both are part of the cache key.  ``smoother="jacobi"``
+    (``storm_hip_amg_create_smoother``): ``jacobi_sweeps`` damped Jacobi sweeps with ``jacobi_omega`` before and after the
+    coarse correction instead of the Chebyshev polynomial -- the smoother for a non-symmetric operator such as upwind
+    convection-diffusion; ``smoother_degree`` and ``smoother_ratio`` are then ignored, :meth:`smooth` is one sweep on its
+    own, and ``refreshable`` / ``nullspace`` are not available (``ValueError``).  The three are part of the cache key."""
 
     def __init__(self, strength_theta: Optional[float] = None, prolongator_omega: Optional[float] = None,
                  smoother_degree: Optional[int] = None, smoother_ratio: Optional[float] = None,
                  max_levels: Optional[int] = None, coarse_rows: Optional[int] = None, reduced_records: bool = False,
-                 refreshable: bool = False, nullspace: Optional[str] = None, matrix=None):
+                 refreshable: bool = False, nullspace: Optional[str] = None, matrix=None, smoother: str = "chebyshev",
+                 jacobi_sweeps: int = 2, jacobi_omega: float = 2.0 / 3.0):
         if nullspace not in (None, "constant"):
             raise ValueError(f"nullspace={nullspace!r}: None or 'constant'")
+        if smoother not in ("chebyshev", "jacobi"):
+            raise ValueError(f"smoother={smoother!r}: 'chebyshev' or 'jacobi'")
+        if smoother == "jacobi" and (refreshable or nullspace is not None):
+            raise ValueError("smoother='jacobi' cannot be combined with refreshable or nullspace: those objects are "
+                             "Chebyshev-only")
+        self.smoother, self.jacobi_sweeps, self.jacobi_omega = smoother, jacobi_sweeps, jacobi_omega
         self.nullspace, self.matrix = nullspace, matrix
         self.params = dict(strength_theta=strength_theta, prolongator_omega=prolongator_omega, smoother_degree=smoother_degree,
                            smoother_ratio=smoother_ratio, max_levels=max_levels, coarse_rows=coarse_rows,
@@ -1151,14 +1162,20 @@ class AmgPreconditioner(Preconditioner):
         # (a matrix whose weights were refreshed is the same handle: close() first -- staleness is the caller's)
         source = any_op.matrix if self.matrix is None else self.matrix
         key = (x_vec.ctx, source._h.value, float(any_op.alpha), float(any_op.beta), tuple(sorted(self.params.items())),
-               self.refreshable, self.nullspace, None if self.matrix is None else self.matrix._h.value)
+               self.refreshable, self.nullspace, None if self.matrix is None else self.matrix._h.value,
+               self.smoother, int(self.jacobi_sweeps), float(self.jacobi_omega))
         if self._h is not None and self._key == key:
             return
         self._free()
         self.ctx, self._op = x_vec.ctx, any_op
         h = C.c_void_p()
         p = _amg_params(**self.params)
-        if self.nullspace is not None:
+        if self.smoother == "jacobi":
+            if self.refreshable or self.nullspace is not None:  # (the attributes may have been set after construction)
+                raise ValueError("smoother='jacobi' cannot be combined with refreshable or nullspace")
+            sm = _lib.AmgSmoother(1, int(self.jacobi_sweeps), float(self.jacobi_omega))
+            check(lib.storm_hip_amg_create_smoother(source._h, any_op.alpha, any_op.beta, C.byref(p), C.byref(sm), C.byref(h)))
+        elif self.nullspace is not None:
             check(lib.storm_hip_amg_create_nullspace(source._h, any_op.alpha, any_op.beta, C.byref(p), int(self.refreshable),
                                                      C.byref(h)))
         else:
@@ -1170,7 +1187,8 @@ class AmgPreconditioner(Preconditioner):
     def get(self, key: str) -> float:
         """``levels``, ``operator_complexity``, ``grid_complexity``, ``setup_seconds``, ``upload_seconds``, ``device_bytes``,
         ``transfer_padding``, ``smoother_degree``, ``reduced``, ``structural``, ``refreshable``, ``refresh_bytes``,
-        ``nullspace`` or ``coarse_shift``."""
+        ``nullspace``, ``coarse_shift``, ``smoother_kind`` (0 Chebyshev, 1 Jacobi), ``jacobi_sweeps``, ``jacobi_omega`` or
+        ``jacobi_sigma_<level>``."""
         v = C.c_double()
         check(lib.storm_hip_amg_get(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -1211,6 +1229,11 @@ class AmgPreconditioner(Preconditioner):
     def prolong_add(self, level: int, coarse, fine) -> None:
         """``fine += P_l coarse`` (``storm_hip_amg_prolong_add``)."""
         check(lib.storm_hip_amg_prolong_add(self._h, level, coarse._h, fine._h))
+
+    def smooth(self, level: int, r, z_in, z_out) -> None:
+        """One Jacobi sweep ``z_out = z_in + sigma_l (s .* (r - A_l z_in))`` (``storm_hip_amg_smooth``; a
+        ``smoother="jacobi"`` object only)."""
+        check(lib.storm_hip_amg_smooth(self._h, level, r._h, z_in._h, z_out._h))
 
     def coarse_solve(self, r_vec, z_vec) -> None:
         """``z = Ainv r`` on the coarsest level (``storm_hip_amg_coarse_solve``)."""

@@ -18,9 +18,15 @@
 //   amg_mean_kernel         S = sum v, then mu = S / n into the object's slot by the block that drew the last ticket
 //   amg_shift_kernel        out_i = v_i - mu
 //   amg_axpy_mean_kernel    level 0's closing z = z + e with S of the stored z in the same launch (option amg_fused)
+// An object of storm_hip_amg_create_smoother with kind 1 smooths by damped Jacobi sweeps instead (no storm_hip_cheb):
+//   amg_jacobi_sweep_kernel z' = z + sigma (s .* (r - A z)) into the other buffer: amg_residual_kernel's shape and product on the
+//                           record policy R (Rec64; Rec32 on the fp32-weight companion with reduced_records), then the scale's
+//                           product and axpbz_value: the bits of storm_hip_op_apply; storm_hip_axpbz(t, 1, r, -1, t);
+//                           storm_hip_vmul(t, s, t); storm_hip_axpbz(z', sigma, t, 1, z), which any other level takes.
 // Every kernel loads the context's api_done word first and tests it before its first store.
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 #include "amg.hpp"
@@ -66,6 +72,50 @@ __global__ __launch_bounds__(kBlock) void amg_residual_kernel(SellArgs A, double
   if (valid && !done_flag) {
     if (NT) __builtin_nontemporal_store(tn, t + row);
     else t[row] = tn;
+  }
+}
+
+// One damped-Jacobi sweep z' = z + sigma (s .* (r - A z)) on a slice per wavefront: amg_residual_kernel with the record policy
+// R, then vmul's product and the axpy statement's a x + 1 y.  z' goes to the OTHER buffer: neighbours still gather the old z.
+template <bool NT, bool XCD, class R>
+__global__ __launch_bounds__(kBlock) void amg_jacobi_sweep_kernel(SellArgs A, double alpha, double beta, double sigma,
+                                                                  const double *__restrict__ r, const double *__restrict__ s,
+                                                                  const double *__restrict__ z, double *__restrict__ z_out,
+                                                                  int64_t n_slices, const int *done) {
+  const int done_flag = done ? *done : 0;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int bidx = (int)blockIdx.x;
+  const int lb = XCD ? (A.xcd_group > 1 ? xcd_remap_grouped(bidx, gridDim.x, A.xcd_group) : xcd_remap(bidx, gridDim.x))
+                     : bidx;
+  const int64_t slice = (int64_t)lb * (kBlock / kWave) + wave;
+  if (slice >= n_slices) return;  // wave-uniform; the kernel has no barrier
+  const int64_t row = slice * kWave + lane;
+  const bool valid = row < A.n_rows;
+  const double zi = valid ? z[row] : 0.0;
+  const double ri = valid ? ld_d<NT>(r + row) : 0.0;  // the row's own streams, early
+  const double si = valid ? ld_d<NT>(s + row) : 0.0;
+  int64_t base;
+  int width;
+  if (A.uniform_width > 0) {
+    width = A.uniform_width;
+    base = slice * (int64_t)(R::kExt + R::kSlot * width);
+  } else {
+    base = A.slice_off[slice];
+    width = (int)((A.slice_off[slice + 1] - base - R::kExt) / R::kSlot);
+  }
+  const char *rec = A.pack + base;
+  const double ext = R::template ext<NT>(rec, lane);
+  const double zi1[1] = {zi};
+  double acc1[1];
+  row_sum_any<NT, 1, R>(rec, width, lane, z, zi1, acc1);
+  const double az = sell_row_result(false, 0.0, beta, zi, alpha, acc1[0], ext);
+  const double tn = ri - az;  // axpbz(t, 1, r, -1, t)
+  const double w = si * tn;   // vmul(t, s, t)
+  const double zn = axpbz_value(sigma, w, 1.0, zi);  // axpbz(z', sigma, t, 1, z): the axpy statement's kernel
+  if (valid && !done_flag) {
+    if (NT) __builtin_nontemporal_store(zn, z_out + row);
+    else z_out[row] = zn;
   }
 }
 
@@ -279,6 +329,75 @@ static int amg_transfer(const storm_hip_amg *h, const storm_hip_amg::Transfer &T
   return STORM_HIP_OK;
 }
 
+// ---- the Jacobi smoother (storm_hip_amg_create_smoother, kind 1) ------------------------------------------------------------
+static bool amg_reduced(const storm_hip_amg *h) { return h->hier->params.reduced_records != 0; }
+
+// z = sigma (s .* r): a sweep from the zero guess.  Fused: cheb_d0_kernel<JACOBI>; otherwise its two statements.
+static int amg_jacobi_start(const storm_hip_amg *h, const storm_hip_amg::Level &L, const storm_hip_vec *r, storm_hip_vec *z) {
+  if (amg_residual_fused(h, L.op)) return cheb_scaled_start(h->ctx, L.n, L.sigma, r->d, L.dinv->d, z->d);
+  STORM_TRY(storm_hip_vmul(z, L.dinv, r));
+  return storm_hip_axpbz(z, L.sigma, z, 0.0, z);
+}
+
+// z_out = z_in + sigma (s .* (r - A_l z_in)); z_out is not z_in, L.t is the statements' work vector
+static int amg_jacobi_sweep(const storm_hip_amg *h, const storm_hip_amg::Level &L, const storm_hip_vec *r, const storm_hip_vec *z_in,
+                            storm_hip_vec *z_out) {
+  storm_hip_ctx *c = h->ctx;
+  const storm_hip_op *op = L.op;
+  const bool reduced = amg_reduced(h);
+  if (reduced) STORM_TRY(op_reduced_require(op, "amg: the Jacobi smoother"));  // (the companion may have been dropped)
+  if (!amg_residual_fused(h, op)) {
+    ++c->n_amg_statement_sweeps;
+    if (reduced) STORM_TRY(storm_hip_op_apply_reduced(op, L.alpha, L.beta, z_in, L.t));
+    else STORM_TRY(storm_hip_op_apply(op, L.alpha, L.beta, z_in, L.t));
+    STORM_TRY(storm_hip_axpbz(L.t, 1.0, r, -1.0, L.t));
+    STORM_TRY(storm_hip_vmul(L.t, L.dinv, L.t));
+    return storm_hip_axpbz(z_out, L.sigma, L.t, 1.0, z_in);
+  }
+  ++c->n_amg_fused_sweeps;
+  SellArgs A{op->d_pack, op->d_slice_off, op->n_rows, op->uniform_width, op->xcd_group_sell, op->d_dict, op->dict_size,
+             op->d_offs, op->offs_size, 0};
+  if (reduced) A.pack = op->d_pack32, A.slice_off = op->d_slice_off32;
+  const dim3 grid(blocks_for(op, op->n_slices)), block(kBlock);
+  const bool nt = c->opt_nt != 0, xcd = op->xcd_group_sell != 0;
+#define AMG_SWEEP_GO(NT_, XCD_)                                                                                                 \
+  do {                                                                                                                          \
+    if (reduced)                                                                                                                \
+      hipLaunchKernelGGL((amg_jacobi_sweep_kernel<NT_, XCD_, Rec32>), grid, block, 0, c->stream, A, L.alpha, L.beta, L.sigma,  \
+                         r->d, L.dinv->d, z_in->d, z_out->d, op->n_slices, c->api_done);                                        \
+    else                                                                                                                        \
+      hipLaunchKernelGGL((amg_jacobi_sweep_kernel<NT_, XCD_, Rec64>), grid, block, 0, c->stream, A, L.alpha, L.beta, L.sigma,  \
+                         r->d, L.dinv->d, z_in->d, z_out->d, op->n_slices, c->api_done);                                        \
+  } while (0)
+  if (nt && xcd) AMG_SWEEP_GO(true, true);
+  else if (nt) AMG_SWEEP_GO(true, false);
+  else if (xcd) AMG_SWEEP_GO(false, true);
+  else AMG_SWEEP_GO(false, false);
+#undef AMG_SWEEP_GO
+  HIP_TRY(hipGetLastError());
+  return STORM_HIP_OK;
+}
+
+static int amg_cycle(const storm_hip_amg *h, size_t l, const storm_hip_vec *r, storm_hip_vec *z);
+
+// THE CYCLE with the Jacobi smoother.  The iterate alternates between the caller's z and the level's e; a sweep from the zero
+// guess into e puts the last of the nu - 1 pre-sweeps where the nu post-sweeps must start to end in z, for every nu.
+static int amg_cycle_jacobi(const storm_hip_amg *h, size_t l, const storm_hip_vec *r, storm_hip_vec *z) {
+  const storm_hip_amg::Level &L = h->levels[l];
+  const storm_hip_amg::Level &N = h->levels[l + 1];
+  const int nu = h->jacobi_sweeps;
+  storm_hip_vec *buf[2] = {z, L.e};
+  int at = 1;
+  STORM_TRY(amg_jacobi_start(h, L, r, buf[at]));
+  for (int k = 1; k < nu; ++k, at ^= 1) STORM_TRY(amg_jacobi_sweep(h, L, r, buf[at], buf[at ^ 1]));
+  STORM_TRY(amg_residual(h, L, r, buf[at], L.t));
+  STORM_TRY(amg_transfer(h, L.R, false, L.t, N.r));
+  STORM_TRY(amg_cycle(h, l + 1, N.r, N.z));
+  STORM_TRY(amg_transfer(h, L.P, true, N.z, buf[at]));
+  for (int k = 0; k < nu; ++k, at ^= 1) STORM_TRY(amg_jacobi_sweep(h, L, r, buf[at], buf[at ^ 1]));
+  return STORM_HIP_OK;  // (at == 0: the last sweep stored into z)
+}
+
 static int amg_cycle(const storm_hip_amg *h, size_t l, const storm_hip_vec *r, storm_hip_vec *z) {
   storm_hip_ctx *c = h->ctx;
   if (l + 1 == h->levels.size()) {
@@ -287,6 +406,7 @@ static int amg_cycle(const storm_hip_amg *h, size_t l, const storm_hip_vec *r, s
     HIP_TRY(hipGetLastError());
     return STORM_HIP_OK;
   }
+  if (h->smoother_kind == 1) return amg_cycle_jacobi(h, l, r, z);
   const storm_hip_amg::Level &L = h->levels[l];
   const storm_hip_amg::Level &N = h->levels[l + 1];
   STORM_TRY(storm_hip_cheb_apply(L.cheb, r, z));
@@ -436,7 +556,8 @@ int amg_build_device(storm_hip_amg *h, storm_hip_op *op0) {
     STORM_TRY(storm_hip_vec_create(c, L.n, 0, &L.dinv));
     STORM_TRY(storm_hip_vec_create(c, L.n, 0, &L.t));
     STORM_TRY(storm_hip_vec_create(c, L.n, 0, &L.e));
-    h->device_bytes += 6 * (int64_t)L.t->bytes;  // ... and the smoother's three
+    const bool jacobi = h->smoother_kind == 1;
+    h->device_bytes += (jacobi ? 3 : 6) * (int64_t)L.t->bytes;  // ... and the Chebyshev smoother's three
     STORM_TRY(storm_hip_op_get_diagonal(L.op, L.alpha, L.beta, 1, L.dinv));
     double lmax = 0.0;
     if (p.reduced_records) {
@@ -444,10 +565,17 @@ int amg_build_device(storm_hip_amg *h, storm_hip_op *op0) {
       STORM_TRY(storm_hip_op_build_reduced(mine));
       if (l > 0) h->device_bytes += mine->device_bytes - before;
       STORM_TRY(storm_hip_op_gershgorin_reduced(L.op, L.alpha, L.beta, L.dinv, &lmax));
-      STORM_TRY(storm_hip_cheb_create_reduced(L.op, L.alpha, L.beta, L.dinv, p.smoother_degree, lmax / p.smoother_ratio, lmax, &L.cheb));
+      if (!jacobi)
+        STORM_TRY(storm_hip_cheb_create_reduced(L.op, L.alpha, L.beta, L.dinv, p.smoother_degree, lmax / p.smoother_ratio, lmax, &L.cheb));
     } else {
       STORM_TRY(storm_hip_op_gershgorin(L.op, L.alpha, L.beta, L.dinv, &lmax));
-      STORM_TRY(storm_hip_cheb_create(L.op, L.alpha, L.beta, L.dinv, p.smoother_degree, lmax / p.smoother_ratio, lmax, &L.cheb));
+      if (!jacobi)
+        STORM_TRY(storm_hip_cheb_create(L.op, L.alpha, L.beta, L.dinv, p.smoother_degree, lmax / p.smoother_ratio, lmax, &L.cheb));
+    }
+    L.lmax = lmax;
+    if (jacobi) {
+      STORM_REQUIRE(std::isfinite(lmax) && lmax > 0.0, "amg_create_smoother: Gershgorin's bound of level %d is %g", (int)l, lmax);
+      L.sigma = 2.0 * h->jacobi_omega / lmax;
     }
     STORM_TRY(amg_upload_transfer(h, H.P, &L.P));
     STORM_TRY(amg_upload_transfer(h, H.R, &L.R));
@@ -489,20 +617,44 @@ using namespace storm;
 
 extern "C" {
 
-int storm_hip_amg_create(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params, storm_hip_amg **out) {
-  STORM_REQUIRE(op && out, "amg_create: null argument");
-  *out = nullptr;
-  STORM_TRY(amg_create_checks(op, alpha, beta, "amg_create"));
+// The Jacobi scale s_i = 1 / a_ii must exist: the first zero or non-finite diagonal of a CSR level operator is refused.
+static int amg_jacobi_diagonal_check(int level, int64_t n, const int64_t *ptr, const int64_t *col64, const int *col32,
+                                     const double *val) {
+  for (int64_t i = 0; i < n; ++i) {
+    double d = 0.0;  // (a row without a stored diagonal has a zero one)
+    for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k)
+      if ((col64 ? col64[k] : (int64_t)col32[k]) == i) d += val[k];
+    STORM_REQUIRE(d != 0.0 && std::isfinite(d), "amg_create_smoother: the diagonal of level %d is %g in row %lld; the Jacobi "
+                  "smoother divides by it", level, d, (long long)i);
+  }
+  return STORM_HIP_OK;
+}
+
+// storm_hip_amg_create, and with `smoother` of kind 1 storm_hip_amg_create_smoother's Jacobi object
+static int amg_create_plain(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params,
+                            const storm_hip_amg_smoother *smoother, const char *who, storm_hip_amg **out) {
+  STORM_TRY(amg_create_checks(op, alpha, beta, who));
   storm_hip_ctx *c = op->ctx;
   HIP_TRY(hipSetDevice(c->device));
   STORM_TRY(lazy_sync(c));
   std::vector<int64_t> ptr, col;
   std::vector<double> val;
   STORM_TRY(amg_decode(op, alpha, beta, false, &ptr, &col, &val));
+  const bool jacobi = smoother != nullptr && smoother->kind == 1;
+  if (jacobi) STORM_TRY(amg_jacobi_diagonal_check(0, op->n_rows, ptr.data(), col.data(), nullptr, val.data()));
   storm_hip_amg_hierarchy *hier = nullptr;
   STORM_TRY(storm_hip_amg_setup_csr(op->n_rows, ptr.data(), col.data(), val.data(), params, &hier));
+  for (size_t l = 1; jacobi && l + 1 < hier->levels.size(); ++l) {
+    const AmgCsr &A = hier->levels[l].A;
+    const int st = amg_jacobi_diagonal_check((int)l, A.n_rows, A.ptr.data(), nullptr, A.col.data(), A.val.data());
+    if (st != STORM_HIP_OK) {
+      (void)storm_hip_amg_hierarchy_destroy(hier);
+      return st;
+    }
+  }
   storm_hip_amg *h = new storm_hip_amg();
   h->ctx = c, h->op = op, h->alpha = alpha, h->beta = beta, h->hier = hier;
+  if (jacobi) h->smoother_kind = 1, h->jacobi_sweeps = smoother->sweeps, h->jacobi_omega = smoother->omega;
   const auto t0 = std::chrono::steady_clock::now();
   const int st = amg_build_device(h, op);
   if (st != STORM_HIP_OK) {
@@ -512,6 +664,55 @@ int storm_hip_amg_create(storm_hip_op *op, double alpha, double beta, const stor
   h->upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   *out = h;
   return STORM_HIP_OK;
+}
+
+int storm_hip_amg_create(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params, storm_hip_amg **out) {
+  STORM_REQUIRE(op && out, "amg_create: null argument");
+  *out = nullptr;
+  return amg_create_plain(op, alpha, beta, params, nullptr, "amg_create", out);
+}
+
+void storm_hip_amg_smoother_default(storm_hip_amg_smoother *s) {
+  if (!s) return;
+  s->kind = 1, s->sweeps = 2, s->omega = 2.0 / 3.0;
+}
+
+int storm_hip_amg_create_smoother(storm_hip_op *op, double alpha, double beta, const storm_hip_amg_params *params,
+                                  const storm_hip_amg_smoother *smoother, storm_hip_amg **out) {
+  STORM_REQUIRE(smoother && out, "amg_create_smoother: null argument");
+  *out = nullptr;
+  // (the smoother is judged before the operator is looked at)
+  STORM_REQUIRE(smoother->kind == 0 || smoother->kind == 1, "amg_create_smoother: kind %d (0: Chebyshev, 1: Jacobi)", smoother->kind);
+  if (smoother->kind == 1) {
+    STORM_REQUIRE(smoother->sweeps >= 1 && smoother->sweeps <= 16, "amg_create_smoother: sweeps %d (1 .. 16)", smoother->sweeps);
+    STORM_REQUIRE(smoother->omega > 0.0 && smoother->omega <= 1.0, "amg_create_smoother: omega %g outside (0, 1]", smoother->omega);
+  }
+  STORM_REQUIRE(op, "amg_create_smoother: null argument");
+  return amg_create_plain(op, alpha, beta, params, smoother, "amg_create_smoother", out);
+}
+
+int storm_hip_amg_smooth(const storm_hip_amg *h, int level, const storm_hip_vec *r, const storm_hip_vec *z_in, storm_hip_vec *z_out) {
+  STORM_REQUIRE(h && r && z_in && z_out, "amg_smooth: null argument");
+  if (h->smoother_kind != 1)
+    STORM_FAIL(STORM_HIP_E_UNSUPPORTED, "amg_smooth: the object has the Chebyshev smoother (a sweep belongs to an object made by "
+                                        "storm_hip_amg_create_smoother with kind 1)");
+  STORM_REQUIRE(level >= 0 && level + 1 < (int)h->levels.size(), "amg_smooth: level %d has no smoother (%d levels)", level,
+                (int)h->levels.size());
+  const storm_hip_amg::Level &L = h->levels[(size_t)level];
+  STORM_REQUIRE(r->ctx == h->ctx && z_in->ctx == h->ctx && z_out->ctx == h->ctx, "amg_smooth: context mismatch");
+  STORM_REQUIRE(z_out != z_in && z_out->d != z_in->d && z_out != r && z_out->d != r->d, "amg_smooth: z_out must not alias z_in or r");
+  STORM_REQUIRE(r->n_owned == L.n && z_in->n_owned == L.n && z_out->n_owned == L.n,
+                "amg_smooth: level %d has %lld rows; the vectors have %lld, %lld and %lld", level, (long long)L.n,
+                (long long)r->n_owned, (long long)z_in->n_owned, (long long)z_out->n_owned);
+  storm_hip_ctx *c = h->ctx;
+  HIP_TRY(hipSetDevice(c->device));
+  STORM_TRY(lazy_sync(c));
+  struct Depth {  // (the statements go out as they are issued, as in storm_hip_amg_apply)
+    storm_hip_ctx *c;
+    explicit Depth(storm_hip_ctx *c_) : c(c_) { ++c->callback_depth; }
+    ~Depth() { --c->callback_depth; }
+  } depth(c);
+  return amg_jacobi_sweep(h, L, r, z_in, z_out);
 }
 
 int storm_hip_amg_destroy(storm_hip_amg *h) {
@@ -621,6 +822,16 @@ int storm_hip_amg_get(const storm_hip_amg *h, const char *key, double *value) {
   else if (!strcmp(key, "nullspace")) *value = h->nullspace ? 1.0 : 0.0;
   else if (!strcmp(key, "smoother_degree")) *value = (double)h->hier->params.smoother_degree;
   else if (!strcmp(key, "reduced")) *value = (double)h->hier->params.reduced_records;
+  else if (!strcmp(key, "smoother_kind")) *value = (double)h->smoother_kind;
+  else if (!strcmp(key, "jacobi_sweeps")) *value = (double)h->jacobi_sweeps;
+  else if (!strcmp(key, "jacobi_omega")) *value = h->jacobi_omega;
+  else if (!strncmp(key, "jacobi_sigma_", 13)) {
+    char *end = nullptr;
+    const long level = strtol(key + 13, &end, 10);
+    STORM_REQUIRE(h->smoother_kind == 1 && end != key + 13 && *end == '\0' && level >= 0 && level + 1 < (long)h->levels.size(),
+                  "amg_get: '%s': no Jacobi smoother on that level (%d levels)", key, (int)h->levels.size());
+    *value = h->levels[(size_t)level].sigma;
+  }
   else return storm_hip_amg_hierarchy_get(h->hier, key, value);
   return STORM_HIP_OK;
 }

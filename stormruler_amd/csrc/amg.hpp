@@ -76,12 +76,16 @@ struct storm_hip_amg {
     double alpha = 1.0, beta = 0.0;
     int64_t n = 0;
     storm_hip_vec *dinv = nullptr;
-    storm_hip_cheb *cheb = nullptr;
+    storm_hip_cheb *cheb = nullptr;  // null with the Jacobi smoother
+    double lmax = 0.0, sigma = 0.0;  // Gershgorin's bound of diag(s) A_l; the Jacobi smoother's 2 omega / lmax
     Transfer P, R;
     storm_hip_vec *r = nullptr, *z = nullptr;  // levels >= 1: the restricted residual and the correction
     storm_hip_vec *t = nullptr, *e = nullptr;
   };
   std::vector<Level> levels;
+  // storm_hip_amg_create_smoother: 0 Chebyshev, 1 damped Jacobi sweeps (the object then holds no storm_hip_cheb)
+  int smoother_kind = 0, jacobi_sweeps = 2;
+  double jacobi_omega = 2.0 / 3.0;
   double *d_ainv = nullptr;
   int64_t n_coarse = 0;
   int64_t device_bytes = 0, transfer_slots = 0, transfer_nnz = 0;
@@ -132,4 +136,6 @@ int amg_decode(const storm_hip_op *op, double alpha, double beta, bool structura
 int amg_build_device(storm_hip_amg *h, storm_hip_op *op0);
 int amg_create_checks(const storm_hip_op *op, double alpha, double beta, const char *who);
 void amg_refresh_free(storm_hip_amg *h);  // amg_refresh.hip
+// d = it (s .* r): cheb_d0_kernel<JACOBI> (precond_cheb.hip), the start of a Jacobi sweep from the zero guess
+int cheb_scaled_start(storm_hip_ctx *c, int64_t n, double inv_theta, const double *r, const double *s, double *d);
 }  // namespace storm

@@ -269,6 +269,7 @@ struct storm_hip_ctx {
   int64_t n_cheb_reduced_applies = 0;  // precond_cheb.hip: applies of a reduced object (counted beside the two above)
   int64_t opt_amg_fused = 1;  // storm_hip_amg_apply: the fused residual kernel where it applies (fp64 records, no CSR tail); 0: the two library statements
   int64_t n_amg_applies = 0, n_amg_fused_residuals = 0, n_amg_statement_residuals = 0;  // amg.hip: applies; which path a residual took
+  int64_t n_amg_fused_sweeps = 0, n_amg_statement_sweeps = 0;  // amg.hip: which path a Jacobi sweep of the cycle (or storm_hip_amg_smooth) took
   int64_t n_amg_refreshes = 0;  // storm_hip_amg_refresh (amg_refresh.hip)
   int64_t n_amg_projections = 0, n_amg_fused_projections = 0;  // a null-space object's Pi (two per apply); the closing axpy fused with its sum
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)

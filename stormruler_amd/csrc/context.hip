@@ -258,6 +258,8 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "amg_applies")) *value = c->n_amg_applies;
   else if (!strcmp(key, "amg_fused_residuals")) *value = c->n_amg_fused_residuals;
   else if (!strcmp(key, "amg_statement_residuals")) *value = c->n_amg_statement_residuals;
+  else if (!strcmp(key, "amg_fused_sweeps")) *value = c->n_amg_fused_sweeps;
+  else if (!strcmp(key, "amg_statement_sweeps")) *value = c->n_amg_statement_sweeps;
   else if (!strcmp(key, "amg_refreshes")) *value = c->n_amg_refreshes;
   else if (!strcmp(key, "option_spmv_dict")) *value = c->opt_spmv_dict;  // (the option's value, for a caller that restores it)
   else if (!strcmp(key, "amg_projections")) *value = c->n_amg_projections;

@@ -128,6 +128,14 @@ __global__ __launch_bounds__(kBlock) void cheb_step_kernel(SellArgs A, double al
   }
 }
 
+int cheb_scaled_start(storm_hip_ctx *c, int64_t n, double inv_theta, const double *r, const double *s, double *d) {
+  if (n <= 0) return STORM_HIP_OK;
+  hipLaunchKernelGGL(cheb_d0_kernel<true>, dim3(stream_blocks(n)), dim3(kBlock), 0, c->stream, n, inv_theta, r, s, d, c->api_done,
+                     stream_nt(c, n));
+  HIP_TRY(hipGetLastError());
+  return STORM_HIP_OK;
+}
+
 static bool cheb_fused_applies(const storm_hip_cheb *h) {
   const storm_hip_op *op = h->op;
   return h->ctx->opt_cheb_fused != 0 && op->pair == 0 && op->dict_size == 0 && op->offs_size == 0 && op->tail_rows == 0 &&
