@@ -392,6 +392,11 @@ int storm_hip_op_create_csr(storm_hip_ctx *ctx, int64_t n_rows, int64_t n_halo,
  *   cg_pz_fold (1): the plane march also folds the step kernel's per-wave partials of <p,z> itself, under its first loads,
  *              where one pass folds them (at most 8 192): two launches an iteration instead of three (0: a one-block launch
  *              folds them in between).  The same bits;
+ *   cg_rr_fold (1): on that road the plane march ends at the group sums of <r,r> (at most 256 groups of 64 slots) and the
+ *              NEXT iteration's step kernel folds them under its first loads and forms beta, the convergence outcome and the
+ *              iteration counter in every block (its first block stores them); a one-wave launch does it behind the last
+ *              iteration of a solve (0: the plane march's last block draws a top-level ticket, folds and runs the scalar
+ *              step).  The same bits;
  *   fused_reduce (1), lin_fuse (1), ticket_reduce (1): engine reductions finished by the partials kernel's last block; two
  *              consecutive vector statements as one pass; fused-loop reductions finished inside the producing kernels;
  *   nontemporal (1), blas1_nt (1): non-temporal record / y traffic of the SpMV; of the BLAS-1 and solver kernels (0 never,

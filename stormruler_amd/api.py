@@ -77,7 +77,7 @@ class Context:
     def counter(self, key: str) -> int:
         """How many solves of this context took a given path ("resident_solves", "latency_solves",
         "throughput_solves", "engine_solves", "cg_fused_steps", "cg_residual_marches", "cg_residual_plane_marches",
-        "cg_pz_consumer_folds"), or how many Gram-Schmidt
+        "cg_pz_consumer_folds", "cg_rr_consumer_folds"), or how many Gram-Schmidt
         steps ran as a chain kernel ("mgs_chain_steps"), as mgs_chain_quad_kernel ("mgs_quad_steps") and as
         mgs_chain_lds_kernel ("mgs_lds_steps"; a chain step that is neither ran the register chain)."""
         v = C.c_int64()

@@ -233,6 +233,7 @@ struct storm_hip_ctx {
   int64_t opt_cg_residual_chunk = 16;  // ... planes per block (2 .. 32); the two planes bounding a chunk are read again: + 2 / chunk of 8 B/row
   int64_t opt_cg_residual_fill = 512;  // ... fewer planes per block on smaller lattices, so that the grid holds about this many blocks (0: cg_residual_chunk as given)
   int64_t opt_cg_pz_fold = 1;  // ... and that kernel folds the step kernel's per-wave partials of <p,z> itself, under its first loads, where one pass folds them (at most kSinglePassPartials): no one-block launch between the two (0: the launch; the same bits)
+  int64_t opt_cg_rr_fold = 1;  // ... and where it does, that kernel ends at the group sums of <r,r>: the NEXT step kernel folds them under its first loads and forms beta, the convergence outcome and the iteration counter in every block (the first stores them); a one-block launch does it behind the solve's last iteration (0: the top-level ticket and the scalar step in the residual kernel's last block; the same bits)
   int64_t opt_cg_fuse = 1;   // fused CG, one rank, tiled format-4 operator: the SpMV kernel ends the previous iteration (x += alpha p, p = r + beta p) itself
   // Vector storage released by vec_destroy, kept for the next vec_create of the same size: a solve
   // allocates its work vectors on entry and frees them on return (the reference re-assigns them in
@@ -275,6 +276,7 @@ struct storm_hip_ctx {
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_cg_pz_consumer_folds = 0;  // ... of those, the solves whose plane march folded <p,z> itself (option cg_pz_fold)
+  int64_t n_cg_rr_consumer_folds = 0;  // ... of those, the solves whose step kernel folded the top level of <r,r> and ran the scalar step itself (option cg_rr_fold)
   int64_t n_mgs_chain_steps = 0, n_mgs_quad_steps = 0;  // Gram-Schmidt steps run as a chain kernel (mgs_chain.hip); ... as mgs_chain_quad_kernel
   int64_t n_mgs_lds_steps = 0;                          // ... as mgs_chain_lds_kernel (the rest: the register chain)
   // communicator
@@ -493,6 +495,11 @@ struct SpmvDot {
     const double *r = nullptr;
     double *p_out = nullptr;
     double ca_imm = 0.0, cb_imm = 0.0;  // with ca / cb null: the values themselves (unsplit marching launch only)
+    // rr_sums != null (unsplit marching launch only, option cg_rr_fold): the state is one STEP_CG_RR behind -- the kernel
+    // folds the rr_ng group sums of <r,r> and forms beta, `done` and the iteration counter itself (its first block stores them)
+    SolverState *st = nullptr;
+    const double *rr_sums = nullptr;
+    int rr_ng = 0;
   } cg;
 };
 int spmv_launch(const storm_hip_op *op, Scal alpha, Scal beta, const double *x, double *y,

@@ -235,6 +235,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *c, const char *key, int64_t value) {
   else if (!strcmp(key, "cg_residual_chunk")) c->opt_cg_residual_chunk = value;
   else if (!strcmp(key, "cg_residual_fill")) c->opt_cg_residual_fill = value;
   else if (!strcmp(key, "cg_pz_fold")) c->opt_cg_pz_fold = value;
+  else if (!strcmp(key, "cg_rr_fold")) c->opt_cg_rr_fold = value;
   else if (!strcmp(key, "spmv_record_index")) c->opt_spmv_record_index = value;
   else if (!strcmp(key, "blas1_nt")) c->opt_blas1_nt = value;
   else if (!strcmp(key, "cheb_fused")) c->opt_cheb_fused = value;
@@ -272,6 +273,7 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "cg_residual_marches")) *value = c->n_cg_residual_marches;
   else if (!strcmp(key, "cg_residual_plane_marches")) *value = c->n_cg_residual_plane_marches;
   else if (!strcmp(key, "cg_pz_consumer_folds")) *value = c->n_cg_pz_consumer_folds;
+  else if (!strcmp(key, "cg_rr_consumer_folds")) *value = c->n_cg_rr_consumer_folds;
   else if (!strcmp(key, "mgs_chain_steps")) *value = c->n_mgs_chain_steps;
   else if (!strcmp(key, "mgs_quad_steps")) *value = c->n_mgs_quad_steps;
   else if (!strcmp(key, "mgs_lds_steps")) *value = c->n_mgs_lds_steps;

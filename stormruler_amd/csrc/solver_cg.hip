@@ -230,7 +230,8 @@ static int cg_r_recompute_run(const storm_hip_op *op, int nbv, Scal alpha, Scal 
 // plane whose neighbours they are, two ahead of the plane being applied.
 //   The per-plane sums stay in the block (each wave's wave_sum_down value in LDS: block_sum256 without its barriers) and
 // are published when the chunk ends, all at once, through ticket_reduce_wave0_slots with cg_r_kernel's block count: one
-// atomic round trip per plane inside the march would serialise it.
+// atomic round trip per plane inside the march would serialise it.  With rr_gate != 0 (option cg_rr_fold) the kernel ends at
+// the group sums -- ticket_reduce_wave0_slots_to_groups -- and the launch behind it folds them and runs the scalar step.
 //   168 VGPRs and 41 KB of LDS at a = 256 (49 KB at a = 512): three blocks per CU.  At 256^3 the 512 blocks of 16 planes
 // are ONE round of two blocks per CU (32 planes, one block per CU: the same time; 8 planes, two rounds: 1.2 % slower), so
 // every block pays the start's round trips: the first planes are requested before anything is waited for.
@@ -247,7 +248,7 @@ template <int HLP, bool IDX>  // HLP: halo pairs per thread and plane: ceil(a / 
 __global__ __launch_bounds__(kBlock) void cg_r_planes_kernel(SolverState *st, double *__restrict__ r, const double *__restrict__ p,
                                                              SellArgs A, ResidualPlanesArgs G, Scal alpha_s, Scal beta_s,
                                                              const double *__restrict__ pz_partials, int n_pz, int reverse,
-                                                             TicketArgs tickets) {
+                                                             TicketArgs tickets, long long rr_gate) {
   const int done = st->done;  // (tested behind the first loads: in a grid of one round every block pays the start's round trips)
   const double gamma = st->s[S_GAMMA];  // (with it: a load behind the fold would be one more round trip in front of the march)
   __shared__ double lds4[4];
@@ -331,6 +332,10 @@ __global__ __launch_bounds__(kBlock) void cg_r_planes_kernel(SolverState *st, do
   if (IDX) rec_table_fill(A, words_sh);
   if (done) return;
   const double alpha = cg_r_alpha(st, folds, pz_flight, n_pz, gamma, lds4);
+  // (option cg_rr_fold, rr_gate != 0: the kernel ends at its group sums and the launch behind it folds them and runs the
+  //  scalar step -- for that launch, which rotates S_GAMMA itself, the <r,r> this step began with and the counter the
+  //  sums will produce: the proof that this kernel ran)
+  if (rr_gate != 0 && blockIdx.x == 0 && threadIdx.x == 0) st->s[S_RR_GAMMA] = gamma, st->s[S_RR_GATE] = (double)rr_gate;
   const double op_alpha = ld_scal2(alpha_s), op_beta = ld_scal2(beta_s);
   // (the first barrier of the march covers dict_sh and the word table)
   for (int s = 0; s < nz; ++s) {
@@ -372,6 +377,10 @@ __global__ __launch_bounds__(kBlock) void cg_r_planes_kernel(SolverState *st, do
   const bool on = lane < nz;
   const double mine = on ? block_sum256_of_waves(wave_part + lane * (kBlock / kWave)) : 0.0;
   const unsigned bxv = on ? (unsigned)(plane(lane) * G.runs_per_plane + yt) : 0u;
+  if (rr_gate != 0) {  // (block-uniform)
+    ticket_reduce_wave0_slots_to_groups(tickets, mine, on, bxv, (unsigned)(G.planes * G.runs_per_plane));
+    return;
+  }
   double total;
   if (ticket_reduce_wave0_slots(tickets, mine, on, bxv, (unsigned)(G.planes * G.runs_per_plane), &total) && threadIdx.x == 0) {
     st->s[S_GAMMA_NEW] = total;
@@ -404,8 +413,10 @@ static bool cg_r_planes_geometry(const storm_hip_op *op, ResidualPlanesArgs *G, 
 }
 // (rr_partials: where the kernel's <r,r> slots go -- the workspace's start, or behind pz_partials where the kernel folds the
 //  step kernel's partials itself: a block that starts late must still find them)
+// (rr_gate != 0: the kernel ends at the group sums of <r,r> in the context's group-sum buffer; see cg_rr_finish_kernel)
 static int cg_r_planes_run(const storm_hip_op *op, const ResidualPlanesArgs &G, int n_blocks, Scal alpha, Scal beta, const double *p,
-                           SolverState *st, double *r, const double *pz_partials, int n_pz, int reverse, double *rr_partials) {
+                           SolverState *st, double *r, const double *pz_partials, int n_pz, int reverse, double *rr_partials,
+                           long long rr_gate = 0) {
   storm_hip_ctx *c = op->ctx;
   STORM_REQUIRE(pz_partials == nullptr || n_pz <= kSinglePassPartials, "cg: the plane march folds at most %d partials of <p,z>, not %d",
                 kSinglePassPartials, n_pz);
@@ -414,7 +425,7 @@ static int cg_r_planes_run(const storm_hip_op *op, const ResidualPlanesArgs &G, 
   const TicketArgs tk{c->d_tickets, rr_partials, c->d_ticket_sums};
 #define PLANES_GO(HLP_, IX_)                                                                                                   \
   hipLaunchKernelGGL((cg_r_planes_kernel<HLP_, IX_>), dim3(n_blocks), dim3(kBlock), lds, c->stream, st, r, p, A, G, alpha, beta, \
-                     pz_partials, n_pz, reverse, tk)
+                     pz_partials, n_pz, reverse, tk, rr_gate)
   if (G.a <= kBlock) {
     if (A.rec_idx != nullptr) PLANES_GO(1, true);
     else PLANES_GO(1, false);
@@ -425,6 +436,22 @@ static int cg_r_planes_run(const storm_hip_op *op, const ResidualPlanesArgs &G, 
 #undef PLANES_GO
   HIP_TRY(hipGetLastError());
   return STORM_HIP_OK;
+}
+
+// Option cg_rr_fold: the scalar step behind a residual kernel that ended at its group sums.  Inside the loop the NEXT
+// iteration's step kernel runs it (spmv_lattice.hip cg_step_march_kernel<.., RR>); behind the solve's last enqueued
+// iteration there is none, and this one wave does: the same fold, the same cg_rr_eval, the same stores.  (cg_xp_kernel,
+// which follows, could: but each of its blocks -- 32 768 at 256^3 -- would fold the sums for one load of alpha, and it
+// serves every other road of the loop.)  The gate: a residual kernel that found the solve done left no sums.
+__global__ __launch_bounds__(kWave) void cg_rr_finish_kernel(SolverState *st, const double *__restrict__ rr_sums, int rr_ng,
+                                                             long long my_iteration) {
+  const double gate = st->s[S_RR_GATE], gamma_bar = st->s[S_RR_GAMMA];
+  const AdvanceIn in{st->initial_error, st->abs_tol, st->rel_tol, my_iteration - 1, st->num_iterations};
+  TicketGroupFlight<1> f;
+  ticket_groups_issue<1, false>(rr_sums, 1, (unsigned)rr_ng, threadIdx.x, f);
+  if (gate != (double)my_iteration) return;
+  const CgRrOutcome o = cg_rr_eval(ticket_fold_groups_flight(f, (unsigned)rr_ng), gamma_bar, in);
+  if (threadIdx.x == 0) cg_rr_store(st, o);
 }
 
 // Five streams (3 loads, 2 stores): measured best with ONE 16-byte access per stream and thread in flight
@@ -491,7 +518,8 @@ struct CgRoads {
   // x += alpha p, p' = r + beta p -- on the rows it loads anyway and applies the operator to p': x and p are no longer
   // streamed by a kernel of their own (cg_xp).  p ping-pongs between two vectors (a tile's old p is another tile's
   // halo).  Two launches + the small first pass per iteration (two where the plane march folds <p,z> itself, option
-  // cg_pz_fold); the last iteration's x update runs behind the loop.
+  // cg_pz_fold -- where, option cg_rr_fold, the plane march also ends at the group sums of <r,r> and the NEXT step kernel
+  // runs the scalar step; behind the loop cg_rr_finish_kernel does); the last iteration's x update runs behind the loop.
   // (on the peer-window transport too: the marching launch also sends p' of the boundary rows, spmv.hip)
   // (on RCCL too, round 4: there the reductions keep their all-reduce between partials and step -- no tickets --, the
   //  step kernel reads alpha, beta and the iteration counter from the slab exactly as cg_xp_kernel does)
@@ -571,7 +599,10 @@ static int solve_cg_body(const FusedSolveArgs &args) {
   // Blocks keep their rows and their partial slots: the same bits either way.  (Per rank: with a communicator too.)
   const int nt_stream = stream_nt(c, n);
   int64_t last_enqueued = -1;
-  bool pz_fold_counted = false;
+  bool pz_fold_counted = false, rr_fold_counted = false;
+  // (option cg_rr_fold: the last enqueued residual kernel ended at its group sums -- the state is one STEP_CG_RR behind)
+  bool rr_pending = false;
+  const int rr_ng = road.r_planes ? (int)(((int64_t)road.planes_args.planes * road.planes_args.runs_per_plane + kTicketGroup - 1) / kTicketGroup) : 0;
   auto enqueue_iteration = [&]() -> int {
     const int q = road.fuse_step ? 0 : (int)(cur_it & 1);  // (fused: the step kernel forward, cg_r backward, always)
     // z = A p, <p,z>                                  SolverCg.hpp:96-97
@@ -580,7 +611,9 @@ static int solve_cg_body(const FusedSolveArgs &args) {
     int st_apply;
     const bool r_march_now = road.r_march && cur_it > 0;
     if (road.fuse_step && cur_it > 0) {
-      const CgStep step{(long long)cur_it, x, r, p_alt};  // ends iteration cur_it - 1 (SolverCg.hpp:98, :123)
+      // ends iteration cur_it - 1 (SolverCg.hpp:98, :123) -- and, where its residual kernel left the group sums, its scalar step
+      const CgStep step{(long long)cur_it, x, r, p_alt, rr_pending ? c->d_ticket_sums : nullptr, rr_ng};
+      rr_pending = false;
       // (<p,z>: per-wave partials for the plane march's fold or the final pass below -- finishing it inside the marching
       //  kernel by tickets was measured for this loop and dropped; the host loop's fused step, lazy.hip, does finish it there: one launch less
       //  in front of a host wait)
@@ -606,9 +639,14 @@ static int solve_cg_body(const FusedSolveArgs &args) {
     if (pz_fold_now && !pz_fold_counted) ++c->n_cg_pz_consumer_folds, pz_fold_counted = true;
     if (!pz_fold_now) STORM_TRY(d.finish_dots(pz_done, nb, 1, S_PZ, p, pz_with, allow, STEP_NONE, &ran, &pz_partials));
     // r -= alpha z; gamma = <r,r>                     SolverCg.hpp:97,99,115
+    // (option cg_rr_fold, on the same road: the kernel ends at its group sums where one batch holds them; the next
+    //  iteration's step kernel -- the marching one: r_march -- or the launch behind the loop takes it from there)
+    const bool rr_fold_now = pz_fold_now && c->opt_cg_rr_fold != 0 && rr_ng >= 1 && rr_ng <= (int)kTicketFoldBatch1;
+    if (rr_fold_now && !rr_fold_counted) ++c->n_cg_rr_consumer_folds, rr_fold_counted = true;
     if (pz_fold_now) {
       STORM_TRY(cg_r_planes_run(op, road.planes_args, road.planes_blocks, host_scal(d.alpha), host_scal(d.beta), p, d.st, r, c->d_partials,
-                                nb, 1 - q, c->d_partials + nb));
+                                nb, 1 - q, c->d_partials + nb, rr_fold_now ? (long long)(cur_it + 1) : 0));
+      rr_pending = rr_fold_now;
     } else if (r_march_now && road.r_planes) {
       STORM_TRY(cg_r_planes_run(op, road.planes_args, road.planes_blocks, host_scal(d.alpha), host_scal(d.beta), p, d.st, r, pz_partials,
                                 (int)kStage2, 1 - q, c->d_partials));
@@ -647,6 +685,10 @@ static int solve_cg_body(const FusedSolveArgs &args) {
     bool stop = false;
     STORM_TRY(post_and_poll(d, it, &stop));
     if (stop) break;
+  }
+  if (rr_pending) {  // the scalar step of the last enqueued iteration: no step kernel behind it
+    hipLaunchKernelGGL(cg_rr_finish_kernel, dim3(1), dim3(kWave), 0, c->stream, d.st, c->d_ticket_sums, rr_ng, (long long)(last_enqueued + 1));
+    HIP_TRY(hipGetLastError());
   }
   if (road.fuse_step && last_enqueued >= 0) {
     // the x update of the last enqueued iteration (a no-op when that iteration never ran: the step kernel of the

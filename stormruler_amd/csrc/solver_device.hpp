@@ -14,23 +14,47 @@ namespace storm {
 __device__ __forceinline__ double safe_divide(double x, double y) { return (y == 0.0) ? 0.0 : (x / y); }
 
 // The body of the for loop in IterativeSolver::solve, Solver.hpp:132-140.
-__device__ inline void advance(SolverState *st, double abs_err) {
-  st->absolute_error = abs_err;
-  st->relative_error = abs_err / st->initial_error;
+// In two halves: the decision as a pure function of what the state holds (any thread may evaluate it, from values it
+// loaded itself), and the stores (one thread).
+struct AdvanceIn {
+  double initial_error, abs_tol, rel_tol;
+  long long iteration, num_iterations;
+};
+struct AdvanceOut {
+  double absolute_error, relative_error;
+  long long iteration;
+  int converged, done;  // 1: set the flag (never cleared here)
+};
+__device__ __forceinline__ AdvanceIn advance_in(const SolverState *st) {
+  return AdvanceIn{st->initial_error, st->abs_tol, st->rel_tol, st->iteration, st->num_iterations};
+}
+__device__ __forceinline__ AdvanceOut advance_eval(const AdvanceIn &in, double abs_err) {
+  AdvanceOut o;
+  o.absolute_error = abs_err;
+  o.relative_error = abs_err / in.initial_error;
   bool conv = false;
-  conv |= (st->abs_tol > 0.0) && (st->absolute_error < st->abs_tol);
-  conv |= (st->rel_tol > 0.0) && (st->relative_error < st->rel_tol);
-  st->iteration += 1;
-  if (st->history) st->history[st->iteration] = abs_err;
-  if (conv) st->converged = 1;
-  if (conv || st->iteration >= st->num_iterations) st->done = 1;
+  conv |= (in.abs_tol > 0.0) && (o.absolute_error < in.abs_tol);
+  conv |= (in.rel_tol > 0.0) && (o.relative_error < in.rel_tol);
+  o.iteration = in.iteration + 1;
+  o.converged = conv ? 1 : 0;
+  o.done = (conv || o.iteration >= in.num_iterations) ? 1 : 0;
+  return o;
+}
+__device__ inline void advance_store(SolverState *st, const AdvanceOut &o) {
+  st->absolute_error = o.absolute_error;
+  st->relative_error = o.relative_error;
+  st->iteration = o.iteration;
+  if (st->history) st->history[o.iteration] = o.absolute_error;
+  if (o.converged) st->converged = 1;
+  if (o.done) st->done = 1;
   // Tell the host (it polls this pinned ring `check_lag` iterations behind): one system-scope store of a word that
   // names its iteration -- the host needs no event behind the kernel to trust it (common.hpp ring_wait).
   if (st->done_ring)
-    __hip_atomic_store(st->done_ring + (st->iteration - 1) % kStateRing,
-                       ring_word(st->ring_gen, (unsigned long long)st->iteration, st->done != 0), __ATOMIC_RELAXED,
+    __hip_atomic_store(st->done_ring + (o.iteration - 1) % kStateRing,
+                       ring_word(st->ring_gen, (unsigned long long)o.iteration, st->done != 0), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_SYSTEM);
 }
+__device__ inline void advance(SolverState *st, double abs_err) { advance_store(st, advance_eval(advance_in(st), abs_err)); }
 
 // After init(): Solver.hpp:122-128.
 __device__ inline void begin(SolverState *st, double initial_error) {

@@ -184,6 +184,7 @@ int Driver::apply(const double *x, double *y, int *nblocks, const ApplyDots &dot
     sd.cg.iteration = &st->iteration, sd.cg.my_iteration = cg->my_iteration;
     sd.cg.ca = slot(S_ALPHA), sd.cg.cb = slot(S_BETA);
     sd.cg.x = cg->x, sd.cg.r = cg->r, sd.cg.p_out = cg->p_out;
+    sd.cg.st = st, sd.cg.rr_sums = cg->rr_sums, sd.cg.rr_ng = cg->rr_ng;
   }
   sd.w = dots.w;
   sd.yy = dots.yy;

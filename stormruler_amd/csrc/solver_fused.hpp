@@ -17,6 +17,10 @@ enum Slot {
   S_TMP, S_HN,
   S_SCRATCH = 32,
   S_ALPHA_SEEN = 48,  // (+ 1: armed) option ticket_verify, RCCL BiCGStab: the alpha the early halo of s was formed with
+  // option cg_rr_fold: what the residual kernel that ends at its group sums leaves for the kernel that folds them -- the
+  // <r,r> its step began with, and (as a double) the iteration counter its sums will produce.  The folding launch reads
+  // them and never writes them: its late blocks find what its first ones found.
+  S_RR_GAMMA = 50, S_RR_GATE,
 };
 
 enum StepKind {
@@ -32,18 +36,35 @@ enum StepKind {
   STEP_GMRES_HN,          // hn = sqrt(tmp)
 };
 
+// STEP_CG_RR in two halves (SolverCg.hpp:110-125): the outcome as a pure function of <r,r> and of what the state holds --
+// every block of a kernel may evaluate it for itself --, and the stores, by one thread.
+struct CgRrOutcome {
+  double gamma, beta;  // the new <r,r>; beta = <r,r> / the previous <r,r>
+  AdvanceOut a;
+};
+__device__ __forceinline__ CgRrOutcome cg_rr_eval(double gamma_new, double gamma_bar, const AdvanceIn &in) {
+  CgRrOutcome o;
+  o.gamma = gamma_new;
+  o.beta = safe_divide(gamma_new, gamma_bar);
+  o.a = advance_eval(in, sqrt(gamma_new));
+  return o;
+}
+__device__ inline void cg_rr_store(SolverState *st, const CgRrOutcome &o) {
+  st->s[S_GAMMA_NEW] = o.gamma;
+  st->s[S_GAMMA] = o.gamma;
+  st->s[S_BETA] = o.beta;
+  advance_store(st, o.a);
+}
+
 __device__ inline void do_step(int kind, SolverState *st, GmresDev g) {
   double *s = st->s;
   switch (kind) {
     case STEP_CG_INIT:  // SolverCg.hpp:82,85
       begin(st, sqrt(s[S_GAMMA]));
       break;
-    case STEP_CG_RR: {  // SolverCg.hpp:110-125
-      const double gamma_bar = s[S_GAMMA];
-      s[S_GAMMA] = s[S_GAMMA_NEW];
-      s[S_BETA] = safe_divide(s[S_GAMMA], gamma_bar);
-      advance(st, sqrt(s[S_GAMMA]));
-    } break;
+    case STEP_CG_RR:  // SolverCg.hpp:110-125
+      cg_rr_store(st, cg_rr_eval(s[S_GAMMA_NEW], s[S_GAMMA], advance_in(st)));
+      break;
     case STEP_BICG_INIT:  // SolverBiCgStab.hpp:88-90
       begin(st, sqrt(s[S_RHO]));
       break;
@@ -114,6 +135,10 @@ struct CgStep {  // the fused CG step of spmv.hip (CgFuseArgs): end iteration my
   double *x;
   const double *r;
   double *p_out;
+  // option cg_rr_fold: that iteration's residual kernel ended at its rr_ng group sums of <r,r> (rr_sums; null: the state
+  // is complete) -- the step kernel folds them and runs STEP_CG_RR itself
+  const double *rr_sums = nullptr;
+  int rr_ng = 0;
 };
 
 struct Driver {

@@ -186,7 +186,8 @@ int spmv_launch(const storm_hip_op *op, Scal alpha, Scal beta, const double *x, 
       STORM_REQUIRE(sd->cg.x != nullptr, "spmv: the fused CG step updates x");
       dot.tickets = nullptr, dot.nblocks_total = 4 * nb_total;  // (the tiled form of the step leaves per-wave partials)
       if (sd->ticketed_out) *sd->ticketed_out = 0;
-      cgf = CgFuseArgs{sd->cg.iteration, sd->cg.my_iteration, sd->cg.ca, sd->cg.cb, sd->cg.x, sd->cg.r, sd->cg.p_out, sd->cg.ca_imm, sd->cg.cb_imm};
+      cgf = CgFuseArgs{sd->cg.iteration, sd->cg.my_iteration, sd->cg.ca, sd->cg.cb, sd->cg.x, sd->cg.r, sd->cg.p_out, sd->cg.ca_imm, sd->cg.cb_imm,
+                       sd->cg.st, sd->cg.rr_sums, sd->cg.rr_ng};
     }
     MarchArgs M;
     int nb_march = 0;
@@ -204,6 +205,7 @@ int spmv_launch(const storm_hip_op *op, Scal alpha, Scal beta, const double *x, 
       return spmv_march_run(op, M, nb_march, alpha, beta, x, y, dot, done, cgf, IpcSendArgs{});
     }
     STORM_REQUIRE(y != nullptr, "spmv: only the marching CG step may leave z = A p' unstored");
+    STORM_REQUIRE(!cg_fused || cgf.rr_sums == nullptr, "spmv: only the marching CG step folds the group sums of <r,r>");
     STORM_REQUIRE(!cg_fused || (cgf.ca != nullptr && cgf.cb != nullptr && cgf.iteration != nullptr),
                   "spmv: a fused CG step with immediate coefficients needs the marching kernel");
     STORM_TRY(launch_range(op, alpha, beta, x, y, nullptr, op->n_slices, dot, fuse_dot, done, accumulate, nullptr,
@@ -222,7 +224,8 @@ int spmv_launch(const storm_hip_op *op, Scal alpha, Scal beta, const double *x, 
       // RCCL: p' = r + beta p of the rows to send is formed by a small kernel on the comm stream and travels while the march
       // below runs; the boundary launch waits for the planes (they land in p_out's halo tail)
       if (over_rccl) STORM_TRY(comm_halo_exchange_begin_direction(op, x, sd->cg.r, sd->cg.cb, sd->cg.p_out));
-      const CgFuseArgs cgf{sd->cg.iteration, sd->cg.my_iteration, sd->cg.ca, sd->cg.cb, sd->cg.x, sd->cg.r, sd->cg.p_out, 0.0, 0.0};
+      STORM_REQUIRE(sd->cg.rr_sums == nullptr, "spmv: a partitioned operator's CG step does not fold the group sums of <r,r>");
+      const CgFuseArgs cgf{sd->cg.iteration, sd->cg.my_iteration, sd->cg.ca, sd->cg.cb, sd->cg.x, sd->cg.r, sd->cg.p_out, 0.0, 0.0, nullptr, nullptr, 0};
       const int nb_b = blocks_for(op, op->n_boundary, true);
       STORM_REQUIRE(8 * (int64_t)(nb_march + nb_b) <= c->partials_capacity, "spmv: %d blocks exceed the partials workspace", nb_march + nb_b);
       dot = DotArgs{sd->cg.p_out, sd->partials, sd->yy ? 1 : 0, 4 * (nb_march + nb_b), 0};

@@ -169,6 +169,13 @@ struct CgFuseArgs {
   const double *r;
   double *p_out;
   double ca_imm, cb_imm;       // marching kernel only: alpha, beta themselves where ca / cb are null (a HOST loop's step: lazy.hip)
+  // marching kernel, unsplit, option cg_rr_fold (rr_sums != null): the state is one scalar step behind -- the residual
+  // kernel of iteration my_iteration - 1 ended at its rr_ng group sums of <r,r> (ticket_device.hpp).  Every block folds
+  // them, forms beta, `done` and the counter for itself (solver_fused.hpp cg_rr_eval); the first block stores the outcome.
+  // `iteration`, `cb` and the launch's `done` are not read then.
+  SolverState *st;
+  const double *rr_sums;
+  int rr_ng;
 };
 
 // ---- the row-record index (option spmv_record_index) -----------------------------------------------------------------

@@ -2,6 +2,7 @@
 // CG step, with the geometry tests that decide when they apply.
 #include <algorithm>
 
+#include "solver_fused.hpp"
 #include "spmv_device.hpp"
 
 namespace storm {
@@ -217,7 +218,13 @@ __global__ __launch_bounds__(kBlock) void spmv_canon_tile_kernel(SellArgs A, Can
   }
 }
 
-template <int HLP, bool IDX>  // HLP: halo pairs per thread and plane: ceil(a / 256); IDX: the row-record index
+// RR (the fused CG loop on one rank, option cg_rr_fold): the residual kernel in front ended at the group sums of <r,r>, and
+// the scalar step behind them -- beta, the convergence rule, the counter -- has not run.  Every wave requests the sums
+// (at most one batch, 1 KiB) and what the step reads of the state in front of its first plane, folds them in
+// ticket_fold_groups' order under that plane's loads and evaluates the step for itself (cg_rr_eval: the same bits in
+// every wave); the first block stores the outcome.  Nothing this launch reads is stored by it -- the residual kernel left
+// a copy of the previous <r,r> and the gate (S_RR_GAMMA, S_RR_GATE) --, so a block of a later round finds what the first found.
+template <int HLP, bool IDX, bool RR>  // HLP: halo pairs per thread and plane: ceil(a / 256); IDX: the row-record index
 __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, MarchArgs M, Scal alpha_s, Scal beta_s,
                                                                const double *__restrict__ p_in, double *__restrict__ z_out,
                                                                DotArgs dot, const int *done, CgFuseArgs F, IpcSendArgs S) {
@@ -227,12 +234,25 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
     ipc_halo_send_block(S.w, S.sp, p_in, (int)blockIdx.x, F.r, *F.cb);
     return;
   }
-  if (F.iteration != nullptr && *F.iteration < F.my_iteration) return;  // enqueued past convergence: that iteration never ran
-  const int done_flag = done ? *done : 0;
+  const int lane = threadIdx.x & (kWave - 1);
+  int done_flag;
+  double cg_a, cg_b;
+  // (RR: the state's part of the step and the group sums, requested first; used behind the first plane's requests)
+  double rr_gate = 0.0, rr_gamma_bar = 0.0;
+  AdvanceIn rr_in{};
+  TicketGroupFlight<1> rr_flight;
+  if constexpr (RR) {
+    const SolverState *st = F.st;
+    rr_gate = st->s[S_RR_GATE], rr_gamma_bar = st->s[S_RR_GAMMA], cg_a = st->s[S_ALPHA];
+    rr_in = AdvanceIn{st->initial_error, st->abs_tol, st->rel_tol, F.my_iteration - 1, st->num_iterations};
+    ticket_groups_issue<1, false>(F.rr_sums, 1, (unsigned)F.rr_ng, (unsigned)lane, rr_flight);
+  } else {
+    if (F.iteration != nullptr && *F.iteration < F.my_iteration) return;  // enqueued past convergence: that iteration never ran
+    done_flag = done ? *done : 0;
+  }
   const CanonTileArgs &T = M.T;
   extern __shared__ __attribute__((aligned(16))) double tile_sh[];  // [3][a + kTileRun + a]
   __shared__ double dict_sh[32];
-  const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n_march = (int)gridDim.x - S.sp.n_blocks, mb = (int)blockIdx.x - S.sp.n_blocks;
   const int bidx = T.reverse ? n_march - 1 - mb : mb;
@@ -250,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
   const int z_begin = zc * M.zc_planes, z_end = min(z_begin + M.zc_planes, T.plane_end);
   const int ldw = kTileRun + 2 * a;
   const double alpha = ld_scal2(alpha_s), beta = ld_scal2(beta_s);
-  const double cg_a = F.ca ? *F.ca : F.ca_imm, cg_b = F.cb ? *F.cb : F.cb_imm;
+  if constexpr (!RR) cg_a = F.ca ? *F.ca : F.ca_imm, cg_b = F.cb ? *F.cb : F.cb_imm;
   const uint32_t last_row = (uint32_t)(A.n_rows - 1);
   const char *pb = reinterpret_cast<const char *>(p_in), *rb = reinterpret_cast<const char *>(F.r);
   const char *pg_base = pb - (size_t)kVecGuard * 8, *rg_base = rb - (size_t)kVecGuard * 8;
@@ -329,6 +349,24 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
     }
   };
 
+  double2v pm[2], pc[2], pn[2];  // p' of the plane behind / at / ahead IN MARCHING ORDER
+  RecRaw<IDX> wc[2];
+  uint32_t rcc[2];
+  bool vac[2], vbc[2];
+  Flight fl;
+  const bool down = M.alternate != 0 && (zc & 1) != 0;  // (block-uniform)
+  const int nz = z_end - z_begin;
+  auto plane = [&](int s) { return down ? z_end - 1 - s : z_begin + s; };  // s = -1 and s = nz: the planes next to the chunk
+  auto lds_of = [&](int zp) { return tile_sh + ((zp % 3 + 3) % 3) * ldw; };
+  if constexpr (RR) {
+    issue(plane(-1), false, fl);  // (nothing of it depends on the step: in flight under the fold)
+    const CgRrOutcome o = cg_rr_eval(ticket_fold_groups_flight(rr_flight, (unsigned)F.rr_ng), rr_gamma_bar, rr_in);
+    // (the gate: the residual kernel of iteration my_iteration - 1 ran -- else the solve ended earlier and its sums are stale)
+    if (rr_gate != (double)F.my_iteration) return;
+    cg_b = o.beta, done_flag = o.a.done;
+    if (blockIdx.x == 0 && threadIdx.x == 0) cg_rr_store(F.st, o);
+  }
+
   if (done_flag) {  // converged in that iteration: only x += alpha p is left to do
     for (int zp = z_begin; zp < z_end; ++zp) {
 #pragma unroll
@@ -351,16 +389,7 @@ __global__ __launch_bounds__(kBlock) void cg_step_march_kernel(SellArgs A, March
     return;
   }
 
-  double2v pm[2], pc[2], pn[2];  // p' of the plane behind / at / ahead IN MARCHING ORDER
-  RecRaw<IDX> wc[2];
-  uint32_t rcc[2];
-  bool vac[2], vbc[2];
-  Flight fl;
-  const bool down = M.alternate != 0 && (zc & 1) != 0;  // (block-uniform)
-  const int nz = z_end - z_begin;
-  auto plane = [&](int s) { return down ? z_end - 1 - s : z_begin + s; };  // s = -1 and s = nz: the planes next to the chunk
-  auto lds_of = [&](int zp) { return tile_sh + ((zp % 3 + 3) % 3) * ldw; };
-  issue(plane(-1), false, fl);
+  if constexpr (!RR) issue(plane(-1), false, fl);
   consume(false, fl, pm, nullptr);
   issue(plane(0), true, fl);
   consume(true, fl, pc, lds_of(plane(0)));
@@ -574,9 +603,19 @@ int spmv_march_run(const storm_hip_op *op, const MarchArgs &M, int n_blocks, Sca
   const size_t lds = sizeof(double) * 3 * (size_t)(kTileRun + 2 * M.T.a) + sizeof(uint64_t) * (size_t)A.rec_words_n;
   const int nb = n_blocks + S.sp.n_blocks;
 #define MARCH_GO(HLP_, IX_)                                                                                                 \
-  hipExtLaunchKernelGGL((cg_step_march_kernel<HLP_, IX_>), dim3(nb), dim3(kBlock), lds, c->stream, ev0, ev1, 0, A, M, alpha, \
-                        beta, x, y, dot, done, cgf, S)
+  do {                                                                                                                      \
+    if (cgf.rr_sums != nullptr)                                                                                             \
+      hipExtLaunchKernelGGL((cg_step_march_kernel<HLP_, IX_, true>), dim3(nb), dim3(kBlock), lds, c->stream, ev0, ev1, 0, A, M, \
+                            alpha, beta, x, y, dot, done, cgf, S);                                                          \
+    else                                                                                                                    \
+      hipExtLaunchKernelGGL((cg_step_march_kernel<HLP_, IX_, false>), dim3(nb), dim3(kBlock), lds, c->stream, ev0, ev1, 0, A, M, \
+                            alpha, beta, x, y, dot, done, cgf, S);                                                          \
+  } while (0)
   STORM_REQUIRE(cgf.x != nullptr, "spmv: the marching step updates x");
+  // (the step folds the group sums of <r,r> itself: one rank's unsplit launch, one batch of sums, the state at hand)
+  STORM_REQUIRE(cgf.rr_sums == nullptr || (S.sp.n_blocks == 0 && cgf.st != nullptr && cgf.ca != nullptr && cgf.rr_ng >= 1 &&
+                                           cgf.rr_ng <= (int)kTicketFoldBatch1),
+                "spmv: the marching step folds at most %d group sums of <r,r>, on one rank", (int)kTicketFoldBatch1);
   if (M.T.a <= kBlock) {
     if (A.rec_idx != nullptr) MARCH_GO(1, true);
     else MARCH_GO(1, false);

@@ -59,34 +59,62 @@ __device__ __forceinline__ double ticket_wave_sum(double v) {
   return wave_sum_all(v);  // (= the xor butterfly's value in every lane, bit for bit: wave_device.hpp)
 }
 
+// The top fold in two halves, so that a kernel with loads of its own can put the fold's behind them: lane i takes groups
+// i, i + 64, ... in ascending order (the order of the sums is fixed); ticket_groups_issue requests one batch of them --
+// kTicketAhead groups per lane and value, all before the first is added --, ticket_groups_add adds the batch to the lane's
+// sums.  Every top fold of the library adds through ticket_groups_add and ends with ticket_wave_sum: the order is written once.
+//   COHERENT: loads at the point of coherence, for the wave that drew the last top-level ticket of a running kernel;
+//   false: plain loads, for a kernel launched behind the one that stored the group sums (the kernel boundary releases them).
+template <int KMAX>
+struct TicketGroupFlight {
+  static constexpr int kAhead = KMAX <= 4 ? 4 : 2;
+  double v[KMAX][kAhead];
+};
+constexpr unsigned kTicketFoldBatch1 = kWave * 4;  // the groups one batch of one value holds (TicketGroupFlight<1>)
+template <int KMAX, bool COHERENT>
+__device__ __forceinline__ void ticket_groups_issue(const double *part2, int k, unsigned ng, unsigned i0, TicketGroupFlight<KMAX> &f) {
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j)
+#pragma unroll
+    for (int u = 0; u < TicketGroupFlight<KMAX>::kAhead; ++u) {
+      const unsigned i = i0 + u * kWave;
+      f.v[j][u] = 0.0;
+      if (j < k && i < ng) {
+        if constexpr (COHERENT) f.v[j][u] = __hip_atomic_load(part2 + (size_t)j * ng + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else f.v[j][u] = part2[(size_t)j * ng + i];
+      }
+    }
+}
+template <int KMAX>
+__device__ __forceinline__ void ticket_groups_add(const TicketGroupFlight<KMAX> &f, unsigned ng, unsigned i0, double (&total)[KMAX]) {
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j)
+#pragma unroll
+    for (int u = 0; u < TicketGroupFlight<KMAX>::kAhead; ++u)
+      if (i0 + u * kWave < ng) total[j] += f.v[j][u];
+}
 // The top fold, by the wave that drew the last top-level ticket: total[j] = the sum of the ng group sums of value j, in
 // all lanes.
 template <int KMAX>
 __device__ __forceinline__ void ticket_fold_groups(const TicketArgs &t, int k, unsigned ng, double (&total)[KMAX]) {
   const unsigned lane = threadIdx.x & (kWave - 1);
-  // lane i takes groups i, i + 64, ... in ascending order (the order of the sums is fixed); four groups per lane and
-  // value are loaded before the first is added
-  constexpr int kAhead = KMAX <= 4 ? 4 : 2;
 #pragma unroll
   for (int j = 0; j < KMAX; ++j) total[j] = 0.0;
-  for (unsigned i0 = lane; i0 < ng; i0 += kWave * kAhead) {
-    double v[KMAX][kAhead];
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j)
-#pragma unroll
-      for (int u = 0; u < kAhead; ++u) {
-        const unsigned i = i0 + u * kWave;
-        v[j][u] = 0.0;
-        if (j < k && i < ng) v[j][u] = __hip_atomic_load(t.part2 + (size_t)j * ng + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j)
-#pragma unroll
-      for (int u = 0; u < kAhead; ++u)
-        if (i0 + u * kWave < ng) total[j] += v[j][u];
+  for (unsigned i0 = lane; i0 < ng; i0 += kWave * TicketGroupFlight<KMAX>::kAhead) {
+    TicketGroupFlight<KMAX> f;
+    ticket_groups_issue<KMAX, true>(t.part2, k, ng, i0, f);
+    ticket_groups_add<KMAX>(f, ng, i0, total);
   }
 #pragma unroll
   for (int j = 0; j < KMAX; ++j) total[j] = ticket_wave_sum(total[j]);
+}
+// ... of ONE value whose ng <= kTicketFoldBatch1 group sums a kernel behind the producer requested with
+// ticket_groups_issue<1, false>(part2, 1, ng, lane, f): ticket_fold_groups<1>'s adds in its order, hence its bits.
+__device__ __forceinline__ double ticket_fold_groups_flight(const TicketGroupFlight<1> &f, unsigned ng) {
+  const unsigned lane = threadIdx.x & (kWave - 1);
+  double total[1] = {0.0};
+  ticket_groups_add<1>(f, ng, lane, total);
+  return ticket_wave_sum(total[0]);
 }
 
 // Wave 0 of every block calls this (all 64 lanes) with the block's partials `mine[0 .. k)` (k <= KMAX).
@@ -140,10 +168,12 @@ __device__ __forceinline__ bool ticket_reduce_wave0(const TicketArgs &t, const d
 // size" is the last), and the group sums and the top fold are ticket_reduce_wave0's: the same values in the same
 // order, whichever hardware block formed them.  Round trips to memory do not grow with the number of slots: every
 // step is issued for all its lanes (or, the group loads, four groups) at a time.
-__device__ __forceinline__ bool ticket_reduce_wave0_slots(const TicketArgs &t, double mine, bool on, unsigned bxv, unsigned nb,
-                                                          double *total) {
+// Level 1 of it: returns the lanes that drew the last ticket of a group (0: none), each with its group's sum in `gsum`;
+// `g`, `ng`: the lane's group and the number of groups.
+__device__ __forceinline__ unsigned long long ticket_slots_level1(const TicketArgs &t, double mine, bool on, unsigned bxv, unsigned nb,
+                                                                  unsigned &g, unsigned &ng, double &gsum) {
   const unsigned lane = threadIdx.x & (kWave - 1);
-  const unsigned g = bxv / kTicketGroup, ng = (nb + kTicketGroup - 1) / kTicketGroup;
+  g = bxv / kTicketGroup, ng = (nb + kTicketGroup - 1) / kTicketGroup;
   const unsigned gsize = (nb - g * kTicketGroup) < (unsigned)kTicketGroup ? (nb - g * kTicketGroup) : (unsigned)kTicketGroup;
   if (on) {
     const double v[1] = {mine};
@@ -167,11 +197,9 @@ __device__ __forceinline__ bool ticket_reduce_wave0_slots(const TicketArgs &t, d
     }
   }
   // the groups this block completed: their sums (ticket_reduce_wave0's loads and wave sum) into the drawing lanes
-  unsigned long long fin = __ballot(go != 0);
-  if (fin == 0ull) return false;
-  const int n_fin = __popcll(fin);
-  double gsum = 0.0;
-  while (fin != 0ull) {
+  const unsigned long long done = __ballot(go != 0);
+  gsum = 0.0;
+  for (unsigned long long fin = done; fin != 0ull;) {
     int at[4];
     double gp[4];
 #pragma unroll
@@ -194,11 +222,21 @@ __device__ __forceinline__ bool ticket_reduce_wave0_slots(const TicketArgs &t, d
       if ((int)lane == at[j]) gsum = sj;
     }
   }
-  if (go) {
+  return done;
+}
+__device__ __forceinline__ bool ticket_reduce_wave0_slots(const TicketArgs &t, double mine, bool on, unsigned bxv, unsigned nb,
+                                                          double *total) {
+  const unsigned lane = threadIdx.x & (kWave - 1);
+  unsigned g, ng;
+  double gsum;
+  const unsigned long long fin = ticket_slots_level1(t, mine, on, bxv, nb, g, ng, gsum);
+  if (fin == 0ull) return false;
+  const int n_fin = __popcll(fin);
+  if ((fin >> lane) & 1ull) {
     const double v[1] = {gsum};
     ticket_publish<1>(t.part2 + g, ng, v, 1);
   }
-  go = 0;
+  int go = 0;
   if (lane == 0) {
     if (__hip_atomic_fetch_add(t.cnt, n_fin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + n_fin == (int)ng) {
       __hip_atomic_store(t.cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -211,6 +249,17 @@ __device__ __forceinline__ bool ticket_reduce_wave0_slots(const TicketArgs &t, d
   ticket_fold_groups<1>(t, 1, ng, tot);
   *total = tot[0];
   return true;
+}
+// ... that ENDS at the group sums: the last block of a group stores its sum to part2[g] with a plain store and nobody
+// draws a top-level ticket -- the kernel boundary releases the sums, and a kernel launched behind this one folds them
+// (ticket_groups_issue<1, false>, ticket_fold_groups_flight): the chain of round trips behind the group sums -- the awaited
+// exchange, the top ticket, the fold's loads -- is gone from the producer's tail.  The group counters re-arm as ever.
+__device__ __forceinline__ void ticket_reduce_wave0_slots_to_groups(const TicketArgs &t, double mine, bool on, unsigned bxv, unsigned nb) {
+  const unsigned lane = threadIdx.x & (kWave - 1);
+  unsigned g, ng;
+  double gsum;
+  const unsigned long long fin = ticket_slots_level1(t, mine, on, bxv, nb, g, ng, gsum);
+  if ((fin >> lane) & 1ull) t.part2[g] = gsum;
 }
 
 }  // namespace storm
