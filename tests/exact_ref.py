@@ -29,6 +29,13 @@ step's own terms; ``StepPins`` holds history[0..K], x_k and their tolerances by 
 with its chain and operator.  The same bodies run on ``Float64Space`` (``cg_float64``, ``bicgstab_float64``) with the
 defects the pins must reject.
 
+Operators with a halo: ``periodic_box`` is the unit-spacing box that is periodic in z as one rank's local graph, the
+rank its own neighbour -- -L (diagonal 6 ... 8) and the same convection-diffusion -- with ``IntOperator.from_local_graph``
+folding the halo columns onto the owned cells they copy; ``StepProblem`` and ``GmresProblem`` take them as kinds
+"periodic" and "periodic_convdiff" (tests/test_gpu_exact_rccl.py).  ``Float64Space`` takes the split A = A_in + A_h
+along the periodic seam, and ``cg`` / ``bicgstab`` the defects of the halo alone (``CG_HALO_DEFECTS``,
+``BICGSTAB_HALO_DEFECTS``): a missed exchange, halo rows formed with the previous beta, alpha or omega.
+
 Plain module, not a conftest: the tests import it by name.
 """
 import math
@@ -381,6 +388,38 @@ class IntOperator:
         cells = np.arange(n)
         return cls(n, np.concatenate([i, i, o, o, cells]), np.concatenate([o, i, i, o, cells]),
                    np.concatenate([w_inner, -w_inner, w_outer, -w_outer, diag_extra]))
+
+    @classmethod
+    def from_local_graph(cls, g, w_inner, w_outer, diag_extra):
+        """``from_face_weights`` for a local graph with a halo whose halo cells are copies of owned cells (a periodic
+        box, the rank its own neighbour): the rows are the owned cells only, a halo column is folded onto the owned
+        cell it is the image of, ``g.global_id[col]``."""
+        n = g.n_cells
+        gid = np.asarray(g.global_id, np.int64)
+        assert g.n_halo > 0 and gid.shape == (g.n_total,) and np.array_equal(gid[:n], np.arange(n))
+        assert int(gid[n:].min()) >= 0 and int(gid[n:].max()) < n, "a halo cell is no copy of an owned cell"
+        i, o = np.asarray(g.inner), np.asarray(g.outer)
+        cells = np.arange(n)
+        rows = np.concatenate([i, i, o, o, cells])
+        cols = np.concatenate([o, i, i, o, cells])
+        vals = np.concatenate([w_inner, -w_inner, w_outer, -w_outer, diag_extra])
+        own = rows < n
+        return cls(n, rows[own], gid[cols[own]], vals[own])
+
+    def seam_split(self, shape):
+        """A = A_in + A_h as fp64 CSR for a box periodic in z: A_h holds the entries that cross the periodic seam --
+        rows of plane 0 with columns in plane nz - 1 and the reverse, what a rank reads from its halo --, A_in the
+        rest.  Three planes or more, so that no neighbour inside the box is also the one across the seam."""
+        nx, ny, nz = shape
+        assert nx * ny * nz == self.n and nz >= 3
+        a = self.csr.tocoo()
+        plane = a.row // (nx * ny), a.col // (nx * ny)
+        seam = ((plane[0] == 0) & (plane[1] == nz - 1)) | ((plane[0] == nz - 1) & (plane[1] == 0))
+        import scipy.sparse as sps
+
+        part = lambda m: sps.coo_matrix((a.data[m].astype(np.float64), (a.row[m], a.col[m])), shape=a.shape).tocsr()  # noqa: E731
+        assert int(seam.sum()) > 0
+        return part(~seam), part(seam)
 
     def apply(self, w):
         w = np.asarray(w)
@@ -762,6 +801,10 @@ def _dot_without_last_row(sp, u, v):
 
 CG_DEFECTS = ("stale_gamma", "old_r", "skip_x", "double_x", "stale_pz", "old_p", "drop_row")
 BICGSTAB_DEFECTS = ("beta_no_ratio", "stale_omega", "skip_x_omega", "old_v", "rho_early")
+# defects of the halo alone: a space whose ``A(v, halo_of=u)`` reads the rows across the periodic seam from u
+# (``Float64Space`` with its split); they change two planes of one operand of one apply
+CG_HALO_DEFECTS = ("halo_stale_p", "halo_old_beta")
+BICGSTAB_HALO_DEFECTS = ("halo_s_old_alpha", "halo_p_old_omega")
 
 
 def cg(sp, K, pre=False, defect=None, at=2):
@@ -777,8 +820,11 @@ def cg(sp, K, pre=False, defect=None, at=2):
       "double_x"     x += alpha p applied twice at the last iteration (the tail kernel after a fused step)
       "stale_pz"     alpha from the previous iteration's <p, z>
       "old_p"        p' = r + beta p_{k-2} at iteration ``at`` (the wrong buffer of the ping-pong)
-      "drop_row"     <r, r> of iteration ``at`` - 1 without its last row (history[``at``])"""
-    assert defect is None or (defect in CG_DEFECTS and at >= 1 and not pre)
+      "drop_row"     <r, r> of iteration ``at`` - 1 without its last row (history[``at``])
+    and in the halo (``CG_HALO_DEFECTS``):
+      "halo_stale_p"  z = A_in p + A_h p_prev at iteration ``at``: the exchange did not happen, or was not waited for
+      "halo_old_beta" from iteration 1 on the halo rows of p' are r + beta_prev p, the previous iteration's beta"""
+    assert defect is None or (defect in CG_DEFECTS + CG_HALO_DEFECTS and at >= 1 and not pre)
     b = sp.b()
     x, r = sp.zero(), b  # :73 (x0 = 0)
     if pre:
@@ -791,8 +837,14 @@ def cg(sp, K, pre=False, defect=None, at=2):
     hist, feeds = [sp.dot(r, r) if pre else gamma], [[r]]  # :83
     xs, ratio = [x], [1]
     gamma_0, pz_prev, p_prev = gamma, None, None
+    p_halo = beta_prev = None  # (what the halo holds where it is not p: the halo defects)
     for it in range(K):
-        z = sp.A(p)  # :96
+        if defect == "halo_stale_p" and it == at:
+            z = sp.A(p, halo_of=p_prev)
+        elif p_halo is not None:
+            z = sp.A(p, halo_of=p_halo)
+        else:
+            z = sp.A(p)  # :96
         pz = sp.dot(p, z)
         alpha = _sdiv(gamma, pz_prev if defect == "stale_pz" and it >= 1 else pz)  # :97
         pz_prev = pz
@@ -812,6 +864,8 @@ def cg(sp, K, pre=False, defect=None, at=2):
             gamma = sp.dot(r, r)  # :115
         beta = _sdiv(gamma, gamma_0 if defect == "stale_gamma" else gamma_bar)  # :122
         lead = z if pre else (r_old if defect == "old_r" and it >= 1 else r)
+        p_halo = lead + beta_prev * p if defect == "halo_old_beta" and it >= 1 else None
+        beta_prev = beta
         p_prev, p = p, lead + beta * (p_prev if defect == "old_p" and it == at else p)  # :123
         hist.append(sp.dot(r, r) if pre else gamma)  # :125
         feeds.append([r])
@@ -833,8 +887,12 @@ def bicgstab(sp, K, defect=None, at=2):
       "stale_omega"   p = r + beta (p - omega v) with the omega of the iteration before the last (from iteration 2 on)
       "skip_x_omega"  x += omega r left out at iteration ``at``
       "old_v"         v_{k-2} read for v_{k-1} in p at iteration ``at`` (the wrong parity buffer)
-      "rho_early"     rho = <r~, r> with the r of before r -= omega t"""
-    assert defect is None or (defect in BICGSTAB_DEFECTS and at >= 2)
+      "rho_early"     rho = <r~, r> with the r of before r -= omega t
+    and in the halo (``BICGSTAB_HALO_DEFECTS``):
+      "halo_s_old_alpha" from iteration 1 on t = A_in s + A_h (r - alpha_prev v): the halo rows of s with the alpha of
+                         the iteration before
+      "halo_p_old_omega" from iteration 2 on the halo rows of p' are r + beta (p - omega_prev v), the omega before the last"""
+    assert defect is None or (defect in BICGSTAB_DEFECTS + BICGSTAB_HALO_DEFECTS and at >= 2)
     r = sp.b()  # :82 (x0 = 0)
     rt = r  # :87
     rho = sp.dot(rt, r)  # :88
@@ -848,13 +906,17 @@ def bicgstab(sp, K, defect=None, at=2):
             rho_bar, rho = rho, sp.dot(rt, s if defect == "rho_early" else r)  # :116-117
             beta = _sdiv(rho, rho_bar) if defect == "beta_no_ratio" else _sdiv(alpha * rho, omega * rho_bar)  # :118
             om = omega_prev if defect == "stale_omega" and it >= 2 else omega
+            p_halo = r + beta * (p - omega_prev * v) if defect == "halo_p_old_omega" and it >= 2 else None
             p = r + beta * (p - om * (v_prev if defect == "old_v" and it == at else v))  # :119
-        v_prev, v = v, sp.A(p)  # :137
-        alpha = _sdiv(rho, sp.dot(rt, v))  # :139
+        v_prev, v = v, (sp.A(p) if it == 0 or p_halo is None else sp.A(p, halo_of=p_halo))  # :137
+        alpha_prev, alpha = alpha, _sdiv(rho, sp.dot(rt, v))  # :139
         x = x + alpha * p  # :140
         r_old, av = r, alpha * v
         r = s = r - av  # :141
-        t = sp.A(r)  # :158
+        if defect == "halo_s_old_alpha" and it >= 1:
+            t = sp.A(r, halo_of=r_old - alpha_prev * v)
+        else:
+            t = sp.A(r)  # :158
         omega_prev, omega = omega, _sdiv(sp.dot(t, r), sp.dot(t, t))  # :159-160
         if not (defect == "skip_x_omega" and it == at):
             x = x + omega * r  # :161
@@ -871,10 +933,12 @@ def bicgstab(sp, K, defect=None, at=2):
 
 class Float64Space:
     """The vector interface in plain fp64 numpy over a scipy CSR matrix: the method bodies above become float64
-    restatements, with their defects."""
+    restatements, with their defects.  ``a_halo``: the optional split A = a + a_halo (``IntOperator.seam_split``), a
+    the entries inside the box and a_halo those across the periodic seam; ``A(v, halo_of=u)`` then multiplies a_halo by u
+    in place of v -- a halo that holds something else than the vector it belongs to."""
 
-    def __init__(self, a, b):
-        self.a, self._b = a, np.asarray(b, np.float64)
+    def __init__(self, a, b, a_halo=None):
+        self.a, self.a_halo, self._b = a, a_halo, np.asarray(b, np.float64)
         self.ndots, self.drop_at = 0, None
 
     def b(self):
@@ -883,8 +947,11 @@ class Float64Space:
     def zero(self):
         return np.zeros(self._b.size)
 
-    def A(self, v):
-        return self.a @ v
+    def A(self, v, halo_of=None):
+        if self.a_halo is None:
+            assert halo_of is None, "a halo defect needs the split A = A_in + A_h"
+            return self.a @ v
+        return self.a @ v + self.a_halo @ (v if halo_of is None else halo_of)
 
     def dot(self, u, v):
         self.ndots += 1
@@ -893,20 +960,21 @@ class Float64Space:
         return float(np.dot(u, v))
 
 
-def _float64_run(method, a, b, K, defect, at):
-    run = method(Float64Space(a, b), K, defect=defect, at=at)
+def _float64_run(method, a, b, K, defect, at, a_halo=None):
+    run = method(Float64Space(a, b, a_halo), K, defect=defect, at=at)
     return np.sqrt(np.array(run.hist_sq, np.float64)), run.xs
 
 
-def cg_float64(a, b, K, defect=None, at=2):
+def cg_float64(a, b, K, defect=None, at=2, a_halo=None):
     """CG's history[0..K] and x_0 ... x_K in plain fp64 numpy (``a``: scipy CSR, fp64): ``cg``'s statements, and the
-    defects the pins must reject (``CG_DEFECTS``)."""
-    return _float64_run(cg, a, b, K, defect, at)
+    defects the pins must reject (``CG_DEFECTS``; with the split ``a`` + ``a_halo`` also ``CG_HALO_DEFECTS``)."""
+    return _float64_run(cg, a, b, K, defect, at, a_halo)
 
 
-def bicgstab_float64(a, b, K, defect=None, at=2):
-    """BiCGStab's history[0..K] and x_0 ... x_K in plain fp64 numpy, with ``BICGSTAB_DEFECTS``."""
-    return _float64_run(bicgstab, a, b, K, defect, at)
+def bicgstab_float64(a, b, K, defect=None, at=2, a_halo=None):
+    """BiCGStab's history[0..K] and x_0 ... x_K in plain fp64 numpy, with ``BICGSTAB_DEFECTS`` (and, with the split,
+    ``BICGSTAB_HALO_DEFECTS``)."""
+    return _float64_run(bicgstab, a, b, K, defect, at, a_halo)
 
 
 def _root(v):
@@ -1338,6 +1406,30 @@ def convdiff_box(mesh, nx, ny, nz, vel=(2.0, 1.0, -1.0)):
     return g, w, op
 
 
+def periodic_box(mesh, nx, ny, nz, vel=None):
+    """The integer operators WITH A HALO: the box at unit spacing, walls in x and y, periodic in z, as one rank's local
+    graph whose halo planes are the images of its own planes nz - 1 and 0 (``mesh.periodic_z_local_graph``).  ``vel``
+    None: -L, diagonal 6 ... 8, off-diagonals -1, symmetric; else first-order upwind convection-diffusion with nu = 1,
+    row sums of |A| <= 20, |A - A^T| = 2.  Returns the local graph, the rows the rank sends (itself), the face weights
+    for ``StencilMatrix.from_face_weights`` (apply with alpha = 1, beta = 0; -L is also ``from_face_graph`` with
+    alpha = -1) and the ``IntOperator`` of the owned cells, the halo folded (``from_local_graph``)."""
+    loc, send_idx = mesh.periodic_z_local_graph(nx, ny, nz, lengths=(float(nx), float(ny), float(nz)))
+    w = mesh.convection_diffusion_weights(loc, 1.0, (0.0, 0.0, 0.0) if vel is None else vel)
+    op = IntOperator.from_local_graph(loc, *w)
+    assert op.rowsum <= (12 if vel is None else 20)
+    return loc, send_idx, w, op
+
+
+def periodic_oracle_op(oracle, loc, send_idx, vel=None, variant="strict"):
+    """The oracle's operator of ``periodic_box``: its face loops over the local graph, the halo filled with the rows
+    the rank would receive."""
+    kw = {} if vel is None else dict(conv=1.0, vel=vel)
+    op = oracle.StencilOperator(loc, -1.0, 0.0, variant=variant, **kw)
+    n = loc.n_cells
+    return oracle.CallbackOperator(n, lambda x: op.apply(np.concatenate([x, x[send_idx]]))[:n])
+
+
+PERIODIC_KINDS = ("periodic", "periodic_convdiff")
 GMRES_VEL = (2.0, 1.0, -1.0)
 GMRES_SEED, GMRES_RANGE = 31, (-3, 3)  # b = int_vector(n, 31, -3, 3): W_t stays in int64 through t = 13
 # shape -> the (K, m) pinned on it (tests/test_gpu_exact_gmres.py names the kernel width each shape is there for).
@@ -1352,14 +1444,21 @@ class GmresProblem:
     """One shape of the GMRES pins: the convection-diffusion box, b, the chain, and the pins of its (K, m), built on
     demand and kept."""
 
-    def __init__(self, oracle, mesh, shape):
-        self.oracle, self.shape = oracle, shape
-        self.g, self.weights, self.A = convdiff_box(mesh, *shape, vel=GMRES_VEL)
+    def __init__(self, oracle, mesh, shape, kind="convdiff"):
+        self.oracle, self.shape, self.kind = oracle, shape, kind
+        if kind in PERIODIC_KINDS:  # the same operators on the z-periodic box: ``g`` is the local graph with its halo
+            self.vel = GMRES_VEL if kind == "periodic_convdiff" else None
+            self.g, self.send_idx, self.weights, self.A = periodic_box(mesh, *shape, vel=self.vel)
+        else:
+            assert kind == "convdiff"
+            self.g, self.weights, self.A = convdiff_box(mesh, *shape, vel=GMRES_VEL)
         self.b = int_vector(self.g.n_cells, GMRES_SEED, *GMRES_RANGE)
         self.basis = OpBasis(self.A, self.b)
         self._pins = {}
 
     def oracle_op(self, variant):
+        if self.kind in PERIODIC_KINDS:
+            return periodic_oracle_op(self.oracle, self.g, self.send_idx, self.vel, variant)
         return self.oracle.StencilOperator(self.g, -1.0, 0.0, conv=1.0, vel=GMRES_VEL, variant=variant)
 
     def pins(self, K, m):
@@ -1605,6 +1704,15 @@ STEP_CASES = {
 STEP_STOP = 3  # the early-exit tests stop at this iteration
 STEP_RANK_SHAPES, STEP_RANK_K = [(64, 16, 24), (32, 16, 18)], 4  # tests/test_gpu_exact_ranks.py: the whole boxes (2 and 3 slabs)
 STEP_BLOCK_SEEDS = (31, 32, 33, 34)  # tests/test_gpu_block.py: the columns of the block CG on 64 x 48 x 40, K = 8
+# tests/test_gpu_exact_rccl.py, the z-periodic boxes over a size-1 communicator: G gets general records; on L and L2 the
+# interior planes get lattice records and CG its fused step.  Only G is below GMRES_X_ROWS (x against the exact x_k)
+PERIODIC_G, PERIODIC_L, PERIODIC_L2 = (20, 12, 9), (32, 32, 24), (64, 16, 40)
+PERIODIC_STEP_CASES = {
+    "cg": [(PERIODIC_G, "periodic"), (PERIODIC_L, "periodic"), (PERIODIC_L2, "periodic")],
+    "bicgstab": [(PERIODIC_G, "periodic"), (PERIODIC_L, "periodic"), (PERIODIC_G, "periodic_convdiff"),
+                 (PERIODIC_L, "periodic_convdiff")],
+}
+PERIODIC_GMRES_CASES = {PERIODIC_G: [(12, 5), (9, 9)], PERIODIC_L: [(12, 5), (9, 9)]}  # on "periodic_convdiff"
 
 
 class StepProblem:
@@ -1613,7 +1721,12 @@ class StepProblem:
 
     def __init__(self, oracle, mesh, shape, kind="poisson", seed=STEP_SEED):
         self.oracle, self.shape, self.kind = oracle, tuple(shape), kind
-        if kind == "convdiff":
+        if kind in PERIODIC_KINDS:
+            self.vel = GMRES_VEL if kind == "periodic_convdiff" else None
+            self.g, self.send_idx, self.weights, self.A = periodic_box(mesh, *shape, vel=self.vel)
+            self.b = int_vector(self.g.n_cells, GMRES_SEED, *GMRES_RANGE)
+            self.basis, self.fs = OpBasis(self.A, self.b), None
+        elif kind == "convdiff":
             self.g, self.weights, self.A = convdiff_box(mesh, *shape, vel=GMRES_VEL)
             self.b = int_vector(self.g.n_cells, GMRES_SEED, *GMRES_RANGE)
             self.basis, self.fs = OpBasis(self.A, self.b), None
@@ -1625,6 +1738,8 @@ class StepProblem:
         self._pins, self._A2 = {}, None
 
     def oracle_op(self, variant):
+        if self.kind in PERIODIC_KINDS:
+            return periodic_oracle_op(self.oracle, self.g, self.send_idx, self.vel, variant)
         if self.kind == "convdiff":
             return self.oracle.StencilOperator(self.g, -1.0, 0.0, conv=1.0, vel=GMRES_VEL, variant=variant)
         return self.oracle.StencilOperator(self.g, -1.0, 0.0, variant=variant)

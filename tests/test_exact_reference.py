@@ -818,3 +818,207 @@ def test_a_dropped_row_in_the_exact_form(env):
     run = er.cg(er.Space(p.basis), 3, defect="drop_row")
     assert run.hist_sq[:2] == pins.run.hist_sq[:2] and run.history[2] != pins.exact[2]
     assert abs(run.history[2] - pins.exact[2]) > 100 * pins.tol[2] * pins.exact[2]
+
+
+# ---- the z-periodic boxes: integer operators with a halo (exact_ref.periodic_box, tests/test_gpu_exact_rccl.py) ------------
+
+PERIODIC_TINY = (5, 4, 3)
+# (method, defect, box): CG on the symmetric operator, BiCGStab on both
+HALO_DEFECTS = [("cg", d, "periodic") for d in er.CG_HALO_DEFECTS] + \
+    [("bicgstab", d, kind) for d in er.BICGSTAB_HALO_DEFECTS for kind in er.PERIODIC_KINDS]
+
+
+def test_periodic_local_graph_without_lengths_is_what_it_was():
+    """``mesh.periodic_z_local_graph(8, 8, 8)`` returns, array for array and bit for bit, what it returned before it took
+    ``lengths`` (tests/golden/periodic_z_local_graph_8x8x8.npz: the arrays of that version)."""
+    import os
+
+    from stormruler_amd import mesh
+
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "periodic_z_local_graph_8x8x8.npz"))
+    loc, send_idx = mesh.periodic_z_local_graph(8, 8, 8)
+    assert [loc.n_cells, loc.dim, loc.n_halo] == list(want["counts"])
+    for name in ("inner", "outer", "area", "center", "volume", "b_cell", "b_area", "b_center", "global_id", "halo_owner"):
+        got = getattr(loc, name)
+        assert got.dtype == want[name].dtype and got.shape == want[name].shape and got.tobytes() == want[name].tobytes(), name
+    assert send_idx.dtype == want["send_idx"].dtype and np.array_equal(send_idx, want["send_idx"])
+
+
+def test_periodic_local_graph_with_lengths():
+    """With ``lengths`` the graph is ``structured_box(..., lengths=...)`` without its z walls, the images of planes nz - 1
+    and 0 shifted by -Lz and +Lz and the seam faces with the area of a z face."""
+    from stormruler_amd import mesh
+
+    nx, ny, nz = 6, 4, 5
+    lengths = (3.0, 8.0, 10.0)
+    loc, send_idx = mesh.periodic_z_local_graph(nx, ny, nz, lengths=lengths)
+    g = mesh.structured_box(nx, ny, nz, lengths=lengths)
+    P, N = nx * ny, nx * ny * nz
+    assert loc.n_cells == N and loc.n_halo == 2 * P and loc.n_faces == g.n_faces + 2 * P
+    assert loc.n_bfaces == g.n_bfaces - 2 * P and not np.any(np.isin(loc.b_center[:, 2], (0.0, lengths[2])))
+    assert np.array_equal(np.sort(loc.b_cell), np.sort(g.b_cell[(g.b_center[:, 2] != 0.0) & (g.b_center[:, 2] != lengths[2])]))
+    assert np.array_equal(loc.center[:N], g.center) and np.array_equal(loc.global_id[N:], send_idx)
+    assert np.array_equal(loc.center[N:N + P], g.center[N - P:] - [0.0, 0.0, lengths[2]])
+    assert np.array_equal(loc.center[N + P:], g.center[:P] + [0.0, 0.0, lengths[2]])
+    assert np.all(loc.area[g.n_faces:] == (lengths[0] / nx) * (lengths[1] / ny))
+    d = loc.center[loc.outer[g.n_faces:]] - loc.center[loc.inner[g.n_faces:]]
+    assert np.allclose(d, [0.0, 0.0, lengths[2] / nz], rtol=0, atol=1e-14)
+
+
+@pytest.mark.parametrize("kind", er.PERIODIC_KINDS)
+@pytest.mark.parametrize("shape", [PERIODIC_TINY, er.PERIODIC_G], ids=lambda s: "x".join(map(str, s)))
+def test_periodic_box_is_the_oracle_operator_on_the_local_graph(env, shape, kind):
+    """``IntOperator.from_local_graph`` -- the halo columns folded onto the owned cells they are images of -- equals the
+    oracle's face loops over the local graph with the halo filled, strict and fma, bit for bit on an integer vector.
+    Every weight is an integer; -L is symmetric with diagonal 6 ... 8 and off-diagonals -1; the convection-diffusion
+    operator has max|A - A^T| = 2 and row sums of |A| of at most 20."""
+    oracle, mesh = env
+    vel = er.GMRES_VEL if kind == "periodic_convdiff" else None
+    loc, send_idx, w, A = er.periodic_box(mesh, *shape, vel=vel)
+    n = loc.n_cells
+    assert n == shape[0] * shape[1] * shape[2] and loc.n_halo == 2 * shape[0] * shape[1] and A.n == n
+    for v in w:
+        assert np.array_equal(v, np.rint(v))
+    b = er.int_vector(n, er.GMRES_SEED, *er.GMRES_RANGE)
+    z = A.apply(b)
+    assert np.array_equal(A.apply(b.astype(object)).astype(np.int64), z)
+    for variant in ("strict", "fma"):
+        kw = {} if vel is None else dict(conv=1.0, vel=vel)
+        full = oracle.StencilOperator(loc, -1.0, 0.0, variant=variant, **kw).apply(np.concatenate([b, b[send_idx]]).astype(np.float64))
+        assert np.array_equal(full[:n], z.astype(np.float64)), variant
+    asym = abs(A.csr - A.csr.T).max()
+    if vel is None:
+        off = A.csr - __import__("scipy.sparse").sparse.diags(A.csr.diagonal())
+        assert asym == 0 and A.rowsum <= 12 and set(A.csr.diagonal()) <= {6, 7, 8} and set(off.data) == {-1}
+        # (no wall in z: a cell away from the x and y walls has all six neighbours, the two across the seam included)
+        assert set(np.diff(A.csr.indptr)) == {5, 6, 7} and np.array_equal(np.diff(A.csr.indptr) - 1, 12 - A.csr.diagonal())
+    else:
+        assert asym == 2 and A.rowsum <= 20
+    with pytest.raises(AssertionError):
+        er.IntOperator.from_face_weights(loc, *w)  # (a graph with a halo is not its business)
+    # the split along the seam: two planes of rows, one entry each, and nothing lost
+    a_in, a_h = A.seam_split(shape)
+    assert abs(a_in + a_h - A.float64()).max() == 0 and a_h.nnz == loc.n_halo
+    assert set(np.flatnonzero(np.diff(a_h.indptr))) == set(send_idx)
+
+
+@pytest.mark.parametrize("method,kind", [("cg", "periodic"), ("bicgstab", "periodic"), ("bicgstab", "periodic_convdiff")])
+def test_step_coefficient_form_on_the_periodic_boxes_against_a_brute_force(env, method, kind):
+    """``cg`` and ``bicgstab`` on coefficient columns over ``OpBasis`` of the periodic operators against the same
+    statements with every element a Fraction (``ElemSpace(op=...)``) on 5 x 4 x 3: the same history, x_k and own-term
+    ratios, exactly."""
+    oracle, mesh = env
+    p = _step_problem(env, PERIODIC_TINY, kind)
+    K = {"cg": 5, "bicgstab": 4}[method]
+    sp, el = er.Space(er.OpBasis(p.A, p.b)), er.ElemSpace(None, p.b, op=p.A)
+    coef, brute = (STEP_METHODS[method](s, K) for s in (sp, el))
+    assert coef.hist_sq == brute.hist_sq and len(coef.hist_sq) == K + 1
+    assert coef.ratio_sq == brute.ratio_sq
+    for k in range(1, K + 1):
+        assert np.array_equal(sp.materialize(coef.xs[k]), np.array([float(v) for v in brute.xs[k]])), k
+        r = p.b.astype(object) - el.A(brute.xs[k])
+        assert sum(v * v for v in r) == brute.hist_sq[k], k
+
+
+@pytest.mark.parametrize("m", [3, 7])
+def test_gmres_coefficient_form_on_the_periodic_box_against_a_brute_force(env, m):
+    """``gmres`` over ``OpBasis`` of the periodic convection-diffusion operator against PREC-digit decimals per element
+    on 5 x 4 x 3: history and x_K to 1e-60, with restarts (m = 3) and without (m = 7)."""
+    from decimal import localcontext
+
+    oracle, mesh = env
+    p = er.GmresProblem(oracle, mesh, PERIODIC_TINY, "periodic_convdiff")
+    sp = er.Space(er.OpBasis(p.A, p.b), decimal=True)
+    el = er.ElemSpace(None, p.b, decimal=True, op=p.A)
+    coef, brute = er.gmres(sp, 7, m), er.gmres(el, 7, m)
+    assert len(coef.hist_sq) == len(brute.hist_sq) == 8
+    with localcontext() as ctx:
+        ctx.prec = er.PREC
+        tiny = er._dec(Fraction(1, 10 ** 60))
+        for c, e in zip(coef.hist_sq, brute.hist_sq):
+            assert abs(c - e) <= abs(e) * tiny
+        xc = sum((er._dec(c) * sp.basis.W[k].astype(object) for k, c in coef.x.c.items()), np.zeros(p.b.size, dtype=object))
+        assert max(abs(a - e) for a, e in zip(xc, brute.x)) <= max(abs(v) for v in brute.x) * tiny
+        r = p.b.astype(object) - p.A.apply(brute.x)
+        assert abs(sum(v * v for v in r) - brute.hist_sq[7]) <= brute.hist_sq[7] * tiny
+
+
+def _periodic_cases():
+    return [(m, shape, kind) for m, cases in er.PERIODIC_STEP_CASES.items() for shape, kind in cases]
+
+
+@pytest.mark.parametrize("case", _periodic_cases(), ids=lambda c: f"{c[0]}-{'x'.join(map(str, c[1]))}-{c[2]}")
+def test_step_pins_of_every_periodic_case(env, case):
+    """Every (method, box) of tests/test_gpu_exact_rccl.py: every cap (tol_k, and tol_res and tol_x at K and at the early
+    exit's iteration, <= TOL_CAP) is asserted as the pins are built, on the reference alone; history[0] is bitwise; both
+    oracle builds lie inside, history and x.  x itself is compared on 20 x 12 x 9 only."""
+    method, shape, kind = case
+    p = _step_problem(env, shape, kind)
+    pins = p.pins(method)
+    K = er.STEP_K[method]
+    assert pins.K == K and pins.tol[0] is None and max(pins.tol[1:]) <= er.TOL_CAP and "closed form" not in pins.rule
+    for k in (er.STEP_STOP, K):
+        e_res, tol_res, rule, e_x, tol_x = pins.x_tolerances(k)
+        assert tol_res <= er.TOL_CAP and (tol_x is None) == (shape != er.PERIODIC_G)
+        assert tol_x is None or tol_x <= er.TOL_CAP
+        for variant in pins.oracle:
+            pins.check_x(pins.oracle_x(variant, k), k, f"{method} {shape} {variant}")
+    assert pins.stop_between(er.STEP_STOP) > 0
+    for variant, hist in pins.oracle.items():
+        pins.check(list(hist), f"{method} {shape} {kind} {variant}")
+    print(f"periodic pins {method} {shape} {kind}: largest tol_k {max(pins.tol[1:]):.1e}, tol_res "
+          f"{max(pins.x_tolerances(k)[1] for k in (er.STEP_STOP, K)):.1e}")
+
+
+@pytest.mark.parametrize("shape", list(er.PERIODIC_GMRES_CASES), ids=lambda s: "x".join(map(str, s)))
+def test_gmres_pins_of_every_periodic_case(env, shape):
+    """The GMRES cases of tests/test_gpu_exact_rccl.py on the periodic convection-diffusion box: the precision guard and
+    every cap are asserted as ``GmresPins`` is built; both oracle builds lie inside."""
+    oracle, mesh = env
+    p = er.GmresProblem(oracle, mesh, shape, "periodic_convdiff")
+    for K, m in er.PERIODIC_GMRES_CASES[shape]:
+        pins = p.pins(K, m)
+        assert pins.tol[0] is None and max(pins.tol[1:]) <= er.TOL_CAP and pins.tol_res <= er.TOL_CAP
+        assert (pins.x is not None) == (shape == er.PERIODIC_G)
+        assert pins.x is None or pins.tol_x <= er.TOL_CAP
+        for variant, hist in pins.oracle.items():
+            pins.check(list(hist), f"gmres({m}) {shape} {variant}")
+            pins.check_x(pins.oracle_x[variant], f"gmres({m}) {shape} {variant}")
+        print(f"periodic pins gmres({m}) K={K} {shape}: largest tol_k {max(pins.tol[1:]):.1e}, tol_res {pins.tol_res:.1e}")
+
+
+def _halo_runs(env, method, kind):
+    p = _step_problem(env, er.PERIODIC_G, kind)
+    a_in, a_h = p.A.seam_split(er.PERIODIC_G)
+    f64 = er.cg_float64 if method == "cg" else er.bicgstab_float64
+    return p, p.pins(method), lambda **kw: f64(a_in, p.b, er.STEP_K[method], a_halo=a_h, **kw)
+
+
+@pytest.mark.parametrize("method,kind", [("cg", "periodic"), ("bicgstab", "periodic"), ("bicgstab", "periodic_convdiff")])
+def test_clean_float64_restatement_with_the_split_lies_within_the_periodic_pins(env, method, kind):
+    p, pins, run = _halo_runs(env, method, kind)
+    h, xs = run()
+    pins.check(list(h), method)
+    for k in (er.STEP_STOP, pins.K):
+        pins.check_x(xs[k], k, method)
+
+
+@pytest.mark.parametrize("method,defect,kind", HALO_DEFECTS, ids=[f"{m}-{d}-{k}" for m, d, k in HALO_DEFECTS])
+def test_halo_defects_fall_outside_the_periodic_pins(env, method, defect, kind):
+    """What the pins of tests/test_gpu_exact_rccl.py are for, on 20 x 12 x 9: the float64 restatement whose HALO alone
+    is wrong -- the exchange missed once (the previous direction still there), the halo rows of p' formed with the
+    previous beta, those of s with the previous alpha, those of BiCGStab's p' with the omega before the last: two planes
+    of one operand -- leaves history[0..1] and x_1 bitwise what the clean restatement gives and lies outside the pin of
+    some history[k], k <= K, by a factor of 1000 or more (printed: |h_k - exact| / (exact tol_k), the largest over k)."""
+    p, pins, run = _halo_runs(env, method, kind)
+    (h0, xs0), (h, xs) = run(), run(defect=defect, at=2)
+    K = pins.K
+    assert np.array_equal(h[:2], h0[:2]) and np.array_equal(xs[1], xs0[1]), defect
+    factor = [abs(h[k] - pins.exact[k]) / (pins.exact[k] * pins.tol[k]) for k in range(1, K + 1)]
+    print(f"halo defect {method} {kind} {defect}: |h_k - exact| / (exact tol_k) = {max(factor):.1e} at k = {1 + int(np.argmax(factor))}, "
+          f"first outside at k = {1 + next(i for i, f in enumerate(factor) if f > 1)}")
+    assert max(factor) >= 1e3, (defect, factor)
+    with pytest.raises(AssertionError):
+        pins.check(list(h), defect)
+    with pytest.raises(AssertionError):  # (a space without the split cannot state them)
+        (er.cg_float64 if method == "cg" else er.bicgstab_float64)(p.A.float64(), p.b, K, defect=defect)
