@@ -444,7 +444,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *ctx, const char *key, int64_t value)
  * fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip), "engine_solves" (csrc/krylov_abi.hip), "jfnk_inner_solves" (inner BiCGStab solves of
  * STORM_HIP_JFNK), "fd_fused_dots" (products of a finite-difference operator whose difference statement took the method's
  * reductions of z along in its pass), "host_reductions" (calls of storm_hip_dot / _norm2 / _multi_dot / _multi_dot_end / _block_dot: the reduction
- * entry points that make the host wait for their sums -- a device-resident loop leaves it where it was), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "op_face_updates" (storm_hip_op_set_face_weights, csrc/op_update.hip), "cheb_fused_applies" / "cheb_statement_applies" (storm_hip_cheb_apply by path), "cheb_reduced_applies" (... of reduced objects, counted in addition), "op_reduced_builds" / "op_reduced_refreshes" (csrc/op_reduced.hip: companions built; converted again behind storm_hip_op_set_face_weights), "cg_fused_steps" (solves whose CG step rode in
+ * entry points that make the host wait for their sums -- a device-resident loop leaves it where it was), "block_solves" (storm_hip_solve_cg_block, csrc/block.hip), "op_face_updates" (storm_hip_op_set_face_weights, csrc/op_update.hip), "nt_stream_launches" (launch sites of the streaming kernels at which the host chose the non-temporal instance, option "blas1_nt": what the host chose, not what instructions that instance holds), "cheb_fused_applies" / "cheb_statement_applies" (storm_hip_cheb_apply by path), "cheb_reduced_applies" (... of reduced objects, counted in addition), "op_reduced_builds" / "op_reduced_refreshes" (csrc/op_reduced.hip: companions built; converted again behind storm_hip_op_set_face_weights), "cg_fused_steps" (solves whose CG step rode in
  * the SpMV launch), "lazy_fused_dots" / "lazy_fused_pairs" / "lazy_apply_dots" / "lazy_cg_steps" / "lazy_waiting" (option
  * lazy_statements: reductions that rode in a statement's kernel, pairs of statements that left as one pass, applies that
  * left with a fused dot, fused CG steps, statements waiting now).  On the peer-window transport, where the time of the exchanges went (ticks of 10 ns of the device's

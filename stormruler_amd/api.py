@@ -79,7 +79,9 @@ class Context:
         "throughput_solves", "engine_solves", "cg_fused_steps", "cg_residual_marches", "cg_residual_plane_marches",
         "cg_pz_consumer_folds", "cg_rr_consumer_folds"), or how many Gram-Schmidt
         steps ran as a chain kernel ("mgs_chain_steps"), as mgs_chain_quad_kernel ("mgs_quad_steps") and as
-        mgs_chain_lds_kernel ("mgs_lds_steps"; a chain step that is neither ran the register chain)."""
+        mgs_chain_lds_kernel ("mgs_lds_steps"; a chain step that is neither ran the register chain), or at how many
+        launch sites of the streaming kernels the host chose the non-temporal instance ("nt_stream_launches", option
+        blas1_nt: the host's choice, not the instructions that instance holds).  The full list: storm_hip.h."""
         v = C.c_int64()
         check(lib.storm_hip_ctx_get_counter(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -193,6 +193,10 @@ struct storm_hip_ctx {
   storm_hip_vec *lazy_spare = nullptr;  // where a fused CG step writes the new direction (lazy.hip: try_cg_step)
   int64_t opt_profile_comm = 0;       // RCCL transport: stamp kernels around the halo exchange and the all-reduces (comm.hip comm_profile_*)
   int64_t opt_blas1_nt = 1;  // non-temporal loads/stores in the streaming kernels: 0 never, 1 for vectors of at least kBlas1NtRows rows, 2 always
+  // Times stream_nt() answered 1 (counter "nt_stream_launches"): the HOST took the non-temporal branch of a launch site.  It
+  // says nothing about the instructions the selected instance holds (blas1_device.hpp records three rounds that shipped
+  // without one); tests use it so that a comparison of the two access modes cannot be vacuous.
+  mutable int64_t n_nt_stream_launches = 0;
   int64_t opt_coop_mgs = 1;             // GMRES: the Gram-Schmidt chain of an Arnoldi step as one cooperative kernel (mgs_chain.hip)
   int64_t opt_latency_publish = 1;      // ... its rows published with awaited atomic exchanges (0: write-through stores, ordered by their acknowledgement)
   int64_t opt_coop_plain = 1;           // the cooperative kernels by ordinary launches (coop_host.hip coop_launch; 0: hipLaunchCooperativeKernel)
@@ -407,7 +411,9 @@ static inline int stream_blocks(int64_t n) {
 // (48 MiB per vector: beyond, a solver's vectors no longer stay in the 256 MiB Infinity Cache between kernels)
 constexpr int64_t kBlas1NtRows = (int64_t)6 << 20;
 static inline int stream_nt(const storm_hip_ctx *c, int64_t n) {
-  return (c->opt_blas1_nt == 2 || (c->opt_blas1_nt == 1 && n >= kBlas1NtRows)) ? 1 : 0;
+  const int nt = (c->opt_blas1_nt == 2 || (c->opt_blas1_nt == 1 && n >= kBlas1NtRows)) ? 1 : 0;
+  c->n_nt_stream_launches += nt;
+  return nt;
 }
 
 // blas1.hip -- all asynchronous on ctx->stream, owned rows only.

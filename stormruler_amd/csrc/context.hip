@@ -253,6 +253,7 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "block_solves")) *value = c->n_block_solves;
   else if (!strcmp(key, "op_face_updates")) *value = c->n_op_face_updates;
   else if (!strcmp(key, "host_reductions")) *value = c->n_host_reductions;
+  else if (!strcmp(key, "nt_stream_launches")) *value = c->n_nt_stream_launches;
   else if (!strcmp(key, "cheb_fused_applies")) *value = c->n_cheb_fused_applies;
   else if (!strcmp(key, "cheb_statement_applies")) *value = c->n_cheb_statement_applies;
   else if (!strcmp(key, "cheb_reduced_applies")) *value = c->n_cheb_reduced_applies;

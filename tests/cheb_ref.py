@@ -41,12 +41,17 @@ def chebyshev_t(k, x):
     return out
 
 
-def closed_form(a, s, r, lmin, lmax, degree):
-    """z = diag(sqrt s) V ((1 - R(w)) / w) V^T diag(sqrt s) r with (w, V) the eigenpairs of diag(sqrt s) A diag(sqrt s) and
-    R(w) = T_{m+1}((theta - w) / delta) / T_{m+1}(theta / delta).  `a` symmetric, s > 0."""
+def eigenpairs(a, s):
+    """(w, V) of diag(sqrt s) A diag(sqrt s): `closed_form`'s decomposition, for a caller that evaluates several degrees."""
     sh = np.sqrt(s)
-    b = (sp.diags(sh) @ a @ sp.diags(sh)).toarray()
-    w, v = np.linalg.eigh(b)
+    return np.linalg.eigh((sp.diags(sh) @ a @ sp.diags(sh)).toarray())
+
+
+def closed_form(a, s, r, lmin, lmax, degree, eig=None):
+    """z = diag(sqrt s) V ((1 - R(w)) / w) V^T diag(sqrt s) r with (w, V) the eigenpairs of diag(sqrt s) A diag(sqrt s) and
+    R(w) = T_{m+1}((theta - w) / delta) / T_{m+1}(theta / delta).  `a` symmetric, s > 0.  `eig`: eigenpairs(a, s), if kept."""
+    sh = np.sqrt(s)
+    w, v = eigenpairs(a, s) if eig is None else eig
     theta, delta = (lmax + lmin) / 2, (lmax - lmin) / 2
     res_poly = chebyshev_t(degree + 1, (theta - w) / delta) / chebyshev_t(degree + 1, np.array([theta / delta]))[0]
     return sh * (v @ (((1 - res_poly) / w) * (v.T @ (sh * r))))

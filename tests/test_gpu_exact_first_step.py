@@ -31,6 +31,7 @@ ODD = (37, 21, 19)  # odd everything: ragged lines, planes and blocks
 # 256 x 256 x 258: the SpMV of iteration 0 leaves more per-wave partials than one pass folds (256^3 sits at exactly
 # kSinglePassPartials = 8192), so the fused CG reaches its branches for nb > kSinglePassPartials
 BIG = (256, 256, 258)
+NT_ROWS = 6 << 20  # kBlas1NtRows (common.hpp): from here on the default blas1_nt = 1 streams non-temporally
 
 
 @pytest.fixture(scope="module")
@@ -44,7 +45,7 @@ def env():
 
 DEFAULTS = (("resident_path", 1), ("latency_path", 1), ("generic_solvers", 0), ("ticket_reduce", 1), ("coop_mgs", 1),
             ("spmv_record_index", 1), ("spmv_dict", 4), ("ell_cap", 0), ("lazy_statements", 0), ("test_disable", 0),
-            ("fused_reduce", 1), ("lin_fuse", 1))
+            ("fused_reduce", 1), ("lin_fuse", 1), ("blas1_nt", 1))
 
 
 @pytest.fixture(autouse=True)
@@ -95,10 +96,22 @@ def _solve(api, ctx, cls, mat, b_h, x0=None, iters=1, **knobs):
     b = api.DeviceVector.from_numpy(ctx, b_h.astype(np.float64))
     x = api.DeviceVector.from_numpy(ctx, np.zeros(b_h.size) if x0 is None else x0.astype(np.float64))
     before = {k: ctx.counter(k) for k in PATHS}
+    nt_before = ctx.counter("nt_stream_launches")
     s.solve(x, b, api.HipStencilOperator(mat, -1.0, 0.0))
     path = {k: ctx.counter(k) - before[k] for k in PATHS}
+    s.nt_stream_launches = ctx.counter("nt_stream_launches") - nt_before
     assert s.path_fallback == 0 and s.iteration == iters and s.history.size == iters + 1
     return s, x.to_numpy(), path
+
+
+def _check_access_mode(s, opts, n_rows):
+    """Option blas1_nt 2: the solve's launch sites chose the non-temporal instances (counter nt_stream_launches: the
+    host's choice); 0, or the default below the size switch: none did."""
+    assert n_rows < NT_ROWS
+    if opts.get("blas1_nt", 1) == 2:
+        assert s.nt_stream_launches > 0, s.nt_stream_launches
+    else:
+        assert s.nt_stream_launches == 0, s.nt_stream_launches
 
 
 def _only(path, key, fused=None):
@@ -304,9 +317,12 @@ CLASSES = {"cgs": "CgsSolver", "tfqmr": "TfqmrSolver", "tfqmr1": "Tfqmr1Solver",
            "bicgstabl": "BiCgStabLSolver", "idrs": "IdrsSolver", "cg": "CgSolver", "fgmres": "FgmresSolver"}
 ENGINE_METHODS = [("cgs", None), ("tfqmr", None), ("tfqmr1", None), ("richardson", None), ("bicgstabl", 1),
                   ("bicgstabl", 2), ("bicgstabl", 3), ("idrs", 1), ("idrs", 2), ("idrs", 4)]
-# each format once with the defaults, each engine option once against the lattice format
+# each format once with the defaults, each engine option once against the lattice format; the non-temporal instances of
+# the engine's statement kernels (blas1_nt 2: krylov_device.hpp lin_kernel, lin2_kernel, the lin_dot / pre_dots bodies), fused
+# and statement by statement
 ENGINE_CONFIGS = [("lattice", {}), ("lattice8", {}), ("fp64", {}), ("tail", {}), ("lattice", {"fused_reduce": 0}),
-                  ("lattice", {"lin_fuse": 0}), ("lattice", {"ticket_reduce": 0})]
+                  ("lattice", {"lin_fuse": 0}), ("lattice", {"ticket_reduce": 0}), ("lattice", {"blas1_nt": 2}),
+                  ("fp64", {"blas1_nt": 2, "lin_fuse": 0})]
 
 _bases, _pins_cache = {}, {}
 
@@ -360,6 +376,7 @@ def test_engine_methods_against_the_exact_reference(env, method, case, shape):
     api.rng_reset()
     s, x, path = _solve(api, ctx, cls, mat, b_h, iters=pins.K, **_knobs(kind, param))
     _only(path, "engine_solves")
+    _check_access_mode(s, opts, g.n_cells)
     assert s.history[0] == fs.h0
     _report(label, pins, pins.check(s.history, label))
     if kind == "bicgstabl" and param >= 2:
@@ -403,13 +420,7 @@ JACOBI_METHODS = [("cg", None), ("cgs", None), ("tfqmr", None), ("idrs", 2), ("f
 FIXED_SIDE = {"richardson": "left", "bicgstabl": "left", "fgmres": "right"}
 
 
-@pytest.mark.parametrize("lin_fuse", [1, 0])
-@pytest.mark.parametrize("side", ["left", "right"])
-@pytest.mark.parametrize("method", JACOBI_METHODS, ids=_method_id)
-@pytest.mark.parametrize("shape", [SMALL, ODD], ids=["small", "odd"])
-def test_engine_methods_with_jacobi(env, shape, method, side, lin_fuse):
-    """api.JacobiPreconditioner on either side, lin_fuse on and off (for CG it switches the fused pre_dots pass,
-    z = P r with <r,z> and <r,r>): history[0..2] against the reference restated with P = diag(fl(1/d))."""
+def _jacobi_case(env, shape, method, side, lin_fuse, blas1_nt=1):
     api, mesh, ctx = env
     kind, param = method
     g, b_h, fs = _problem(mesh, shape)
@@ -421,14 +432,34 @@ def test_engine_methods_with_jacobi(env, shape, method, side, lin_fuse):
     if kind == "cg":
         ctx.set_option("generic_solvers", 1)
     ctx.set_option("lin_fuse", lin_fuse)
+    ctx.set_option("blas1_nt", blas1_nt)
     knobs = dict(_knobs(kind, param), pre_op=api.JacobiPreconditioner(),
                  pre_side=api.PreconditionerSide.Left if side == "left" else api.PreconditionerSide.Right)
     api.rng_reset()
     s, _, path = _solve(api, ctx, getattr(api, CLASSES[kind]), mat, b_h, iters=pins.K, **knobs)
     _only(path, "engine_solves")
-    label = f"{_method_id(method)} jacobi-{side} lin_fuse{lin_fuse} {shape}"
+    _check_access_mode(s, {"blas1_nt": blas1_nt}, g.n_cells)
+    label = f"{_method_id(method)} jacobi-{side} lin_fuse{lin_fuse} blas1_nt{blas1_nt} {shape}"
     _report(label, pins, pins.check(s.history, label))
     mat.close()
+
+
+@pytest.mark.parametrize("lin_fuse", [1, 0])
+@pytest.mark.parametrize("side", ["left", "right"])
+@pytest.mark.parametrize("method", JACOBI_METHODS, ids=_method_id)
+@pytest.mark.parametrize("shape", [SMALL, ODD], ids=["small", "odd"])
+def test_engine_methods_with_jacobi(env, shape, method, side, lin_fuse):
+    """api.JacobiPreconditioner on either side, lin_fuse on and off (for CG it switches the fused pre_dots pass,
+    z = P r with <r,z> and <r,r>): history[0..2] against the reference restated with P = diag(fl(1/d))."""
+    _jacobi_case(env, shape, method, side, lin_fuse)
+
+
+@pytest.mark.parametrize("lin_fuse", [1, 0])
+@pytest.mark.parametrize("method", JACOBI_METHODS, ids=_method_id)
+@pytest.mark.parametrize("shape", [SMALL, ODD], ids=["small", "odd"])
+def test_engine_methods_with_jacobi_non_temporal(env, shape, method, lin_fuse):
+    """The same pins with every streaming launch of the solve on its non-temporal instance (blas1_nt 2), side left."""
+    _jacobi_case(env, shape, method, "left", lin_fuse, blas1_nt=2)
 
 
 @pytest.mark.parametrize("cls", ["CgsSolver", "TfqmrSolver", "Tfqmr1Solver", "IdrsSolver", "BiCgStabLSolver"])

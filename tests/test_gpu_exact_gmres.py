@@ -75,10 +75,18 @@ VARIANTS = {
 # front of the chain instead of inside it -- the same bits, as today; 2 no prefetch under the all-reduce; 128 row chunks
 # dealt by block index; 256 the basis vectors in ascending order for every k; 512 the earlier rotations after
 # everything else
+# classical Gram-Schmidt applied twice (solver attribute gram_schmidt = 1: multi-dots and multi-axpys): in exact arithmetic
+# the same iteration, so the same pins; and the per-step kernels and that form with every streaming launch on its
+# non-temporal instance (blas1_nt 2) -- on the two small shapes, NT_SHAPES.  "step": without tickets one step per pass
+# (mgs_step_kernel, each pass folding the partials of the one before)
+VARIANTS["cgs2"] = ({"gram_schmidt": 1}, None)
+VARIANTS["step"] = ({"coop_mgs": 0, "ticket_reduce": 0}, None)
+VARIANTS.update({f"{name}-nt": (dict(VARIANTS[name][0], blas1_nt=2), None) for name in ("steps2", "steps3", "steps4", "cgs2", "step")})
+NT_SHAPES = ((7, 5, 3), ODD)
 HOOKS = (1, 2, 128, 256, 512)
 VARIANTS.update({f"quad-test_disable{bit}": (dict(QUAD, test_disable=bit), "quad") for bit in HOOKS})
 DEFAULTS = (("generic_solvers", 0), ("coop_mgs", 1), ("coop_mgs_quad", 1), ("coop_mgs_lds", 1), ("mgs_steps", 4),
-            ("test_disable", 0), ("spmv_dict", 4))
+            ("test_disable", 0), ("spmv_dict", 4), ("blas1_nt", 1), ("ticket_reduce", 1))
 COUNTERS = ("mgs_chain_steps", "mgs_quad_steps", "mgs_lds_steps")
 
 
@@ -93,6 +101,8 @@ def _cases():
                         continue  # (a forced family that does not take the size is the register chain again)
                     if "test_disable" in name:
                         continue  # (the hooks: on HOOKED alone, below)
+                    if (name.endswith("-nt") or name in ("cgs2", "step")) and shape not in NT_SHAPES:
+                        continue
                     if fmt == "fp64" and family is None:
                         continue  # (the per-step kernels read w: the records' format does not reach them)
                     out.append((shape, fmt, K, m, name))
@@ -169,19 +179,25 @@ def _expected(shape, family, K):
 
 def _solve(env, mat, p, K, m, opts):
     api, mesh, oracle, ctx = env
+    opts = dict(opts)
+    gram_schmidt = opts.pop("gram_schmidt", 0)
     for k, v in opts.items():
         ctx.set_option(k, v)
     s = api.GmresSolver()
+    s.gram_schmidt = gram_schmidt
     s.num_iterations, s.num_inner_iterations, s.record_history = K, m, True
     s.absolute_error_tolerance = s.relative_error_tolerance = 0.0
     b = api.DeviceVector.from_numpy(ctx, p.b.astype(np.float64))
     x = api.DeviceVector.from_numpy(ctx, np.zeros(p.b.size))
-    before = {k: ctx.counter(k) for k in COUNTERS}
+    before = {k: ctx.counter(k) for k in COUNTERS + ("nt_stream_launches",)}
     s.solve(x, b, api.HipStencilOperator(mat, 1.0, 0.0))
     moved = {k: ctx.counter(k) - before[k] for k in COUNTERS}
+    nt_launches = ctx.counter("nt_stream_launches") - before["nt_stream_launches"]
     for k, v in DEFAULTS:
         ctx.set_option(k, v)
     assert s.path_fallback == 0 and s.iteration == K and s.history.size == K + 1
+    # the host's choice of instance at the streaming launch sites (every shape is below the default's size switch)
+    assert (nt_launches > 0) == (opts.get("blas1_nt", 1) == 2), (opts, nt_launches)
     return np.array(s.history), x.to_numpy(), moved
 
 

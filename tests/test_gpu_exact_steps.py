@@ -91,7 +91,7 @@ def _solve(api, ctx, cls, op, p, iters, stop=0.0):
     s.record_history = True
     b = api.DeviceVector.from_numpy(ctx, p.b.astype(np.float64))
     x = api.DeviceVector.from_numpy(ctx, np.zeros(p.b.size))
-    before = {k: ctx.counter(k) for k in PATHS + FUSED_COUNTERS[1:]}
+    before = {k: ctx.counter(k) for k in PATHS + FUSED_COUNTERS[1:] + ("nt_stream_launches",)}
     s.solve(x, b, op)
     moved = {k: ctx.counter(k) - before[k] for k in before}
     assert s.path_fallback == 0
@@ -130,6 +130,8 @@ def _small_case(env, shape, case, cls, method, k=None, fused=None):
     stop = 0.0 if k is None else pins.stop_between(k)
     s, x, moved = _solve(api, ctx, cls, api.HipStencilOperator(mat, -1.0, 0.0), p, pins.K, stop)
     _only({name: moved[name] for name in PATHS}, key, fused)
+    # (the host's choice of instance at the streaming launch sites; both shapes are far below the default's size switch)
+    assert (moved["nt_stream_launches"] > 0) == (opts.get("blas1_nt", 1) == 2), (opts, moved)
     _check(pins, f"{method} {_shape_id(shape)} {_case_id(case)}" + ("" if k is None else f" stop{k}"), s, x, k)
     mat.close()
 
@@ -155,6 +157,28 @@ def test_cg_steps_resident_with_forced_planes(env, shape, planes):
     _only({name: moved[name] for name in PATHS}, "resident_solves", 0)
     _check(pins, f"cg {_shape_id(shape)} resident planes {planes}", s, x)
     mat.close()
+
+
+def _non_temporal(rows):
+    """The throughput and engine rows of a first-step table with every streaming launch on its non-temporal instance
+    (blas1_nt 2: cg_r_kernel, cg_xp_kernel, the BiCGStab statements, the engine's): the same path, the same pins."""
+    return [(c[0], dict(c[1], blas1_nt=2)) + tuple(c[2:]) for c in rows if c[2] in ("throughput_solves", "engine_solves")]
+
+
+CG_NT, BICG_NT = _non_temporal(CG_SMALL), _non_temporal(BICG)
+assert len(CG_NT) == 9 and len(BICG_NT) == 5
+
+
+@pytest.mark.parametrize("shape", [SMALL, ODD], ids=_shape_id)
+@pytest.mark.parametrize("case", CG_NT, ids=_case_id)
+def test_cg_steps_non_temporal(env, shape, case):
+    _small_case(env, shape, case, env[0].CgSolver, "cg", fused=case[3])
+
+
+@pytest.mark.parametrize("shape", [SMALL, ODD], ids=_shape_id)
+@pytest.mark.parametrize("case", BICG_NT, ids=_case_id)
+def test_bicgstab_steps_non_temporal(env, shape, case):
+    _small_case(env, shape, case, env[0].BiCgStabSolver, "bicgstab")
 
 
 # ---- CG: the fused step -------------------------------------------------------------------------------------------------------
