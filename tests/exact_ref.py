@@ -582,8 +582,10 @@ class Run:
     """What a method restated on a space gives: the exact squares of history[0..K] (``hist_sq``), x_K, and per
     history entry the vectors whose norms formed it (``feeds``: the floor of the tolerance reads their terms)."""
 
-    def __init__(self, hist_sq, x, feeds):
+    def __init__(self, hist_sq, x, feeds, xs=None, ratio_sq=None):
         self.hist_sq, self.x, self.feeds = hist_sq, x, feeds
+        if xs is not None:  # x_0 ... x_K and, per history entry, M / h^2 of the statements that formed it (``EnginePins``)
+            self.xs, self.ratio_sq = xs, ratio_sq
 
     @property
     def history(self):
@@ -605,9 +607,25 @@ def _ops(sp, side):
     return op
 
 
-def cgs(sp, K, side=None, defect=None):
-    """SolverCgs.hpp:57-174.  ``defect`` (the separation tests only): "stale_beta" forms beta from the rho of the
-    previous pass alone, "shadow_r" takes r for r~ in the shadow dots."""
+CGS_X_DEFECTS = ("skip_x", "double_x", "x_wrong_side")
+TFQMR_X_DEFECTS = ("d_wrong_vector", "x_sn_for_cs", "d_not_scaled")
+TFQMR1_X_DEFECTS = ("copy_always", "copy_never")
+BICGSTABL_X_DEFECTS = ("skip_x_mr", "gbb_shift")
+BICGSTABL_DEFECTS = ("rho_without_omega", "beta_without_alpha")
+IDRS_X_DEFECTS = ("skip_x_omega", "x_omega_wrong_side")
+
+
+def cgs(sp, K, side=None, defect=None, at=None):
+    """SolverCgs.hpp:57-174.  Besides ``Run``'s fields the result carries ``xs`` (x_0 ... x_K) and ``ratio_sq[k]``, M / h^2
+    of history[k] from the step's own terms: r_k = r_{k-1} - alpha w, M = |r_{k-1}|^2 + alpha^2 |w|^2.
+
+    ``defect`` (the separation tests only; ``at``: the 0-based iteration of the one-shot ones, None: every iteration):
+      "stale_beta"   beta from the rho of the previous pass alone
+      "shadow_r"     r for r~ in the shadow dots
+      "skip_x"       x += alpha (u + q) left out at iteration ``at``
+      "double_x"     ... applied twice at the last iteration
+      "x_wrong_side" side right: x += alpha v, the vector after the apply, for alpha u, the one P gave"""
+    assert defect != "x_wrong_side" or side == "right"
     b = sp.b()
     r = b  # :80 (x0 = 0)
     if side == "left":
@@ -616,13 +634,15 @@ def cgs(sp, K, side=None, defect=None):
     shadow = (lambda: r) if defect == "shadow_r" else (lambda: rt)
     rho = sp.dot(rt, r)  # :86
     x, hist, feeds = sp.zero(), [rho], [[r]]
+    xs, ratio = [x], [1]
     for it in range(K):
         if it == 0:
             u = r  # :113-115
             p = u
         else:
             rho_bar, rho = rho, sp.dot(shadow(), r)  # :117-118
-            beta = _sdiv(rho_bar if defect == "stale_beta" else rho, rho_bar)  # :119
+            stale = defect == "stale_beta" and at in (None, it)
+            beta = _sdiv(rho_bar if stale else rho, rho_bar)  # :119
             u = r + beta * q  # :120
             p = u + beta * (q + beta * p)  # :121
         if side == "left":
@@ -636,29 +656,45 @@ def cgs(sp, K, side=None, defect=None):
         alpha = _sdiv(rho, sp.dot(shadow(), v))  # :139
         q = u - alpha * v  # :140
         v = u + q  # :141
+        r_old = r
         if side == "left":
-            x = x + alpha * v  # :160-162
+            dx = alpha * v  # :160-162
             u = sp.A(v)
             v = sp.P(u)
-            r = r - alpha * v
+            dr = alpha * v
         elif side == "right":
             u = sp.P(v)  # :164-166
             v = sp.A(u)
-            x = x + alpha * u
-            r = r - alpha * v
+            dx = alpha * (v if defect == "x_wrong_side" else u)
+            dr = alpha * v
         else:
             u = sp.A(v)  # :168-170
-            x = x + alpha * v
-            r = r - alpha * u
+            dx = alpha * v
+            dr = alpha * u
+        if not (defect == "skip_x" and it == at):
+            x = x + dx
+        if defect == "double_x" and it == K - 1:
+            x = x + dx
+        r = r - dr
         hist.append(sp.dot(r, r))  # :173
         feeds.append([r])
-    return Run(hist, x, feeds)
+        xs.append(x)
+        ratio.append(_own_ratio(sp, [r_old, dr], hist[-1]))
+    return Run(hist, x, feeds, xs, ratio)
 
 
-def tfqmr(sp, K, side=None, l1=False, defect=None):
+def tfqmr(sp, K, side=None, l1=False, defect=None, at=None):
     """SolverTfqmr.hpp:44-209 (``l1``: TFQMR1).  Rational throughout in the squares: tau^2, omega^2 and the rotation's
     cs^2 = tau^2 / (tau^2 + omega^2), sn^2 = omega^2 / (tau^2 + omega^2) (sym_ortho, MathUtils.hpp:165-179); only the
-    history takes a root.  ``defect`` as for ``cgs``."""
+    history takes a root.  ``xs``, and ``ratio_sq[k]`` from the two u -= alpha s of the iteration (the larger M / h^2);
+    for TFQMR1 ``preds``, the outcome of omega < tau at every half-step.
+
+    ``defect``: "stale_beta", "shadow_r" as for ``cgs``; of x alone
+      "d_wrong_vector" side right: d += alpha y for alpha z
+      "x_sn_for_cs"    x += sn^2 d for cs^2 d
+      "d_not_scaled"   d *= sn^2 left out
+      "copy_always", "copy_never"  TFQMR1: x <- d whatever omega < tau says, or never"""
+    assert defect != "d_wrong_vector" or side == "right"
     op = _ops(sp, side)
     d = x = sp.zero()  # :74-78 (x0 = 0: d = x = 0 for both variants)
     y = sp.b()  # :79
@@ -670,44 +706,64 @@ def tfqmr(sp, K, side=None, l1=False, defect=None):
     rho = sp.dot(rt, u)  # :86
     tau2 = rho
     hist, feeds = [tau2], [[u]]
+    xs, ratio, preds = [x], [1], []
     for it in range(K):
         if it == 0:
             s, z = op(y)  # :128-130
             v = s  # :131
         else:
             rho_bar, rho = rho, sp.dot(shadow(), u)  # :133-134
-            beta = _sdiv(rho_bar if defect == "stale_beta" else rho, rho_bar)  # :135
+            stale = defect == "stale_beta" and at in (None, it)
+            beta = _sdiv(rho_bar if stale else rho, rho_bar)  # :135
             v = s + beta * v  # :136
             y = u + beta * y  # :137
             s, z = op(y)  # :138-140
             v = s + beta * v  # :141
         alpha = _sdiv(rho, sp.dot(shadow(), v))  # :173
-        fed = []
+        fed, own = [], []
         for m in (0, 1):
-            u = u - alpha * s  # :175
-            d = d + alpha * (z if side == "right" else y)  # :176
+            u_old, du = u, alpha * s
+            u = u - du  # :175
+            d = d + alpha * (z if side == "right" and defect != "d_wrong_vector" else y)  # :176
             om2 = sp.dot(u, u)  # :177
             fed.append(u)
+            own.append(_own_ratio(sp, [u_old, du], om2))
             if l1:
-                if om2 < tau2:  # :178-179
-                    tau2, x = om2, d
+                preds.append(bool(om2 < tau2))
+                if preds[-1]:  # :178-179
+                    tau2 = om2
+                if defect == "copy_always" or (preds[-1] and defect != "copy_never"):
+                    x = d
             else:
                 h2 = tau2 + om2  # :181-184
                 cs2, sn2 = (tau2 / h2, om2 / h2) if h2 > 0 else (sp.one, 0 * sp.one)
                 tau2 = om2 * cs2
-                x = x + cs2 * d
-                d = sn2 * d
+                x = x + (sn2 if defect == "x_sn_for_cs" else cs2) * d
+                if defect != "d_not_scaled":
+                    d = sn2 * d
             if m == 0:
                 y = y - alpha * v  # :187
                 s, z = op(y)  # :188-190
         hist.append(tau2 if l1 else tau2 * (2 * it + 3))  # :202-206
         feeds.append(fed)
-    return Run(hist, x, feeds)
+        xs.append(x)
+        ratio.append(max(own))
+    run = Run(hist, x, feeds, xs, ratio)
+    run.preds = preds
+    return run
 
 
-def bicgstab_l(sp, K, l, pre=False, defect=None):
+def bicgstab_l(sp, K, l, pre=False, defect=None, at=None):
     """SolverBiCgStab.hpp:194-375, BiCGStab(l); a preconditioner is always applied on the left (:226-229, :275-279,
-    :295-299).  ``defect`` as for ``cgs``."""
+    :295-299).  ``xs``, and ``ratio_sq[k]`` from the terms that form r_0 in the iteration: r_0, alpha u_1 and, at the end
+    of a cycle, the gamma-bar_j r_j of the MR part.
+
+    ``defect``: "stale_beta" (at iteration ``at``, None: every one), "shadow_r" as for ``cgs``;
+      "rho_without_omega"  rho *= -omega at the end of a cycle left out
+      "beta_without_alpha" beta = rho / rho-bar at iteration ``at``
+    and of x alone, at the end of every cycle:
+      "skip_x_mr"  x += gamma_1 r_0 left out
+      "gbb_shift"  gamma-bar-bar_j formed from gamma_j ... for gamma_{j+1} ... (l >= 2)"""
     b = sp.b()
     r, u = [b] + [sp.zero()] * l, [sp.zero()] * (l + 1)  # :208-211, :224-225 (x0 = 0)
     if pre:
@@ -716,6 +772,7 @@ def bicgstab_l(sp, K, l, pre=False, defect=None):
     shadow = (lambda: r[0]) if defect == "shadow_r" else (lambda: rt)
     rho = sp.dot(rt, r[0])  # :231
     x, hist, feeds = sp.zero(), [rho], [[r[0]]]
+    xs, ratio = [x], [1]
     alpha = None
 
     def apply(v):
@@ -728,11 +785,14 @@ def bicgstab_l(sp, K, l, pre=False, defect=None):
             u[0] = r[0]  # :265-266
         else:
             rho_bar, rho = rho, sp.dot(shadow(), r[j])  # :268-269
-            beta = _sdiv(alpha * (rho_bar if defect == "stale_beta" else rho), rho_bar)  # :270
+            stale = defect == "stale_beta" and at in (None, it)
+            a = 1 if defect == "beta_without_alpha" and it == at else alpha
+            beta = _sdiv(a * (rho_bar if stale else rho), rho_bar)  # :270
             for i in range(j + 1):
                 u[i] = r[i] - beta * u[i]  # :271-273
         u[j + 1] = apply(u[j])  # :275-279
         alpha = _sdiv(rho, sp.dot(shadow(), u[j + 1]))  # :280
+        terms = [r[0], alpha * u[1]]
         for i in range(j + 1):
             r[i] = r[i] - alpha * u[i + 1]  # :281-283
         x = x + alpha * u[0]  # :294
@@ -745,16 +805,20 @@ def bicgstab_l(sp, K, l, pre=False, defect=None):
                 sigma[jj] = sp.dot(r[jj], r[jj])
                 gbar[jj] = _sdiv(sp.dot(r[0], r[jj]), sigma[jj])
             omega = gam[l] = gbar[l]  # :339
-            rho = rho * -omega
+            if defect != "rho_without_omega":
+                rho = rho * -omega
             for jj in range(l - 1, 0, -1):  # :340-345
                 gam[jj] = gbar[jj]
                 for i in range(jj + 1, l + 1):
                     gam[jj] = gam[jj] - tau[jj, i] * gam[i]
+            sh = 0 if defect == "gbb_shift" else 1
             for jj in range(1, l):  # :346-351
-                gbb[jj] = gam[jj + 1]
+                gbb[jj] = gam[jj + sh]
                 for i in range(jj + 1, l):
-                    gbb[jj] = gbb[jj] + tau[jj, i] * gam[i + 1]
-            x = x + gam[1] * r[0]  # :364-366
+                    gbb[jj] = gbb[jj] + tau[jj, i] * gam[i + sh]
+            terms += [gbar[jj] * r[jj] for jj in range(1, l + 1)]
+            if defect != "skip_x_mr":
+                x = x + gam[1] * r[0]  # :364-366
             r[0] = r[0] - gbar[l] * r[l]
             u[0] = u[0] - gam[l] * u[l]
             for jj in range(1, l):  # :367-371
@@ -763,24 +827,32 @@ def bicgstab_l(sp, K, l, pre=False, defect=None):
                 u[0] = u[0] - gam[jj] * u[jj]
         hist.append(sp.dot(r[0], r[0]))  # :374
         feeds.append([r[0]])
-    return Run(hist, x, feeds)
+        xs.append(x)
+        ratio.append(_own_ratio(sp, terms, hist[-1]))
+    return Run(hist, x, feeds, xs, ratio)
 
 
 def richardson(sp, K, omega, pre=False):
-    """SolverRichardson.hpp:51-96: the preconditioner, if any, acts on the residual (left) whatever the side."""
+    """SolverRichardson.hpp:51-96: the preconditioner, if any, acts on the residual (left) whatever the side.  ``xs``, and
+    ``ratio_sq[k]`` from r = b - A x (both under P with a preconditioner)."""
     b = sp.b()
     x, r = sp.zero(), b  # :65 (x0 = 0)
+    pb = b
     if pre:
-        r = sp.P(r)  # :66-69
+        r = pb = sp.P(r)  # :66-69
     hist, feeds = [sp.dot(r, r)], [[r]]  # :71
+    xs, ratio = [x], [1]
     for _ in range(K):
         x = x + omega * r  # :88
-        r = b - sp.A(x)  # :89
+        ax = sp.A(x)
+        r = b - ax  # :89
         if pre:
             r = sp.P(r)  # :90-93
         hist.append(sp.dot(r, r))  # :95
         feeds.append([r])
-    return Run(hist, x, feeds)
+        xs.append(x)
+        ratio.append(_own_ratio(sp, [pb, sp.P(ax) if pre else ax], hist[-1]))
+    return Run(hist, x, feeds, xs, ratio)
 
 
 def _own_ratio(sp, terms, h_sq):
@@ -937,9 +1009,18 @@ class Float64Space:
     the entries inside the box and a_halo those across the periodic seam; ``A(v, halo_of=u)`` then multiplies a_halo by u
     in place of v -- a halo that holds something else than the vector it belongs to."""
 
-    def __init__(self, a, b, a_halo=None):
+    one, scalar, root = 1.0, float, staticmethod(math.sqrt)  # (the scalars of ``tfqmr`` and ``idrs`` in fp64)
+
+    def __init__(self, a, b, a_halo=None, dinv=None):
         self.a, self.a_halo, self._b = a, a_halo, np.asarray(b, np.float64)
+        self._dinv = None if dinv is None else np.asarray(dinv, np.float64)
         self.ndots, self.drop_at = 0, None
+
+    def P(self, v):
+        return self._dinv * v
+
+    def fixed(self, values):
+        return np.asarray(values, np.float64).copy()
 
     def b(self):
         return self._b.copy()
@@ -981,36 +1062,45 @@ def _root(v):
     return _dec(v).sqrt()
 
 
-def idrs(sp, K, s, shadow=(), side=None):
-    """SolverIdrs.hpp:62-283, IDR(s), in decimals (p_0 = r / |r| and the normalisations take roots); every dot is
-    exact before its one conversion.  ``shadow``: the s - 1 fp64 vectors fill_randomly draws for p_1 ... p_{s-1}."""
+def idrs(sp, K, s, shadow=(), side=None, prec=None, defect=None, at=None):
+    """SolverIdrs.hpp:62-283, IDR(s), in decimals of ``prec`` digits (PREC; p_0 = r / |r| and the normalisations take
+    roots); every dot is exact before its one conversion.  ``shadow``: the s - 1 fp64 vectors fill_randomly draws for
+    p_1 ... p_{s-1}.  ``xs``, and ``ratio_sq[k]`` from r -= beta g_k and, at the end of a cycle, r -= omega v.  A space
+    may bring its own scalars (``scalar``, ``root``: ``Float64Space``).
+
+    ``defect`` (of x alone, at the end of the cycle that iteration ``at`` closes):
+      "skip_x_omega"        x += omega r left out
+      "x_omega_wrong_side"  side right: x += omega r for omega z, z = P r"""
+    assert defect != "x_omega_wrong_side" or side == "right"
     op = _ops(sp, side)
+    dec, root = getattr(sp, "scalar", _dec), getattr(sp, "root", _root)
     with localcontext() as ctx:
-        ctx.prec = PREC
+        ctx.prec = prec or PREC
         r = sp.b()  # :94 (x0 = 0)
         if side == "left":
             r = sp.P(r)  # :95-98
-        phi, gamma, mu = [Decimal(0)] * s, [Decimal(0)] * s, {}
-        phi[0] = _root(sp.dot(r, r))  # :99
+        phi, gamma, mu = [dec(0)] * s, [dec(0)] * s, {}
+        phi[0] = root(sp.dot(r, r))  # :99
         x, hist, feeds = sp.zero(), [phi[0] * phi[0]], [[r]]
+        xs, ratio = [x], [1]
         g, u, p = [sp.zero()] * s, [sp.zero()] * s, [None] * s
         omega = None
         for it in range(K):
             k = it % s  # Solver.hpp:239
             if k == 0:
                 if it == 0:
-                    omega = mu[0, 0] = Decimal(1)  # :131
+                    omega = mu[0, 0] = dec(1)  # :131
                     p[0] = r / phi[0]  # :132
                     for i in range(1, s):  # :133-141
-                        mu[i, i], phi[i] = Decimal(1), Decimal(0)
+                        mu[i, i], phi[i] = dec(1), dec(0)
                         p[i] = sp.fixed(shadow[i - 1])
                         for j in range(i):
-                            mu[i, j] = Decimal(0)
-                            p[i] = p[i] - _dec(sp.dot(p[i], p[j])) * p[j]
-                        p[i] = p[i] / _root(sp.dot(p[i], p[i]))
+                            mu[i, j] = dec(0)
+                            p[i] = p[i] - dec(sp.dot(p[i], p[j])) * p[j]
+                        p[i] = p[i] / root(sp.dot(p[i], p[i]))
                 else:
                     for i in range(s):  # :143-145
-                        phi[i] = _dec(sp.dot(p[i], r))
+                        phi[i] = dec(sp.dot(p[i], r))
             for i in range(k, s):  # :167-173
                 gamma[i] = phi[i]
                 for j in range(k, i):
@@ -1026,35 +1116,59 @@ def idrs(sp, K, s, shadow=(), side=None):
                 u[k] = u[k] + gamma[i] * u[i]  # :204-206
             g[k] = sp.P(sp.A(u[k])) if side == "left" else sp.A(u[k])  # :207-211
             for i in range(k):  # :221-226
-                a = _sdiv(_dec(sp.dot(p[i], g[k])), mu[i, i])
+                a = _sdiv(dec(sp.dot(p[i], g[k])), mu[i, i])
                 u[k] = u[k] - a * u[i]
                 g[k] = g[k] - a * g[i]
             for i in range(k, s):
-                mu[i, k] = _dec(sp.dot(p[i], g[k]))  # :234-236
+                mu[i, k] = dec(sp.dot(p[i], g[k]))  # :234-236
             beta = _sdiv(phi[k], mu[k, k])  # :244
             x = x + beta * u[k]  # :245
+            terms = [r, beta * g[k]]
             r = r - beta * g[k]  # :246
             for i in range(k + 1, s):
                 phi[i] -= beta * mu[i, k]  # :254-256
             if k == s - 1:
                 v, z = op(r)  # :272-274
-                omega = _sdiv(_dec(sp.dot(v, r)), _dec(sp.dot(v, v)))  # :276-277
-                x = x + omega * (z if side == "right" else r)  # :278
+                omega = _sdiv(dec(sp.dot(v, r)), dec(sp.dot(v, v)))  # :276-277
+                if not (defect == "skip_x_omega" and it == at):
+                    wrong = defect == "x_omega_wrong_side" and it == at
+                    x = x + omega * (z if side == "right" and not wrong else r)  # :278
+                terms.append(omega * v)
                 r = r - omega * v  # :279
-            hist.append(_dec(sp.dot(r, r)))  # :282
+            hist.append(dec(sp.dot(r, r)))  # :282
             feeds.append([r])
-    return Run(hist, x, feeds)
+            xs.append(x)
+            ratio.append(_own_ratio(sp, terms, hist[-1]))
+    return Run(hist, x, feeds, xs, ratio)
 
 
-def fgmres(sp, K, m):
+def fgmres(sp, K, m, prec=None):
     """SolverGmres.hpp:51-249 with Flexible = true: a preconditioner is applied on the right whatever the side
-    (:69-70, :125-130), z_k = P q_k kept per k (:152-153), x += sum beta_i z_i at the end of a cycle (:237-240)."""
+    (:69-70, :125-130), z_k = P q_k kept per k (:152-153), x += sum beta_i z_i at the end of a cycle (:237-240) and at
+    exit inside one (Solver.hpp:253-255).  ``xs[k]``: the x the solver leaves after k iterations -- inner_finalize on
+    the Hessenberg columns formed so far; ``ratio_sq[k]`` as ``gmres`` records its ratio: w = A z_k - sum_i H_ik q_i,
+    M = |A z_k|^2 + sum_i H_ik^2, h = H_{k+1,k}, the largest over the steps of the cycle so far.  Without a
+    preconditioner (``sp.P`` absent from the chain) z_k = q_k."""
+    pre = sp.basis.pre if hasattr(sp, "basis") else sp._dinv is not None
     with localcontext() as ctx:
-        ctx.prec = PREC
+        ctx.prec = prec or PREC
         b = sp.b()
         x = sp.zero()
         q, z, H, cs, sn, beta = [None] * (m + 1), [None] * m, {}, [None] * m, [None] * m, [Decimal(0)] * (m + 1)
         hist, feeds = [], []
+        xs, ratio = [x], [1]
+
+        def finalized(k):  # inner_finalize, :207-240, on a copy of beta
+            y = list(beta)
+            for i in range(k, -1, -1):
+                for j in range(i + 1, k + 1):
+                    y[i] -= H[i, j] * y[j]
+                y[i] /= H[i, i]
+            out = x
+            for i in range(k + 1):
+                out = out + y[i] * z[i]
+            return out
+
         for it in range(K + 1):
             if it == 0 or it % m == 0:  # outer_init (:82-88) and inner_init (:110-116) alike
                 q[0] = b - sp.A(x) if it else b
@@ -1063,16 +1177,20 @@ def fgmres(sp, K, m):
                     hist.append(beta[0] * beta[0])
                     feeds.append([q[0]])
                 q[0] = q[0] / beta[0]
+                worst = Decimal(0)
             if it == K:
                 break
             k = it % m
-            z[k] = sp.P(q[k])  # :152-153
+            z[k] = sp.P(q[k]) if pre else q[k]  # :152-153
             w = sp.A(z[k])
+            mag = _dec(sp.dot(w, w))
             for i in range(k + 1):  # :157-160
                 H[i, k] = _dec(sp.dot(w, q[i]))
                 w = w - H[i, k] * q[i]
+                mag += H[i, k] * H[i, k]
             H[k + 1, k] = _root(sp.dot(w, w))  # :161
             q[k + 1] = w / H[k + 1, k]  # :162
+            worst = max(worst, mag / (H[k + 1, k] * H[k + 1, k]))
             for i in range(k):  # :176-180
                 chi = cs[i] * H[i, k] + sn[i] * H[i + 1, k]
                 H[i + 1, k] = -sn[i] * H[i, k] + cs[i] * H[i + 1, k]
@@ -1084,14 +1202,11 @@ def fgmres(sp, K, m):
             beta[k + 1], beta[k] = -sn[k] * beta[k], cs[k] * beta[k]  # :189
             hist.append(beta[k + 1] * beta[k + 1])  # :191
             feeds.append([w])
-            if k == m - 1:  # inner_finalize, :207-240
-                for i in range(k, -1, -1):
-                    for j in range(i + 1, k + 1):
-                        beta[i] -= H[i, j] * beta[j]
-                    beta[i] /= H[i, i]
-                for i in range(k + 1):
-                    x = x + beta[i] * z[i]
-    return Run(hist, x, feeds)
+            xs.append(finalized(k))
+            ratio.append(worst)
+            if k == m - 1:
+                x = xs[-1]
+    return Run(hist, xs[-1], feeds, xs, ratio)
 
 
 def gmres(sp, K, m, prec=None):
@@ -1244,24 +1359,27 @@ def shadow_vectors(oracle, n, s):
     return [oracle.fill_randomly(n) for _ in range(s - 1)]
 
 
-def exact_run(sp, method, param, K, side=None, shadow=()):
-    """The method restated on a space (``Space`` or ``ElemSpace``, decimal for DECIMAL_METHODS); ``side`` None: no
-    preconditioner, else the space's dinv on that side (or the method's own)."""
+def exact_run(sp, method, param, K, side=None, shadow=(), prec=None, defect=None, at=None):
+    """The method restated on a space (``Space`` or ``ElemSpace``, decimal for DECIMAL_METHODS; ``Float64Space`` for the
+    defects); ``side`` None: no preconditioner, else the space's dinv on that side (or the method's own).  ``prec``: the
+    digits of the decimal methods (PREC)."""
     pre = side is not None
+    kw = {} if defect is None else dict(defect=defect, at=at)
     if method == "cgs":
-        return cgs(sp, K, side)
+        return cgs(sp, K, side, **kw)
     if method in ("tfqmr", "tfqmr1"):
-        return tfqmr(sp, K, side, l1=method == "tfqmr1")
+        return tfqmr(sp, K, side, l1=method == "tfqmr1", **kw)
     if method == "bicgstabl":
-        return bicgstab_l(sp, K, param, pre=pre)
+        return bicgstab_l(sp, K, param, pre=pre, **kw)
     if method == "idrs":
-        return idrs(sp, K, param, shadow, side)
+        return idrs(sp, K, param, shadow, side, prec=prec, **kw)
+    assert defect is None
     if method == "richardson":
         return richardson(sp, K, OMEGA, pre=pre)
     if method == "cg":
         return cg(sp, K, pre=pre)
     if method == "fgmres":
-        return fgmres(sp, K, param)
+        return fgmres(sp, K, param, prec=prec)
     raise ValueError(method)
 
 
@@ -1648,6 +1766,10 @@ class StepPins:
         assert self.exact[k] * 1.05 < mid < min(self.exact[:k]) / 1.05
         return mid
 
+    def res_exact(self, k):
+        """The exact ||b - A x_k||: for CG and BiCGStab without a preconditioner it is history[k]."""
+        return self.exact[k]
+
     def oracle_x(self, variant, k):
         if (k, variant) not in self._ox:
             self._ox[k, variant] = self._solve(variant, k).x
@@ -1665,7 +1787,7 @@ class StepPins:
         """(e_res, tol_res, rule, e_x, tol_x) of x_k; the last two None where the exact x is not formed."""
         if k not in self._xt:
             assert 1 <= k <= self.K
-            want = self.exact[k]
+            want = self.res_exact(k)
             xs = [self.oracle_x(v, k) for v in ("strict", "fma")]
             e_res = max(abs(true_residual(self.A, self.b, x) - want) / want for x in xs)
             tol_res = self._cap(max(self.floor[k], 16 * e_res), f"tol_res({k})")
@@ -1681,8 +1803,8 @@ class StepPins:
         """Assert a solution after k iterations (K by default); returns |res - exact| / exact (and |x - exact| / |exact|)."""
         k = self.K if k is None else k
         e_res, tol_res, rule, e_x, tol_x = self.x_tolerances(k)
-        res, want = true_residual(self.A, self.b, x), self.exact[k]
-        assert close(res, want, tol_res), f"{label} |b - A x_{k}| = {res!r}, exact history[{k}] {want!r}: rel " \
+        res, want = true_residual(self.A, self.b, x), self.res_exact(k)
+        assert close(res, want, tol_res), f"{label} |b - A x_{k}| = {res!r}, exact {want!r}: rel " \
                                           f"{abs(res - want) / want:.3e} > tol {tol_res:.3e} ({rule})"
         out = [abs(res - want) / want]
         if tol_x is not None:
@@ -1735,7 +1857,7 @@ class StepProblem:
             self.A = poisson_operator(mesh, self.g)
             self.b = int_vector(self.g.n_cells, seed)
             self.basis, self.fs = Basis(shape, self.b), FirstStep(Sums(shape, self.b))
-        self._pins, self._A2 = {}, None
+        self._pins, self._A2, self._pre_basis = {}, None, None
 
     def oracle_op(self, variant):
         if self.kind in PERIODIC_KINDS:
@@ -1756,6 +1878,182 @@ class StepProblem:
                 self._pins[key] = StepPins(self.oracle, self.oracle_op, Space(self.basis), self.A, self.b, method,
                                            key[1], fs=self.fs)
         return self._pins[key]
+
+    def engine_pins(self, method, param=None, side=None, K=None):
+        """``EnginePins`` of an engine method on this box (``side``: the Jacobi preconditioner on it; Poisson boxes)."""
+        key = ("engine", method, param, side, K)
+        if key not in self._pins:
+            dinv = None
+            basis = self.basis
+            if side is not None:
+                assert self.kind == "poisson"
+                dinv = 1.0 / int_diagonal(self.shape)
+                if self._pre_basis is None:
+                    self._pre_basis = Basis(self.shape, self.b, dinv)
+                basis = self._pre_basis
+            self._pins[key] = EnginePins(self.oracle, self.oracle_op, basis, self.A, self.b, method, param, K, side, dinv)
+        return self._pins[key]
+
+
+# ---- the engine's other methods past their second step ----------------------------------------------------------------
+
+ENGINE_STEP_BOXES = [((64, 48, 40), "poisson"), ((37, 21, 19), "poisson")]
+ENGINE_STEP_K = [("cgs", None, 4), ("tfqmr", None, 4), ("tfqmr1", None, 4), ("bicgstabl", 1, 3), ("bicgstabl", 2, 5),
+                 ("bicgstabl", 3, 7), ("idrs", 1, 4), ("idrs", 2, 6), ("idrs", 4, 6)]
+# (BiCGStab(l): 2 l + 1, a second cycle's beta.  IDR(4): 6, not 7 -- on 37 x 21 x 19 the oracle's own x_7 lies 9.6e-12 from
+# the exact one, and 16 times that is above TOL_CAP: NOTES.md)
+# The early exit on 64 x 48 x 40: (K, the iteration an absolute tolerance stops at).  Iteration 3 of K wherever
+# history[3] lies below every earlier entry.  IDR(2) and IDR(4) are not monotone there -- history[3] is above history[1]
+# -- so no tolerance makes iteration 3 the first to meet it: IDR(2) stops at 6 of 7 (the end of its third cycle), IDR(4)
+# at 5 of 6 (inside its second), the first iterations after 1 that lie below all before them
+ENGINE_STOPS = {(m, p): (K, STEP_STOP) for m, p, K in ENGINE_STEP_K}
+ENGINE_STOPS.update({("idrs", 2): (7, 6), ("idrs", 4): (6, 5)})
+ENGINE_GMRES_STOPS = (5, 7)  # GMRES(5) of 12 iterations on the convection-diffusion boxes: a cycle's last step, inside one
+ENGINE_FGMRES_M, ENGINE_FGMRES_STOPS = 2, [(2, 3), (3, 4)]  # FGMRES(2) with Jacobi on the Poisson boxes: (stop at, of K)
+ENGINE_STEP_CONVDIFF = [("cgs", None, 4, (40, 30, 17)), ("tfqmr", None, 4, (40, 30, 17)), ("bicgstabl", 2, 5, (40, 30, 17)),
+                        ("tfqmr1", None, 6, (7, 5, 3))]  # on 7 x 5 x 3 TFQMR1's omega < tau comes out both ways
+ENGINE_JACOBI = [("cg", None), ("cgs", None), ("tfqmr", None), ("idrs", 2), ("bicgstabl", 2), ("fgmres", 1), ("fgmres", 30),
+                 ("richardson", None)]
+ENGINE_JACOBI_K = 3
+# the side the reference applies the preconditioner on whatever pre_side says (tests/test_gpu_exact_first_step.py)
+ENGINE_FIXED_SIDE = {"richardson": "left", "bicgstabl": "left", "fgmres": "right"}
+# (method, param, side, shape, box, K): every case tests/test_gpu_exact_engine_steps.py pins; tests/test_exact_reference.py
+# asserts every cap of every one on the reference alone
+ENGINE_STEP_CASES = [(m, p, None, shape, kind, K) for shape, kind in ENGINE_STEP_BOXES for m, p, K in ENGINE_STEP_K] + \
+    [(m, p, None, shape, "convdiff", K) for m, p, K, shape in ENGINE_STEP_CONVDIFF] + \
+    [(m, p, side, shape, kind, ENGINE_JACOBI_K) for shape, kind in ENGINE_STEP_BOXES for m, p in ENGINE_JACOBI
+     for side in ("left", "right") if ENGINE_FIXED_SIDE.get(m, side) == side]
+
+
+def oracle_solutions(oracle, make_op, b, method, param, k, side=None, dinv=None):
+    """``oracle_histories`` with the operator given (``make_op(variant)``) and the whole result kept: history[0..k] and
+    the x the oracle leaves after k iterations, in both of its arithmetic variants."""
+    out = {}
+    bf = np.asarray(b, np.float64)
+    for variant in ("strict", "fma"):
+        op = make_op(variant)
+        pre = None if dinv is None else oracle.DiagOperator(dinv, variant=variant)
+        common = dict(num_iterations=k, abs_tol=0.0, rel_tol=0.0, variant=variant)
+        if method == "fgmres":
+            r, _ = oracle.solve_gmres_pre(op, pre, bf, side=side or "right", flexible=True, num_inner_iterations=param, **common)
+        else:
+            kw = {}
+            if method in ("bicgstabl", "idrs"):
+                kw["num_inner_iterations"] = param
+            if method == "richardson":
+                kw["relaxation_factor"] = float(OMEGA)
+            if method == "idrs":
+                oracle.rng_reset(variant)
+            if pre is not None:
+                kw.update(pre=pre, side=side)
+            r = oracle.solve(method, op, bf, **common, **kw)
+        assert r.history.size == k + 1, (method, r.history)
+        out[variant] = r
+    return out
+
+
+def engine_float64(A, b, method, param, K, side=None, dinv=None, shadow=(), defect=None, at=None):
+    """An engine method's history[0..K] and x_0 ... x_K in plain fp64 numpy (``A``: an ``IntOperator``): the statements of
+    the restatement on ``Float64Space``, with the defects the pins must reject."""
+    sp = Float64Space(A.float64(), b, dinv=dinv)
+    run = exact_run(sp, method, param, K, side, shadow, defect=defect, at=at)
+    return np.sqrt(np.array(run.hist_sq, np.float64)), run.xs
+
+
+class EnginePins(StepPins):
+    """history[0..K] and x_0 ... x_K of an engine method (CGS, TFQMR, TFQMR1, BiCGStab(l), IDR(s), FGMRES, Richardson, CG
+    with a preconditioner) from x0 = 0, with ``StepPins``' rule and its ``check``, ``check_x`` and ``stop_between``:
+
+    - history[0] bitwise where r0 is b; otherwise tol_k = max(floor_k, 16 e_k) <= TOL_CAP (asserted), e_k the larger
+      relative distance of the oracle's strict and fma builds from the exact value, floor_k = ``floor_tol`` with the
+      ratio sqrt(M) / h of the statements that form the entry (``ratio_sq`` of the restatements -- not the power-basis
+      terms, which cancel) and c = k C1[method], plus 4 k + 1 under a preconditioner.
+    - x: ``true_residual(A, b, x)`` against the exact ||b - A x_k||, formed from ``xs[k]`` in the space -- NOT history[k]:
+      TFQMR's history is the bound tau sqrt(2 k + 1), a left-preconditioned method's the norm of P r -- within
+      max(floor_k, 16 e_res), e_res the same quantity of the oracle's two x; at or below GMRES_X_ROWS rows also x against
+      the exact x_k by relative 2-norm under the same rule.
+    - the decimal methods run at PREC and at 2 PREC digits and must agree to 1e-40 (asserted), history and residuals.
+
+    ``preds``: for TFQMR1 the outcome of omega < tau at every half-step."""
+
+    def __init__(self, oracle, make_op, basis, A, b, method, param=None, K=None, side=None, dinv=None):
+        b = np.asarray(b, np.int64)
+        pre = side is not None
+        assert basis.pre == pre and (dinv is not None) == pre
+        self.method, self.param, self.side, self.dinv = method, param, side, dinv
+        self.K = K = iterations(method, param, pre) if K is None else K
+        self.n, self.A, self.b = b.size, A, b
+        self._oracle, self._make_op = oracle, make_op
+        self.decimal = method in DECIMAL_METHODS
+        self.shadow = shadow_vectors(oracle, b.size, param) if method == "idrs" else ()
+        self.space = Space(basis, decimal=self.decimal)
+        self.run = run = exact_run(self.space, method, param, K, side, self.shadow)
+        self._fine = exact_run(Space(basis, decimal=True), method, param, K, side, self.shadow, prec=2 * PREC) if self.decimal else None
+        if self.decimal:
+            self._agree(run.hist_sq, self._fine.hist_sq, "history")
+        self.preds = getattr(run, "preds", None)
+        self.exact = exact = run.history
+        self.oracle, self._ox, self._x, self._res, self._xt = {}, {}, {}, {}, {}
+        for variant, r in self._solve(K).items():
+            self.oracle[variant], self._ox[K, variant] = r.history, r.x
+        self.e = [max(abs(h[k] - exact[k]) / exact[k] for h in self.oracle.values()) for k in range(K + 1)]
+        self.floor = [floor_tol(self.n, math.sqrt(float(run.ratio_sq[k])), _c(method, param, k, pre)) for k in range(K + 1)]
+        self.tol, self.rule = [], []
+        for k in range(K + 1):
+            if k == 0 and run.feeds[0][0].c == self.space.b().c:
+                assert exact[0] == math.sqrt(float(exact_dot(b, b)))
+                self.tol.append(None), self.rule.append("exact")
+            else:
+                self.tol.append(self._cap(max(self.floor[k], 16 * self.e[k]), f"tol_{k}"))
+                self.rule.append("16 e_k" if self.tol[k] > self.floor[k] else "floor")
+
+    @staticmethod
+    def _agree(coarse, fine, what):
+        with localcontext() as ctx:
+            ctx.prec = 2 * PREC
+            for k, (c, f) in enumerate(zip(coarse, fine)):
+                assert abs(c - f) <= abs(f) * Decimal(10) ** -40, f"{what}[{k}]^2 depends on the precision: {c} {f}"
+
+    def _cap(self, tol, what):
+        assert tol <= TOL_CAP, f"{self.method}({self.param}) {self.side} K={self.K} n={self.n}: {what} = {tol:.3e} above the cap {TOL_CAP}"
+        return tol
+
+    def stop_between(self, k):
+        """``StepPins.stop_between`` for a history that need not fall: the midpoint of the exact history[k] and the
+        smallest earlier entry (history[k - 1] where the history is monotone)."""
+        mid = 0.5 * (self.exact[k] + min(self.exact[:k]))
+        assert self.exact[k] * 1.05 < mid < min(self.exact[:k]) / 1.05
+        return mid
+
+    def _solve(self, k):
+        return oracle_solutions(self._oracle, self._make_op, self.b, self.method, self.param, k, self.side, self.dinv)
+
+    def oracle_x(self, variant, k):
+        if (k, variant) not in self._ox:
+            for v, r in self._solve(k).items():
+                self._ox[k, v] = r.x
+        return self._ox[k, variant]
+
+    def _res_sq(self, run, k, prec):
+        sp = self.space
+        with localcontext() as ctx:
+            ctx.prec = prec
+            r = sp.b() - sp.A(run.xs[k])
+            n = sp.ndots
+            sq = sp.dot(r, r)
+            sp.ndots = n
+        return sq
+
+    def res_exact(self, k):
+        """The exact ||b - A x_k||, from ``xs[k]`` in the space."""
+        if k not in self._res:
+            sq = self._res_sq(self.run, k, PREC)
+            if self.decimal:
+                self._agree([sq], [self._res_sq(self._fine, k, 2 * PREC)], f"|b - A x_{k}|")
+            with localcontext() as ctx:
+                ctx.prec = PREC
+                self._res[k] = float(_dec(sq).sqrt())
+        return self._res[k]
 
 
 def richardson_integers(shape, b, k):

@@ -1022,3 +1022,207 @@ def test_halo_defects_fall_outside_the_periodic_pins(env, method, defect, kind):
         pins.check(list(h), defect)
     with pytest.raises(AssertionError):  # (a space without the split cannot state them)
         (er.cg_float64 if method == "cg" else er.bicgstab_float64)(p.A.float64(), p.b, K, defect=defect)
+
+
+# ---- the engine's other methods past their second step (exact_ref.EnginePins, tests/test_gpu_exact_engine_steps.py) ----------
+
+# (method, param, side, K) at the K of the table, on 4 x 3 x 3; TFQMR1 also on the tiny convection-diffusion box
+ENGINE_BRUTE = sorted({(m, p, side, K) for m, p, side, _, _, K in er.ENGINE_STEP_CASES}, key=str) + \
+    [("fgmres", er.ENGINE_FGMRES_M, "right", K) for _, K in er.ENGINE_FGMRES_STOPS]
+
+
+def _dec_close(a, b, scale=None):
+    from decimal import localcontext
+
+    with localcontext() as ctx:
+        ctx.prec = er.PREC
+        return abs(er._dec(a) - er._dec(b)) <= abs(er._dec(b) if scale is None else scale) * er._dec(Fraction(1, 10 ** 60))
+
+
+@pytest.mark.parametrize("method,param,side,K", ENGINE_BRUTE, ids=[f"{_mid(m, p)}-{s}-K{K}" for m, p, s, K in ENGINE_BRUTE])
+def test_engine_step_coefficient_form_against_a_brute_force(env, method, param, side, K):
+    """Every restatement at the K the GPU tests pin, on coefficient columns and with every element exact (Fractions; for
+    IDR(s) and FGMRES PREC-digit decimals, to 1e-60): the same history, the same ``ratio_sq``, the same x_k for EVERY k,
+    and the same ||b - A x_k||^2 formed from it; TFQMR1's predicates alike.  K = 6 of TFQMR1 runs on the
+    convection-diffusion box 4 x 3 x 3."""
+    oracle, mesh = env
+    shape, n = (4, 3, 3), 36
+    dec = method in er.DECIMAL_METHODS
+    rng = np.random.default_rng(11)
+    shadow = [rng.integers(1, 1 << 20, n) / float(1 << 21) for _ in range(3)]
+    if method == "tfqmr1" and K == 6:
+        g, w, A = er.convdiff_box(mesh, *shape)
+        b = er.int_vector(n, er.GMRES_SEED, *er.GMRES_RANGE)
+        sp, el = er.Space(er.OpBasis(A, b)), er.ElemSpace(None, b, op=A)
+    else:
+        b = er.int_vector(n, 7)
+        dinv = 1.0 / er.int_diagonal(shape) if side else None
+        sp, el = er.Space(er.Basis(shape, b, dinv), decimal=dec), er.ElemSpace(shape, b, dinv, decimal=dec)
+    coef, brute = (er.exact_run(s, method, param, K, side, shadow) for s in (sp, el))
+    assert len(coef.hist_sq) == len(brute.hist_sq) == len(coef.xs) == len(brute.xs) == len(coef.ratio_sq) == K + 1
+    assert getattr(coef, "preds", None) == getattr(brute, "preds", None)
+    from decimal import localcontext
+
+    with localcontext() as ctx:
+        ctx.prec = er.PREC
+        for k in range(K + 1):
+            rc, rb = sp.b() - sp.A(coef.xs[k]), el.b() - el.A(brute.xs[k])
+            res_c, res_b = sp.dot(rc, rc), el.dot(rb, rb)
+            if not dec:
+                assert coef.hist_sq[k] == brute.hist_sq[k] and coef.ratio_sq[k] == brute.ratio_sq[k] and res_c == res_b, k
+                if k:
+                    assert np.array_equal(sp.materialize(coef.xs[k]), np.array([float(v) for v in brute.xs[k]])), k
+                continue
+            assert _dec_close(coef.hist_sq[k], brute.hist_sq[k]) and _dec_close(res_c, res_b), k
+            assert _dec_close(coef.ratio_sq[k], brute.ratio_sq[k]), k
+            if k:
+                xc = sum((er._dec(c) * sp.basis.W[t].astype(object) for t, c in coef.xs[k].c.items()), np.zeros(n, dtype=object))
+                scale = max(abs(v) for v in brute.xs[k])
+                assert all(_dec_close(a, e, scale) for a, e in zip(xc, brute.xs[k])), k
+    # the x a method leaves is consistent with its history wherever the history is the true residual's norm: not TFQMR's
+    # bound, not the norm of P r under a left preconditioner
+    if method not in ("tfqmr", "tfqmr1") and (side is None or method == "cg" or er.ENGINE_FIXED_SIDE.get(method, side) == "right"):
+        with localcontext() as ctx:
+            ctx.prec = er.PREC
+            rb = el.b() - el.A(brute.xs[K])
+            assert _dec_close(el.dot(rb, rb), brute.hist_sq[K]) if dec else el.dot(rb, rb) == brute.hist_sq[K]
+
+
+_engine_problems = {}
+
+
+def _engine_problem(env, shape, kind):
+    oracle, mesh = env
+    if (shape, kind) not in _engine_problems:
+        _engine_problems[shape, kind] = er.StepProblem(oracle, mesh, shape, kind)
+    return _engine_problems[shape, kind]
+
+
+def _engine_cases():
+    out = [c + ((c[5],),) for c in er.ENGINE_STEP_CASES]
+    out += [(m, p, None, SMALL, "poisson", K, (k,)) for (m, p), (K, k) in er.ENGINE_STOPS.items()]
+    out += [("fgmres", er.ENGINE_FGMRES_M, "right", shape, kind, K, (k,)) for shape, kind in er.ENGINE_STEP_BOXES
+            for k, K in er.ENGINE_FGMRES_STOPS]
+    return out
+
+
+@pytest.mark.parametrize("case", _engine_cases(),
+                         ids=lambda c: f"{_mid(c[0], c[1])}-{c[2]}-{'x'.join(map(str, c[3]))}-{c[4]}-K{c[5]}-x{c[6][0]}")
+def test_engine_step_pins_of_every_gpu_case(env, case):
+    """Every case of tests/test_gpu_exact_engine_steps.py on the reference alone: every cap (tol_k, and tol_res and tol_x
+    at the iterations whose x is checked, <= TOL_CAP) and the decimal methods' precision guard are asserted as the pins
+    are built; both oracle builds lie inside, history and x; the early exits' tolerances exist (``stop_between``)."""
+    method, param, side, shape, kind, K, ks = case
+    p = _engine_problem(env, shape, kind)
+    pins = p.engine_pins(method, param, side, K)
+    assert pins.K == K and max(t for t in pins.tol if t is not None) <= er.TOL_CAP
+    assert (pins.tol[0] is None) == (side != "left" or method == "cg")  # (bitwise where r0 is b: CG's preconditioner has no side)
+    for k in ks:
+        e_res, tol_res, rule, e_x, tol_x = pins.x_tolerances(k)
+        assert tol_res <= er.TOL_CAP and (tol_x is None) == (p.b.size > er.GMRES_X_ROWS)
+        assert tol_x is None or tol_x <= er.TOL_CAP
+        for variant in pins.oracle:
+            pins.check_x(pins.oracle_x(variant, k), k, f"{method} {shape} {variant}")
+        if k < K:
+            assert pins.stop_between(k) > 0
+    for variant, hist in pins.oracle.items():
+        pins.check(list(hist), f"{_mid(method, param)} {side} {shape} {variant}")
+    if method == "tfqmr1" and kind == "convdiff":
+        assert pins.preds == [True] * 8 + [False] * 4  # both outcomes of omega < tau
+    print(f"engine pins {_mid(method, param)} {side} {shape} {kind} K={K}: largest tol_k "
+          f"{max(t for t in pins.tol if t is not None):.1e}, e_k {max(pins.e):.1e}, floor {max(pins.floor):.1e}, " +
+          " ".join(f"e_res({k}) {pins.x_tolerances(k)[0]:.1e} tol_res({k}) {pins.x_tolerances(k)[1]:.1e}" for k in ks))
+
+
+def test_tfqmr_history_is_not_the_residual_of_x(env):
+    """Why ``check_x`` forms ||b - A x_k|| from ``xs[k]``: TFQMR's history is the bound tau sqrt(2 k + 1), and on
+    37 x 21 x 19 at K = 4 the exact residual of x_4 is 0.5687 of it."""
+    pins = _engine_problem(env, ODD, "poisson").engine_pins("tfqmr", None, None, 4)
+    assert abs(pins.res_exact(4) / pins.exact[4] - 0.5687) < 1e-4
+
+
+def test_idrs_history_is_not_monotone_on_the_small_box(env):
+    """Why IDR(2) and IDR(4) stop elsewhere than at iteration 3 (er.ENGINE_STOPS): history[3] is above history[1]."""
+    p = _engine_problem(env, SMALL, "poisson")
+    for s in (2, 4):
+        K, k = er.ENGINE_STOPS["idrs", s]
+        pins = p.engine_pins("idrs", s, None, K)
+        assert pins.exact[3] > pins.exact[1]
+        with pytest.raises(AssertionError):
+            pins.stop_between(3)
+        assert k == next(j for j in range(2, K + 1) if pins.exact[j] * 1.05 < min(pins.exact[:j]))
+
+
+# (method, param, side, shape, box, K, defect, at)
+X_DEFECTS = [
+    ("cgs", None, None, ODD, "poisson", 4, "skip_x", 2), ("cgs", None, None, ODD, "poisson", 4, "double_x", None),
+    ("cgs", None, "right", ODD, "poisson", 3, "x_wrong_side", None),
+    ("tfqmr", None, "right", ODD, "poisson", 3, "d_wrong_vector", None),
+    ("tfqmr", None, None, ODD, "poisson", 4, "x_sn_for_cs", None), ("tfqmr", None, None, ODD, "poisson", 4, "d_not_scaled", None),
+    ("tfqmr1", None, None, (7, 5, 3), "convdiff", 6, "copy_always", None),
+    ("tfqmr1", None, None, (7, 5, 3), "convdiff", 6, "copy_never", None),
+    ("bicgstabl", 2, None, ODD, "poisson", 5, "skip_x_mr", None), ("bicgstabl", 2, None, ODD, "poisson", 5, "gbb_shift", None),
+    ("bicgstabl", 3, None, ODD, "poisson", 7, "gbb_shift", None),
+    ("idrs", 2, None, ODD, "poisson", 6, "skip_x_omega", 3), ("idrs", 2, "right", ODD, "poisson", 3, "x_omega_wrong_side", 1),
+]
+HISTORY_DEFECTS = [
+    ("bicgstabl", 1, None, ODD, "poisson", 3, "rho_without_omega", None),
+    ("bicgstabl", 2, None, ODD, "poisson", 5, "rho_without_omega", None),
+    ("bicgstabl", 1, None, ODD, "poisson", 3, "beta_without_alpha", 2),
+    ("bicgstabl", 2, None, ODD, "poisson", 5, "beta_without_alpha", 2),
+    ("bicgstabl", 3, None, ODD, "poisson", 7, "beta_without_alpha", 3),
+    ("cgs", None, None, ODD, "poisson", 4, "stale_beta", 3), ("tfqmr", None, None, ODD, "poisson", 4, "stale_beta", 3),
+]
+
+
+def _defect_id(c):
+    return f"{_mid(c[0], c[1])}-{c[2]}-{c[6]}" + ("" if c[7] is None else f"-at{c[7]}")
+
+
+def _engine_defect(env, case):
+    method, param, side, shape, kind, K, defect, at = case
+    assert any(c[:6] == case[:6] for c in er.ENGINE_STEP_CASES)  # (a case the GPU tests pin)
+    p = _engine_problem(env, shape, kind)
+    pins = p.engine_pins(method, param, side, K)
+    kw = dict(side=side, dinv=pins.dinv, shadow=pins.shadow)
+    clean = er.engine_float64(p.A, p.b, method, param, K, **kw)
+    bad = er.engine_float64(p.A, p.b, method, param, K, defect=defect, at=at, **kw)
+    pins.check(list(clean[0]), "clean fp64"), pins.check_x(clean[1][K], K, "clean fp64")
+    first = 1 if pins.tol[0] is None else 0
+    by_history = max(abs(bad[0][k] - pins.exact[k]) / (pins.exact[k] * pins.tol[k]) for k in range(first, K + 1))
+    res = er.true_residual(p.A, p.b, bad[1][K])
+    by_x = abs(res - pins.res_exact(K)) / (pins.res_exact(K) * pins.x_tolerances(K)[1])
+    return pins, clean, bad, by_history, by_x
+
+
+@pytest.mark.parametrize("case", X_DEFECTS, ids=_defect_id)
+def test_engine_x_defects_are_invisible_to_the_history_and_far_outside_check_x(env, case):
+    """What ``check_x`` is for: the float64 restatement with one statement of x wrong -- an update left out or applied
+    twice, the vector of the other side of the preconditioner, the rotation's other factor, a predicate ignored --
+    leaves the history BITWISE what the clean restatement gives (below 1 x tol_k of the exact one) and moves
+    ||b - A x_K|| by 100 x tol_res or more.  Prints error / tolerance (NOTES.md records them)."""
+    pins, clean, bad, by_history, by_x = _engine_defect(env, case)
+    K = pins.K
+    assert np.array_equal(bad[0], clean[0]) and by_history < 1, (case, by_history)
+    print(f"engine x defect {_defect_id(case)}: error / tolerance {by_history:.1e} (history) {by_x:.1e} (x_K)")
+    assert by_x >= 100, (case, by_x)
+    pins.check(list(bad[0]), "defect")
+    with pytest.raises(AssertionError):
+        pins.check_x(bad[1][K], K, "defect")
+
+
+@pytest.mark.parametrize("case", HISTORY_DEFECTS, ids=_defect_id)
+def test_engine_history_defects_of_the_newly_reached_iterations(env, case):
+    """What the larger K is for: BiCGStab(l)'s rho *= -omega left out, or its beta without alpha in a second cycle, and a
+    stale beta at iteration 3 of CGS and TFQMR, leave every entry the K of ``er.iterations`` pins bitwise alone and move a
+    later one by 100 x tol_k or more."""
+    method, param, side, shape, kind, K, defect, at = case
+    pins, clean, bad, by_history, by_x = _engine_defect(env, case)
+    old = er.iterations(method, param, False)
+    if (method, param) == ("bicgstabl", 2):
+        old = 2  # (its K = 3 already forms the second cycle's first beta; K = 5 forms the third's)
+    assert np.array_equal(bad[0][:old + 1], clean[0][:old + 1]), case
+    print(f"engine history defect {_defect_id(case)}: error / tolerance {by_history:.1e} (history) {by_x:.1e} (x_K)")
+    assert by_history >= 100, (case, by_history)
+    with pytest.raises(AssertionError):
+        pins.check(list(bad[0]), "defect")
