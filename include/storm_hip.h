@@ -381,6 +381,8 @@ int storm_hip_op_create_csr(storm_hip_ctx *ctx, int64_t n_rows, int64_t n_halo,
  *   generic_solvers (0): 1 sends storm_hip_krylov_solve through the engine even where a fused loop exists;
  *   cheb_fused (1): storm_hip_cheb_apply runs its fused step kernel where it applies (fp64 records, no CSR tail); 0: the
  *              statement path everywhere (the same bits);
+ *   recycle_fused (1): storm_hip_recycle_guess / _update run their fused kernels; 0: the same recipe out of library launchers
+ *              (the same bits; counters "recycle_fused_launches" / "recycle_statement_launches");
  *   cg_fuse (1), cg_march (8), cg_march_fill (2048): the SpMV launch of a tiled format-4 operator ends the previous CG
  *              iteration (x += alpha p, p = r + beta p) itself, as blocks marching through this many planes (0: tiles), fewer
  *              planes per block on small lattices so that the grid holds about cg_march_fill blocks (0: as given);
@@ -1123,6 +1125,75 @@ int storm_hip_amg_create_smoother(storm_hip_op *op, double alpha, double beta, c
                                   const storm_hip_amg_smoother *smoother, storm_hip_amg **out);
 int storm_hip_amg_smooth(const storm_hip_amg *h, int level, const storm_hip_vec *r, const storm_hip_vec *z_in,
                          storm_hip_vec *z_out);
+
+/* ---- successive right-hand sides: the initial guess projected onto past solves ----------------------------------------
+ * A time loop solves with one operator and a slowly changing right-hand side.  storm_hip_recycle keeps up to m pairs
+ * (u_j, v_j = A u_j) of earlier solutions, made orthogonal as they arrive, and one device scalar g_j per pair; guess() is
+ * the best initial guess in their span (Fischer, Projection techniques for iterative solution of Ax = b with successive
+ * right-hand sides, CMAME 163 (1998)).  The object never applies A: the caller hands it A x.  No scalar of it visits the
+ * host during guess or update (counter "host_reductions" does not move).  Added within ABI 6 (additive).
+ *
+ * THE RECIPE (restated in tests/recycle_ref.py).
+ *   kind 0 is the energy projection, for SPD operators: the test vector is t_j = u_j, the norm is N(a, b) = <a, b> on
+ *     (u, v), and g_j = 1 / <u_j, v_j>.
+ *   kind 1 is residual-minimising, for any operator: t_j = v_j, the norm is <v, v>, and g_j = 1 / <v_j, v_j>.
+ *   count is known to the host.  Slots j >= count are empty.  A slot with g_j = 0 contributes nothing.
+ *
+ *   guess(b, x):
+ *     e_j = <t_j, b> for j < count.
+ *     c_j = g_j * e_j.  The c values are kept on the device for the next update.
+ *     x = ((0 + c_0 u_0) + c_1 u_1) + ...: one fma per term, ascending j, starting from +0.0.
+ *     Owned rows only.  Halo rows are left as they are.
+ *     count == 0 gives x = 0.
+ *
+ *   update(x, ax), count < m, s = count:
+ *     d = x - sum_{j<s} c_j u_j and ad = ax - sum_{j<s} c_j v_j.  Each is a chain fma(-c_j, ., acc) in ascending j,
+ *       starting from x or ax.
+ *     e_j = <t_j, ad>.  nu0 = <d, ad> for kind 0, <ad, ad> for kind 1.
+ *     beta_j = g_j e_j.  u_s = d - sum beta_j u_j and v_s = ad - sum beta_j v_j, the same chains.
+ *     nu = <u_s, v_s> for kind 0, <v_s, v_s> for kind 1.
+ *     g_s = 1 / nu if nu is finite, nu > 0 and nu > 2^-40 nu0.  Otherwise g_s = 0.  (The 2^-40 guard is the multigrid coarse
+ *       level's pivot rule.)  g_s is decided by the block that finishes the reduction.
+ *     count += 1.
+ *     An update with no guess since the last update uses c = 0, so d = x (the first chain is not run).
+ *
+ *   update at count == m: restart.
+ *     u_0 = x, v_0 = ax, nu = N(x, ax), g_0 by the same guard with nu0 = nu.
+ *     g_j = 0 for j > 0.
+ *     count = 1.  The restarts counter goes up by one.
+ *
+ *   reset() sets count = 0 and clears every g_j.
+ *
+ * Capacity is 1 .. 16.  Above 8 the chains continue across launches of 8, as the multi-axpy chunks them.
+ *
+ * LAUNCHES.  Option recycle_fused = 1 (the default): guess is the multi-dot and recycle_guess_kernel; update is
+ * recycle_defect_kernel (d and ad formed in registers from one read of the 2 s + 2 vectors, written into slot s, with the
+ * s + 1 sums finished by tickets) and recycle_orth_kernel (slot s updated in place, nu finished by tickets, its last block
+ * writes g_s); the restart -- and the first pair of an empty object -- is one launch.  More than 8 slots: one more launch
+ * per kernel and one multi-dot.  recycle_fused = 0 runs the same recipe out of the library's multi-dot, multi-axpy, copy
+ * and fill launchers and a one-block scalar kernel: the reference the fused kernels are held to, bit for bit (with option
+ * ticket_reduce at its default).  Counters: "recycle_guesses", "recycle_updates", "recycle_restarts",
+ * "recycle_fused_launches", "recycle_statement_launches".
+ *
+ * storm_hip_recycle_get keys: "capacity", "count", "kind", "updates", "restarts", "device_bytes" (no wait);
+ *   "weight_<j>" (g_j) and "coef_<j>" (c_j of the last guess; 0 when an update has followed it): wait for the stream.
+ * storm_hip_recycle_get_slot / _set_slot: for checkpointing a time loop and for tests.  get_slot copies pair j < count into
+ *   u and v (either may be null) and g_j into *g (may be null; waits when it is not).  set_slot needs j <= count; j == count
+ *   appends (j < capacity).  The caller answers for the pairs being orthogonal in the kind's sense.
+ * STORM_HIP_E_INVALID: a null argument, a capacity outside 1 .. 16, a kind other than 0 / 1, vectors of another context or
+ *   size, x aliasing b in guess, x aliasing ax in update.  STORM_HIP_E_UNSUPPORTED: a context with a communicator (the sums
+ *   here are local: single rank for now).  An operator that changes between solves leaves the pairs stale: reset() is the
+ *   caller's job. */
+typedef struct storm_hip_recycle storm_hip_recycle;
+enum storm_hip_recycle_kind { STORM_HIP_RECYCLE_ENERGY = 0, STORM_HIP_RECYCLE_RESIDUAL = 1 };
+int storm_hip_recycle_create(storm_hip_ctx *ctx, int64_t n_owned, int64_t n_halo, int capacity, int kind, storm_hip_recycle **out);
+int storm_hip_recycle_destroy(storm_hip_recycle *h);
+int storm_hip_recycle_guess(storm_hip_recycle *h, const storm_hip_vec *b, storm_hip_vec *x);
+int storm_hip_recycle_update(storm_hip_recycle *h, const storm_hip_vec *x, const storm_hip_vec *ax);
+int storm_hip_recycle_reset(storm_hip_recycle *h);
+int storm_hip_recycle_get(const storm_hip_recycle *h, const char *key, double *value);
+int storm_hip_recycle_get_slot(const storm_hip_recycle *h, int j, storm_hip_vec *u, storm_hip_vec *v, double *g);
+int storm_hip_recycle_set_slot(storm_hip_recycle *h, int j, const storm_hip_vec *u, const storm_hip_vec *v, double g);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -1066,6 +1066,62 @@ private:
   storm_hip_amg_smoother _built_smoother{};
 };
 
+/// The initial guess of a solve projected onto the solutions of earlier solves with the same operator (storm_hip_recycle_*;
+/// the recipe: storm_hip.h): up to `capacity` (1 .. 16) pairs (u_j, A u_j) on the device, made orthogonal as they arrive; a
+/// full object restarts from the newest pair.  Energy kind for SPD operators, residual kind for any.  Point
+/// IterativeSolver::recycler at one, or call guess() before and update() after a solve yourself.  No scalar visits the
+/// host in either.  Single rank.  An operator that changes between solves leaves the pairs stale: reset() is the caller's job.
+class SolutionRecycler {
+public:
+  SolutionRecycler(const Context& ctx, std::size_t n_owned, std::size_t n_halo = 0, int capacity = 8,
+                   int kind = STORM_HIP_RECYCLE_ENERGY)
+      : _ctx(&ctx), _n_owned(n_owned), _n_halo(n_halo) {
+    detail::check(storm_hip_recycle_create(ctx.handle(), (int64_t)n_owned, (int64_t)n_halo, capacity, kind, &_h));
+  }
+  SolutionRecycler(const SolutionRecycler&) = delete;
+  SolutionRecycler& operator=(const SolutionRecycler&) = delete;
+  ~SolutionRecycler() { (void)storm_hip_recycle_destroy(_h); }
+
+  /// x = the projection of the solution of A x = b onto the stored pairs (zeros while there is none)
+  void guess(const DeviceVector& b_vec, DeviceVector& x_vec) {
+    detail::check(storm_hip_recycle_guess(_h, b_vec.handle(), x_vec.handle()));
+  }
+  /// take a solve's x in, with ax = A x
+  void update(const DeviceVector& x_vec, const DeviceVector& ax_vec) {
+    detail::check(storm_hip_recycle_update(_h, x_vec.handle(), ax_vec.handle()));
+  }
+  /// ... with A x formed by `any_op` in a scratch vector of the object's
+  void update(const DeviceVector& x_vec, const Operator<DeviceVector>& any_op) {
+    if (_ax == nullptr) _ax = std::make_unique<DeviceVector>(*_ctx, _n_owned, _n_halo);
+    any_op.mul(*_ax, x_vec);
+    update(x_vec, *_ax);
+  }
+  void reset() { detail::check(storm_hip_recycle_reset(_h)); }
+  /// "capacity", "count", "kind", "updates", "restarts", "device_bytes"; "weight_<j>", "coef_<j>" (these two wait for the stream)
+  real_t get(const char* key) const {
+    double v = 0.0;
+    detail::check(storm_hip_recycle_get(_h, key, &v));
+    return v;
+  }
+  /// copies of pair j into u and v; returns its weight g_j (for a checkpoint, for tests)
+  real_t slot(int j, DeviceVector& u, DeviceVector& v) const {
+    double g = 0.0;
+    detail::check(storm_hip_recycle_get_slot(_h, j, u.handle(), v.handle(), &g));
+    return g;
+  }
+  /// load pair j <= count (j == count appends); the caller answers for the pairs being orthogonal
+  void set_slot(int j, const DeviceVector& u, const DeviceVector& v, real_t g) {
+    detail::check(storm_hip_recycle_set_slot(_h, j, u.handle(), v.handle(), g));
+  }
+  storm_hip_recycle* handle() const noexcept { return _h; }
+
+private:
+  storm_hip_recycle* _h = nullptr;
+  const Context* _ctx;
+  std::size_t _n_owned, _n_halo;
+  std::unique_ptr<DeviceVector> _ax;
+};
+
 #ifndef STORM_HIP_NO_SOLVERS
 // ---------------------------------------------------------------------------------------------
 template<class InVector, class OutVector = InVector>
@@ -1230,6 +1286,10 @@ public:
   /// `false`: every statement is a launch of its own when it is called.
   bool lazy_statements{true};
   std::size_t num_applies{0}, num_pre_applies{0};  ///< of the last device-loop solve
+  real_t initial_error{0.0};  ///< |r0| of the last solve
+  /// Not owned.  When set (DeviceVector solves), solve() takes its guess for x before init and hands it x and A x -- one more
+  /// apply -- after the loop; null: solve() is the plain one.
+  SolutionRecycler* recycler{nullptr};
   int path_fallback{0};  ///< storm_hip_solver_result::path_fallback of the last device-loop solve (0: the chosen path ran)
 
 protected:
@@ -1261,6 +1321,19 @@ protected:
 
 public:
   bool solve(InVector& x_vec, const OutVector& b_vec, const Operator<InVector, OutVector>& any_op) final {
+    if constexpr (std::is_same_v<InVector, DeviceVector> && std::is_same_v<OutVector, DeviceVector>) {
+      if (recycler != nullptr) {
+        recycler->guess(b_vec, x_vec);
+        const bool converged = solve_plain(x_vec, b_vec, any_op);
+        recycler->update(x_vec, any_op);
+        return converged;
+      }
+    }
+    return solve_plain(x_vec, b_vec, any_op);
+  }
+
+private:
+  bool solve_plain(InVector& x_vec, const OutVector& b_vec, const Operator<InVector, OutVector>& any_op) {
     if (pre_op != nullptr) pre_op->build(x_vec, b_vec, any_op);
     if constexpr (std::is_same_v<InVector, DeviceVector> && std::is_same_v<OutVector, DeviceVector>) {
       if (device_method() >= 0 && device_loop) {
@@ -1271,7 +1344,7 @@ public:
         int64_t n_pre = 0;
         _engine.finish(storm_hip_krylov_solve(_engine.handle(), b_vec.handle(), x_vec.handle(), &p, &r, nullptr, &n_pre));
         iteration = (std::size_t)r.iterations;
-        absolute_error = r.absolute_error, relative_error = r.relative_error;
+        absolute_error = r.absolute_error, relative_error = r.relative_error, initial_error = r.initial_error;
         num_applies = (std::size_t)r.num_applies, num_pre_applies = (std::size_t)n_pre;
         path_fallback = r.path_fallback;
         collect(_engine.handle());
@@ -1281,7 +1354,7 @@ public:
     }
     // Host loop with the reference's rule: stop on abs_tol > 0 && abs < abs_tol, or rel_tol > 0 && abs / initial < rel_tol.
     detail::LazyScope lazy(x_vec, lazy_statements);
-    const real_t initial_error = init(x_vec, b_vec, any_op, pre_op.get());
+    initial_error = init(x_vec, b_vec, any_op, pre_op.get());
     absolute_error = initial_error;
     const auto met = [this](real_t value, real_t tolerance) { return tolerance > 0.0 && value < tolerance; };
     bool converged = met(absolute_error, absolute_error_tolerance);

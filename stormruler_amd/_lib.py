@@ -236,6 +236,14 @@ SIGNATURES = {
     "storm_hip_amg_create_smoother": (C.c_int, [vp, C.c_double, C.c_double, C.POINTER(AmgParams), C.POINTER(AmgSmoother),
                                                 C.POINTER(vp)]),
     "storm_hip_amg_smooth": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "storm_hip_recycle_create": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(vp)]),
+    "storm_hip_recycle_destroy": (C.c_int, [vp]),
+    "storm_hip_recycle_guess": (C.c_int, [vp, vp, vp]),
+    "storm_hip_recycle_update": (C.c_int, [vp, vp, vp]),
+    "storm_hip_recycle_reset": (C.c_int, [vp]),
+    "storm_hip_recycle_get": (C.c_int, [vp, C.c_char_p, f64p]),
+    "storm_hip_recycle_get_slot": (C.c_int, [vp, C.c_int, vp, vp, f64p]),
+    "storm_hip_recycle_set_slot": (C.c_int, [vp, C.c_int, vp, vp, C.c_double]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -999,6 +999,77 @@ class ChebyshevPreconditioner(Preconditioner):
             pass
 
 
+class SolutionRecycler:
+    """The initial guess of a solve projected onto the solutions of earlier solves with the same operator
+    (``storm_hip_recycle_*``; the recipe: include/storm_hip.h): up to ``capacity`` (1 .. 16) pairs ``(u_j, A u_j)`` on the
+    device, made orthogonal as they arrive; when the object is full an update restarts it from the newest pair.
+    ``kind="energy"`` for SPD operators, ``"residual"`` for any.  Set it as ``IterativeSolver.recycler`` or call
+    :meth:`guess` before and :meth:`update` after a solve yourself.  No scalar visits the host in either.  Single rank.  An
+    operator that changes between solves leaves the pairs stale: call :meth:`reset`."""
+
+    KINDS = {"energy": 0, "residual": 1}
+
+    def __init__(self, ctx: Context, n_owned: int, n_halo: int = 0, capacity: int = 8, kind="energy"):
+        self.ctx, self.n_owned, self.n_halo = ctx, int(n_owned), int(n_halo)
+        self._h, self._ax = None, None
+        code = self.KINDS.get(kind, kind)
+        h = C.c_void_p()
+        check(lib.storm_hip_recycle_create(ctx._h, self.n_owned, self.n_halo, int(capacity), int(code), C.byref(h)))
+        self._h = h
+        ctx._children.add(self)
+
+    def guess(self, b_vec: DeviceVector, x_vec: DeviceVector) -> None:
+        """``x`` = the projection of the solution of ``A x = b`` onto the stored pairs (zeros while there is none)."""
+        check(lib.storm_hip_recycle_guess(self._h, b_vec._h, x_vec._h))
+
+    def update(self, x_vec: DeviceVector, ax_vec: Optional[DeviceVector] = None, op=None) -> None:
+        """Take the solve's ``x`` in; ``ax_vec`` is ``A x``, or ``op`` forms it in a scratch vector of the object's."""
+        if ax_vec is None:
+            if op is None:
+                raise ValueError("SolutionRecycler.update needs ax_vec or op")
+            if self._ax is None:
+                self._ax = DeviceVector(self.ctx, self.n_owned, self.n_halo)
+            op.mul(self._ax, x_vec)
+            ax_vec = self._ax
+        check(lib.storm_hip_recycle_update(self._h, x_vec._h, ax_vec._h))
+
+    def reset(self) -> None:
+        check(lib.storm_hip_recycle_reset(self._h))
+
+    def get(self, key: str) -> float:
+        """``capacity``, ``count``, ``kind``, ``updates``, ``restarts``, ``device_bytes``; ``weight_<j>`` and ``coef_<j>``
+        (these two wait for the stream)."""
+        v = C.c_double()
+        check(lib.storm_hip_recycle_get(self._h, key.encode(), C.byref(v)))
+        return v.value
+
+    def slot(self, j: int):
+        """``(u_j, v_j, g_j)``: copies of pair ``j`` as new vectors, and its weight (for a checkpoint, for tests)."""
+        u, v, g = DeviceVector(self.ctx, self.n_owned, self.n_halo), DeviceVector(self.ctx, self.n_owned, self.n_halo), C.c_double()
+        check(lib.storm_hip_recycle_get_slot(self._h, int(j), u._h, v._h, C.byref(g)))
+        return u, v, g.value
+
+    def set_slot(self, j: int, u_vec: DeviceVector, v_vec: DeviceVector, g: float) -> None:
+        """Load pair ``j <= count`` (``j == count`` appends); the caller answers for the pairs being orthogonal."""
+        check(lib.storm_hip_recycle_set_slot(self._h, int(j), u_vec._h, v_vec._h, float(g)))
+
+    def _free(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):
+                lib.storm_hip_recycle_destroy(self._h)
+            self._h = None
+        self._ax = None
+
+    def close(self):
+        self._free()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self._free()
+        except Exception:
+            pass
+
+
 def _amg_params(**kw) -> "_lib.AmgParams":
     p = _lib.AmgParams()
     lib.storm_hip_amg_params_default(C.byref(p))
@@ -1386,6 +1457,8 @@ class IterativeSolver(Solver):
         self.device_loop = True
         self.lazy_statements = True  # the host loop runs with the library's option of that name (csrc/lazy.hip)
         self._engine: Optional[_Engine] = None
+        # a SolutionRecycler: solve() takes its guess for x before init, and hands it x and A x (one more apply) after the loop
+        self.recycler: Optional[SolutionRecycler] = None
 
     # -- the reference's stepping hooks ------------------------------------------------------
     def init(self, x_vec, b_vec, any_op, pre_op) -> float:
@@ -1435,7 +1508,20 @@ class IterativeSolver(Solver):
         ``stormruler_amd.solvers`` at INFO level."""
         _LOG.info("n_iter: %4d, abs_err: %-12e, rel_err: %-12e", self.iteration, self.absolute_error, self.relative_error)
 
+    def _solve_recycled(self, x_vec, b_vec, any_op) -> bool:
+        """solve() between the recycler's guess and update; the solve in the middle is the plain one."""
+        recycler, self.recycler = self.recycler, None
+        try:
+            recycler.guess(b_vec, x_vec)
+            converged = self.solve(x_vec, b_vec, any_op)
+            recycler.update(x_vec, op=any_op)
+        finally:
+            self.recycler = recycler
+        return converged
+
     def solve(self, x_vec, b_vec, any_op) -> bool:  # Solver.hpp:116-147
+        if self.recycler is not None:
+            return self._solve_recycled(x_vec, b_vec, any_op)
         if self.pre_op is not None:
             self.pre_op.build(x_vec, b_vec, any_op)
         if self._method is not None and self.device_loop:

@@ -95,18 +95,26 @@ class CavityProjection:
     """Device-resident projection stepper.  ``step()`` returns (cg_iterations, seconds)."""
 
     def __init__(self, ctx, n: int, nu: float = 0.01, dt: float = None, graph: FaceGraph = None, plan=None,
-                 pressure_preconditioner: str = None):
+                 pressure_preconditioner: str = None, pressure_recycle: int = 0):
         """``graph``/``plan``: this rank's local face graph and halo plan (``stormruler_amd.partition``)
         for a row-partitioned run (config 5 is 4 GPUs); ``ctx`` must then carry a communicator.
         ``pressure_preconditioner``: ``None`` (plain CG, the default) or ``"amg"``: the multigrid preconditioner for the
         pure-Neumann pressure operator (``AmgPreconditioner(nullspace="constant")``), single rank only.  Its hierarchy is
-        built from a second copy of ``L_N`` on fp64 records; the solve's own ``L_N`` keeps its compact records."""
+        built from a second copy of ``L_N`` on fp64 records; the solve's own ``L_N`` keeps its compact records.
+        ``pressure_recycle``: ``0`` (the default) warm-starts the pressure from the previous step; ``m > 0`` starts it from
+        the projection onto up to ``m`` earlier pressures instead (``api.SolutionRecycler``, energy kind, capacity ``m``;
+        single rank).  ``L_N`` is singular: a constant pressure gives ``nu = <x, L_N x> = 0``, so its pair gets the weight
+        ``g = 0`` by the recycler's guard and contributes nothing to a guess."""
         from . import api
 
         if pressure_preconditioner not in (None, "amg"):
             raise ValueError(f"pressure_preconditioner={pressure_preconditioner!r}: None or 'amg'")
         if pressure_preconditioner == "amg" and (graph is not None or plan is not None or ctx.n_ranks != 1):
             raise ValueError("pressure_preconditioner='amg' is single-rank: no graph, no plan, no communicator")
+        if pressure_recycle < 0 or pressure_recycle > 16:
+            raise ValueError(f"pressure_recycle={pressure_recycle!r}: 0 (warm start) or a capacity of 1 .. 16")
+        if pressure_recycle and (graph is not None or plan is not None or ctx.n_ranks != 1):
+            raise ValueError("pressure_recycle is single-rank: no graph, no plan, no communicator")
 
         self.api, self.ctx, self.n, self.nu = api, ctx, n, nu
         h = 1.0 / n
@@ -146,6 +154,9 @@ class CavityProjection:
         # per step to `tol` x |rhs|.
         self.tol = 1e-8
         self.solver.relative_error_tolerance = 0.0
+        self.pressure_recycle = int(pressure_recycle)
+        if self.pressure_recycle:
+            self.solver.recycler = api.SolutionRecycler(ctx, N, g.n_halo, capacity=self.pressure_recycle, kind="energy")
         self.total_time = 0.0
         self.steps = 0
 
@@ -166,7 +177,7 @@ class CavityProjection:
             self.D[d].apply(1.0, 0.0, self.us[d], self.t1)
             self.rhs -= (1.0 / dt) * self.t1
         self.solver.absolute_error_tolerance = self.tol * api.norm_2(self.rhs)
-        ok = self.solver.solve(self.p, self.rhs, self.A_p)  # p keeps its previous value: warm start
+        ok = self.solver.solve(self.p, self.rhs, self.A_p)  # p keeps its previous value: warm start (or the recycler's guess)
         # corrector
         for d in range(3):
             self.G[d].apply(1.0, 0.0, self.p, self.t1)

@@ -624,6 +624,382 @@ int k_multi_axpy(storm_hip_ctx *c, double *y, const double *d_coef, double sign,
   return multi_axpy_impl(c, y, nullptr, d_coef, sign, xs, k, n, done);
 }
 
+// ---- solution recycling: the fused kernels of storm_hip_recycle (recycle.hip) --------------------------------
+// The recipe is in include/storm_hip.h.  Every chain is one fma per term in ascending j -- what multi_axpy_kernel's
+// `y += cf x` contracts to --, every sum takes multi_dot_accumulate's order per thread (row pairs ascending, .x before .y,
+// the odd last row by block 0 / thread 0 at the end), block_sum_multi and ticket_reduce_wave0 over a grid of
+// stream_blocks(n): the bits of k_multi_dot / k_multi_axpy on the same data, whatever the chunking (a sum's tree does
+// not depend on how many sums share its kernel).  A launch takes up to kRecycleChunk slots; a longer chain continues
+// in the next launch from what this one stored.
+struct RecyclePtrs {
+  const double *u[kRecycleChunk], *v[kRecycleChunk];
+};
+
+// g_s = 1 / nu, unless nu is not finite, not positive, or lost against nu0 (the multigrid coarse level's pivot rule)
+__device__ __forceinline__ double recycle_weight(double nu, double nu0) {
+  return (__builtin_isfinite(nu) && nu > 0.0 && nu > 0x1p-40 * nu0) ? 1.0 / nu : 0.0;
+}
+
+// x = (first ? +0 : x) + sum_j c_j u_j with c_j = g_j e_j formed per thread; thread 0 of block 0 stores c.
+template <int KB>
+__global__ __launch_bounds__(kBlock) void recycle_guess_kernel(int64_t n, double *x, RecyclePtrs p, const double *__restrict__ g,
+                                                               const double *__restrict__ e, double *__restrict__ c_out,
+                                                               int first, int nt) {
+  double cf[KB];
+#pragma unroll
+  for (int j = 0; j < KB; ++j) cf[j] = g[j] * e[j];
+  const int64_t n2 = n >> 1;
+  double2v *x2 = reinterpret_cast<double2v *>(x);
+  constexpr int U = KB <= 2 ? kUnroll : (KB <= 4 ? 2 : 1);
+  nt_dispatch(nt, [&](auto nt) {
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * kUnroll) + threadIdx.x; base < n2;
+       base += (int64_t)gridDim.x * (kBlock * kUnroll)) {
+#pragma unroll
+    for (int u0 = 0; u0 < kUnroll; u0 += U) {
+      double2v vy[U], vx[U][KB];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (u0 + u) * kBlock;
+        if (i < n2) {
+          vy[u] = first ? double2v{0.0, 0.0} : ld2(x2 + i, nt);
+#pragma unroll
+          for (int j = 0; j < KB; ++j) vx[u][j] = ld2(reinterpret_cast<const double2v *>(p.u[j]) + i, nt);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (u0 + u) * kBlock;
+        if (i < n2) {
+#pragma unroll
+          for (int j = 0; j < KB; ++j) {
+            vy[u].x = __builtin_fma(cf[j], vx[u][j].x, vy[u].x);
+            vy[u].y = __builtin_fma(cf[j], vx[u][j].y, vy[u].y);
+          }
+          st2(x2 + i, vy[u], nt);
+        }
+      }
+    }
+  }
+  });
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (n & 1) {
+      double vy = first ? 0.0 : x[n - 1];
+#pragma unroll
+      for (int j = 0; j < KB; ++j) vy = __builtin_fma(cf[j], p.u[j][n - 1], vy);
+      x[n - 1] = vy;
+    }
+#pragma unroll
+    for (int j = 0; j < KB; ++j) c_out[j] = cf[j];
+  }
+}
+
+// (us, vs) = (xin, axin) - sum_j c_j (u_j, v_j) in registers (xin / axin may be us / vs themselves: a later chunk of the
+// chain); c == null: no chain, the vectors are copied.  sums != 0: e_out[j] = <t_j, vs> (t_j = u_j, or v_j for kind 1)
+// and *nu0_out = <us, vs> (kind 1: <vs, vs>), finished with tickets.
+template <int KB>
+__global__ __launch_bounds__(kBlock) void recycle_defect_kernel(int64_t n, const double *xin, const double *axin, double *us,
+                                                                double *vs, RecyclePtrs p, const double *__restrict__ c,
+                                                                int kind, int sums, TicketArgs t, double *__restrict__ e_out,
+                                                                double *__restrict__ nu0_out, int nt) {
+  __shared__ double lds[KB + 1][4];
+  double cf[KB], acc[KB + 1];
+#pragma unroll
+  for (int j = 0; j < KB; ++j) cf[j] = c ? -c[j] : 0.0;
+#pragma unroll
+  for (int j = 0; j <= KB; ++j) acc[j] = 0.0;
+  const bool chain = c != nullptr;
+  const int64_t n2 = n >> 1;
+  const double2v *x2 = reinterpret_cast<const double2v *>(xin), *ax2 = reinterpret_cast<const double2v *>(axin);
+  double2v *us2 = reinterpret_cast<double2v *>(us), *vs2 = reinterpret_cast<double2v *>(vs);
+  constexpr int U = KB <= 1 ? 2 : 1;  // 2 KB + 2 streams
+  nt_dispatch(nt, [&](auto nt) {
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * kUnroll) + threadIdx.x; base < n2;
+       base += (int64_t)gridDim.x * (kBlock * kUnroll)) {
+#pragma unroll
+    for (int u0 = 0; u0 < kUnroll; u0 += U) {
+      double2v d[U], ad[U], vu[U][KB], vv[U][KB];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (u0 + u) * kBlock;
+        if (i < n2) {
+          d[u] = ld2(x2 + i, nt), ad[u] = ld2(ax2 + i, nt);
+#pragma unroll
+          for (int j = 0; j < KB; ++j) {
+            vu[u][j] = ld2(reinterpret_cast<const double2v *>(p.u[j]) + i, nt);
+            vv[u][j] = ld2(reinterpret_cast<const double2v *>(p.v[j]) + i, nt);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (u0 + u) * kBlock;
+        if (i < n2) {
+          if (chain) {
+#pragma unroll
+            for (int j = 0; j < KB; ++j) {
+              d[u].x = __builtin_fma(cf[j], vu[u][j].x, d[u].x), d[u].y = __builtin_fma(cf[j], vu[u][j].y, d[u].y);
+              ad[u].x = __builtin_fma(cf[j], vv[u][j].x, ad[u].x), ad[u].y = __builtin_fma(cf[j], vv[u][j].y, ad[u].y);
+            }
+          }
+          st2(us2 + i, d[u], nt), st2(vs2 + i, ad[u], nt);
+#pragma unroll
+          for (int j = 0; j < KB; ++j) {
+            const double2v tj = kind ? vv[u][j] : vu[u][j];
+            acc[j] += ad[u].x * tj.x;
+            acc[j] += ad[u].y * tj.y;
+          }
+          const double2v w = kind ? ad[u] : d[u];
+          acc[KB] += ad[u].x * w.x;
+          acc[KB] += ad[u].y * w.y;
+        }
+      }
+    }
+  }
+  });
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t i = n - 1;
+    double d = xin[i], ad = axin[i];
+    if (chain) {
+#pragma unroll
+      for (int j = 0; j < KB; ++j) d = __builtin_fma(cf[j], p.u[j][i], d), ad = __builtin_fma(cf[j], p.v[j][i], ad);
+    }
+    us[i] = d, vs[i] = ad;
+#pragma unroll
+    for (int j = 0; j < KB; ++j) acc[j] += ad * (kind ? p.v[j][i] : p.u[j][i]);
+    acc[KB] += ad * (kind ? ad : d);
+  }
+  if (!sums) return;
+  double mine[KB + 1], total[KB + 1];
+  block_sum_multi<KB + 1>(acc, lds, mine);
+  if (threadIdx.x >= kWave) return;
+  if (ticket_reduce_wave0<KB + 1>(t, mine, KB + 1, blockIdx.x, gridDim.x, total) && threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < KB; ++j) e_out[j] = total[j];
+    *nu0_out = total[KB];
+  }
+}
+
+// (us, vs) -= sum_j beta_j (u_j, v_j) in place with beta_j = g_j e_j formed per thread.  last != 0: nu = <us, vs> (kind 1:
+// <vs, vs>) finished with tickets; the block that finishes it stores nu and g_s = recycle_weight(nu, *nu0).
+template <int KB>
+__global__ __launch_bounds__(kBlock) void recycle_orth_kernel(int64_t n, double *us, double *vs, RecyclePtrs p,
+                                                              const double *__restrict__ g, const double *__restrict__ e, int kind,
+                                                              int last, TicketArgs t, const double *__restrict__ nu0,
+                                                              double *__restrict__ nu_out, double *__restrict__ g_out, int nt) {
+  __shared__ double lds[1][4];
+  double bf[KB], acc[1] = {0.0};
+#pragma unroll
+  for (int j = 0; j < KB; ++j) bf[j] = -(g[j] * e[j]);
+  const int64_t n2 = n >> 1;
+  double2v *us2 = reinterpret_cast<double2v *>(us), *vs2 = reinterpret_cast<double2v *>(vs);
+  constexpr int U = KB <= 1 ? 2 : 1;
+  nt_dispatch(nt, [&](auto nt) {
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * kUnroll) + threadIdx.x; base < n2;
+       base += (int64_t)gridDim.x * (kBlock * kUnroll)) {
+#pragma unroll
+    for (int u0 = 0; u0 < kUnroll; u0 += U) {
+      double2v d[U], ad[U], vu[U][KB], vv[U][KB];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (u0 + u) * kBlock;
+        if (i < n2) {
+          d[u] = ld2(us2 + i, nt), ad[u] = ld2(vs2 + i, nt);
+#pragma unroll
+          for (int j = 0; j < KB; ++j) {
+            vu[u][j] = ld2(reinterpret_cast<const double2v *>(p.u[j]) + i, nt);
+            vv[u][j] = ld2(reinterpret_cast<const double2v *>(p.v[j]) + i, nt);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (u0 + u) * kBlock;
+        if (i < n2) {
+#pragma unroll
+          for (int j = 0; j < KB; ++j) {
+            d[u].x = __builtin_fma(bf[j], vu[u][j].x, d[u].x), d[u].y = __builtin_fma(bf[j], vu[u][j].y, d[u].y);
+            ad[u].x = __builtin_fma(bf[j], vv[u][j].x, ad[u].x), ad[u].y = __builtin_fma(bf[j], vv[u][j].y, ad[u].y);
+          }
+          st2(us2 + i, d[u], nt), st2(vs2 + i, ad[u], nt);
+          const double2v w = kind ? ad[u] : d[u];
+          acc[0] += ad[u].x * w.x;
+          acc[0] += ad[u].y * w.y;
+        }
+      }
+    }
+  }
+  });
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t i = n - 1;
+    double d = us[i], ad = vs[i];
+#pragma unroll
+    for (int j = 0; j < KB; ++j) d = __builtin_fma(bf[j], p.u[j][i], d), ad = __builtin_fma(bf[j], p.v[j][i], ad);
+    us[i] = d, vs[i] = ad;
+    acc[0] += ad * (kind ? ad : d);
+  }
+  if (!last) return;
+  double mine[1], total[1];
+  block_sum_multi<1>(acc, lds, mine);
+  if (threadIdx.x >= kWave) return;
+  if (ticket_reduce_wave0<1>(t, mine, 1, blockIdx.x, gridDim.x, total) && threadIdx.x == 0) {
+    *nu_out = total[0];
+    *g_out = recycle_weight(total[0], *nu0);
+  }
+}
+
+// The restart (and the first pair of an empty object): (u0, v0) = (x, ax), nu = <x, ax> (kind 1: <ax, ax>); the block that
+// finishes the sum stores nu (twice: it is its own nu0), g_0 = recycle_weight(nu, nu) and g_j = 0 for 0 < j < m.
+__global__ __launch_bounds__(kBlock) void recycle_restart_kernel(int64_t n, const double *__restrict__ x, const double *__restrict__ ax,
+                                                                 double *__restrict__ u0, double *__restrict__ v0, int kind,
+                                                                 TicketArgs t, double *__restrict__ nu0_out, double *__restrict__ nu_out,
+                                                                 double *__restrict__ g, int m, int nt) {
+  __shared__ double lds[1][4];
+  double acc[1] = {0.0};
+  const int64_t n2 = n >> 1;
+  const double2v *x2 = reinterpret_cast<const double2v *>(x), *ax2 = reinterpret_cast<const double2v *>(ax);
+  double2v *u2 = reinterpret_cast<double2v *>(u0), *v2 = reinterpret_cast<double2v *>(v0);
+  nt_dispatch(nt, [&](auto nt) {
+  for (int64_t base = (int64_t)blockIdx.x * (kBlock * kUnroll) + threadIdx.x; base < n2;
+       base += (int64_t)gridDim.x * (kBlock * kUnroll)) {
+    double2v d[kUnroll], ad[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int64_t i = base + u * kBlock;
+      if (i < n2) d[u] = ld2(x2 + i, nt), ad[u] = ld2(ax2 + i, nt);
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int64_t i = base + u * kBlock;
+      if (i < n2) {
+        st2(u2 + i, d[u], nt), st2(v2 + i, ad[u], nt);
+        const double2v w = kind ? ad[u] : d[u];
+        acc[0] += ad[u].x * w.x;
+        acc[0] += ad[u].y * w.y;
+      }
+    }
+  }
+  });
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+    const double d = x[n - 1], ad = ax[n - 1];
+    u0[n - 1] = d, v0[n - 1] = ad;
+    acc[0] += ad * (kind ? ad : d);
+  }
+  double mine[1], total[1];
+  block_sum_multi<1>(acc, lds, mine);
+  if (threadIdx.x >= kWave) return;
+  if (ticket_reduce_wave0<1>(t, mine, 1, blockIdx.x, gridDim.x, total) && threadIdx.x == 0) {
+    *nu0_out = total[0], *nu_out = total[0];
+    g[0] = recycle_weight(total[0], total[0]);
+    for (int j = 1; j < m; ++j) g[j] = 0.0;
+  }
+}
+
+// The statement path's scalars, one block: mode 0: out[j] = g[j] e[j], j < k (c of a guess, beta of an update);
+// 1: g[s] = recycle_weight(*nu, *nu0); 2: the restart's g array.
+__global__ void recycle_scalar_kernel(int mode, int k, double *g, const double *e, double *out, const double *nu, const double *nu0,
+                                      int s, int m) {
+  const int j = threadIdx.x;
+  if (mode == 0) {
+    if (j < k) out[j] = g[j] * e[j];
+  } else if (mode == 1) {
+    if (j == 0) g[s] = recycle_weight(*nu, *nu0);
+  } else if (j < m) {
+    g[j] = j == 0 ? recycle_weight(*nu, *nu) : 0.0;
+  }
+}
+
+static RecyclePtrs recycle_ptrs(const double *const *us, const double *const *vs, int j0, int kb) {
+  RecyclePtrs p;
+  for (int j = 0; j < kRecycleChunk; ++j) p.u[j] = us[j0 + (j < kb ? j : 0)], p.v[j] = vs ? vs[j0 + (j < kb ? j : 0)] : nullptr;
+  return p;
+}
+static TicketArgs recycle_tickets(storm_hip_ctx *c) { return TicketArgs{c->d_tickets, c->d_partials, c->d_ticket_sums}; }
+
+int k_recycle_guess(storm_hip_ctx *c, int64_t n, double *x, const double *const *us, int k, const double *g, const double *e,
+                    double *c_out, int *launches) {
+  if (n <= 0 || k <= 0) return STORM_HIP_OK;
+  const dim3 grid(stream_blocks(n)), block(kBlock);
+  const int nt = stream_nt(c, n);
+  for (int j0 = 0; j0 < k; j0 += kRecycleChunk) {
+    const int kb = (k - j0) < kRecycleChunk ? (k - j0) : kRecycleChunk;
+    const RecyclePtrs p = recycle_ptrs(us, nullptr, j0, kb);
+#define RG_GO(K_) hipLaunchKernelGGL(recycle_guess_kernel<K_>, grid, block, 0, c->stream, n, x, p, g + j0, e + j0, c_out + j0, j0 == 0 ? 1 : 0, nt)
+    STORM_K_SWITCH(kb, RG_GO);
+#undef RG_GO
+    HIP_TRY(hipGetLastError());
+    ++*launches;
+  }
+  return STORM_HIP_OK;
+}
+
+// Slot s = (x, ax) - sum_{j<s} coef_j (u_j, v_j) (coef == null: a copy), e_out[j] = <t_j, v_s>, *nu0_out as above; 1 <= s.
+// More than kRecycleChunk slots: the last launch carries the sums of its own slots and nu0, a multi-dot the earlier ones'.
+int k_recycle_defect(storm_hip_ctx *c, int64_t n, const double *x, const double *ax, double *const *us, double *const *vs, int s,
+                     const double *coef, int kind, double *e_out, double *nu0_out, int *launches) {
+  if (n <= 0) return STORM_HIP_OK;
+  const dim3 grid(stream_blocks(n)), block(kBlock);
+  STORM_TRY(partials_reserve(c, (int64_t)(kRecycleChunk + 1) * grid.x));
+  const int nt = stream_nt(c, n);
+  const TicketArgs t = recycle_tickets(c);
+  for (int j0 = 0; j0 < s; j0 += kRecycleChunk) {
+    const int kb = (s - j0) < kRecycleChunk ? (s - j0) : kRecycleChunk;
+    const RecyclePtrs p = recycle_ptrs(us, vs, j0, kb);
+    const double *xin = j0 == 0 ? x : us[s], *axin = j0 == 0 ? ax : vs[s];
+    const int sums = j0 + kb == s ? 1 : 0;
+#define RD_GO(K_)                                                                                                     \
+  hipLaunchKernelGGL(recycle_defect_kernel<K_>, grid, block, 0, c->stream, n, xin, axin, us[s], vs[s], p, coef ? coef + j0 : nullptr, \
+                     kind, sums, t, e_out + j0, nu0_out, nt)
+    STORM_K_SWITCH(kb, RD_GO);
+#undef RD_GO
+    HIP_TRY(hipGetLastError());
+    ++*launches;
+  }
+  for (int j0 = 0; j0 + kRecycleChunk < s; j0 += kRecycleChunk) {  // the sums of the chunks before the last
+    STORM_TRY(k_multi_dot(c, vs[s], kind ? vs + j0 : us + j0, kRecycleChunk, n, e_out + j0, nullptr));
+    ++*launches;
+  }
+  return STORM_HIP_OK;
+}
+
+int k_recycle_orth(storm_hip_ctx *c, int64_t n, double *const *us, double *const *vs, int s, const double *g, const double *e,
+                   int kind, const double *nu0, double *nu_out, double *g_all, int *launches) {
+  if (n <= 0) return STORM_HIP_OK;
+  const dim3 grid(stream_blocks(n)), block(kBlock);
+  const int nt = stream_nt(c, n);
+  const TicketArgs t = recycle_tickets(c);
+  for (int j0 = 0; j0 < s; j0 += kRecycleChunk) {
+    const int kb = (s - j0) < kRecycleChunk ? (s - j0) : kRecycleChunk;
+    const RecyclePtrs p = recycle_ptrs(us, vs, j0, kb);
+    const int last = j0 + kb == s ? 1 : 0;
+#define RO_GO(K_)                                                                                                          \
+  hipLaunchKernelGGL(recycle_orth_kernel<K_>, grid, block, 0, c->stream, n, us[s], vs[s], p, g + j0, e + j0, kind, last, t, nu0, \
+                     nu_out, g_all + s, nt)
+    STORM_K_SWITCH(kb, RO_GO);
+#undef RO_GO
+    HIP_TRY(hipGetLastError());
+    ++*launches;
+  }
+  return STORM_HIP_OK;
+}
+
+int k_recycle_restart(storm_hip_ctx *c, int64_t n, const double *x, const double *ax, double *u0, double *v0, int kind,
+                      double *nu0_out, double *nu_out, double *g_all, int m, int *launches) {
+  if (n <= 0) return STORM_HIP_OK;
+  hipLaunchKernelGGL(recycle_restart_kernel, dim3(stream_blocks(n)), dim3(kBlock), 0, c->stream, n, x, ax, u0, v0, kind,
+                     recycle_tickets(c), nu0_out, nu_out, g_all, m, stream_nt(c, n));
+  HIP_TRY(hipGetLastError());
+  ++*launches;
+  return STORM_HIP_OK;
+}
+
+int k_recycle_scalar(storm_hip_ctx *c, int mode, int k, double *g, const double *e, double *out, const double *nu,
+                     const double *nu0, int s, int m, int *launches) {
+  hipLaunchKernelGGL(recycle_scalar_kernel, dim3(1), dim3(kWave), 0, c->stream, mode, k, g, e, out, nu, nu0, s, m);
+  HIP_TRY(hipGetLastError());
+  ++*launches;
+  return STORM_HIP_OK;
+}
+
 }  // namespace storm
 
 using namespace storm;

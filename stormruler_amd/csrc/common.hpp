@@ -277,6 +277,9 @@ struct storm_hip_ctx {
   int64_t n_amg_fused_sweeps = 0, n_amg_statement_sweeps = 0;  // amg.hip: which path a Jacobi sweep of the cycle (or storm_hip_amg_smooth) took
   int64_t n_amg_refreshes = 0;  // storm_hip_amg_refresh (amg_refresh.hip)
   int64_t n_amg_projections = 0, n_amg_fused_projections = 0;  // a null-space object's Pi (two per apply); the closing axpy fused with its sum
+  int64_t opt_recycle_fused = 1;  // storm_hip_recycle: the fused kernels (blas1.hip recycle_*_kernel); 0: the same recipe out of library launchers
+  int64_t n_recycle_guesses = 0, n_recycle_updates = 0, n_recycle_restarts = 0;  // recycle.hip: calls; updates that restarted
+  int64_t n_recycle_fused_launches = 0, n_recycle_statement_launches = 0;        // ... what the two paths enqueued
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_cg_pz_consumer_folds = 0;  // ... of those, the solves whose plane march folded <p,z> itself (option cg_pz_fold)
@@ -435,6 +438,20 @@ int k_multi_dot_partials(storm_hip_ctx *c, const double *a, const double *const 
 // y += sum_j coef[j] * xs[j]; coefficients from device memory (d_coef, sign applied).
 int k_multi_axpy(storm_hip_ctx *c, double *y, const double *d_coef, double sign,
                  const double *const *xs, int k, int64_t n, const int *done);
+// The fused kernels of storm_hip_recycle (recycle.hip; the recipe: include/storm_hip.h).  us / vs: the object's slots; g, e,
+// c_out, nu0, nu: its device scalars.  A launch takes kRecycleChunk slots; *launches counts what was enqueued.
+constexpr int kRecycleChunk = 8;
+int k_recycle_guess(storm_hip_ctx *c, int64_t n, double *x, const double *const *us, int k, const double *g, const double *e,
+                    double *c_out, int *launches);
+int k_recycle_defect(storm_hip_ctx *c, int64_t n, const double *x, const double *ax, double *const *us, double *const *vs, int s,
+                     const double *coef, int kind, double *e_out, double *nu0_out, int *launches);
+int k_recycle_orth(storm_hip_ctx *c, int64_t n, double *const *us, double *const *vs, int s, const double *g, const double *e,
+                   int kind, const double *nu0, double *nu_out, double *g_all, int *launches);
+int k_recycle_restart(storm_hip_ctx *c, int64_t n, const double *x, const double *ax, double *u0, double *v0, int kind,
+                      double *nu0_out, double *nu_out, double *g_all, int m, int *launches);
+// ... and the statement path's one-block scalar kernel: mode 0: out[j] = g[j] e[j], j < k; 1: g[s] from *nu, *nu0; 2: the restart's g
+int k_recycle_scalar(storm_hip_ctx *c, int mode, int k, double *g, const double *e, double *out, const double *nu,
+                     const double *nu0, int s, int m, int *launches);
 // Final pass over per-block partials: out[j] = sum_b partials[j * nblocks + b].
 int k_dot_partials(storm_hip_ctx *c, const double *a, const double *b, int64_t n, double *partials, int nb,
                    const int *done);

@@ -240,6 +240,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *c, const char *key, int64_t value) {
   else if (!strcmp(key, "blas1_nt")) c->opt_blas1_nt = value;
   else if (!strcmp(key, "cheb_fused")) c->opt_cheb_fused = value;
   else if (!strcmp(key, "amg_fused")) c->opt_amg_fused = value;
+  else if (!strcmp(key, "recycle_fused")) c->opt_recycle_fused = value;
   else STORM_FAIL(STORM_HIP_E_INVALID, "ctx_set_option: unknown key '%s'", key);
   return STORM_HIP_OK;
 }
@@ -263,6 +264,11 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "amg_fused_sweeps")) *value = c->n_amg_fused_sweeps;
   else if (!strcmp(key, "amg_statement_sweeps")) *value = c->n_amg_statement_sweeps;
   else if (!strcmp(key, "amg_refreshes")) *value = c->n_amg_refreshes;
+  else if (!strcmp(key, "recycle_guesses")) *value = c->n_recycle_guesses;
+  else if (!strcmp(key, "recycle_updates")) *value = c->n_recycle_updates;
+  else if (!strcmp(key, "recycle_restarts")) *value = c->n_recycle_restarts;
+  else if (!strcmp(key, "recycle_fused_launches")) *value = c->n_recycle_fused_launches;
+  else if (!strcmp(key, "recycle_statement_launches")) *value = c->n_recycle_statement_launches;
   else if (!strcmp(key, "option_spmv_dict")) *value = c->opt_spmv_dict;  // (the option's value, for a caller that restores it)
   else if (!strcmp(key, "amg_projections")) *value = c->n_amg_projections;
   else if (!strcmp(key, "amg_fused_projections")) *value = c->n_amg_fused_projections;
