@@ -904,7 +904,24 @@ int storm_hip_cheb_create_reduced(const storm_hip_op *op, double alpha, double b
  * bits of the two statements; amg_fused = 0 takes the statements everywhere, and with cheb_fused = 0 as well the cycle holds
  * no fused kernel but the transfers.  All settings give the same bits (tests/test_gpu_amg.py).  Counters
  * (storm_hip_ctx_get_counter): "amg_applies", "amg_fused_residuals", "amg_statement_residuals".  About 11 launches per level:
- * small meshes are launch-bound. */
+ * small meshes are launch-bound.
+ *
+ * THE TAIL (option amg_tail, default 0; csrc/amg_tail.hip).  With amg_tail = 1 the cycle from a level t down to the coarsest
+ * level and back up to t is ONE cooperative kernel: the statements above, in their order, as phases between grid barriers, each
+ * row through the device functions the launched kernels call -- the same bits (tests/test_gpu_amg_tail.py).  t is the first
+ * level with at most amg_tail_rows rows (option; default 0 = no level, see below) from which every level is eligible: fp64 records, no CSR tail,
+ * no compact format, option amg_fused on; level 0 of a null-space object is never eligible (its projections stay launches); a
+ * tail of the coarsest level alone is not taken.  Levels above t stay launches; when the whole hierarchy is small t = 0 and
+ * an apply is one launch.  Both smoothers, fp64 and reduced records, plain, refreshable (a refresh drops the kernel's tables)
+ * and null-space objects, inside a solve and stand-alone.  A launch that is refused takes the launches for that apply.  Should
+ * a wait inside the kernel give up (10 s; a device shared with another cooperative kernel), a solve is re-run without the tail
+ * (storm_hip_solver_result::path_fallback 2); after a stand-alone storm_hip_amg_apply the next storm_hip_ctx_sync returns
+ * STORM_HIP_E_HIP, and z of that apply is UNDEFINED.  Counters "amg_tail_applies" (applies whose tail ran as the kernel;
+ * the per-path counters above do not move for its levels) and "amg_tail_refusals"; storm_hip_amg_get keys "tail_level" (t
+ * under the current amg_tail_rows, -1: none; the coarsest level's index: no tail is taken), "tail_blocks", "tail_barriers".
+ * MEASURED (profiles/INDEX_r34.md): the kernel is SLOWER than the launches at every level size tried, 1.3x to 3x -- a phase
+ * costs three dependent trips through the fabric (coherent gathers, the publishing exchange, the barrier) where a launch on a
+ * warm stream costs about 2 us.  Hence amg_tail_rows = 0 by default: amg_tail = 1 changes nothing until a size is named. */
 #define STORM_HIP_HAS_AMG 1
 typedef struct storm_hip_amg_params {
   double strength_theta;    /* 0.25 */

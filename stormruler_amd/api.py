@@ -1261,7 +1261,9 @@ class AmgPreconditioner(Preconditioner):
         """``levels``, ``operator_complexity``, ``grid_complexity``, ``setup_seconds``, ``upload_seconds``, ``device_bytes``,
         ``transfer_padding``, ``smoother_degree``, ``reduced``, ``structural``, ``refreshable``, ``refresh_bytes``,
         ``nullspace``, ``coarse_shift``, ``smoother_kind`` (0 Chebyshev, 1 Jacobi), ``jacobi_sweeps``, ``jacobi_omega`` or
-        ``jacobi_sigma_<level>``."""
+        ``jacobi_sigma_<level>``; the cooperative tail of the cycle (context options ``amg_tail``, ``amg_tail_rows``):
+        ``tail_level`` (the level the tail starts at under the current ``amg_tail_rows``; -1: none; the coarsest level's index:
+        no tail is taken), ``tail_blocks`` and ``tail_barriers`` of its kernel (0 where none is taken)."""
         v = C.c_double()
         check(lib.storm_hip_amg_get(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -24,14 +24,15 @@
 //                           product and axpbz_value: the bits of storm_hip_op_apply; storm_hip_axpbz(t, 1, r, -1, t);
 //                           storm_hip_vmul(t, s, t); storm_hip_axpbz(z', sigma, t, 1, z), which any other level takes.
 // Every kernel loads the context's api_done word first and tests it before its first store.
+// A row's arithmetic lives in amg_device.hpp, shared with amg_tail.hip: with option amg_tail the cycle hands a level, everything
+// below it and the way back up to ONE cooperative kernel (amg_cycle asks amg_tail_run first; refused: the launches below).
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
 #include "amg.hpp"
-#include "blas1_device.hpp"
-#include "sell_device.hpp"
+#include "amg_device.hpp"
 #include "ticket_device.hpp"
 #include "wave_device.hpp"
 
@@ -53,22 +54,8 @@ __global__ __launch_bounds__(kBlock) void amg_residual_kernel(SellArgs A, double
   const bool valid = row < A.n_rows;
   const double zi = valid ? z[row] : 0.0;
   const double ri = valid ? ld_d<NT>(r + row) : 0.0;  // the row's own stream, early
-  int64_t base;
-  int width;
-  if (A.uniform_width > 0) {
-    width = A.uniform_width;
-    base = slice * (int64_t)(kExtBytes + kSlotBytes * width);
-  } else {
-    base = A.slice_off[slice];
-    width = (int)((A.slice_off[slice + 1] - base - kExtBytes) / kSlotBytes);
-  }
-  const char *rec = A.pack + base;
-  const double ext = Rec64::ext<NT>(rec, lane);
-  const double zi1[1] = {zi};
-  double acc1[1];
-  row_sum_any<NT, 1, Rec64>(rec, width, lane, z, zi1, acc1);
-  const double az = sell_row_result(false, 0.0, beta, zi, alpha, acc1[0], ext);
-  const double tn = ri - az;  // axpbz(t, 1, r, -1, t): the multiplications by +-1 are exact
+  const double az = sell_row_apply<NT, Rec64>(A, slice, lane, z, zi, alpha, beta);
+  const double tn = amg_residual_value(ri, az);
   if (valid && !done_flag) {
     if (NT) __builtin_nontemporal_store(tn, t + row);
     else t[row] = tn;
@@ -95,24 +82,8 @@ __global__ __launch_bounds__(kBlock) void amg_jacobi_sweep_kernel(SellArgs A, do
   const double zi = valid ? z[row] : 0.0;
   const double ri = valid ? ld_d<NT>(r + row) : 0.0;  // the row's own streams, early
   const double si = valid ? ld_d<NT>(s + row) : 0.0;
-  int64_t base;
-  int width;
-  if (A.uniform_width > 0) {
-    width = A.uniform_width;
-    base = slice * (int64_t)(R::kExt + R::kSlot * width);
-  } else {
-    base = A.slice_off[slice];
-    width = (int)((A.slice_off[slice + 1] - base - R::kExt) / R::kSlot);
-  }
-  const char *rec = A.pack + base;
-  const double ext = R::template ext<NT>(rec, lane);
-  const double zi1[1] = {zi};
-  double acc1[1];
-  row_sum_any<NT, 1, R>(rec, width, lane, z, zi1, acc1);
-  const double az = sell_row_result(false, 0.0, beta, zi, alpha, acc1[0], ext);
-  const double tn = ri - az;  // axpbz(t, 1, r, -1, t)
-  const double w = si * tn;   // vmul(t, s, t)
-  const double zn = axpbz_value(sigma, w, 1.0, zi);  // axpbz(z', sigma, t, 1, z): the axpy statement's kernel
+  const double az = sell_row_apply<NT, R>(A, slice, lane, z, zi, alpha, beta);
+  const double zn = amg_jacobi_value(ri, az, si, sigma, zi);
   if (valid && !done_flag) {
     if (NT) __builtin_nontemporal_store(zn, z_out + row);
     else z_out[row] = zn;
@@ -131,20 +102,10 @@ __global__ __launch_bounds__(kBlock) void amg_transfer_kernel(const char *__rest
   if (slice >= n_slices) return;  // wave-uniform
   const int64_t row = slice * kWave + lane;
   const bool valid = row < n_rows;
-  const int64_t base = off[slice];
-  const int width = (int)((off[slice + 1] - base) / (kWave * 12));
-  const int *__restrict__ cp = reinterpret_cast<const int *>(pack + base) + lane;
-  const double *__restrict__ vp = reinterpret_cast<const double *>(pack + base + (int64_t)width * (kWave * 4)) + lane;
   double yi = 0.0;
   if (ADD) yi = valid ? y[row] : 0.0;
-  double acc = 0.0;
-#pragma unroll 4  // (the loads of four slots in flight; the sum stays in slot order)
-  for (int k = 0; k < width; ++k) {  // (padding: column 0, weight 0 -- inside x for every lane of the slice)
-    const int c = __builtin_nontemporal_load(cp + k * kWave);
-    const double w = __builtin_nontemporal_load(vp + k * kWave);
-    acc = fma(w, x[c], acc);
-  }
-  if (valid && !done_flag) y[row] = ADD ? yi + acc : acc;
+  const double yn = amg_transfer_row<ADD>(pack, off, slice, lane, x, yi);
+  if (valid && !done_flag) y[row] = yn;
 }
 
 __global__ __launch_bounds__(kBlock) void amg_coarse_kernel(const double *__restrict__ ainv, int64_t n, const double *__restrict__ r,
@@ -154,10 +115,7 @@ __global__ __launch_bounds__(kBlock) void amg_coarse_kernel(const double *__rest
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t row = (int64_t)blockIdx.x * (kBlock / kWave) + wave;
   if (row >= n) return;  // wave-uniform: all 64 lanes take part in the sum
-  const double *__restrict__ a = ainv + row * n;
-  double acc = 0.0;
-  for (int64_t j = lane; j < n; j += kWave) acc = fma(a[j], r[j], acc);
-  acc = wave_sum_down(acc);  // the total in lane 0
+  const double acc = amg_coarse_row(ainv, n, row, lane, r);  // the total in lane 0
   if (lane == 0 && !done_flag) z[row] = acc;
 }
 
@@ -284,7 +242,7 @@ static int amg_shift(const storm_hip_amg *h, const storm_hip_vec *v, int slot, s
 int op_create_csr_fp64(storm_hip_ctx *c, int64_t n_rows, const int64_t *row_ptr, const int64_t *col, const double *val,
                        bool source_map, storm_hip_op **out);  // spmv_build.hip
 
-static bool amg_residual_fused(const storm_hip_amg *h, const storm_hip_op *op) {
+bool amg_residual_fused(const storm_hip_amg *h, const storm_hip_op *op) {
   return h->ctx->opt_amg_fused != 0 && op->pair == 0 && op->dict_size == 0 && op->offs_size == 0 && op->tail_rows == 0 &&
          op->d_bnd_pack == nullptr && op->n_rows > 0;
 }
@@ -400,6 +358,11 @@ static int amg_cycle_jacobi(const storm_hip_amg *h, size_t l, const storm_hip_ve
 
 static int amg_cycle(const storm_hip_amg *h, size_t l, const storm_hip_vec *r, storm_hip_vec *z) {
   storm_hip_ctx *c = h->ctx;
+  if ((int)l == h->tail.at) {  // option amg_tail: this level, everything below it and the way back up in one cooperative kernel
+    bool taken = false;
+    STORM_TRY(amg_tail_run(h, l, r, z, &taken));
+    if (taken) return STORM_HIP_OK;  // (refused: this apply goes on with the launches)
+  }
   if (l + 1 == h->levels.size()) {
     hipLaunchKernelGGL(amg_coarse_kernel, dim3((unsigned)((h->n_coarse + 3) / 4)), dim3(kBlock), 0, c->stream, h->d_ainv,
                        h->n_coarse, r->d, z->d, c->api_done);
@@ -728,6 +691,7 @@ int storm_hip_amg_destroy(storm_hip_amg *h) {
   (void)storm_hip_vec_destroy(h->rp);
   (void)hipFree(h->d_mu), (void)hipFree(h->d_mean_part1), (void)hipFree(h->d_mean_part2), (void)hipFree(h->d_mean_cnt);
   amg_refresh_free(h);
+  amg_tail_free(h);
   (void)storm_hip_amg_hierarchy_destroy(h->hier);
   delete h;
   return STORM_HIP_OK;
@@ -750,6 +714,7 @@ int storm_hip_amg_apply(const storm_hip_amg *h, const storm_hip_vec *r, storm_hi
     ~Depth() { --c->callback_depth; }
   } depth(c);
   ++c->n_amg_applies;
+  h->tail.at = amg_tail_choose(h);
   if (!h->nullspace) return amg_cycle(h, 0, r, z);
   // B = Pi V Pi: rp = r - mean(r); z = V(rp), whose closing statement leaves mean(z) in the second slot; z = z - mean(z)
   c->n_amg_projections += 2;
@@ -808,6 +773,7 @@ int storm_hip_amg_coarse_solve(const storm_hip_amg *h, const storm_hip_vec *r, s
                 (long long)h->n_coarse, (long long)r->n_owned, (long long)z->n_owned);
   HIP_TRY(hipSetDevice(h->ctx->device));
   STORM_TRY(lazy_sync(h->ctx));
+  h->tail.at = -1;
   return amg_cycle(h, h->levels.size() - 1, r, z);
 }
 
@@ -832,7 +798,11 @@ int storm_hip_amg_get(const storm_hip_amg *h, const char *key, double *value) {
                   "amg_get: '%s': no Jacobi smoother on that level (%d levels)", key, (int)h->levels.size());
     *value = h->levels[(size_t)level].sigma;
   }
-  else return storm_hip_amg_hierarchy_get(h->hier, key, value);
+  else {
+    bool known = false;  // tail_level, tail_blocks, tail_barriers (amg_tail.hip)
+    STORM_TRY(amg_tail_get(h, key, value, &known));
+    if (!known) return storm_hip_amg_hierarchy_get(h->hier, key, value);
+  }
   return STORM_HIP_OK;
 }
 

@@ -127,6 +127,17 @@ struct storm_hip_amg {
   double *d_mu = nullptr;
   int *d_mean_cnt = nullptr;
   double *d_mean_part1 = nullptr, *d_mean_part2 = nullptr;
+  // The cooperative tail (amg_tail.hip, option amg_tail): the level and phase tables of the kernel that runs the cycle from
+  // `built_level` down and back, on the device; rebuilt when the start level changes, dropped by a refresh (the coefficients
+  // move).  `at`: the level at which the CURRENT apply hands over to the kernel (-1: none), set by storm_hip_amg_apply.
+  struct Tail {
+    int at = -1;
+    int built_level = -1, blocks = 0, barriers = 0, n_phases = 0;
+    char *d_table = nullptr;
+    size_t table_bytes = 0;
+    const char *top_pack32 = nullptr;  // the start level's companion records as built (level 0's may be dropped and built again)
+  };
+  mutable Tail tail;
 };
 
 namespace storm {
@@ -138,4 +149,16 @@ int amg_create_checks(const storm_hip_op *op, double alpha, double beta, const c
 void amg_refresh_free(storm_hip_amg *h);  // amg_refresh.hip
 // d = it (s .* r): cheb_d0_kernel<JACOBI> (precond_cheb.hip), the start of a Jacobi sweep from the zero guess
 int cheb_scaled_start(storm_hip_ctx *c, int64_t n, double inv_theta, const double *r, const double *s, double *d);
+// a level whose residual (and smoother) runs on fp64 records without a CSR tail or a compact format: option amg_fused on
+bool amg_residual_fused(const storm_hip_amg *h, const storm_hip_op *op);
+// amg_tail.hip.  amg_tail_level: the first level with at most amg_tail_rows rows from which every level is eligible (it may be
+// the coarsest, which alone is no tail), -1: none.  amg_tail_choose: the level at which an apply hands over to the kernel
+// under the context's options now (-1: none).  amg_tail_run: levels l .. coarsest .. l in one launch; *taken = false: refused
+// or not launchable, nothing ran, the caller goes on with the launches.
+int amg_tail_level(const storm_hip_amg *h);
+int amg_tail_choose(const storm_hip_amg *h);
+int amg_tail_run(const storm_hip_amg *h, size_t l, const storm_hip_vec *r, storm_hip_vec *z, bool *taken);
+int amg_tail_get(const storm_hip_amg *h, const char *key, double *value, bool *known);
+void amg_tail_invalidate(const storm_hip_amg *h);  // the tables are built again by the next apply
+void amg_tail_free(storm_hip_amg *h);
 }  // namespace storm

@@ -594,6 +594,7 @@ int storm_hip_amg_refresh(storm_hip_amg *h) {
   HIP_TRY(hipSetDevice(c->device));
   STORM_TRY(lazy_sync(c));
   h->invalid = 1;  // until every step is through
+  amg_tail_invalidate(h);  // (the smoothers' coefficients move: the tail kernel's tables are built again)
   STORM_TRY(rf_run(h));
   h->invalid = 0;
   ++c->n_amg_refreshes;

@@ -124,7 +124,7 @@ struct storm_hip_ctx {
   int64_t partials_capacity = 0;
   double *d_partials2 = nullptr;      // [kMaxMulti * kStage2] second-stage partials
   double *d_scalars = nullptr;        // [kMaxMulti] results of host-visible reductions
-  unsigned long long lat_seq = 0;     // running sequence number of the cooperative Gram-Schmidt chains' all-reduces
+  unsigned long long lat_seq = 0;     // running sequence number of the cooperative Gram-Schmidt chains' all-reduces (and the multigrid tail's barriers)
   double *d_gmres = nullptr;          // GMRES' Hessenberg matrix, beta, cs, sn of the fused loop (grown on demand, kept)
   size_t gmres_capacity = 0;
   double *d_ticket_sums = nullptr;    // ... and the groups' sums (a buffer of their own: d_partials2 may hold a first pass a kernel is still reading)
@@ -277,6 +277,12 @@ struct storm_hip_ctx {
   int64_t n_amg_fused_sweeps = 0, n_amg_statement_sweeps = 0;  // amg.hip: which path a Jacobi sweep of the cycle (or storm_hip_amg_smooth) took
   int64_t n_amg_refreshes = 0;  // storm_hip_amg_refresh (amg_refresh.hip)
   int64_t n_amg_projections = 0, n_amg_fused_projections = 0;  // a null-space object's Pi (two per apply); the closing axpy fused with its sum
+  // amg_tail.hip: from the first level with at most amg_tail_rows rows (and every level below it eligible) down to the coarsest
+  // and back, the cycle is ONE cooperative kernel; 0 (the default): every level is launches.  amg_tail_rows defaults to 0 -- no
+  // level: at every level size measured the kernel was slower than the launches (profiles/INDEX_r34.md); a caller names a size
+  int64_t opt_amg_tail = 0, opt_amg_tail_rows = 0;
+  int64_t n_amg_tail_applies = 0, n_amg_tail_refusals = 0;  // tails that ran as one kernel; launches refused (the apply took the launches)
+  int amg_tail_unchecked = 0;  // a tail kernel ran outside a solve: storm_hip_ctx_sync looks at the give-up flag
   int64_t opt_recycle_fused = 1;  // storm_hip_recycle: the fused kernels (blas1.hip recycle_*_kernel); 0: the same recipe out of library launchers
   int64_t n_recycle_guesses = 0, n_recycle_updates = 0, n_recycle_restarts = 0;  // recycle.hip: calls; updates that restarted
   int64_t n_recycle_fused_launches = 0, n_recycle_statement_launches = 0;        // ... what the two paths enqueued

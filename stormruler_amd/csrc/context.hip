@@ -129,6 +129,11 @@ int storm_hip_ctx_sync(storm_hip_ctx *c) {
   STORM_TRY(lazy_sync(c));
   HIP_TRY(hipStreamSynchronize(c->comm_stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->amg_tail_unchecked) {  // a stand-alone storm_hip_amg_apply ran its tail as a cooperative kernel: did a wait give up?
+    c->amg_tail_unchecked = 0, c->coop_ran = 1;  // (a solve in between may have taken its own look and lowered coop_ran)
+    const int st = lat_check_gave_up(c);
+    if (st != STORM_HIP_OK) return st == kStatusCoopGaveUp ? STORM_HIP_E_HIP : st;  // (z of that apply is undefined)
+  }
   return comm_check_error(c);
 }
 
@@ -240,6 +245,11 @@ int storm_hip_ctx_set_option(storm_hip_ctx *c, const char *key, int64_t value) {
   else if (!strcmp(key, "blas1_nt")) c->opt_blas1_nt = value;
   else if (!strcmp(key, "cheb_fused")) c->opt_cheb_fused = value;
   else if (!strcmp(key, "amg_fused")) c->opt_amg_fused = value;
+  else if (!strcmp(key, "amg_tail")) c->opt_amg_tail = value;
+  else if (!strcmp(key, "amg_tail_rows")) {
+    STORM_REQUIRE(value >= 0, "ctx_set_option: amg_tail_rows %lld (>= 0)", (long long)value);
+    c->opt_amg_tail_rows = value;
+  }
   else if (!strcmp(key, "recycle_fused")) c->opt_recycle_fused = value;
   else STORM_FAIL(STORM_HIP_E_INVALID, "ctx_set_option: unknown key '%s'", key);
   return STORM_HIP_OK;
@@ -264,6 +274,8 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "amg_fused_sweeps")) *value = c->n_amg_fused_sweeps;
   else if (!strcmp(key, "amg_statement_sweeps")) *value = c->n_amg_statement_sweeps;
   else if (!strcmp(key, "amg_refreshes")) *value = c->n_amg_refreshes;
+  else if (!strcmp(key, "amg_tail_applies")) *value = c->n_amg_tail_applies;
+  else if (!strcmp(key, "amg_tail_refusals")) *value = c->n_amg_tail_refusals;
   else if (!strcmp(key, "recycle_guesses")) *value = c->n_recycle_guesses;
   else if (!strcmp(key, "recycle_updates")) *value = c->n_recycle_updates;
   else if (!strcmp(key, "recycle_restarts")) *value = c->n_recycle_restarts;

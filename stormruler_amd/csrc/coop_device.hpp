@@ -1,5 +1,6 @@
 // Device helpers shared by the persistent, grid-synchronising kernels (latency.hip: one kernel per solve for small
-// operators; mgs_chain.hip: the Gram-Schmidt chain; resident.hip: block-resident lattice solves): coherent accesses, the
+// operators; mgs_chain.hip: the Gram-Schmidt chain; resident.hip: block-resident lattice solves; amg_tail.hip: the coarse
+// levels of the multigrid cycle): coherent accesses, the
 // bounded wait, the tagged all-reduce slots in their three layouts, the wave sum.
 #pragma once
 

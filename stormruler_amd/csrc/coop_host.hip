@@ -1,5 +1,6 @@
 // The host side of every cooperative path -- kernels whose blocks are all resident and synchronise through memory: the
-// latency solvers (latency.hip), the Gram-Schmidt chains (mgs_chain.hip), the resident lattice solves (resident.hip):
+// latency solvers (latency.hip), the Gram-Schmidt chains (mgs_chain.hip), the resident lattice solves (resident.hip), the
+// multigrid cycle's tail (amg_tail.hip):
 // the occupancy question, the launch that may be refused, the look at the give-up flag of the bounded waits
 // (coop_device.hpp co_bounded_wait) and the re-run of a solve whose kernel gave up.
 #include <algorithm>
@@ -82,7 +83,7 @@ int coop_solve_with_fallback(storm_hip_ctx *c, storm_hip_vec *x, int (*run)(void
   const int64_t n_total = x->n_owned + x->n_halo;
   storm_hip_vec *x0 = nullptr;  // the start vector, kept for the re-run (pooled storage: no allocation, no stream wait per solve)
   const bool keep = c->comm == nullptr && c->coop_disabled == 0 &&
-                    (c->opt_latency_path != 0 || c->opt_coop_mgs != 0 || c->opt_resident_path != 0) &&
+                    (c->opt_latency_path != 0 || c->opt_coop_mgs != 0 || c->opt_resident_path != 0 || c->opt_amg_tail != 0) &&
                     n_total > 0 && n_total <= ((int64_t)1 << 23);  // (no cooperative kernel takes more rows than that)
   if (keep) {
     STORM_TRY(vec_create_work_batch(x, 1, &x0));

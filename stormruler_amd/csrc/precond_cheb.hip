@@ -18,8 +18,7 @@
 #include <cstring>
 #include <utility>
 
-#include "sell_device.hpp"
-#include "blas1_device.hpp"
+#include "amg_device.hpp"
 
 namespace storm {
 
@@ -59,19 +58,16 @@ __global__ __launch_bounds__(kBlock) void cheb_d0_kernel(int64_t n, double inv_t
       for (int u = 0; u < kUnroll; ++u) {
         const int64_t i = base + u * kBlock;
         if (i < n2) {
-          double2v t = vr[u];
-          if (JACOBI) t.x = vs[u].x * t.x, t.y = vs[u].y * t.y;
           double2v o;
-          o.x = inv_theta * t.x, o.y = inv_theta * t.y;
+          o.x = cheb_d0_value<JACOBI>(inv_theta, vr[u].x, JACOBI ? vs[u].x : 1.0);
+          o.y = cheb_d0_value<JACOBI>(inv_theta, vr[u].y, JACOBI ? vs[u].y : 1.0);
           st2(d2 + i, o, nt_);
         }
       }
     }
   });
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-    double t = r[n - 1];
-    if (JACOBI) t = s[n - 1] * t;
-    d[n - 1] = inv_theta * t;
+    d[n - 1] = cheb_d0_value<JACOBI>(inv_theta, r[n - 1], JACOBI ? s[n - 1] : 1.0);
   }
 }
 
@@ -98,33 +94,15 @@ __global__ __launch_bounds__(kBlock) void cheb_step_kernel(SellArgs A, double al
   double si = 1.0, zi = 0.0;
   if (JACOBI) si = valid ? ld_d<NT>(C.s + row) : 0.0;
   if (!FIRST) zi = valid ? ld_d<NT>(C.z + row) : 0.0;
-  int64_t base;
-  int width;
-  if (A.uniform_width > 0) {
-    width = A.uniform_width;
-    base = slice * (int64_t)(R::kExt + R::kSlot * width);
-  } else {
-    base = A.slice_off[slice];
-    width = (int)((A.slice_off[slice + 1] - base - R::kExt) / R::kSlot);
-  }
-  const char *rec = A.pack + base;
-  const double ext = R::template ext<NT>(rec, lane);
-  const double xi1[1] = {xi};
-  double acc1[1];
-  row_sum_any<NT, 1, R>(rec, width, lane, dv, xi1, acc1);
-  const double t = sell_row_result(false, 0.0, beta, xi, alpha, acc1[0], ext);
-  const double rn = ri - t;
-  double w = rn;
-  if (JACOBI) w = si * rn;
-  const double dn = axpbz_value(C.c1, xi, C.c2, w);
-  const double zn = FIRST ? xi + dn : dn + zi;
+  const double t = sell_row_apply<NT, R>(A, slice, lane, dv, xi, alpha, beta);
+  const ChebRow o = cheb_step_row<JACOBI, FIRST>(t, ri, si, xi, zi, C.c1, C.c2);
   if (valid && !done_flag) {
     if (!LAST) {
-      if (NT) __builtin_nontemporal_store(rn, C.res_out + row), __builtin_nontemporal_store(dn, C.d_out + row);
-      else C.res_out[row] = rn, C.d_out[row] = dn;
+      if (NT) __builtin_nontemporal_store(o.rn, C.res_out + row), __builtin_nontemporal_store(o.dn, C.d_out + row);
+      else C.res_out[row] = o.rn, C.d_out[row] = o.dn;
     }
-    if (NT) __builtin_nontemporal_store(zn, C.z + row);
-    else C.z[row] = zn;
+    if (NT) __builtin_nontemporal_store(o.zn, C.z + row);
+    else C.z[row] = o.zn;
   }
 }
 
