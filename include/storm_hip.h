@@ -372,6 +372,17 @@ int storm_hip_op_create_csr(storm_hip_ctx *ctx, int64_t n_rows, int64_t n_halo,
  * Paths (which loop a solve takes; every path gives the reference's iteration to rounding):
  *   latency_path (1), latency_cache (1): CG / BiCGStab of a small halo-free operator as ONE cooperative kernel per solve
  *              (0: neither this nor the resident path; 2: this path only); operator records held in registers where they fit;
+ *   latency_pre (0): 1 = storm_hip_krylov_solve with method CG and a preconditioner takes that path too (csrc/latency.hip,
+ *              pcg_latency_kernel: z = P r, p = z + beta p, gamma = <r, z>, the error norm_2(r); two synchronisation points per
+ *              iteration with a diagonal, degree + 2 with a Chebyshev polynomial) when ALL of these hold: the operator is the
+ *              unpreconditioned path's (a native single-stage operator with a compact copy -- latency_rows, no halo, no CSR
+ *              tail --, no communicator, latency_path != 0) and not one the resident path takes; generic_solvers == 0; the
+ *              preconditioner is a diagonal (storm_hip_krylov_set_preconditioner_diag) or a storm_hip_cheb that is not reduced
+ *              and was created on the solve's own operator with the solve's alpha and beta.  Any side (CG has none).  Everything
+ *              else -- a Chebyshev object on another operator, a callback or multigrid preconditioner, a two-stage operator,
+ *              BiCGStab, more than two slices of rows per wavefront -- runs the engine as before; a refused launch or a kernel
+ *              that gave up re-runs on the engine (path_fallback 1 / 2).  iterations, converged, the errors, history,
+ *              num_applies and *pre_applies are what the engine reports for the same solve;
  *   resident_path (1), resident_max_rows (2^22), resident_planes (0 = automatic), resident_early (1): CG / BiCGStab of a
  *              halo-free LATTICE operator as one persistent kernel in which every block owns a box of the lattice
  *              (csrc/resident.hip); surfaces travelling under the all-reduces;
@@ -442,7 +453,8 @@ int storm_hip_ctx_set_option(storm_hip_ctx *ctx, const char *key, int64_t value)
 
 /* Which path the solves of this context took so far (no reference counterpart: a diagnostic of this library; the
  * reference logs one line per solve, Solver.hpp:144-145).  Keys: "resident_solves" (csrc/resident.hip),
- * "latency_solves" (csrc/latency.hip: one cooperative kernel per solve), "throughput_solves" (a kernel per statement,
+ * "latency_solves" (csrc/latency.hip: one cooperative kernel per solve), "latency_pre_solves" (those of them that were CG with
+ * a preconditioner, option latency_pre: such a solve moves both and neither "engine_solves" nor the cheb_*_applies), "throughput_solves" (a kernel per statement,
  * fused loops of csrc/solver_cg.hip, solver_bicgstab.hip, solver_gmres.hip), "engine_solves" (csrc/krylov_abi.hip), "jfnk_inner_solves" (inner BiCGStab solves of
  * STORM_HIP_JFNK), "fd_fused_dots" (products of a finite-difference operator whose difference statement took the method's
  * reductions of z along in its pass), "host_reductions" (calls of storm_hip_dot / _norm2 / _multi_dot / _multi_dot_end / _block_dot: the reduction

@@ -72,10 +72,16 @@ class Context:
         return {"name": name.value.decode(), "num_cus": cus.value, "total_mem": mem.value}
 
     def set_option(self, key: str, value: int):
+        """``storm_hip_ctx_set_option``: format, path and test knobs of this context (the list: storm_hip.h).  Among the
+        paths: ``latency_path`` (1; 2 = the one-kernel path but not the resident one, 0 = neither) and ``latency_pre``
+        (0; 1 = CG with a :class:`JacobiPreconditioner`, or with a :class:`ChebyshevPreconditioner` built on the solve's own
+        operator and not on reduced records, runs as one cooperative kernel per solve on operators the unpreconditioned
+        latency path takes; everything else stays on the engine)."""
         check(lib.storm_hip_ctx_set_option(self._h, key.encode(), int(value)))
 
     def counter(self, key: str) -> int:
         """How many solves of this context took a given path ("resident_solves", "latency_solves",
+        "latency_pre_solves" -- the preconditioned ones among them, option latency_pre --,
         "throughput_solves", "engine_solves", "cg_fused_steps", "cg_residual_marches", "cg_residual_plane_marches",
         "cg_pz_consumer_folds", "cg_rr_consumer_folds"), or how many Gram-Schmidt
         steps ran as a chain kernel ("mgs_chain_steps"), as mgs_chain_quad_kernel ("mgs_quad_steps") and as

@@ -206,6 +206,7 @@ struct storm_hip_ctx {
   int coop_fallback = 0;                // what happened in the current solve (storm_hip_solver_result::path_fallback)
   int64_t coop_skip = 0, coop_backoff = 0;  // solves still to run without cooperative kernels after one gave up; the length of the last back-off
   int64_t opt_latency_path = 1;         // small operators: CG as one cooperative persistent kernel (latency.hip)
+  int64_t opt_latency_pre = 0;          // ... CG with a diagonal or a Chebyshev preconditioner too (pcg_latency_kernel; 0: the engine's loop)
   // resident.hip: lattice operators as one persistent kernel per solve, every block owning a box of the lattice
   int64_t opt_resident_path = 1;
   int64_t opt_resident_max_rows = (int64_t)1 << 22;
@@ -263,6 +264,7 @@ struct storm_hip_ctx {
   const int *api_done = nullptr;
   // diagnostics: which path the solves took (storm_hip_ctx_get_counter)
   int64_t n_resident_solves = 0, n_latency_solves = 0, n_throughput_solves = 0, n_engine_solves = 0, n_cg_fused_steps = 0;
+  int64_t n_latency_pre_solves = 0;  // ... of n_latency_solves, the preconditioned ones (option latency_pre)
   int64_t n_host_reductions = 0;    // reduction entry points that made the host wait for their sums (storm_hip_dot ...)
   int64_t n_jfnk_inner_solves = 0;  // krylov_abi.hip: inner solves of STORM_HIP_JFNK
   int64_t n_fd_fused_dots = 0;      // krylov_engine.hip: finite-difference products whose difference statement took the reductions of z along
@@ -624,6 +626,11 @@ int bicgstab_latency_solve(const storm_hip_op *op, double alpha, double beta, co
 int cg2_latency_solve(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const double *b,
                       double *x, double *const work[3], SolverState *d_state, bool *taken);
 
+// CG with z = scale .* r (cheb == nullptr) or with a Chebyshev object on `op` itself; work: p, u, d0, d1 (zero-filled, the last
+// two with cheb only)
+int pcg_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x, const double *scale,
+                      const storm_hip_cheb *cheb, double *const work[4], SolverState *d_state, bool *taken);
+
 // mgs_chain.hip
 // What the cooperative chain needs to finish an Arnoldi step itself (fused GMRES loop): the state, the Hessenberg and
 // rotation arrays, and where sqrt(<w,w>) goes.
@@ -650,6 +657,12 @@ int gmres_orthogonalize(storm_hip_ctx *c, int64_t n, const SolverState *st, cons
 int cg2_latency_try(const storm_hip_op *op, double alpha1, double beta1, double alpha2, double beta2, const storm_hip_vec *b,
                     storm_hip_vec *x, const storm_hip_solver_params *params, storm_hip_solver_result *result, double *history,
                     bool *taken);
+
+// ... and CG with a diagonal (`diag`) or a Chebyshev (`cheb`) preconditioner (pcg_latency_kernel); the eligibility rule is the
+// caller's (krylov_abi.hip).  *pre_applies: one per iteration and one for the init, as the engine counts them.
+int pcg_latency_try(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *diag, const storm_hip_cheb *cheb,
+                    const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_solver_params *params, storm_hip_solver_result *result,
+                    double *history, int64_t *pre_applies, bool *taken);
 
 // resident.hip
 bool res_eligible(const storm_hip_op *op, bool bicgstab);

@@ -162,6 +162,7 @@ int storm_hip_ctx_set_option(storm_hip_ctx *c, const char *key, int64_t value) {
     c->opt_comm_wait_seconds = value;
   }
   else if (!strcmp(key, "latency_path")) c->opt_latency_path = value;
+  else if (!strcmp(key, "latency_pre")) c->opt_latency_pre = value;
   else if (!strcmp(key, "resident_path")) c->opt_resident_path = value;
   else if (!strcmp(key, "resident_max_rows")) c->opt_resident_max_rows = value;
   else if (!strcmp(key, "resident_planes")) c->opt_resident_planes = value;
@@ -259,6 +260,7 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   STORM_REQUIRE(c && key && value, "ctx_get_counter: null argument");
   if (!strcmp(key, "resident_solves")) *value = c->n_resident_solves;
   else if (!strcmp(key, "latency_solves")) *value = c->n_latency_solves;
+  else if (!strcmp(key, "latency_pre_solves")) *value = c->n_latency_pre_solves;
   else if (!strcmp(key, "throughput_solves")) *value = c->n_throughput_solves;
   else if (!strcmp(key, "engine_solves")) *value = c->n_engine_solves;
   else if (!strcmp(key, "block_solves")) *value = c->n_block_solves;

@@ -230,6 +230,36 @@ int solve_cg2_on(storm_hip_krylov *k, const storm_hip_vec *b, storm_hip_vec *x, 
   return st;
 }
 
+// CG with a preconditioner the one-kernel path holds (latency.hip, pcg_latency_kernel; option latency_pre): a diagonal, or a
+// Chebyshev object on the solve's own operator with its alpha and beta, reading the fp64 records.  CG has no preconditioner
+// side.  (An operator the resident path takes without a preconditioner stays on the engine with one.)
+bool pcg_latency_wanted(const K *k) {
+  const storm_hip_ctx *c = k->c;
+  if (c->opt_latency_pre == 0 || c->opt_generic_solvers != 0 || k->method != STORM_HIP_CG || !k->op.is(Operator::NATIVE)) return false;
+  const storm_hip_op *op = k->op.stencil;
+  if (!cg_latency_eligible(op) || res_eligible(op, false)) return false;
+  if (k->pre_diag != nullptr) return true;
+  const storm_hip_cheb *h = k->pre_cheb;
+  return h != nullptr && h->reduced == 0 && h->op == op && h->alpha == k->op.alpha && h->beta == k->op.beta;
+}
+// One attempt: the kernel where a register variant holds the rows, else -- and after a refused launch -- the engine's loop.
+int solve_pcg_on(storm_hip_krylov *k, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_solver_params *params,
+                 storm_hip_solver_result *result, double *history, int64_t *pre_applies) {
+  storm_hip_ctx *c = k->c;
+  int st = solve_with_fallback(c, x, result, [&]() -> int {
+    const Operator &op = k->op;
+    bool taken = false;
+    STORM_TRY(pcg_latency_try(op.stencil, op.alpha, op.beta, k->pre_diag, k->pre_cheb, b, x, params, result, history, pre_applies,
+                              &taken));
+    if (taken) return STORM_HIP_OK;
+    // (no register variant holds the rows, the launch was refused, or the kernel gave up -- noted in result->path_fallback)
+    ++c->n_engine_solves;
+    return krylov_solve_engine(k, b, x, params, result, history, pre_applies);
+  });
+  if (st == STORM_HIP_OK) st = comm_check_error(c);
+  return st;
+}
+
 // A(s) for the inner engine of a JFNK object: the outer object's operator, whatever its kind, as library launches
 // (predicated on the inner solve's flag like any callback's).
 int jfnk_outer_apply(void *user, storm_hip_vec *y, const storm_hip_vec *x) {
@@ -440,6 +470,7 @@ int storm_hip_krylov_solve(storm_hip_krylov *k, const storm_hip_vec *b, storm_hi
     return solve_cg2_on(k, b, x, params, result, history);
   }
   if (fused_for(k, params) != nullptr) return krylov_solve_engine(k, b, x, params, result, history, pre_applies);
+  if (pcg_latency_wanted(k)) return solve_pcg_on(k, b, x, params, result, history, pre_applies);
   ++c->n_engine_solves;
   return solve_with_fallback(c, x, result, [&] { return krylov_solve_engine(k, b, x, params, result, history, pre_applies); });
 }

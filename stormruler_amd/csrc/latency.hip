@@ -24,7 +24,9 @@
 //     SpMV values are bit-identical; dot products group their terms differently (rounding-level differences).
 //
 // Taken by storm_hip_solve_cg / storm_hip_solve_bicgstab / storm_hip_solve_cg2 (the two-stage operator: cg2_latency_kernel) when the operator has a latency copy (n_rows <= option `latency_rows`, no halo, no
-// CSR tail), the context has no communicator, and option `latency_path` != 0.
+// CSR tail), the context has no communicator, and option `latency_path` != 0.  With option `latency_pre` != 0,
+// storm_hip_krylov_solve takes it for CG with a diagonal or a Chebyshev preconditioner too (pcg_latency_kernel, below; the
+// rule: krylov_abi.hip pcg_latency_wanted).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -34,6 +36,7 @@
 #include "coop_device.hpp"
 #include "spmv_device.hpp"
 #include "solver_device.hpp"
+#include "amg_device.hpp"
 
 namespace storm {
 
@@ -526,16 +529,195 @@ __global__ __launch_bounds__(kLatBlock) void bicgstab_latency_kernel(LatArgs a) 
   lat_finish(a.st, g);
 }
 
+// ---- preconditioned CG on the latency path ------------------------------------------------------------------------
+// SolverCg.hpp:54-126 with pre_op != nullptr inside Solver.hpp:116-147: z = P r, p = z + beta p, gamma = <r, z>, the
+// reported error is norm_2(r).  cg_latency_kernel with the preconditioned residual u = P r in r's place: the rows of u
+// and of the CURRENT p are published, a gathering wave forms the neighbour's next direction as u[c] + beta p_prev[c]
+// (LatDirection pointed at u: the owner's expression, the same bits).  Three kinds of P, both of the library:
+//   DIAG         u_i = d_i r_i (storm_hip_krylov_set_preconditioner_diag; d_i in a register).  Row-local: TWO
+//                synchronisation points per iteration -- <p, A p>, then one lat_allreduce2 of (<r, u>, <r, r>).
+//   CHEB         u = p_m(A) r, and
+//   CHEB_JACOBI  u = p_m(diag(s) A) diag(s) r: a storm_hip_cheb object on the solve's own operator, degree m (a run-time
+//                loop, coefficients in the argument struct).  Every row goes through cheb_d0_value / cheb_step_row
+//                (amg_device.hpp) and lat_row / lat_row_cached: nothing that rounds is restated, u has the bits of
+//                storm_hip_cheb_apply.  The recurrence has no reduction, only neighbour rows of its direction d_k between
+//                the products: m + 2 points per iteration --
+//                  A. <p, A p>;
+//                  B. behind the published rows of d_0 (and of p); it carries <r, r>: every block has the verdict BEFORE
+//                     the polynomial, and a solve that ends here does not run it (the count of preconditioner applies the
+//                     host reports is the engine's, which does);
+//                  C_1 .. C_{m-1}. behind the published d_k, between the products; no sum (cg2_latency_kernel's form);
+//                  D. behind the published u; it carries <r, u>.
+// The init has the same shape without A (r = b - A x from the caller's x in its place).
+//   Overwrite safety: a buffer is rewritten only behind a point that every block enters after its last gather from it.
+//     p, u   gathered (as the direction u + beta p_prev) by the product in front of A only.  p is rewritten behind A, u behind
+//            the last product of the polynomial (DIAG: behind A), which is behind A too.
+//     d[0]   d_0 is written behind A of iteration k.  Its last readers are the even products of iteration k - 1's polynomial,
+//            each in front of a point C or D of that iteration, all of which every block has entered before it enters A.
+//            d_2, d_4, ... are written by product j - 1 (j even) behind C_{j-1}; the last readers of the previous content
+//            d_{j-2} are product j - 2, in front of C_{j-1}.
+//     d[1]   d_1 is written by product 0, behind B; the last readers of d[1] belong to the previous polynomial (in front of
+//            its D, hence of this A and B).  d_3, d_5, ...: as for d[0], product j - 1 (j odd) writes behind C_{j-1}, the
+//            readers of d_{j-2} finished in front of it.
+// Registers: x, r, p, u (+ d) and, CHEB*, the polynomial's residual and direction (+ s); z = A p lives from A to the
+// residual update only.  Instantiated where that fits 128 VGPRs without scratch (NOTES.md has the table).
+enum LatPre { LAT_PRE_DIAG = 0, LAT_PRE_CHEB = 1, LAT_PRE_CHEB_JACOBI = 2 };
+struct LatPcgArgs {
+  LatArgs a;          // (a.r, a.v0, a.v1, a.t stay null)
+  const double *s;    // DIAG: the diagonal d; CHEB_JACOBI: the scale s
+  double *u;          // published rows of u = P r
+  double *d0, *d1;    // CHEB*: published rows of the polynomial's direction, even / odd products
+  int degree;
+  double inv_theta;
+  double c1[kChebMaxDegree], c2[kChebMaxDegree];
+};
+
+template <int S, int W, int PRE>
+__global__ __launch_bounds__(kLatBlock) void pcg_latency_kernel(LatPcgArgs A) {
+  constexpr bool CHEB = PRE != LAT_PRE_DIAG, JACOBI = PRE == LAT_PRE_CHEB_JACOBI, SCALED = PRE != LAT_PRE_CHEB;
+  __shared__ double lds[2 * kLatWaves];
+  const LatArgs &a = A.a;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave_id = (int64_t)blockIdx.x * kLatWaves + (threadIdx.x >> 6);
+  const int64_t n_waves = (int64_t)gridDim.x * kLatWaves;
+  unsigned long long seq = 0, seen = 0;  // seen: what the publishing exchanges returned (consumed at the all-reduces)
+  double x[S], r[S], p[S], u[S], sc[SCALED ? S : 1], res[CHEB ? S : 1], dk[CHEB ? S : 1];
+  LatRecords<S, W> rec;
+  lat_load_records<S, W>(a, wave_id, n_waves, lane, rec);
+  auto apply_row = [&](int q, int64_t s, const auto &get, double vi) -> double {
+    if constexpr (W > 0) return lat_row_cached<S, W>(a, rec, q, get, vi);
+    else return lat_row(a, s, lane, get, vi);
+  };
+#pragma unroll
+  for (int q = 0; q < S; ++q) {
+    const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+    const bool valid = s < a.n_slices && row < a.n_rows;
+    x[q] = valid ? a.x[row] : 0.0;
+    r[q] = p[q] = u[q] = 0.0;
+    if (SCALED) sc[q] = valid ? A.s[row] : 0.0;
+    if (CHEB) res[q] = dk[q] = 0.0;
+  }
+
+  // One trip = the residual of the step (the first: r = b - A x, SolverCg.hpp:54-84; then :86-126), u = P r, the rule.
+  // (a.p arrives zero-filled -- a fresh work vector -- and the registers' p is 0: the first direction u + 0 * p is u)
+  LatProgress g{};
+  double gamma = 0.0, beta = 0.0;
+  for (bool first = true;; first = false) {
+    double acc_rr = 0.0, acc_ru = 0.0;
+    if (first) {
+#pragma unroll
+      for (int q = 0; q < S; ++q) {
+        const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+        if (s < a.n_slices) {
+          const double ax = apply_row(q, s, LatPlain{a.x}, x[q]);  // x is not written before the kernel's end
+          r[q] = (row < a.n_rows) ? a.b[row] - ax : 0.0;
+        }
+      }
+    } else {
+      // entering: registers hold x, r and the direction p of the own rows; memory holds u and the PREVIOUS direction,
+      // from which a neighbour's current direction is u[c] + beta p_prev[c]
+      double z[S], acc = 0.0;
+      const LatDirection dir{A.u, a.p, beta};
+#pragma unroll
+      for (int q = 0; q < S; ++q) {
+        const int64_t s = wave_id + q * n_waves;
+        z[q] = 0.0;
+        if (s < a.n_slices) {
+          z[q] = apply_row(q, s, dir, p[q]);
+          z[q] = (s * kWave + lane < a.n_rows) ? z[q] : 0.0;
+          acc += p[q] * z[q];
+        }
+      }
+      // A: every gather of u and p is done once all blocks have published their <p, z> partial
+      const double alpha = safe_divide(gamma, lat_allreduce(acc, a.slots, ++seq, lds, false));
+#pragma unroll
+      for (int q = 0; q < S; ++q) {
+        const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+        x[q] += alpha * p[q];
+        r[q] -= alpha * z[q];
+        if (s < a.n_slices && row < a.n_rows) co_publish(a.p + row, p[q], a.publish_xchg, seen);
+      }
+    }
+    // the new residual's first part of u = P r, and <r, r>
+#pragma unroll
+    for (int q = 0; q < S; ++q) {
+      const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+      const bool valid = s < a.n_slices && row < a.n_rows;
+      acc_rr += r[q] * r[q];
+      if constexpr (CHEB) {
+        res[q] = r[q];
+        dk[q] = cheb_d0_value<JACOBI>(A.inv_theta, r[q], JACOBI ? sc[q] : 1.0);
+        if (valid) co_publish(A.d0 + row, dk[q], a.publish_xchg, seen);
+      } else {
+        u[q] = sc[q] * r[q];
+        acc_ru += r[q] * u[q];
+        if (valid) co_publish(A.u + row, u[q], a.publish_xchg, seen);
+      }
+    }
+    if constexpr (CHEB) acc_rr = lat_allreduce(acc_rr, a.slots, ++seq, lds, true, seen);  // B
+    else lat_allreduce2(acc_ru, acc_rr, a.slots, ++seq, lds, true, seen);
+    // the rule                                                                    Solver.hpp:124-128, :130-147
+    if (first) {
+      g = lat_progress_begin(a.st, acc_rr);
+    } else {
+      g.abs_err = sqrt(acc_rr);
+      g.rel_err = g.abs_err / g.initial_error;
+      g.converged = (g.abs_tol > 0.0 && g.abs_err < g.abs_tol) || (g.rel_tol > 0.0 && g.rel_err < g.rel_tol);
+      ++g.it;
+      if (blockIdx.x == 0 && threadIdx.x == 0 && g.history) g.history[g.it] = g.abs_err;
+    }
+    if (g.converged || g.it >= g.num_iterations) break;  // (uniform: every block holds the same sums)
+    if constexpr (CHEB) {
+      // u = d_0 + d_1 + ... + d_m;  t = A d_k;  res' = res - t;  d' = c1 d + c2 (s .* res')
+      for (int k = 0; k < A.degree; ++k) {
+        const LatPublished of_d{(k & 1) ? A.d1 : A.d0};
+        double *d_next = (k & 1) ? A.d0 : A.d1;
+        const double c1 = A.c1[k], c2 = A.c2[k];
+        const bool last = k + 1 == A.degree;
+#pragma unroll
+        for (int q = 0; q < S; ++q) {
+          const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+          if (s < a.n_slices) {
+            double t = apply_row(q, s, of_d, dk[q]);
+            t = (row < a.n_rows) ? t : 0.0;
+            const double si = JACOBI ? sc[q] : 1.0;
+            const ChebRow o = k == 0 ? cheb_step_row<JACOBI, true>(t, res[q], si, dk[q], u[q], c1, c2)
+                                     : cheb_step_row<JACOBI, false>(t, res[q], si, dk[q], u[q], c1, c2);
+            res[q] = o.rn, dk[q] = o.dn, u[q] = o.zn;
+            if (row < a.n_rows) co_publish((last ? A.u : d_next) + row, last ? u[q] : dk[q], a.publish_xchg, seen);
+            if (last) acc_ru += r[q] * u[q];
+          }
+        }
+        if (!last) (void)lat_allreduce(0.0, a.slots, ++seq, lds, true, seen);  // C: d_{k+1} is out
+      }
+      acc_ru = lat_allreduce(acc_ru, a.slots, ++seq, lds, true, seen);  // D
+    }
+    const double gamma_bar = gamma;
+    gamma = acc_ru;
+    beta = first ? 0.0 : safe_divide(gamma, gamma_bar);
+#pragma unroll
+    for (int q = 0; q < S; ++q) p[q] = u[q] + beta * p[q];
+  }
+#pragma unroll
+  for (int q = 0; q < S; ++q) {
+    const int64_t s = wave_id + q * n_waves, row = s * kWave + lane;
+    if (s < a.n_slices && row < a.n_rows) a.x[row] = x[q];
+  }
+  lat_finish(a.st, g);
+}
+
 bool cg_latency_eligible(const storm_hip_op *op) {
   const storm_hip_ctx *c = op->ctx;
   return c->opt_latency_path != 0 && c->coop_disabled == 0 && c->comm == nullptr && op->d_lat_pack != nullptr &&
          c->opt_profile_spmv == 0;
 }
 
-// The whole solve; fills the SolverState on the device (the caller reads it back).  `family`: which of the three
-// kernels; work vectors p, r (CG), p, r, v0, v1 (BiCGStab) and p, r, t (two-stage CG) arrive zero-filled.
-enum LatFamily { LAT_CG, LAT_BICGSTAB, LAT_CG2 };
-static int latency_solve(LatFamily family, const storm_hip_op *op, LatArgs a, bool *taken) {
+// The whole solve; fills the SolverState on the device (the caller reads it back).  `family`: which of the four
+// kernels; work vectors p, r (CG), p, r, v0, v1 (BiCGStab), p, r, t (two-stage CG) and p, u, d0, d1 (preconditioned CG)
+// arrive zero-filled.  LAT_PCG: `pcg` is the kernel's argument (its LatArgs are filled from `a` here), `pre` its LatPre.
+enum LatFamily { LAT_CG, LAT_BICGSTAB, LAT_CG2, LAT_PCG };
+static int latency_solve(LatFamily family, const storm_hip_op *op, LatArgs a, bool *taken, LatPcgArgs *pcg = nullptr,
+                         int pre = LAT_PRE_DIAG) {
   storm_hip_ctx *c = op->ctx;
   *taken = false;
   const int64_t n_slices = (op->n_rows + kWave - 1) / kWave;
@@ -556,12 +738,23 @@ static int latency_solve(LatFamily family, const storm_hip_op *op, LatArgs a, bo
       pick((const void *)cg2_latency_kernel<1, 0>, (const void *)cg2_latency_kernel<1, 4>, (const void *)cg2_latency_kernel<1, 8>),
       pick((const void *)cg2_latency_kernel<2, 0>, (const void *)cg2_latency_kernel<2, 4>, (const void *)cg2_latency_kernel<2, 8>),
       (const void *)cg2_latency_kernel<4, 0>, (const void *)cg2_latency_kernel<8, 0>};
-  const void *const *variants = family == LAT_BICGSTAB ? bi : family == LAT_CG2 ? cg2 : cg;
+  // (preconditioned CG: only the instances that need no scratch at 128 VGPRs exist, NOTES.md -- where the cached form of a
+  //  width is not among them the re-reading one stands in; none holds more than two slices per wavefront)
+#define STORM_PCG_KERNEL(S_, W_, PRE_) (const void *)pcg_latency_kernel<S_, W_, PRE_>
+#define STORM_PCG_VARIANTS(PRE_, W8_)                                                                     \
+  {pick(STORM_PCG_KERNEL(1, 0, PRE_), STORM_PCG_KERNEL(1, 4, PRE_), STORM_PCG_KERNEL(1, W8_, PRE_)), \
+   STORM_PCG_KERNEL(2, 0, PRE_), (const void *)nullptr, (const void *)nullptr}
+  // (eight slots of records beside the polynomial's vectors: 92 bytes of scratch, with four neighbours in flight too)
+  const void *pcg_v[3][4] = {STORM_PCG_VARIANTS(LAT_PRE_DIAG, 8), STORM_PCG_VARIANTS(LAT_PRE_CHEB, 0),
+                             STORM_PCG_VARIANTS(LAT_PRE_CHEB_JACOBI, 0)};
+#undef STORM_PCG_KERNEL
+#undef STORM_PCG_VARIANTS
+  const void *const *variants = family == LAT_BICGSTAB ? bi : family == LAT_CG2 ? cg2 : family == LAT_PCG ? pcg_v[pre] : cg;
   const int capacity[4] = {1, 2, 4, 8};
   const void *fn = nullptr;
   int64_t blocks = 0;
   for (int v = 0; v < 4 && fn == nullptr; ++v) {
-    if (occupancy_cached(c, variants[v], kLatBlock, 0) < 1) continue;
+    if (variants[v] == nullptr || occupancy_cached(c, variants[v], kLatBlock, 0) < 1) continue;
     blocks = std::max<int64_t>(1, std::min<int64_t>(std::min(c->num_cus, 256), (n_slices + kLatWaves - 1) / kLatWaves));
     const int64_t waves = blocks * kLatWaves;
     if ((n_slices + waves - 1) / waves <= capacity[v]) fn = variants[v];
@@ -573,7 +766,8 @@ static int latency_solve(LatFamily family, const storm_hip_op *op, LatArgs a, bo
   HIP_TRY(hipMemsetAsync(c->d_lat_slots, 0, (size_t)2 * 256 * kLatSlotStride + 256, c->stream));  // tags restart at 1; flag down
   a.pack = op->d_lat_pack, a.rec_off = op->d_lat_off, a.n_rows = op->n_rows, a.n_slices = n_slices, a.slots = c->d_lat_slots;
   a.publish_xchg = (int)(c->opt_latency_publish != 0);
-  void *args[] = {&a};
+  if (pcg != nullptr) pcg->a = a;
+  void *args[] = {pcg != nullptr ? (void *)pcg : (void *)&a};
   *taken = coop_launch(c, fn, (unsigned)blocks, args);
   return STORM_HIP_OK;
 }
@@ -598,6 +792,26 @@ int cg2_latency_solve(const storm_hip_op *op, double alpha1, double beta1, doubl
   a.alpha = alpha1, a.beta = beta1, a.alpha2 = alpha2, a.beta2 = beta2, a.b = b, a.x = x;
   a.p = work[0], a.r = work[1], a.t = work[2], a.st = d_state;
   return latency_solve(LAT_CG2, op, a, taken);
+}
+
+// CG with a diagonal (cheb == nullptr: z = scale .* r) or a Chebyshev polynomial preconditioner (cheb: an object on `op` with
+// the solve's alpha and beta, not reduced; its scale, if any, is the kernel's).  work: p, u, d0, d1 (zero-filled; the
+// last two with cheb only).
+int pcg_latency_solve(const storm_hip_op *op, double alpha, double beta, const double *b, double *x, const double *scale,
+                      const storm_hip_cheb *cheb, double *const work[4], SolverState *d_state, bool *taken) {
+  LatArgs a{};
+  a.alpha = alpha, a.beta = beta, a.b = b, a.x = x, a.p = work[0], a.st = d_state;
+  LatPcgArgs g{};
+  g.s = scale, g.u = work[1];
+  int pre = LAT_PRE_DIAG;
+  if (cheb != nullptr) {
+    pre = cheb->dinv != nullptr ? LAT_PRE_CHEB_JACOBI : LAT_PRE_CHEB;
+    g.s = cheb->dinv != nullptr ? cheb->dinv->d : nullptr;
+    g.d0 = work[2], g.d1 = work[3], g.degree = cheb->degree, g.inv_theta = cheb->inv_theta;
+    std::memcpy(g.c1, cheb->c1, sizeof g.c1);
+    std::memcpy(g.c2, cheb->c2, sizeof g.c2);
+  }
+  return latency_solve(LAT_PCG, op, a, taken, &g, pre);
 }
 
 }  // namespace storm

@@ -723,6 +723,33 @@ int cg2_latency_try(const storm_hip_op *op, double alpha1, double beta1, double 
   return st;
 }
 
+// CG with a diagonal or a Chebyshev preconditioner as one cooperative kernel (latency.hip, pcg_latency_kernel), under the same
+// rules.  The counts are the engine's for the same solve: one operator and one preconditioner apply for the init and per iteration.
+int pcg_latency_try(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *diag, const storm_hip_cheb *cheb,
+                    const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_solver_params *params, storm_hip_solver_result *result,
+                    double *history, int64_t *pre_applies, bool *taken) {
+  *taken = false;
+  if (!cg_latency_eligible(op)) return STORM_HIP_OK;
+  storm_hip_ctx *c = op->ctx;
+  const FusedSolveArgs args{op, alpha, beta, b, x, params, result, history, nullptr};
+  Driver d;
+  STORM_TRY(prepare_state(args, &d));
+  VecPool pool;
+  int st = pool.make(x, cheb != nullptr ? 4 : 2);  // p, u, d0, d1; zero-filled: the kernel relies on that for the first direction
+  if (st == STORM_HIP_OK) {
+    double *const work[4] = {pool.v[0]->d, pool.v[1]->d, cheb != nullptr ? pool.v[2]->d : nullptr, cheb != nullptr ? pool.v[3]->d : nullptr};
+    st = pcg_latency_solve(op, alpha, beta, b->d, x->d, diag != nullptr ? diag->d : nullptr, cheb, work, c->d_state, taken);
+  }
+  if (st == STORM_HIP_OK && *taken) {
+    ++c->n_latency_solves, ++c->n_latency_pre_solves;
+    st = collect(d, args, 1);
+    if (st == STORM_HIP_OK && pre_applies) *pre_applies = 1 + result->iterations;
+    return st;
+  }
+  if (d.d_history) (void)hipFree(d.d_history), d.d_history = nullptr;
+  return st;
+}
+
 }  // namespace storm
 
 extern "C" int storm_hip_solve_cg(const storm_hip_op *op, double alpha, double beta, const storm_hip_vec *b, storm_hip_vec *x,
