@@ -1224,6 +1224,77 @@ int storm_hip_recycle_get(const storm_hip_recycle *h, const char *key, double *v
 int storm_hip_recycle_get_slot(const storm_hip_recycle *h, int j, storm_hip_vec *u, storm_hip_vec *v, double *g);
 int storm_hip_recycle_set_slot(storm_hip_recycle *h, int j, const storm_hip_vec *u, const storm_hip_vec *v, double g);
 
+/* ---- Mixed-precision CG: fp32 inner iterations under fp64 refinement (STORM_HIP_HAS_MIXED_CG, added within ABI 6) -----------
+ * CG for A = beta I + alpha M whose inner iterations live on fp32 vectors and on the operator's fp32-weight companion records
+ * (A~, storm_hip_op_build_reduced: 51.9 instead of 79.8 B/row of records, 56 instead of 112 B/row of vectors), inside an fp64
+ * outer loop that holds the answer to the reference's rule (Solver.hpp:116-147) on the TRUE fp64 residual: iterative
+ * refinement.  Strictly opt-in: no other entry point changes its path or its bits.  Single rank.
+ *
+ * THE ALGORITHM (normative; tests/mixed_cg_ref.py restates it in numpy).
+ *   r = b - A x on the fp64 records;  rho_0 = |r|;  the early exit of the rule (abs_tol > 0 and rho_0 < abs_tol)
+ *   target = the norm at which the rule stops: the larger of abs_tol and rel_tol rho_0 over the criteria that are enabled
+ *   outer step k = 1, 2, ...:
+ *     rho = |r|;  s = 1.0 / rho                                          (fp64, on the device)
+ *     r32 = fl32(r_i s);  d32 = 0;  p32 = r32        (keep_direction = 1 and k > 1: p32 = fl32(p32_i (rho_prev / rho)))
+ *     g = <r32, r32>;  eta = max(inner_tolerance, 0.5 target / rho)       (never deeper than the outer rule needs)
+ *     inner iteration j = 1 .. inner_max:
+ *       q32 = fl32(A~ p32);  pq = <p32, q32>;  a = g / pq;   BROKEN when pq <= 0 or pq is not finite (nothing more is stored)
+ *       d32 = fl32(a p + d);  r32 = fl32(-a q + r);  g' = <r32, r32>;  bt = g' / g
+ *       p32 = fl32(r + fl(bt p));  g = g';   leave when sqrt(g') <= eta;  BROKEN when g' is not finite
+ *     x = fma(rho, (double)d32_i, x_i)                                    (fp64; skipped when BROKEN)
+ *     r = b - A x on the fp64 records;  the rule on |r|: converged -> done
+ *     BROKEN (2), or |r| not smaller than rho (1), or k == max_outer or the inner iterations have reached
+ *       params.num_iterations (3): finish with storm_hip_solve_cg from this x with the iterations that are left, held to the
+ *       same residual norm (its relative tolerance rescaled by rho_0 / |r|); the number is storm_hip_mixed_result::finished_fp64.
+ *
+ * THE CONTRACT extends the reduced records' to vectors: an fp32 vector element is widened, exactly, where a kernel loads it;
+ * every operation is the fp64 kernel's in the same order with the same contraction; ONE IEEE round-to-nearest-even conversion
+ * at each fp32 store; sums accumulate in fp64.  So every vector statement of the inner loop gives, BIT FOR BIT, (float) of what
+ * storm_hip_op_apply_reduced, storm_hip_axpy (d, r) and storm_hip_xpay (p) give on the widened operands; a and bt are single
+ * fp64 divisions of the device's own sums (tests/test_gpu_mixed_cg.py).
+ *
+ * Three launches per inner iteration and no host wait in it: the host polls the inner loop's done word check_lag iterations
+ * behind; one host wait per outer step (the true residual's norm).  result->iterations counts the inner iterations plus those
+ * of an fp64 finish; num_applies every operator product, A~ and A alike; history (NULL or room for num_iterations + 1) gets the
+ * TRUE residual norms, one per outer step behind the initial one, then the finishing loop's; absolute_error, relative_error
+ * and converged are those of the last true residual.  Counters: "mixed_solves", "mixed_inner_iterations",
+ * "mixed_outer_steps", "mixed_fp64_finishes".
+ *
+ * STORM_HIP_E_UNSUPPORTED, decided on the host before any launch: an operator that is not on fp64 records; one with a CSR
+ * tail; one without a companion (nothing is built behind the caller's back: call storm_hip_op_build_reduced first), also in a
+ * solve after storm_hip_op_drop_reduced; a halo plan, halo columns or a communicator.  STORM_HIP_E_INVALID: inner_tolerance
+ * not in (0, 1), inner_max < 0, max_outer < 1, keep_direction other than 0 / 1, a null argument, vectors of another context
+ * or size.  storm_hip_op_set_face_weights refreshes the companion: an updatable operator needs nothing new.  The operator
+ * must outlive the object.
+ *
+ * The stepping entry points (tests, benchmarks): _begin forms r, rho and the conversion of the first outer step (one host
+ * wait); _inner enqueues exactly n inner iterations with no exit test (enqueue-only); _end_outer updates x, forms the true
+ * residual and returns its norm (one host wait); _get_vector widens "r32" | "p32" | "q32" | "d32" into an fp64 vector
+ * (enqueue-only); _get_scalar reads "rho" | "g" | "pq" | "alpha" | "beta" (waits for the stream). */
+#define STORM_HIP_HAS_MIXED_CG 1
+typedef struct storm_hip_mixed_params {
+  double inner_tolerance;   /* default 1e-3 */
+  int64_t inner_max;        /* inner iterations per outer step; 0 (default) = params.num_iterations */
+  int32_t max_outer;        /* default 16 */
+  int32_t keep_direction;   /* default 0: the direction restarts at every outer step; 1: kept, rescaled */
+} storm_hip_mixed_params;
+typedef struct storm_hip_mixed_result {
+  int64_t outer_steps, inner_iterations, fp64_iterations;
+  int32_t finished_fp64;    /* 0 no; 1 the true residual did not fall; 2 BROKEN; 3 max_outer or the iteration budget */
+} storm_hip_mixed_result;
+typedef struct storm_hip_mixed_cg storm_hip_mixed_cg;
+void storm_hip_mixed_params_default(storm_hip_mixed_params *p);
+int storm_hip_mixed_cg_create(const storm_hip_op *op, double alpha, double beta, const storm_hip_mixed_params *mixed_params,
+                              storm_hip_mixed_cg **out);
+int storm_hip_mixed_cg_destroy(storm_hip_mixed_cg *m);
+int storm_hip_mixed_cg_solve(storm_hip_mixed_cg *m, const storm_hip_vec *b, storm_hip_vec *x, const storm_hip_solver_params *params,
+                             storm_hip_solver_result *result, double *history, storm_hip_mixed_result *mixed_result);
+int storm_hip_mixed_cg_begin(storm_hip_mixed_cg *m, const storm_hip_vec *b, const storm_hip_vec *x);
+int storm_hip_mixed_cg_inner(storm_hip_mixed_cg *m, int64_t n_iterations);
+int storm_hip_mixed_cg_end_outer(storm_hip_mixed_cg *m, storm_hip_vec *x, double *rho);
+int storm_hip_mixed_cg_get_vector(storm_hip_mixed_cg *m, const char *name, storm_hip_vec *out);
+int storm_hip_mixed_cg_get_scalar(storm_hip_mixed_cg *m, const char *name, double *value);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -1504,6 +1504,51 @@ protected:
 /// SolverCg.hpp:47-128.
 template<class Vector>
 class CgSolver final : public detail::DeviceIterativeSolver<Vector, STORM_HIP_CG> {};
+/// CG whose inner iterations run on fp32 vectors and the matrix's fp32-weight companion records under an fp64 refinement
+/// loop held to the reference's rule on the TRUE residual (storm_hip_mixed_cg_*; algorithm and contract:
+/// include/storm_hip.h).  Opt-in, a knob holder like the solvers above: the reference's knobs and the mixed ones, the
+/// results of the last solve.  Takes a HipStencilOperator on fp64 records (option spmv_dict = 0) without a CSR tail whose
+/// matrix has a companion (HipStencilOperator::build_reduced); anything else throws.
+class MixedCgSolver final {
+public:
+  std::size_t num_iterations{2000};
+  real_t absolute_error_tolerance{1.0e-6}, relative_error_tolerance{1.0e-6};
+  real_t inner_tolerance{1.0e-3};   ///< the inner loop leaves at this relative residual (or where the outer rule needs less)
+  std::size_t inner_max{0};         ///< inner iterations per outer step; 0: num_iterations
+  int max_outer{16};
+  bool keep_direction{false};       ///< the direction survives the outer step (rescaled) instead of restarting
+  int check_lag{0};
+
+  // the last solve
+  std::size_t iteration{0}, num_applies{0};  ///< inner iterations plus those of an fp64 finish; operator products, A~ and A alike
+  real_t absolute_error{0.0}, relative_error{0.0}, initial_error{0.0};  ///< of the last TRUE residual
+  std::size_t outer_steps{0}, inner_iterations{0}, fp64_iterations{0};
+  int finished_fp64{0};  ///< 0 no; 1 the true residual did not fall; 2 broken; 3 max_outer or the iteration budget
+
+  bool solve(DeviceVector& x_vec, const DeviceVector& b_vec, const HipStencilOperator& op) {
+    storm_hip_mixed_params mp;
+    storm_hip_mixed_params_default(&mp);
+    mp.inner_tolerance = inner_tolerance, mp.inner_max = (int64_t)inner_max, mp.max_outer = max_outer;
+    mp.keep_direction = keep_direction ? 1 : 0;
+    storm_hip_mixed_cg* h = nullptr;
+    detail::check(storm_hip_mixed_cg_create(op.matrix().handle(), op.alpha(), op.beta(), &mp, &h));
+    storm_hip_solver_params p;
+    storm_hip_solver_params_default(&p);
+    p.num_iterations = (int64_t)num_iterations;
+    p.absolute_error_tolerance = absolute_error_tolerance, p.relative_error_tolerance = relative_error_tolerance;
+    p.check_lag = check_lag;
+    storm_hip_solver_result r{};
+    storm_hip_mixed_result mr{};
+    const int status = storm_hip_mixed_cg_solve(h, b_vec.handle(), x_vec.handle(), &p, &r, nullptr, &mr);
+    (void)storm_hip_mixed_cg_destroy(h);
+    detail::check(status);
+    iteration = (std::size_t)r.iterations, num_applies = (std::size_t)r.num_applies;
+    absolute_error = r.absolute_error, relative_error = r.relative_error, initial_error = r.initial_error;
+    outer_steps = (std::size_t)mr.outer_steps, inner_iterations = (std::size_t)mr.inner_iterations;
+    fp64_iterations = (std::size_t)mr.fp64_iterations, finished_fp64 = mr.finished_fp64;
+    return r.converged != 0;
+  }
+};
 /// SolverBiCgStab.hpp:52-167.
 template<class Vector>
 class BiCgStabSolver final : public detail::DeviceIterativeSolver<Vector, STORM_HIP_BICGSTAB> {};

@@ -69,7 +69,17 @@ class AmgSmoother(C.Structure):
     _fields_ = [("kind", C.c_int32), ("sweeps", C.c_int32), ("omega", C.c_double)]
 
 
-ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
+class MixedParams(C.Structure):
+    _fields_ = [("inner_tolerance", C.c_double), ("inner_max", C.c_int64), ("max_outer", C.c_int32),
+                ("keep_direction", C.c_int32)]
+
+
+class MixedResult(C.Structure):
+    _fields_ = [("outer_steps", C.c_int64), ("inner_iterations", C.c_int64), ("fp64_iterations", C.c_int64),
+                ("finished_fp64", C.c_int32)]
+
+
+ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                           C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double))
 
@@ -244,6 +254,16 @@ SIGNATURES = {
     "storm_hip_recycle_get": (C.c_int, [vp, C.c_char_p, f64p]),
     "storm_hip_recycle_get_slot": (C.c_int, [vp, C.c_int, vp, vp, f64p]),
     "storm_hip_recycle_set_slot": (C.c_int, [vp, C.c_int, vp, vp, C.c_double]),
+    "storm_hip_mixed_params_default": (None, [C.POINTER(MixedParams)]),
+    "storm_hip_mixed_cg_create": (C.c_int, [vp, C.c_double, C.c_double, C.POINTER(MixedParams), C.POINTER(vp)]),
+    "storm_hip_mixed_cg_destroy": (C.c_int, [vp]),
+    "storm_hip_mixed_cg_solve": (C.c_int, [vp, vp, vp, C.POINTER(SolverParams), C.POINTER(SolverResult), f64p,
+                                           C.POINTER(MixedResult)]),
+    "storm_hip_mixed_cg_begin": (C.c_int, [vp, vp, vp]),
+    "storm_hip_mixed_cg_inner": (C.c_int, [vp, C.c_int64]),
+    "storm_hip_mixed_cg_end_outer": (C.c_int, [vp, vp, f64p]),
+    "storm_hip_mixed_cg_get_vector": (C.c_int, [vp, C.c_char_p, vp]),
+    "storm_hip_mixed_cg_get_scalar": (C.c_int, [vp, C.c_char_p, f64p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1937,3 +1937,104 @@ class BlockCgSolver:
             _LOG.info("column %d: n_iter: %4d, abs_err: %-12e, rel_err: %-12e", j, res[j].iterations, res[j].absolute_error,
                       res[j].relative_error)
         return bool(self.converged.all())
+
+
+class MixedCgSolver(IterativeSolver):
+    """CG whose inner iterations run on fp32 vectors and the matrix's fp32-weight companion records under an fp64
+    refinement loop held to the reference's rule on the true residual (``storm_hip_mixed_cg_*``; algorithm and
+    contract: include/storm_hip.h).  Opt-in; takes a :class:`HipStencilOperator` on fp64 records (option
+    ``spmv_dict = 0``) without a CSR tail whose matrix has a companion (:meth:`StencilMatrix.build_reduced`).
+
+    Knobs beside the reference's: ``inner_tolerance`` (1e-3), ``inner_max`` (0: ``num_iterations``), ``max_outer``
+    (16), ``keep_direction`` (0).  After ``solve``: ``iteration`` counts the inner iterations plus those of an fp64
+    finish, ``history`` (with ``record_history``) holds the TRUE residual norms, one per outer step behind the
+    initial one, and ``outer_steps``, ``inner_iterations``, ``fp64_iterations``, ``finished_fp64`` are the mixed
+    result (``finished_fp64``: 0 no; 1 the true residual did not fall; 2 broken; 3 ``max_outer`` or the budget)."""
+
+    def __init__(self):
+        super().__init__()
+        p = _lib.MixedParams()
+        lib.storm_hip_mixed_params_default(C.byref(p))
+        self.inner_tolerance = p.inner_tolerance
+        self.inner_max = p.inner_max
+        self.max_outer = p.max_outer
+        self.keep_direction = p.keep_direction
+        self.outer_steps = self.inner_iterations = self.fp64_iterations = self.finished_fp64 = 0
+        self._h = None
+        self._key = None
+        self._ctx = None
+
+    def _mixed_params(self) -> "_lib.MixedParams":
+        p = _lib.MixedParams()
+        p.inner_tolerance, p.inner_max = float(self.inner_tolerance), int(self.inner_max)
+        p.max_outer, p.keep_direction = int(self.max_outer), int(self.keep_direction)
+        return p
+
+    def _bound(self, any_op) -> None:
+        """The native object for this operator and these knobs (made again when either changes)."""
+        if not isinstance(any_op, HipStencilOperator):
+            raise TypeError("MixedCgSolver needs a HipStencilOperator")
+        key = (any_op.matrix._h.value if hasattr(any_op.matrix._h, "value") else any_op.matrix._h, any_op.alpha, any_op.beta,
+               float(self.inner_tolerance), int(self.inner_max), int(self.max_outer), int(self.keep_direction))
+        if self._h is not None and key == self._key:
+            return
+        self._free()
+        p, h = self._mixed_params(), C.c_void_p()
+        check(lib.storm_hip_mixed_cg_create(any_op.matrix._h, any_op.alpha, any_op.beta, C.byref(p), C.byref(h)))
+        self._h, self._key, self._ctx, self._matrix = h, key, any_op.matrix.ctx, any_op.matrix
+
+    def solve(self, x_vec, b_vec, any_op) -> bool:
+        if self.pre_op is not None:
+            raise ValueError("MixedCgSolver takes no preconditioner")
+        if self.recycler is not None:
+            return self._solve_recycled(x_vec, b_vec, any_op)
+        self._bound(any_op)
+        p, r, mr = self._params(), _lib.SolverResult(), _lib.MixedResult()
+        hist = np.zeros(self.num_iterations + 1) if self.record_history else None
+        check(lib.storm_hip_mixed_cg_solve(self._h, b_vec._h, x_vec._h, C.byref(p), C.byref(r),
+                                           None if hist is None else hist.ctypes.data_as(_lib.f64p), C.byref(mr)))
+        self.iteration = r.iterations
+        self.absolute_error, self.relative_error = r.absolute_error, r.relative_error
+        self.initial_error, self.num_applies, self.num_pre_applies = r.initial_error, r.num_applies, 0
+        self.path_fallback = r.path_fallback
+        self.outer_steps, self.inner_iterations = mr.outer_steps, mr.inner_iterations
+        self.fp64_iterations, self.finished_fp64 = mr.fp64_iterations, mr.finished_fp64
+        self.history = None if hist is None else hist[: mr.outer_steps + mr.fp64_iterations + 1]
+        self._log()
+        return bool(r.converged)
+
+    # -- the stepping entry points (tests, benchmarks) --
+    def begin(self, x_vec, b_vec, any_op) -> None:
+        self._bound(any_op)
+        check(lib.storm_hip_mixed_cg_begin(self._h, b_vec._h, x_vec._h))
+
+    def inner(self, n: int) -> None:
+        check(lib.storm_hip_mixed_cg_inner(self._h, int(n)))
+
+    def end_outer(self, x_vec) -> float:
+        rho = C.c_double()
+        check(lib.storm_hip_mixed_cg_end_outer(self._h, x_vec._h, C.byref(rho)))
+        return rho.value
+
+    def get_vector(self, name: str, out: DeviceVector) -> None:
+        check(lib.storm_hip_mixed_cg_get_vector(self._h, name.encode(), out._h))
+
+    def get_scalar(self, name: str) -> float:
+        v = C.c_double()
+        check(lib.storm_hip_mixed_cg_get_scalar(self._h, name.encode(), C.byref(v)))
+        return v.value
+
+    def _free(self):
+        if getattr(self, "_h", None) is not None:
+            if getattr(self._ctx, "_h", None):  # never touch a dead context (destroy does not read the operator)
+                lib.storm_hip_mixed_cg_destroy(self._h)
+            self._h = None
+
+    def close(self):
+        self._free()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self._free()
+        except Exception:
+            pass

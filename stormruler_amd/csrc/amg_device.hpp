@@ -10,8 +10,9 @@
 namespace storm {
 
 // (beta x + alpha M x)_row on the records of the row's slice: row_sum_any, then sell_row_result.  xi: the row's own x.
-template <bool NT, class R, bool CO = false>
-__device__ __forceinline__ double sell_row_apply(const SellArgs &A, int64_t slice, int lane, const double *__restrict__ x, double xi,
+// X: the gathered vector's element type (double; float for the fp32 vectors of mixed_cg.hip, widened where they are loaded).
+template <bool NT, class R, bool CO = false, class X = double>
+__device__ __forceinline__ double sell_row_apply(const SellArgs &A, int64_t slice, int lane, const X *__restrict__ x, double xi,
                                                  double alpha, double beta) {
   int64_t base;
   int width;
@@ -26,7 +27,7 @@ __device__ __forceinline__ double sell_row_apply(const SellArgs &A, int64_t slic
   const double ext = R::template ext<NT>(rec, lane);
   const double xi1[1] = {xi};
   double acc1[1];
-  row_sum_any<NT, 1, R, CO>(rec, width, lane, x, xi1, acc1);
+  row_sum_any<NT, 1, R, CO, X>(rec, width, lane, x, xi1, acc1);
   return sell_row_result(false, 0.0, beta, xi, alpha, acc1[0], ext);
 }
 

@@ -326,6 +326,8 @@ int k_copy(storm_hip_ctx *c, double *y, const double *x, int64_t n, const int *d
 int k_scale(storm_hip_ctx *c, double *y, int64_t n, Scal s, bool divide, const int *done) {
   return launch_ew(c, n, EwPtrs{y, nullptr, nullptr}, ScaleF{s, divide, 0.0}, done);
 }
+int stream_nt_of(const storm_hip_ctx *c, int64_t n) { return stream_nt(c, n); }
+
 int k_axpbz(storm_hip_ctx *c, double *y, Scal a, const double *x, Scal b, const double *z, int64_t n,
             const int *done) {
   return launch_ew(c, n, EwPtrs{y, x, z}, AxpbzF{a, b, 0.0, 0.0}, done);

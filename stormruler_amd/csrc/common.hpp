@@ -288,6 +288,8 @@ struct storm_hip_ctx {
   int64_t opt_recycle_fused = 1;  // storm_hip_recycle: the fused kernels (blas1.hip recycle_*_kernel); 0: the same recipe out of library launchers
   int64_t n_recycle_guesses = 0, n_recycle_updates = 0, n_recycle_restarts = 0;  // recycle.hip: calls; updates that restarted
   int64_t n_recycle_fused_launches = 0, n_recycle_statement_launches = 0;        // ... what the two paths enqueued
+  // mixed_cg.hip: solves; their fp32 inner iterations and outer steps; solves that the fp64 loop finished
+  int64_t n_mixed_solves = 0, n_mixed_inner_iterations = 0, n_mixed_outer_steps = 0, n_mixed_fp64_finishes = 0;
   int64_t n_cg_residual_marches = 0;  // fused CG solves whose r -= alpha z recomputed z (option cg_residual_march)
   int64_t n_cg_residual_plane_marches = 0;  // ... of them, those whose recompute marched over planes (option cg_residual_planes)
   int64_t n_cg_pz_consumer_folds = 0;  // ... of those, the solves whose plane march folded <p,z> itself (option cg_pz_fold)
@@ -614,6 +616,10 @@ int op_reduced_check(const storm_hip_op *op, const char *who);     // fp64 recor
 int op_reduced_require(const storm_hip_op *op, const char *who);   // ... and a companion: nothing is built behind the caller's back
 int op_reduced_convert(storm_hip_op *op, int *d_flag);             // enqueue the conversion kernels (d_flag: the range flag, or null)
 int op_reduced_apply(const storm_hip_op *op, double alpha, double beta, const double *x, double *y, const int *done);
+// The access-mode choices of mixed_cg.hip, made by the units that own the two options: the non-temporal instance of a kernel
+// on the companion records (op_reduced.hip), of a streaming kernel over n rows (blas1.hip; counted like stream_nt()).
+bool op_reduced_nt(const storm_hip_op *op);
+int stream_nt_of(const storm_hip_ctx *c, int64_t n);
 
 // latency.hip
 bool cg_latency_eligible(const storm_hip_op *op);

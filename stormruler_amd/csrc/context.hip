@@ -286,6 +286,10 @@ int storm_hip_ctx_get_counter(storm_hip_ctx *c, const char *key, int64_t *value)
   else if (!strcmp(key, "option_spmv_dict")) *value = c->opt_spmv_dict;  // (the option's value, for a caller that restores it)
   else if (!strcmp(key, "amg_projections")) *value = c->n_amg_projections;
   else if (!strcmp(key, "amg_fused_projections")) *value = c->n_amg_fused_projections;
+  else if (!strcmp(key, "mixed_solves")) *value = c->n_mixed_solves;
+  else if (!strcmp(key, "mixed_inner_iterations")) *value = c->n_mixed_inner_iterations;
+  else if (!strcmp(key, "mixed_outer_steps")) *value = c->n_mixed_outer_steps;
+  else if (!strcmp(key, "mixed_fp64_finishes")) *value = c->n_mixed_fp64_finishes;
   else if (!strcmp(key, "op_reduced_builds")) *value = c->n_op_reduced_builds;
   else if (!strcmp(key, "op_reduced_refreshes")) *value = c->n_op_reduced_refreshes;
   else if (!strcmp(key, "jfnk_inner_solves")) *value = c->n_jfnk_inner_solves;

@@ -165,6 +165,8 @@ int op_reduced_convert(storm_hip_op *op, int *d_flag) {
   return STORM_HIP_OK;
 }
 
+bool op_reduced_nt(const storm_hip_op *op) { return op->ctx->opt_nt != 0; }
+
 int op_reduced_apply(const storm_hip_op *op, double alpha, double beta, const double *x, double *y, const int *done) {
   if (op->n_slices == 0) return STORM_HIP_OK;
   const SellArgs A{op->d_pack32, op->d_slice_off32, op->n_rows, op->uniform_width, op->xcd_group_sell, nullptr, 0, nullptr, 0, 0};

@@ -11,10 +11,15 @@ namespace storm {
 // The K values of cell `col`.  K even: 16-byte loads (a block vector starts on a 16-byte boundary and a cell is K * 8 bytes).
 // CO (one column only): x is written by other blocks of the SAME launch (amg_tail.hip) -- co_load's access (coop_device.hpp),
 // a relaxed agent-scope atomic load; the value, hence everything summed from it, is the plain load's.
-template <int K, bool CO = false>
-__device__ __forceinline__ void ld_cols(const double *__restrict__ x, int col, double (&out)[K]) {
+// X: the gathered vector's element type -- double, or float (mixed_cg.hip: one column, plain gathers), widened exactly
+// where it is loaded.
+template <int K, bool CO = false, class X = double>
+__device__ __forceinline__ void ld_cols(const X *__restrict__ x, int col, double (&out)[K]) {
   static_assert(!CO || K == 1, "ld_cols: coherent gathers take one column");
-  if constexpr (CO) {
+  static_assert(std::is_same<X, double>::value || (K == 1 && !CO), "ld_cols: an fp32 vector is one column, gathered plainly");
+  if constexpr (!std::is_same<X, double>::value) {
+    out[0] = (double)x[col];
+  } else if constexpr (CO) {
     out[0] = __hip_atomic_load(x + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   } else if constexpr (K == 1) {
     out[0] = x[col];
@@ -109,8 +114,8 @@ struct Rec32 {
 // (W compile-time, S0 even).  The (col, val) record is loaded once for all columns (by the record policy R); the
 // neighbours' values are gathered kGather slots at a time (every slot at once up to
 // K = 4: at most 32 doubles in flight per lane), the sums run over the slots in order whatever the chunking.
-template <bool NT, int W, int K, class R = Rec64, bool CO = false>
-__device__ __forceinline__ void row_sum_block(const char *rec, int width, int lane, const double *__restrict__ x,
+template <bool NT, int W, int K, class R = Rec64, bool CO = false, class X = double>
+__device__ __forceinline__ void row_sum_block(const char *rec, int width, int lane, const X *__restrict__ x,
                                               const double (&xi)[K], double (&acc)[K], int s0 = 0) {
   constexpr int W1 = W > 0 ? W : 1;
   constexpr int kGather = K <= 4 ? W1 : 4;
@@ -124,7 +129,7 @@ __device__ __forceinline__ void row_sum_block(const char *rec, int width, int la
     double xg[kGather][K];
 #pragma unroll
     for (int s = 0; s < kGather; ++s)
-      if (g0 + s < W) ld_cols<K, CO>(x, col[g0 + s], xg[s]);
+      if (g0 + s < W) ld_cols<K, CO, X>(x, col[g0 + s], xg[s]);
 #pragma unroll
     for (int s = 0; s < kGather; ++s) {
       if (g0 + s < W) {
@@ -136,26 +141,26 @@ __device__ __forceinline__ void row_sum_block(const char *rec, int width, int la
 }
 
 // Rows wider than 8 slots: chunk sums of 8, then the remainder.
-template <bool NT, int K, class R = Rec64, bool CO = false>
-__device__ __forceinline__ void row_sum_wide_block(const char *rec, int width, int lane, const double *__restrict__ x,
+template <bool NT, int K, class R = Rec64, bool CO = false, class X = double>
+__device__ __forceinline__ void row_sum_wide_block(const char *rec, int width, int lane, const X *__restrict__ x,
                                                    const double (&xi)[K], double (&acc)[K]) {
   double part[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) acc[j] = 0.0, part[j] = 0.0;
   int s0 = 0;
   for (; s0 + 8 <= width; s0 += 8) {
-    row_sum_block<NT, 8, K, R, CO>(rec, width, lane, x, xi, part, s0);
+    row_sum_block<NT, 8, K, R, CO, X>(rec, width, lane, x, xi, part, s0);
 #pragma unroll
     for (int j = 0; j < K; ++j) acc[j] += part[j];
   }
   switch (width - s0) {
-    case 1: row_sum_block<NT, 1, K, R, CO>(rec, width, lane, x, xi, part, s0); break;
-    case 2: row_sum_block<NT, 2, K, R, CO>(rec, width, lane, x, xi, part, s0); break;
-    case 3: row_sum_block<NT, 3, K, R, CO>(rec, width, lane, x, xi, part, s0); break;
-    case 4: row_sum_block<NT, 4, K, R, CO>(rec, width, lane, x, xi, part, s0); break;
-    case 5: row_sum_block<NT, 5, K, R, CO>(rec, width, lane, x, xi, part, s0); break;
-    case 6: row_sum_block<NT, 6, K, R, CO>(rec, width, lane, x, xi, part, s0); break;
-    case 7: row_sum_block<NT, 7, K, R, CO>(rec, width, lane, x, xi, part, s0); break;
+    case 1: row_sum_block<NT, 1, K, R, CO, X>(rec, width, lane, x, xi, part, s0); break;
+    case 2: row_sum_block<NT, 2, K, R, CO, X>(rec, width, lane, x, xi, part, s0); break;
+    case 3: row_sum_block<NT, 3, K, R, CO, X>(rec, width, lane, x, xi, part, s0); break;
+    case 4: row_sum_block<NT, 4, K, R, CO, X>(rec, width, lane, x, xi, part, s0); break;
+    case 5: row_sum_block<NT, 5, K, R, CO, X>(rec, width, lane, x, xi, part, s0); break;
+    case 6: row_sum_block<NT, 6, K, R, CO, X>(rec, width, lane, x, xi, part, s0); break;
+    case 7: row_sum_block<NT, 7, K, R, CO, X>(rec, width, lane, x, xi, part, s0); break;
     default: return;
   }
 #pragma unroll
@@ -165,23 +170,23 @@ __device__ __forceinline__ void row_sum_wide_block(const char *rec, int width, i
 // The row's sum for a slice of `width` slots.  The width is wave-uniform: dispatch to a body with the width as a
 // compile-time constant, so all (col, val) loads of the row are issued back to back, then the gathers, then the FMAs --
 // no branch (and no s_waitcnt) between the gathers of one row.
-template <bool NT, int K, class R = Rec64, bool CO = false>
-__device__ __forceinline__ void row_sum_any(const char *rec, int width, int lane, const double *__restrict__ x,
+template <bool NT, int K, class R = Rec64, bool CO = false, class X = double>
+__device__ __forceinline__ void row_sum_any(const char *rec, int width, int lane, const X *__restrict__ x,
                                             const double (&xi)[K], double (&acc)[K]) {
   switch (width) {
     case 0:
 #pragma unroll
       for (int j = 0; j < K; ++j) acc[j] = 0.0;
       break;
-    case 1: row_sum_block<NT, 1, K, R, CO>(rec, 1, lane, x, xi, acc); break;
-    case 2: row_sum_block<NT, 2, K, R, CO>(rec, 2, lane, x, xi, acc); break;
-    case 3: row_sum_block<NT, 3, K, R, CO>(rec, 3, lane, x, xi, acc); break;
-    case 4: row_sum_block<NT, 4, K, R, CO>(rec, 4, lane, x, xi, acc); break;
-    case 5: row_sum_block<NT, 5, K, R, CO>(rec, 5, lane, x, xi, acc); break;
-    case 6: row_sum_block<NT, 6, K, R, CO>(rec, 6, lane, x, xi, acc); break;
-    case 7: row_sum_block<NT, 7, K, R, CO>(rec, 7, lane, x, xi, acc); break;
-    case 8: row_sum_block<NT, 8, K, R, CO>(rec, 8, lane, x, xi, acc); break;
-    default: row_sum_wide_block<NT, K, R, CO>(rec, width, lane, x, xi, acc); break;
+    case 1: row_sum_block<NT, 1, K, R, CO, X>(rec, 1, lane, x, xi, acc); break;
+    case 2: row_sum_block<NT, 2, K, R, CO, X>(rec, 2, lane, x, xi, acc); break;
+    case 3: row_sum_block<NT, 3, K, R, CO, X>(rec, 3, lane, x, xi, acc); break;
+    case 4: row_sum_block<NT, 4, K, R, CO, X>(rec, 4, lane, x, xi, acc); break;
+    case 5: row_sum_block<NT, 5, K, R, CO, X>(rec, 5, lane, x, xi, acc); break;
+    case 6: row_sum_block<NT, 6, K, R, CO, X>(rec, 6, lane, x, xi, acc); break;
+    case 7: row_sum_block<NT, 7, K, R, CO, X>(rec, 7, lane, x, xi, acc); break;
+    case 8: row_sum_block<NT, 8, K, R, CO, X>(rec, 8, lane, x, xi, acc); break;
+    default: row_sum_wide_block<NT, K, R, CO, X>(rec, width, lane, x, xi, acc); break;
   }
 }
 
